@@ -2,12 +2,18 @@
 """Headline benchmark: NEWT forward throughput (audio samples/s, x real-time) on 4 s @ 16 kHz clips.
 
     python bench.py [--gpus N --steps K --warmup W] [--batch 64] [--frames 500] [--exact] [--gather rccl|copy]
+                    [--dump-outputs DIR] [--full]
 
 Contract: a step = one NeuralWaveshaping.forward over a batch of `--batch` synthetic
 utterances per GPU (torch.rand F0/control exactly like the reference's scripts/time_forward_pass.py:27-40,
 vn checkpoint, FastNEWT LUT), inputs resident in HBM, the two RNG draws of forward() made on the device
 inside the step; with N>1 the rendered waveforms are all-gathered (RCCL, or `--gather copy`: copy-engine
 peer writes) inside the timed region, overlapped with the next step's kernels.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, primes and warms up, times the K steps and prints the headline line.  `--full` adds everything
+else the benchmark measures or checks, outside the timed steps: live per-kernel timing inside the timed region, the
+pipeline's bit-exactness self-check, per-stage times, batch-1 and streaming latency, the extra legs, the roofline with
+its hardware counters, the CPU baseline and, with N>1, the exchange regions.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` (one rank per GPU) after checking that the box HAS N GPUs;
@@ -113,7 +119,33 @@ def parse():
                          "this script (FETCH_SIZE, WRITE_SIZE, SQ counters: separate passes, never combined with traces); file = "
                          "the committed profiles/<round>/pmc_kernels.json; auto = live when rocprofv3 is on the box, else file")
     ap.add_argument("--pmc-child", type=int, default=0, help=argparse.SUPPRESS)   # internal: the workload the PMC passes profile
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline (see the module docstring); --no-cpu-baseline, "
+                         "--cpu-seconds, --batch1-iters, --legs, --leg-steps and --pmc shape what it adds")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/waveforms.npy (float32, B x N; "
+                         "N > 1: rank 0's gathered batch of every rank).  Beyond 64 MB a fixed, seeded sample of its rows")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6 - 4096     # --dump-outputs: 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32, DUMP_LIMIT_BYTES in all (arrays are 2-D (rows, samples);
+    one beyond its share is cut to a seeded sample of rows, kept in their original order)"""
+    os.makedirs(out_dir, exist_ok=True)
+    limit = DUMP_LIMIT_BYTES // len(arrays)
+    for name, x in arrays.items():
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.nbytes > limit:
+            keep = max(1, limit // (x.shape[1] * 4))
+            rows = np.sort(np.random.default_rng(0).choice(x.shape[0], size=min(keep, x.shape[0]), replace=False))
+            x = x[rows]
+            if x.nbytes > limit:       # a single row beyond the limit: a seeded sample of its samples
+                cols = np.sort(np.random.default_rng(1).choice(x.shape[1], size=limit // 4, replace=False))
+                x = x[:, cols]
+        np.save(os.path.join(out_dir, name + ".npy"), x)
 
 
 def launch_ranks(a):
@@ -447,6 +479,9 @@ def main(hooks=None):
         sys.exit(2)
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
+    # the forward's two RNG draws come from the device's default generator (N = 1): seeded, so that equal arguments give equal
+    # draws from run to run (torch seeds its default generators differently in every process)
+    torch.cuda.manual_seed(2000 + rank)
     distributed = world > 1 or force_dist
     if distributed:
         import torch.distributed as dist
@@ -573,10 +608,15 @@ def main(hooks=None):
             return work
         return par.gather_full(full[i % nbuf], y)
 
+    # --dump-outputs at N = 1: the batch each step returns is kept until the next step replaces it (N > 1: the gather buffers)
+    last_y = {} if (a.dump_outputs and not distributed) else None
+
     def step(i, pending, do_gather=True, do_compute=True, plain=False):
         if use_pipe:
             if not distributed or plain:
-                pipe.submit(f0, control)        # the single-GPU issue pattern (also timed beside the N > 1 one: world1_overhead)
+                y = pipe.submit(f0, control)    # the single-GPU issue pattern (also timed beside the N > 1 one: world1_overhead)
+                if last_y is not None:
+                    last_y["y"] = y
                 return None
             slot_i = i % nbuf
             if not do_compute:
@@ -621,7 +661,9 @@ def main(hooks=None):
                 if do_gather:
                     return gather(i, y if y is not None else gather_src)
                 return None
-            model(f0, control)
+            y = model(f0, control)
+            if last_y is not None:
+                last_y["y"] = y
         return None
 
     def join_streams():
@@ -679,19 +721,30 @@ def main(hooks=None):
             xchg.drain(peer.flush if peer is not None else None)
         join_streams()
         torch.cuda.synchronize()
-        # live HIP-event timing of the dominant kernel (and the GRU) on their launch streams, inside the timed region
-        _lib.check(_lib.lib().nws_profile_begin(a.steps, (1 << 3) | (1 << 1)))
+        if a.full:
+            # live HIP-event timing of the dominant kernel (and the GRU) on their launch streams, inside the timed region
+            _lib.check(_lib.lib().nws_profile_begin(a.steps, (1 << 3) | (1 << 1)))
         elapsed, per_rank = timed(a.steps)
         extra["host_issue_ms_per_step"] = round(host_issue["s_per_step"] * 1e3, 4)
+        if a.dump_outputs and rank == 0:
+            # what the last timed step returned: the batch (N = 1), the gathered batch of every rank (N > 1)
+            if distributed:
+                got = full[(a.steps - 1) % nbuf]
+                if blocks is not None and peer is None:      # RCCL sub-batches fill the buffer block-major
+                    got = par.block_major_view(got, world, len(blocks)).reshape(world * B, N)
+            else:
+                got = last_y["y"]
+            dump_outputs(a.dump_outputs, {"waveforms": got.float().cpu().numpy()})
         hooks.extra(extra, a.steps, xchg, peer)
-        ms = (C.c_float * (a.steps * 6))()
         n = C.c_int(0)
-        _lib.check(_lib.lib().nws_profile_collect(ms, C.byref(n)))
-        k_ms = float(np.mean([ms[i * 6 + 3] for i in range(n.value)])) if n.value else float("nan")
-        gru_ms_live = float(np.mean([ms[i * 6 + 1] for i in range(n.value)])) if n.value else float("nan")
-        _lib.lib().nws_profile_end()
+        if a.full:
+            ms = (C.c_float * (a.steps * 6))()
+            _lib.check(_lib.lib().nws_profile_collect(ms, C.byref(n)))
+            k_ms = float(np.mean([ms[i * 6 + 3] for i in range(n.value)])) if n.value else float("nan")
+            gru_ms_live = float(np.mean([ms[i * 6 + 1] for i in range(n.value)])) if n.value else float("nan")
+            _lib.lib().nws_profile_end()
 
-        if distributed:
+        if distributed and a.full:
             # the gathered batch must hold every rank's rows (rank r at rows [r*B, (r+1)*B))
             last = full[(a.steps - 1) % nbuf]
             assert torch.isfinite(last).all() and float(last[B * (world - 1):].abs().max()) > 0.0
@@ -736,7 +789,7 @@ def main(hooks=None):
                 # the price of the exchange machinery with nothing to send; at N > 1 what the exchange costs each rank
                 extra["exchange"]["world1_overhead" if world == 1 else "step_over_single_gpu_pattern"] = (elapsed / a.steps) / (p_el / k2)
 
-        if use_pipe:
+        if use_pipe and a.full:
             # self-check outside the timed region: the issue pattern of the timed loop (pipeline, and the all-gather when
             # distributed) must return bit for bit what a plain forward returns for the same draws
             gchk = torch.Generator(device=dev).manual_seed(4242)   # the same draws on every rank, like the timed loop
@@ -803,7 +856,7 @@ def main(hooks=None):
                 tw = torch.tensor([wrong], dtype=torch.float64, device="cpu" if share_gpu else dev)
                 dist.all_reduce(tw, op=dist.ReduceOp.SUM)
                 extra["pipeline_selfcheck"]["mismatching_all_ranks"] = int(tw.item())
-        if rank == 0:
+        if rank == 0 and a.full:
             # per-stage breakdown (diagnostic, outside the timed region)
             _lib.check(_lib.lib().nws_profile_begin(10, 0x3F))
             for _ in range(10):
@@ -834,7 +887,7 @@ def main(hooks=None):
                                    "x_realtime_p50": round(dur_ms / float(np.percentile(lat, 50)), 1),
                                    "rtf_mean": float(np.mean(lat) / dur_ms)}
 
-    if rank == 0 and world == 1 and a.batch1_iters > 0:
+    if rank == 0 and world == 1 and a.batch1_iters > 0 and a.full:
         # config "streaming 256-sample hop": stateless forward of one 16 ms buffer, captured once into a hipGraph
         with torch.no_grad():
             fs, cs = torch.rand(1, 1, 2, device=dev), torch.rand(1, 2, 2, device=dev)
@@ -914,7 +967,7 @@ def main(hooks=None):
             extra["batch1_hipgraph"] = {"p50_ms": round(float(np.percentile(lat, 50)), 4),
                                         "p90_ms": round(float(np.percentile(lat, 90)), 4),
                                         "x_realtime_p50": round(dur_ms / float(np.percentile(lat, 50)), 1)}
-    if rank == 0 and world == 1 and a.legs and use_pipe and not distributed:
+    if rank == 0 and world == 1 and a.legs and use_pipe and not distributed and a.full:
         # extra legs, driver-timed like the headline: the same issue pattern for the other arithmetic / inputs / shapers
         legs = {}
         n_audio, n_control = len(pipe.audio), len(pipe.control)
@@ -949,6 +1002,9 @@ def main(hooks=None):
         total_samples = B * world * N * a.steps
         value = total_samples / elapsed
         ms_per_step = elapsed / a.steps * 1e3
+        one_term = bool(opts & 2) and not a.exact
+        hybrid = bool(opts & (4 | 8)) and not one_term and not a.exact
+    if rank == 0 and a.full:
         st = extra.get("stage_ms", {})
         pmc, pmc_src, pmc_note = None, None, None
         if a.pmc in ("auto", "live") and world == 1 and st:
@@ -966,8 +1022,6 @@ def main(hooks=None):
             pmc, pmc_src = load_pmc()
             if pmc and (pmc.get("batch_per_gpu") != B or pmc.get("frames") != T or a.exact or pmc.get("exciter_opts", 0) != opts):
                 pmc = None        # counters of another workload: not quoted
-        one_term = bool(opts & 2) and not a.exact
-        hybrid = bool(opts & (4 | 8)) and not one_term and not a.exact
         # fp16 MFMAs per (M-tile, K-step): 3 with both operands two-term, 2 with one-term sines, 1 with one-term weights too;
         # K-step 0 always 3 in the hybrid forms; 6 K-steps of 16 slots + one of 8
         per_step = 2 if one_term else (2 if (opts & 4) else 1 if (opts & 8) else 3)
@@ -1041,6 +1095,7 @@ def main(hooks=None):
                 e["hbm_algorithmic_bytes"] = kb
                 if (e.get("hbm") or {}).get("traffic"):
                     e["traffic_over_algorithmic"] = e["hbm"]["traffic"] / kb
+    if rank == 0:
         if a.exact:
             dtype = "f32 (101->64 mixer, frame MLPs, FIR noise: fp16x2-split MFMA contractions = 22-bit products, fp32 accumulate; exact sin-MLP shapers in fp32)"
         elif one_term:
@@ -1072,11 +1127,12 @@ def main(hooks=None):
                        else f"whole forwards round-robin on {len(streams)} streams"},
             "x_realtime_aggregate": value / 16000.0,
             "rtf_per_utterance": (ms_per_step * 1e-3) / (N / 16000.0) / B,
-            "ms_per_step_per_rank": [round(t / a.steps * 1e3, 4) for t in per_rank],
-            "roofline": roofline, "roofline_all": roofline_all,
+            "ms_per_step_per_rank": [round(t / a.steps * 1e3, 4) for t in per_rank], "full": a.full,
         }
+        if a.full:
+            out.update(roofline=roofline, roofline_all=roofline_all)
         out.update(extra)
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and not a.no_cpu_baseline and a.full:
             out["cpu_baseline"] = cpu_baseline(wpath, T, a.cpu_seconds)
     if distributed:
         if xchg is not None:

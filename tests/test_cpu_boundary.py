@@ -9,11 +9,10 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import GOLDEN, ROOT, write_lightning_ckpt
 
 nws = importlib.import_module("neural-waveshaping-synthesis_amd")
 _lib = importlib.import_module("neural-waveshaping-synthesis_amd._lib")
-REF_GIN = "/root/reference/gin/models/newt.gin"
 
 
 def _declared_symbols(headers=("nws_hip.h", "nws_hip_debug.h")):
@@ -130,9 +129,21 @@ def test_bad_arguments_return_codes_without_touching_the_gpu():
     assert L.nws_forward_workspace_bytes(None, 1, 4) == 0
 
 
-def test_gin_reader_parses_reference_and_packaged_config():
+def test_gin_reader_parses_reference_and_packaged_config(tmp_path):
+    """The packaged model config, and the same config in the macro style of the reference's model files (every value bound
+    once as a macro `m = v`, the binding as `X.y = %m`)."""
     gin = nws.gin
-    for path in ([REF_GIN] if os.path.exists(REF_GIN) else []) + [nws.DEFAULT_GIN]:
+    macro_style, n = [], 0
+    for line in open(nws.DEFAULT_GIN).read().splitlines():
+        code = line.split("#")[0].strip()
+        if "=" in code:
+            name, value = (t.strip() for t in code.split("=", 1))
+            macro_style += [f"v{n} = {value}", f"{name} = %v{n}"]
+            n += 1
+    assert n >= 20
+    macro_gin = tmp_path / "newt_macros.gin"
+    macro_gin.write_text("\n".join(macro_style) + "\n")
+    for path in (str(macro_gin), nws.DEFAULT_GIN):
         gin.clear_config()
         gin.parse_config_file(path)
         assert gin.query_parameter("Reverb.sr") == 16000
@@ -189,16 +200,17 @@ def test_module_surface_and_state_dict_keys(weights):
         nws.TimeDistributedMLP(8, 8, 8, depth=2)
 
 
-def test_checkpoint_loading_npz_and_lightning_ckpt(weights):
+def test_checkpoint_loading_npz_and_lightning_ckpt(weights, tmp_path):
     m = nws.NeuralWaveshaping.load_from_checkpoint(os.path.join(ROOT, "tests", "golden", "weights_vn.npz"))
     for k, v in weights.items():
         assert np.array_equal(m.state_dict()[k].numpy(), v), k
-    ck = "/root/reference/checkpoints/nws/vn/last.ckpt"
-    if os.path.exists(ck):   # build container only; the GPU box has no reference tree
-        m2 = nws.NeuralWaveshaping.load_from_checkpoint(ck)
-        for k, v in weights.items():
-            assert np.array_equal(m2.state_dict()[k].numpy(), v), k
-        assert m2.hparams["n_waveshapers"] == 64
+    # a pytorch-lightning style .ckpt of the same weights (the form the reference's checkpoints ship in)
+    ck = str(tmp_path / "last.ckpt")
+    write_lightning_ckpt(ck, weights)
+    m2 = nws.NeuralWaveshaping.load_from_checkpoint(ck)
+    for k, v in weights.items():
+        assert np.array_equal(m2.state_dict()[k].numpy(), v), k
+    assert m2.hparams["n_waveshapers"] == 64
 
 
 def test_no_cpu_fallback_anywhere():
@@ -258,11 +270,11 @@ def test_normalisation_front_end(tmp_path):
     assert np.allclose(f0.numpy()[0], f0_hz, rtol=1e-6)
     assert np.allclose(control.numpy()[0], (f0_hz - mean[0, 0]) / std[0, 0], rtol=1e-5)
     assert np.allclose(control.numpy()[1], (loud - mean[1, 0]) / std[1, 0], rtol=1e-5)
-    ref = "/root/reference/checkpoints/nws/vn"
-    if os.path.exists(ref):
-        m2, s2 = ck.load_normalisation(ref)
-        w = np.load(os.path.join(ROOT, "tests", "golden", "weights_vn.npz"))
-        assert np.allclose(m2[:2], w["__data_mean__"]) and np.allclose(s2[:2], w["__data_std__"])
+    # the vn checkpoint's own statistics files (tests/golden/vn_normalisation: data_mean.npy / data_std.npy, 19 feature rows)
+    m2, s2 = ck.load_normalisation(os.path.join(GOLDEN, "vn_normalisation"))
+    w = np.load(os.path.join(ROOT, "tests", "golden", "weights_vn.npz"))
+    assert m2.shape == s2.shape == (19,) and s2.dtype == np.float64
+    assert np.allclose(m2[:2], w["__data_mean__"]) and np.allclose(s2[:2], w["__data_std__"])
 
 
 def test_loudness_front_end_binds_like_the_reference_and_has_no_cpu_fallback():

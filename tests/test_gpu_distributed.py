@@ -15,7 +15,7 @@ from gpu_util import build_model, dev
 
 pytestmark = pytest.mark.gpu
 ENV = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", GPU_MAX_HW_QUEUES="16")
-SMALL = ["--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--batch1-iters", "0", "--batch", "4", "--frames", "16"]
+SMALL = ["--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--batch1-iters", "0", "--batch", "4", "--frames", "16"]
 
 
 def _json_line(stdout):
@@ -101,7 +101,7 @@ def test_sub_batch_exchange_two_ranks_and_rccl_world1():
     block (nws_forward_audio_pre + nws_forward_reverb_rows), every block leaves for the peers right behind its own reverb.
     Two ranks sharing the GPU (peer-copy form) and RCCL at world size 1 (list-of-views all_gather): every gathered row and
     every batch of the timed issue pattern bit-equal to the plain forward."""
-    args = ["--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--batch1-iters", "0", "--frames", "16", "--batch", "16",
+    args = ["--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--batch1-iters", "0", "--frames", "16", "--batch", "16",
             "--gather-chunks", "4"]
     port = 29700 + (os.getpid() + 77) % 200
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
@@ -190,7 +190,7 @@ def test_world1_overhead_of_the_multi_gpu_issue_pattern():
     parked on the exchange queue; completion-driven exchange + measured queue placement: +0-2 % (profiles/r06/fake_peers_ab.txt).
     Bound 1.05 for the default form (VERDICT r5 #4: the old 1.10 on 60 steps would have let a regression to +8 % through)."""
     def run(kind):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "200", "--warmup", "5", "--no-cpu-baseline",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "200", "--warmup", "5", "--no-cpu-baseline",
                             "--pmc", "off", "--legs", "0", "--batch1-iters", "0", "--gather", kind],
                            env=dict(ENV, NWS_BENCH_FORCE_DIST="1"), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
@@ -230,7 +230,7 @@ def test_eight_rank_queue_population_rehearsed_with_fake_peers():
     from gpu_util import record
 
     def run():
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "200", "--warmup", "5", "--no-cpu-baseline",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "200", "--warmup", "5", "--no-cpu-baseline",
                             "--pmc", "off", "--legs", "0", "--batch1-iters", "0"],
                            env=dict(ENV, NWS_BENCH_FAKE_PEERS="7"), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]

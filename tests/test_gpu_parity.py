@@ -630,31 +630,16 @@ def test_exciter_options_on_golden_vectors(models):
 def test_lightning_style_ckpt_loads_on_the_gpu_box(weights, tmp_path):
     """The reference's users hand `load_from_checkpoint` a pytorch-lightning 1.2.8 `.ckpt` (scripts/resynthesise_dataset.py:47,
     colab cell 6): a torch zip-pickle with `state_dict`, `hyper_parameters` and a `callbacks` dict keyed by the
-    ModelCheckpoint CLASS - the one global of the pickle that needs Lightning.  The shipped .ckpt files cannot travel to
-    the GPU box, so an equivalent file is written here from the weights fixture (with a throw-away stand-in class at
-    pickling time, removed again before loading) and read through checkpoint.read_checkpoint's zip-pickle branch."""
+    ModelCheckpoint CLASS - the one global of the pickle that needs Lightning.  The shipped .ckpt files are not part of the
+    repository, so an equivalent file is written here from the weights fixture (conftest.write_lightning_ckpt) and read through
+    checkpoint.read_checkpoint's zip-pickle branch."""
     import sys
-    import types
 
     import nws_amd as nws
+    from conftest import LIGHTNING_MODULES as names, write_lightning_ckpt
 
-    names = ["pytorch_lightning", "pytorch_lightning.callbacks", "pytorch_lightning.callbacks.model_checkpoint"]
-    assert not any(n in sys.modules for n in names)                      # no Lightning on the box
-    mods = {n: types.ModuleType(n) for n in names}
-    ModelCheckpoint = type("ModelCheckpoint", (), {"__module__": names[2]})
-    mods[names[2]].ModelCheckpoint = ModelCheckpoint
     path = str(tmp_path / "last.ckpt")
-    sys.modules.update(mods)
-    try:
-        torch.save({"epoch": 3, "global_step": 120000, "pytorch-lightning_version": "1.2.8",
-                    "callbacks": {ModelCheckpoint: {"best_model_score": torch.tensor(1.0), "best_model_path": "x.ckpt"}},
-                    "optimizer_states": [], "lr_schedulers": [],
-                    "state_dict": {k: torch.as_tensor(v) for k, v in weights.items()},
-                    "hyper_parameters": {"n_waveshapers": 64, "control_hop": 128, "sample_rate": 16000, "learning_rate": 1e-3,
-                                         "lr_decay": 0.9, "lr_decay_interval": 10000, "log_audio": False}}, path)
-    finally:
-        for n in names:
-            sys.modules.pop(n, None)
+    write_lightning_ckpt(path, weights)
     with pytest.raises(Exception):
         torch.load(path, map_location="cpu", weights_only=False)      # the pickle really needs the missing class ...
     nws.ensure_default_config()

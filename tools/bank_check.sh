@@ -4,7 +4,7 @@ set -x
 export TMPDIR=/tmp
 mkdir -p gpurun_out/bk
 timeout 300 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -p no:cacheprovider -k "e2e or exact or bank or newt_and_fastnewt or full_size or batch64" > gpurun_out/bk/pytest_exact.txt 2>&1; tail -3 gpurun_out/bk/pytest_exact.txt
-Q="--no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --exact --steps 50"
+Q="--full --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --exact --steps 50"
 timeout 120 python bench.py $Q > gpurun_out/bk/exact_new_1.json 2>/dev/null
 NWS_EXCITER_BANK_LDS_PAD=35840 timeout 120 python bench.py $Q > gpurun_out/bk/exact_pad_1.json 2>/dev/null
 timeout 120 python bench.py $Q > gpurun_out/bk/exact_new_2.json 2>/dev/null

@@ -9,7 +9,7 @@ R=${1:-r04}
 OUT=gpurun_out/prof_$R
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python bench.py --no-cpu-baseline --batch1-iters 0 --warmup 5 --legs 0 --pmc off ${NWS_PROFILE_ARGS:-}"
+BENCH="python bench.py --full --no-cpu-baseline --batch1-iters 0 --warmup 5 --legs 0 --pmc off ${NWS_PROFILE_ARGS:-}"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_default" -- $BENCH --steps 50 > "$OUT/trace_default.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_1stream" -- $BENCH --steps 30 --pipeline 0 --streams 1 > "$OUT/trace_1stream.log" 2>&1
 P="$BENCH --steps 6 --pipeline 0 --streams 1"

@@ -1,15 +1,16 @@
 set -x
 export TMPDIR=/tmp
 mkdir -p gpurun_out/ev
+EV=$_     # the evidence folder just made (bash: the last argument of the previous command)
 rm -f gpurun_out/ev/streaming_stateful.txt
 python -m pytest tests -m gpu -x -q > gpurun_out/ev/pytest_gpu.txt 2>&1; tail -2 gpurun_out/ev/pytest_gpu.txt
-python bench.py > gpurun_out/ev/bench_default.json 2> gpurun_out/ev/bench_default.err
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/ev/bench_driver_k20.json 2>/dev/null
-python bench.py --no-cpu-baseline --exciter-opts 8 --legs 0 --pmc off > gpurun_out/ev/bench_hybrid_w_optin.json 2>/dev/null
-python bench.py --no-cpu-baseline --inputs realistic --legs 0 --pmc off > gpurun_out/ev/bench_realistic_inputs.json 2>/dev/null
-python bench.py --no-cpu-baseline --exact --steps 50 --legs 0 --pmc off > gpurun_out/ev/bench_exact_shapers.json 2>/dev/null
-NWS_BENCH_FORCE_DIST=1 python bench.py --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --gather rccl > gpurun_out/ev/bench_world1_rccl.json 2>/dev/null
-NWS_BENCH_FORCE_DIST=1 python bench.py --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --gather copy > gpurun_out/ev/bench_world1_copy.json 2>/dev/null
+python bench.py --full > "$EV/bench_default.json" 2> "$EV/bench_default.err"
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$EV/bench_driver_k20.json" 2>/dev/null
+python bench.py --full --no-cpu-baseline --exciter-opts 8 --legs 0 --pmc off > "$EV/bench_hybrid_w_optin.json" 2>/dev/null
+python bench.py --full --no-cpu-baseline --inputs realistic --legs 0 --pmc off > "$EV/bench_realistic_inputs.json" 2>/dev/null
+python bench.py --full --no-cpu-baseline --exact --steps 50 --legs 0 --pmc off > "$EV/bench_exact_shapers.json" 2>/dev/null
+NWS_BENCH_FORCE_DIST=1 python bench.py --full --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --gather rccl > "$EV/bench_world1_rccl.json" 2>/dev/null
+NWS_BENCH_FORCE_DIST=1 python bench.py --full --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --gather copy > "$EV/bench_world1_copy.json" 2>/dev/null
 # round 5: the N > 1 issue pattern at world size 1, same-box A/B (single / rccl / copy / sub-batches / the round-4 queued form)
 bash tools/world1_check.sh > gpurun_out/ev/world1_ab.txt 2>&1
 bash tools/scale_check.sh --dry-run --out gpurun_out/ev/scale_dry > gpurun_out/ev/scale_check_dry_run.txt 2>&1

@@ -5,7 +5,7 @@
 # forms with nothing to send.  -> gpurun_out/fake_peers_ab.txt (committed as profiles/r06/fake_peers_ab.txt)
 export TMPDIR=/tmp
 mkdir -p gpurun_out/fp
-Q="--no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --steps ${K:-200}"
+Q="--full --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --steps ${K:-200}"
 run() {   # name, env..., -- args
     name=$1; shift
     envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift

@@ -4,7 +4,7 @@
 set -x
 export TMPDIR=/tmp
 mkdir -p gpurun_out/fc
-Q="--no-cpu-baseline --pmc off --legs 0 --batch1-iters 0"
+Q="--full --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0"
 timeout 420 python -m pytest tests -m gpu -x -q -p no:cacheprovider > gpurun_out/fc/pytest_gpu.txt 2>&1; tail -3 gpurun_out/fc/pytest_gpu.txt
 NWS_EXCITER_XCD=0 NWS_MLP_XCD=0 timeout 120 python bench.py $Q > gpurun_out/fc/ab_old_1.json 2>/dev/null
 timeout 120 python bench.py $Q > gpurun_out/fc/ab_new_1.json 2>/dev/null

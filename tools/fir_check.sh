@@ -2,7 +2,7 @@
 export TMPDIR=/tmp
 mkdir -p gpurun_out/fir
 [ -n "$SKIP_TESTS" ] || { timeout 600 python -m pytest tests -m gpu -x -q -p no:cacheprovider -k "noise or e2e or streamed or stream" > gpurun_out/fir/pytest.txt 2>&1; tail -1 gpurun_out/fir/pytest.txt; }
-Q="--no-cpu-baseline --pmc off --legs 0 --batch1-iters 0"
+Q="--full --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0"
 timeout 120 python bench.py $Q --steps 200 > gpurun_out/fir/pipe.json 2>/dev/null
 python -c "
 import json; d=json.loads(open('gpurun_out/fir/pipe.json').read().strip().splitlines()[-1]); print('ms/step', d['ms_per_step'], d['stage_ms'])"

@@ -21,7 +21,7 @@ for h in ("1", "2"):
 a, b = torch.load("gpurun_out/hpb/y1.pt"), torch.load("gpurun_out/hpb/y2.pt")
 print("one-hop workgroups bit-equal to two-hop:", bool(torch.equal(a, b)), float((a - b).abs().max()))
 PY
-Q="--no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --steps 200"
+Q="--full --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --steps 200"
 for i in 1 2; do
   for h in 2 1; do
     NWS_EXCITER_HPB=$h timeout 120 python bench.py $Q > gpurun_out/hpb/pipe_$h.json 2>/dev/null

@@ -4,7 +4,7 @@ set -x
 export TMPDIR=/tmp
 mkdir -p gpurun_out/lr
 NWS_EXCITER_LOWREG=1 timeout 300 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -p no:cacheprovider -k "e2e or full_size or batch64 or hipgraph" > gpurun_out/lr/pytest_lowreg.txt 2>&1; tail -2 gpurun_out/lr/pytest_lowreg.txt
-Q="--no-cpu-baseline --pmc off --legs 0 --batch1-iters 0"
+Q="--full --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0"
 for i in 1 2; do
   for lr in 0 1; do
     NWS_EXCITER_LOWREG=$lr timeout 120 python bench.py $Q --pipeline 0 --streams 1 --steps 100 > gpurun_out/lr/one_$lr.json 2>/dev/null

@@ -5,7 +5,7 @@
 # 1 with three tiny launches per step on it, NWS_BENCH_DIAG=blit3).  profiles/r05/queue_placement.txt is a run of this script.
 export TMPDIR=/tmp
 rm -rf gpurun_out/qo; mkdir -p gpurun_out/qo
-Q="--no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --steps 150 --warmup 10"
+Q="--full --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --steps 150 --warmup 10"
 ORDERS=${ORDERS:-"a0,a1,c0,c1 a0,a1,c0,d,c1 a0,a1,c0,d,d,c1 a0,a1,c0,d,d,d,c1 a0,a1,c0,d,d,d,d,c1 a0,a1,c0,h,c1 a0,a1,c0,h,h,c1 a0,d,a1,c0,c1 c0,c1,d,a0,a1 x,a0,a1,c0,c1"}
 i=0
 for o in $ORDERS; do

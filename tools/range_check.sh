@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 mkdir -p gpurun_out/rg
 timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -p no:cacheprovider -k "range_proven" > gpurun_out/rg/pytest.txt 2>&1; tail -1 gpurun_out/rg/pytest.txt
-Q="--no-cpu-baseline --pmc off --legs 0 --batch1-iters 0"
+Q="--full --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0"
 for i in 1 2; do
   for nr in 1 ""; do
     NWS_EXCITER_NO_RANGE=$nr timeout 120 python bench.py $Q --steps 200 > gpurun_out/rg/pipe_$nr.json 2>/dev/null

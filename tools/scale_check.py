@@ -28,7 +28,7 @@ def run_cell(n, gather, chunks, steps, out_dir, dry, extra, forced=False, tag=""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **(env_extra or {}))
     if forced:      # the N > 1 issue pattern at world size 1 (real RCCL, nothing to send): what the exchange machinery costs by itself
         env["NWS_BENCH_FORCE_DIST"] = "1"
-    args = ["--gpus", str(n), "--steps", str(steps), "--warmup", "10", "--no-cpu-baseline", "--pmc", "off", "--legs", "0",
+    args = ["--full", "--gpus", str(n), "--steps", str(steps), "--warmup", "10", "--no-cpu-baseline", "--pmc", "off", "--legs", "0",
             "--batch1-iters", "0", "--gather", gather, "--gather-chunks", str(chunks), *extra]
     if dry and n > 1:
         env["NWS_BENCH_SHARE_GPU"] = "1"

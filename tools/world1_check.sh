@@ -3,7 +3,7 @@
 # Everything lands under gpurun_out/w1/.
 export TMPDIR=/tmp
 mkdir -p gpurun_out/w1
-Q="--no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --steps ${K:-200}"
+Q="--full --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --steps ${K:-200}"
 run() {   # name, env..., -- args
     name=$1; shift
     envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift

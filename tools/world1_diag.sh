@@ -6,7 +6,7 @@
 # wprof adds the helper thread's per-exchange times (wait / issue / record) to the line.
 export TMPDIR=/tmp
 rm -rf gpurun_out/w1d; mkdir -p gpurun_out/w1d
-Q="--no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --steps 200"
+Q="--full --no-cpu-baseline --pmc off --legs 0 --batch1-iters 0 --steps 200"
 timeout 120 python bench.py $Q > gpurun_out/w1d/00_single.json 2>/dev/null
 i=0
 for g in rccl copy; do
