@@ -1,9 +1,7 @@
 /*
- * Diagnostic entry points of libnws_hip.so - NOT part of the product ABI (include/nws_hip.h): timing ablations of the hot kernels
- * and candidate sine implementations.  (The probes that demonstrate the MI355X co-execution hazard live in a library of their
- * own, include/nws_probe.h -> libnws_probe.so: their kernels contain the instruction form the build refuses in this one.)
- * Used by tools/ and by the tests that keep them alive; outputs of ablation variants are meaningless by construction.
- * A binding of the product path never needs this file.
+ * Diagnostic entry points of libnws_hip.so - NOT part of the product ABI (include/nws_hip.h).  (The probes that demonstrate the
+ * MI355X co-execution hazard live in a library of their own, include/nws_probe.h -> libnws_probe.so: their kernels contain the
+ * instruction form the build refuses in this one.)  Used by tools/ and tests; a binding of the product path never needs this file.
  */
 #ifndef NWS_HIP_DEBUG_H
 #define NWS_HIP_DEBUG_H
@@ -12,40 +10,9 @@
 extern "C" {
 #endif
 
-/* Measurements / tests: which frame-MLP kernel nws_frame_mlps launches - 0 automatic (wave-resident frames from 8192 frames up,
- * tile kernels below; env NWS_MLP_KERNEL=tiles|frames), 1 the tile kernels, 2 wave-resident frames at any size.  mode 2 + (A << 8):
- * timing ablation A of the wave-resident kernel (1 no LayerNorm, 2 no MFMAs, 3 no weight reads, 5 no split, 6 cycle timeline,
- * 7 / 8 only the newt.mlp / only the h_generator workgroups); outputs of ablations are meaningless or partial. */
+/* Tests / measurements: which frame-MLP kernel nws_frame_mlps launches - 0 automatic (wave-resident frames from 8192 frames up,
+ * tile kernels below), 1 the tile kernels, 2 wave-resident frames at any size.  Any other mode: NWS_ERR_BAD_ARG. */
 int nws_debug_frame_mlps_kernel(int mode);
-int nws_debug_frame_mlps_probe(void* buf /* device, 4096 B: cycle timeline written by mode 2 + (6 << 8) */);
-
-/* Diagnostics only: ablation variants of the fused kernel for timing.  0-4: the round-1 form (0 as is, 1 no sin, 2 no LUT gather, 3 no
- * shaper tail, 4 no MFMA); 5 / 6 prologue only (product configuration / fragment records by LDS-DMA); 10 + OPT bits: compile-time options
- * of the two-hop kernel - 44 the product kernel, 108 the same with the FiLM rows as fragment records by LDS-DMA; 21-24: the PRODUCT
- * configuration without its sines / table gathers / tail / mixer MFMAs; 26-29: the product configuration without the global loads in front
- * of its barrier (26 none of them; 27 / 28 / 29 no FiLM rows / no fragment DMA / no F0, carry, phase shifts) - tools/exciter_ablate.sh,
- * profiles/r06/exciter_ablations.txt.  Outputs of variants 1-6 and 21-29 are meaningless. */
-int nws_debug_exciter_newt(int variant, const NwsWeights* w, const float* f0, const double* carry, const float* phase_u,
-                           const float* rand_phase, const float* film, int B, int T, float sample_rate,
-                           float* newt_out, void* stream);
-
-/* Diagnostics only (tools/film_dma_ab.py; round 6, measured as nothing: profiles/r06/film_dma_ab.txt): per-frame FiLM fragment records
- * for variants 6 (prologue only) and 108 (whole kernel) of nws_debug_exciter_newt, which take them in place of `film` and bring them
- * to LDS by LDS-DMA instead of splitting the fp32 rows in the kernel.  film (B, T, 256) frame-major rows [g_idx | b_idx | g_norm |
- * b_norm] -> frags_out = B T records of NWS_FILM_REC_BYTES (3 parameter types x 64 shapers x {bf16 t0, t1, t2, 0}: the value in
- * table units / times newt.mixer.weight as three bf16 terms, exact for any fp32) followed by B T aux entries of 16 bytes
- * {sum_s newt.mixer.weight[s] b_norm[s], 0, 64-bit range-proof mask}. */
-int nws_debug_film_frags(const NwsWeights* w, const float* film, int B, int T, void* frags_out /* device, B T (NWS_FILM_REC_BYTES + 16) bytes */,
-                         void* stream);
-
-/* Diagnostics only: timing ablations of control_gru_kernel (0 product; 1 half the LDS reads of h, 2 half the FMAs, 3 no
- * transcendentals in the gates, 4 no per-step barrier, 5 no LDS reads of h).  Outputs of variants != 0 are meaningless. */
-int nws_debug_control_gru(int variant, const NwsWeights* w, const float* control, int B, int C, int T, float* gru_out,
-                          void* stream);
-
-/* Diagnostics only: candidate sine implementations (0 = nws_sinf as shipped, 1 = v_sin_f32 after an exact-product
- * reduction to turns, 2 = single odd polynomial after the same reduction); y[i] = sum of `reps` sines (reps = 1: sin(x[i])). */
-int nws_debug_sin(int mode, const float* x, float* y, int64_t n, int reps, void* stream);
 
 /* Diagnostics only (tools/cu_pressure.py): a resident load of `groups` 256-thread workgroups that keep their CUs' vector pipes
  * busy for `spin_us` microseconds of the wall clock - what a collective's ring kernels take from the oscillator kernel. */

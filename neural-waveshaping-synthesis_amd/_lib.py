@@ -110,7 +110,6 @@ _PROTOTYPES = {
     "nws_frame_mlps": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
     "nws_mlp_frags": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, _fp]),
     "nws_debug_frame_mlps_kernel": (C.c_int, [C.c_int]),
-    "nws_debug_frame_mlps_probe": (C.c_int, [_fp]),
     "nws_fir_design_matrix": (C.c_int, [_fp, _fp, _fp]),
     "nws_fir_noise": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "nws_fir_noise_window": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp]),
@@ -127,7 +126,6 @@ _PROTOTYPES = {
     "nws_shaper_table": (C.c_int, [C.POINTER(NwsWeights), C.c_int, C.c_float, C.c_float, _fp, _fp]),
     "nws_mixer_frags": (C.c_int, [_fp, _fp, _fp, _fp]),
     "nws_exciter_bound": (C.c_int, [_fp, _fp, _fp, _fp]),
-    "nws_debug_film_frags": (C.c_int, [C.POINTER(NwsWeights), _fp, C.c_int, C.c_int, _fp, _fp]),
     "nws_shaper_turns": (C.c_int, [_fp, _fp, _fp]),
     "nws_lut_pairs": (C.c_int, [_fp, C.c_int, _fp, _fp]),
     "nws_shaper_apply": (C.c_int, [C.POINTER(NwsWeights), _fp, C.c_int64, C.c_int64, _fp, _fp]),
@@ -151,10 +149,6 @@ _PROTOTYPES = {
     "nws_loudness_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "nws_loudness": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_float, C.c_float, C.c_int, _fp, _fp,
                                C.c_size_t, _fp]),
-    "nws_debug_exciter_newt": (C.c_int, [C.c_int, C.POINTER(NwsWeights), _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_float,
-                                         _fp, _fp]),
-    "nws_debug_control_gru": (C.c_int, [C.c_int, C.POINTER(NwsWeights), _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
-    "nws_debug_sin": (C.c_int, [C.c_int, _fp, _fp, C.c_int64, C.c_int, _fp]),
     "nws_oscillator": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_float, _fp, _fp]),
     "nws_newt_apply": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "nws_td_mlp": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),

@@ -152,12 +152,12 @@ def check_valu_mfma_hazard(obj, wait_states=2):
 # 4 / 6 / 8 waves = 128 / 80 / 64 registers; the third workgroup was worth 3-6 %).  (substring of the mangled kernel name,
 # largest VGPR + AGPR count, what it buys); a kernel that outgrows its line fails the build instead of silently losing occupancy.
 REGISTER_BUDGETS = (
-    ("exciter_newt_kernelILi4ELi0ELi2ELi34E", 80, "default oscillator kernel: three 8-wave workgroups per CU"),
-    ("exciter_newt_kernelILi4ELi0ELi2ELi38E", 80, "one-term variant: three 8-wave workgroups per CU"),
-    ("exciter_newt_kernelILi4ELi0ELi2ELi42E", 80, "hybrid variant: three 8-wave workgroups per CU"),
-    ("exciter_newt_kernelILi4ELi0ELi2ELi58E", 80, "hybrid-W variant: three 8-wave workgroups per CU"),
-    ("exciter_newt_kernelILi5ELi0ELi1ELi0E", 128, "exact-shaper bank kernel: four 4-wave workgroups per CU (38.8 KB of LDS each)"),
-    ("exciter_newt_kernelILi6ELi0ELi1ELi0E", 128, "exact-shaper bank kernel (no v_fract): four 4-wave workgroups per CU"),
+    ("exciter_newt_kernelILi4ELi2ELi2E", 80, "default oscillator kernel: three 8-wave workgroups per CU"),
+    ("exciter_newt_kernelILi4ELi2ELi6E", 80, "one-term variant: three 8-wave workgroups per CU"),
+    ("exciter_newt_kernelILi4ELi2ELi10E", 80, "hybrid variant: three 8-wave workgroups per CU"),
+    ("exciter_newt_kernelILi4ELi2ELi26E", 80, "hybrid-W variant: three 8-wave workgroups per CU"),
+    ("exciter_newt_kernelILi5ELi1ELi0E", 128, "exact-shaper bank kernel: four 4-wave workgroups per CU (38.8 KB of LDS each)"),
+    ("exciter_newt_kernelILi6ELi1ELi0E", 128, "exact-shaper bank kernel (no v_fract): four 4-wave workgroups per CU"),
     ("g_exciter_newt_mfma_kernel", 128, "runtime-size oscillator kernel: four 4-wave workgroups per CU"),
 )
 

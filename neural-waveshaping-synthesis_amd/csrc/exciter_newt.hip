@@ -15,7 +15,6 @@
 // indistinguishable from the exact-fp32 MFMA it replaced, at 1/5 of its matrix-pipe time, and unlike
 // the fp32 MFMA it overlaps with the VALU work.  The 64x32 accumulator tile then goes straight through
 // FiLM -> LUT (or sin-MLP) -> FiLM -> 64->1 mix in registers; one coalesced 128 B store per wave.
-#include <cstdlib>
 #include <type_traits>
 
 #include "nws_common.h"
@@ -28,10 +27,7 @@ constexpr int kKPad = 16 * kKSteps;         // 112
 constexpr int kS = NWS_N_SHAPERS;           // 64
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-#ifndef NWS_LUT_GROUP
-#define NWS_LUT_GROUP 4
-#endif
-constexpr int kLutGroup = NWS_LUT_GROUP;   // table gathers in flight together in the fused tail (one memory round trip per group)
+constexpr int kLutGroup = 4;               // table gathers in flight together in the fused tail (one memory round trip per group)
 constexpr int kTile = 128;                  // samples per workgroup (= control hop)
 constexpr float kTau = 6.283185307179586f;  // fl32(math.tau)
 constexpr float kPi = 3.141592653589793f;   // fl32(math.pi)
@@ -39,22 +35,13 @@ constexpr float kPi = 3.141592653589793f;   // fl32(math.pi)
 // OPT bits of exciter_newt_kernel (compile-time variants of the FastNEWT hot path)
 enum Opt {
   // (bit 1 was kOptScalarSines, the main loop in scalar fp32: measured slower in round 2, selected by no path since; retired in round 5)
-  kOptFilmMfma = 2,     // FiLM interpolation (3 parameter types x 64 shapers x 32 samples per wave) as six bf16 MFMAs
+  kOptFilmMfma = 2,     // FiLM interpolation (3 parameter types x 64 shapers x 32 samples per wave) as six bf16 MFMAs; the tail
+                        // keeps at most two FiLM tiles live (80 VGPRs: three 8-wave workgroups per CU)
   kOptOneTerm = 4,      // sines as ONE fp16 term in EVERY K-step (drops W_hi * v_lo: 2 MFMAs per product; 11-bit activations)
   kOptHybrid = 8,       // two-term sines in K-step 0 (mixer bias + harmonics 1..15), one term in K-steps 1..6
   kOptHybridW = 16,     // with kOptHybrid: the mixer WEIGHTS of harmonics 16..101 as one fp16 term too (1 MFMA per product)
-  kOptLowReg = 32,      // with kOptFilmMfma: the tail keeps at most two FiLM tiles live (80 VGPRs: three 8-wave workgroups per CU)
-  // with kOptFilmMfma | kOptLowReg, two hops per workgroup: the FiLM rows arrive as per-FRAME bf16x3 fragment records
-  // (NWS_FILM_REC_BYTES per frame, film_frag_record below) and go to LDS by the LDS-DMA path - no staging arithmetic in this
-  // kernel.  Round 6, VERDICT r5 #3: built, 3.6e-9 RMS from the product kernel, and MEASURED AS NOTHING - prologue-only launch
-  // 36.8 -> 34.7 us, whole kernel 266.8 -> 263.6 us (profiles/r06/film_dma_ab.txt; another box: 35.8 -> 34.4, 257.4 -> 255.0): per workgroup the prologue-only launch is one
-  // memory round trip and one barrier (16 000 workgroups / 768 slots = 21 rounds x 1.6 us), not the staging arithmetic (~100 of a
-  // wave's ~800 vector instructions on three of eight waves), and in the real kernel the CU's other two workgroups work meanwhile.
-  // Not on the product path (the records would cost the frame-MLP kernel 17 MB more stores per step); kept behind
-  // nws_debug_exciter_newt variants 6 / 108.
-  kOptFilmDma = 64
 };
-static_assert((kOptFilmMfma ^ kOptOneTerm ^ kOptHybrid ^ kOptHybridW ^ kOptLowReg ^ kOptFilmDma) == 126, "Opt bits must be distinct");
+static_assert((kOptFilmMfma ^ kOptOneTerm ^ kOptHybrid ^ kOptHybridW) == 30, "Opt bits must be distinct");
 enum Mode { kModeLut = 0, kModeExact = 1, kModeExciterOnly = 2, kModeLutPairs = 3, kModeLutPairsDiv6 = 4, kModeExactBank = 5,
             kModeExactBankNF = 6 };   // NF: no v_fract in front of the sines of the hidden and output layers (NWS_EXCITER_BANK_NOFRACT)
 __host__ __device__ constexpr bool is_bank(int mode) { return mode == kModeExactBank || mode == kModeExactBankNF; }
@@ -389,22 +376,6 @@ __device__ __forceinline__ LutParams make_lut_params(const NwsWeights& w) {
   return P;
 }
 
-// Per-frame FiLM fragment record (kOptFilmDma): for type ty in {0 index gain, 1 index bias, 2 output gain} and shaper s, 8 bytes
-// at (ty * 64 + s) * 8 = the value as THREE bf16 terms by truncation {t0, t1, t2, 0} (8 + 8 + 8 bits: exact for any fp32),
-//   ty 0: (size / 6) g_idx        ty 1: (size / 6) (b_idx - lut_min)        ty 2: newt.mixer.weight[s] g_norm
-// (the table-unit scaling and the folded 64 -> 1 mixer weight of the staging code above).  As the A operand of
-// v_mfma_f32_32x32x16_bf16, lane (shaper i, half h) holds the record of frame f + h in K slots 8 h + 0..3 (slots 8 h + 4..7 zero);
-// against B = {1 - w, 1 - w, 1 - w, 0, ...} in half 0 and {w, w, w, 0, ...} in half 1 (w = interpolation weight, a multiple of
-// 1 / 256 below 1: w and 1 - w are exact in bf16) the instruction returns (1 - w) p[f] + w p[f + 1]: F.upsample's own formula
-// (neural_waveshaping.py:75 semantics, shaping.py:69) for 32 shapers x 32 samples, from records that know nothing of their
-// neighbours - which is what would let the frame-MLP kernel write them.  Beside the records, 16 bytes per frame (film_frag_aux):
-// { sum_s newt.mixer.weight[s] b_norm[s] (float), 0, range-proof mask (64 bits: shaper s cannot leave the table at this frame) }.
-struct FilmAux {
-  float bsum, pad;
-  unsigned long long mask;
-};
-static_assert(sizeof(FilmAux) == 16, "FilmAux");
-
 // Mixer weights as two fp16 terms, W = W_hi + W_lo (22+ significant bits), in MFMA A-fragment order:
 // fragment (ks, m, h, i) = 8 halfs = W[32m + i][16ks + 8h .. +7]; lane (i, h) reads it with one ds_read_b128.
 struct ExcLds {
@@ -424,11 +395,8 @@ struct ExcLds {
     // fp32, fp32 exponent range), against the B operand {1, 1, 1, w, w, w, 0, 0} (w = interpolation weight, a multiple of
     // 1/256: exact in bf16) one v_mfma_f32_32x32x16_bf16 returns a + w d for 32 shapers x 32 samples.
     uint4 ffrag[3][3][2][32];
-    // kOptFilmDma: the fragment records of the workgroup's four frames (jb-1 .. jb+2, clamped), as they lie in memory
-    unsigned char frec[4][NWS_FILM_REC_BYTES];
   };
   float bsum[4];
-  unsigned long long fmask[4];   // kOptFilmDma: per-FRAME range-proof masks (a frame pair is proven where both frames are)
   // bit s of okmask[slot]: the table index of shaper s provably stays inside the table for every sample that interpolates
   // between the slot's two frames (staging, from NwsWeights.exciter_bound); 0 = unknown -> the clamped lookup
   unsigned long long okmask[3];
@@ -495,43 +463,6 @@ __device__ __forceinline__ float wave_sum_to_lane63(float v) {
   return v;
 }
 
-__device__ __forceinline__ uint2 bf16x3(float v) {
-  auto top16 = [](float x) { return __builtin_bit_cast(unsigned, x) & 0xffff0000u; };
-  const unsigned t0 = top16(v);
-  const float r = v - __builtin_bit_cast(float, t0);
-  const unsigned t1 = top16(r);
-  const unsigned t2 = top16(r - __builtin_bit_cast(float, t1));
-  return uint2{(t0 >> 16) | t1, t2 >> 16};
-}
-
-// the record and aux entry of one frame from its fp32 FiLM row [g_idx | b_idx | g_norm | b_norm] (lane = shaper)
-__device__ __forceinline__ void film_frag_record(const NwsWeights& w, const float* __restrict__ row, int lane, unsigned char* __restrict__ rec,
-                                                 FilmAux* __restrict__ aux) {
-  const float c = (float)w.lut_size * (1.0f / 6.0f);
-  const float ow = w.newt_out_w[lane];
-  const float ga = row[lane] * c, ba = (row[kS + lane] - w.lut_min) * c, gn = ow * row[2 * kS + lane];
-  uint2* out = reinterpret_cast<uint2*>(rec);
-  out[lane] = bf16x3(ga);
-  out[kS + lane] = bf16x3(ba);
-  out[2 * kS + lane] = bf16x3(gn);
-  const float bs = wave_sum_to_lane63(ow * row[3 * kS + lane]);
-  // range proof at this frame (shaping.py:136-151 clamps `lower` into the table; inside it the clamp is the identity): idx = G x + B
-  // with |x| <= X[s]; one table cell of margin plus 2^-9 |G| X for every rounding between here and the lookup.  Between two
-  // frames idx is the convex combination of the frames' values for the same x, and so is the margin: a pair is proven where both
-  // frames are.  NaN-safe by construction: every comparison with a NaN operand is false (no fmin / fmax in the chain).
-  const float X = w.exciter_bound != nullptr ? w.exciter_bound[lane] : __builtin_inff();
-  const float r = fabsf(ga) * X;
-  const float e = 1.0f + r * (1.0f / 512.0f);
-  const unsigned long long m = __ballot((ba - r) >= e && (ba + r) <= (float)(w.lut_size - 1) - e);
-  if (lane == 63) *aux = FilmAux{bs, 0.0f, m};
-}
-
-__global__ __launch_bounds__(64) void film_frags_kernel(NwsWeights w, const float* __restrict__ film, unsigned char* __restrict__ recs,
-                                                        FilmAux* __restrict__ aux) {
-  const size_t f = blockIdx.x;
-  film_frag_record(w, film + f * NWS_FILM_CH, threadIdx.x, recs + f * NWS_FILM_REC_BYTES, aux + f);
-}
-
 // (Round 4, measured and dropped: mask-and-subtract instead - hi = bits & 0xFFFFE000, lo = v - hi, two v_cvt_pk - is two
 // instructions more per pair in cheaper classes and times the same (0.2605 against 0.2598 ms); LABBOOK.md.  Pitfall met on the
 // way: hipcc 7.2 reads element 0 for __builtin_bit_cast(unsigned, v.y) of an ext_vector - tools/ubench/split_probe.hip.)
@@ -549,7 +480,7 @@ __device__ __forceinline__ f16x2 split_lo2(f16x2 hi, f32x2 v) {
 // hot-loop form: n = rint(x C_hi), then t = fma(x, C_hi, -n) - the EXACT product minus an integer, rounded once: |t| <= 1/2,
 // so the rounding costs <= 3e-8 turns - and t += x C_lo.  Three packed instructions and two v_rndne_f32 per pair; the
 // v_fract form before it (p, its exact rounding error e, fract(p) + (x C_lo + e)) needed four and two v_fract_f32, and
-// its reduced argument in [0,1) was one bit coarser (~1.9e-7 against ~0.9e-7 absolute on the sine, tools/measure_sin.py).
+// its reduced argument in [0,1) was one bit coarser (~1.9e-7 against ~0.9e-7 absolute on the sine).
 // Same box, B=64, all harmonics live: 0.2232 against 0.2279 ms (hybrid-W), 0.2872 against 0.2939 ms (two-term).
 __device__ __forceinline__ f32x2 sin_turns2_fract(f32x2 x) {
   const f32x2 c_hi = splat2(0.15915493667125702f), c_lo = splat2(6.4206382432985265e-09f);
@@ -575,10 +506,6 @@ __device__ __forceinline__ void split_f16(float v, _Float16& hi, _Float16& lo) {
   lo = (_Float16)(v - (float)hi);
 }
 
-// DBG != 0 instantiations exist only for nws_debug_exciter_newt (ablation timing; results are wrong by design):
-//   1: sin() replaced by its argument (scaled into the range proof's domain)   2: LUT gather skipped   3: whole FiLM/shaper tail skipped
-//   4: MFMAs skipped   5: prologue only   6: no global load in front of the barrier (7 / 8 / 9: no FiLM rows / no fragment DMA / no F0, carry,
-//   shifts): what the prologue's memory LATENCY costs the launch
 // second launch-bound = minimum waves per SIMD: without it hipcc hoists all 32 LUT gathers of the tail, takes 256
 // VGPRs and drops the kernel to 1 wave/SIMD (measured 2x slower); 4 waves/SIMD = 128 VGPRs, LDS allows 5 blocks/CU
 // HPB = hops (128-sample tiles) per workgroup = 4 HPB waves.  Two hops share one copy of the 28 KB fragment table and one
@@ -586,8 +513,8 @@ __device__ __forceinline__ void split_f16(float v, _Float16& hi, _Float16& lo) {
 // The bound of 7 waves/SIMD (72 VGPRs) is deliberate: at 8 (64 VGPRs) hipcc spills 24 B/lane to scratch, which is slower
 // (0.328 ms).  (Wrong results seen with that build under two overlapping audio streams were first blamed on the scratch;
 // the multi-stream problem turned out to be independent of it, see pipeline.py.  The build still rejects scratch.)
-template <int MODE, int DBG = 0, int HPB = 1, int OPT = 0>
-__global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) ? 4 : ((OPT & kOptLowReg) ? 6 : (OPT & kOptFilmMfma) ? 5 : (HPB == 2 ? 7 : 5)))) void exciter_newt_kernel(NwsWeights w, const float* __restrict__ f0,
+template <int MODE, int HPB = 1, int OPT = 0>
+__global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) ? 4 : ((OPT & kOptFilmMfma) ? 6 : (HPB == 2 ? 7 : 5)))) void exciter_newt_kernel(NwsWeights w, const float* __restrict__ f0,
                                                            const float* __restrict__ f0_up,
                                                            const double* __restrict__ carry,
                                                            const float* __restrict__ phase_u,
@@ -597,7 +524,7 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
                                                            float* __restrict__ newt_out,
                                                            const float* __restrict__ bank = nullptr,
                                                            const float* __restrict__ add_in = nullptr,
-                                                           const int xcd_groups = 0, const int xcd_aux = 0 /* kOptFilmDma: B T */) {
+                                                           const int xcd_groups = 0) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   ExcLds& L = *reinterpret_cast<ExcLds*>(smem_raw);
   ShaperLds& SH = *reinterpret_cast<ShaperLds*>(smem_raw + ((sizeof(ExcLds) + 15) & ~size_t(15)));
@@ -636,10 +563,6 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
   const int n = (hop_live ? j : jb) * kTile + w4 * 32 + col;
   const NwsLerp lc = nws_lerp_coeff(n, T);
   float f0_a, f0_b = 0.0f;
-  if (DBG == 6 || DBG == 9) {
-    f0_a = 0.3f + 1.0e-4f * (float)col;
-    f0_b = 0.31f;
-  } else
   if (f0_up != nullptr) {
     f0_a = f0_up[(size_t)b * N + n];
   } else {
@@ -647,12 +570,9 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
     f0_a = x[lc.i0];
     f0_b = x[lc.i1];
   }
-  const double carry_in = (DBG == 6 || DBG == 9) ? 0.4 * (double)n : carry[(size_t)b * (N / 32) + (n >> 5)];
+  const double carry_in = carry[(size_t)b * (N / 32) + (n >> 5)];
 
   // ---- stage the workgroup constants in LDS ----
-  if (DBG == 6 || DBG == 8) {
-    for (int e = tid; e < (int)(sizeof(L.whi) + sizeof(L.wlo)) / 16; e += kThreads) reinterpret_cast<uint4*>(L.whi)[e] = uint4{0x2e662e66u, 0x2e662e66u, 0x2e662e66u, 0x2e662e66u};
-  } else
   if (w.mixer_frags != nullptr) {
     // pre-split fragment table (nws_mixer_frags): 28 KB = 28 pieces of 1 KB, copied by the LDS-DMA path
     // (global_load_lds_dwordx4: per-lane global address, wave-uniform LDS base + 16 B per lane; no VGPR round trip).
@@ -693,32 +613,6 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
   // FiLM slots (one shaper per lane), bias sums, phase shifts and harmonic numbers, spread over the waves:
   //   4 waves: 0/1 slots 0/1, 2 bsum[0..1], 3 bsum[2] + shifts;   8 waves: 0..2 slots, 3..6 bsum[0..3], 7 shifts
   constexpr int kSlots = HPB + 1;
-  constexpr bool kFilmDma = (OPT & kOptFilmDma) != 0;
-  static_assert(!kFilmDma || (HPB == 2 && (OPT & kOptFilmMfma) && (OPT & kOptLowReg) && MODE == kModeLutPairsDiv6),
-                "kOptFilmDma: the default two-hop LUT kernel only");
-  if (kFilmDma) {
-    // the four frames' fragment records (`bank` carries their base here: records of all B T frames, then the aux entries): 6 KB =
-    // six 1 KB pieces, one per wave 0..5, straight to LDS.  A piece straddles records, and clamped frames at the utterance's
-    // ends break the contiguity: every lane finds its own 16 source bytes
-    typedef __attribute__((address_space(1))) const void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
-    const unsigned char* recs = reinterpret_cast<const unsigned char*>(bank) + (size_t)b * T * NWS_FILM_REC_BYTES;
-    auto frame_of = [&](int q) {
-      const int f = jb - 1 + q;
-      return f < 0 ? 0 : (f > T - 1 ? T - 1 : f);
-    };
-    if (wave < 6) {
-      const int o = wave * 1024 + lane * 16;
-      const int q = (o >= NWS_FILM_REC_BYTES) + (o >= 2 * NWS_FILM_REC_BYTES) + (o >= 3 * NWS_FILM_REC_BYTES);
-      const unsigned char* src = recs + (size_t)frame_of(q) * NWS_FILM_REC_BYTES + (o - q * NWS_FILM_REC_BYTES);
-      __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(&L.frec[0][0] + wave * 1024), 16, 0, 0);
-    } else if (wave == 6 && lane < 4) {
-      const FilmAux* aux = reinterpret_cast<const FilmAux*>(reinterpret_cast<const unsigned char*>(bank) + (size_t)xcd_aux * NWS_FILM_REC_BYTES);
-      const FilmAux a = aux[(size_t)b * T + frame_of(lane)];
-      L.bsum[lane] = a.bsum;
-      L.fmask[lane] = a.mask;
-    }
-  } else
   if (MODE != kModeExciterOnly) {
     const float* fb = film + (size_t)b * T * NWS_FILM_CH;
     auto frame_of = [&](int q) {
@@ -726,13 +620,13 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
       return f < 0 ? 0 : (f > T - 1 ? T - 1 : f);
     };
     auto bias_sum = [&](int q) {  // sum_s out_w[s] * b_norm[frame q][s]
-      const float v = wave_sum_to_lane63((DBG == 6 || DBG == 7) ? 1.0e-3f * (float)lane : w.newt_out_w[lane] * fb[(size_t)frame_of(q) * NWS_FILM_CH + 3 * kS + lane]);
+      const float v = wave_sum_to_lane63(w.newt_out_w[lane] * fb[(size_t)frame_of(q) * NWS_FILM_CH + 3 * kS + lane]);
       if (lane == 63) L.bsum[q] = v;
     };
     if (wave < kSlots) {
       const float* r0 = fb + (size_t)frame_of(wave) * NWS_FILM_CH + lane;
       const float* r1 = fb + (size_t)frame_of(wave + 1) * NWS_FILM_CH + lane;
-      const float ow = (DBG == 6 || DBG == 7) ? 0.02f : w.newt_out_w[lane];
+      const float ow = w.newt_out_w[lane];
       if (OPT & kOptFilmMfma) {
         // index FiLM pre-scaled to table units: idx = (size/6) (g x + b - min) = g' x + b'  (a few ulp of idx away from the
         // reference's rounding chain, like the folded origin of the kModeLutPairsDiv6 path; held to the same e2e parity bar)
@@ -740,7 +634,7 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
         float ga = 0.0f, gd = 0.0f, ba = 0.0f, bd = 0.0f;
 #pragma unroll
         for (int ty = 0; ty < 3; ++ty) {
-          const float u0 = (DBG == 6 || DBG == 7) ? 0.3f + 0.001f * (float)(lane + ty) : r0[ty * kS], u1 = (DBG == 6 || DBG == 7) ? 0.31f + 0.001f * (float)(lane + ty) : r1[ty * kS];
+          const float u0 = r0[ty * kS], u1 = r1[ty * kS];
           float a, d;
           if (ty == 0) {
             a = u0 * c;
@@ -768,7 +662,7 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
           const unsigned d2 = top16(rd - __builtin_bit_cast(float, d1));
           L.ffrag[wave][ty][lane >> 5][lane & 31] = uint4{(a0 >> 16) | a1, (a2 >> 16) | d0, (d1 >> 16) | d2, 0u};
         }
-        if ((OPT & kOptLowReg) && MODE == kModeLutPairsDiv6) {
+        if (MODE == kModeLutPairsDiv6) {
           // Range proof for this slot's lookups (shaping.py:136-151 clamps `lower` into the table; inside the table the clamp
           // is the identity).  idx = G x + B with G, B linear in the interpolation weight between the slot's two frames and
           // |x| <= X[s] whatever the oscillator does, so idx lies between the extremes taken at the two frames:
@@ -776,7 +670,7 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
           // the tail (the three-term FiLM interpolation, the 22-bit - or, opted in, 11-bit - mixer products).  A NaN anywhere
           // must end as "not proven": fminf / fmaxf DROP a NaN operand (a NaN gain or bias of the right frame alone would vanish
           // from lo / hi), hence the explicit self-comparisons - a FiLM frame with a NaN always takes the clamped form.
-          const float X = (DBG == 6 || DBG == 7) ? 2.0f : (w.exciter_bound != nullptr ? w.exciter_bound[lane] : __builtin_inff());
+          const float X = w.exciter_bound != nullptr ? w.exciter_bound[lane] : __builtin_inff();
           const float r_a = fabsf(ga) * X, r_b = fabsf(ga + gd) * X;
           const float e = 1.0f + fmaxf(r_a, r_b) * (1.0f / 512.0f);
           const float lo = fminf(ba - r_a, (ba + bd) - r_b), hi = fmaxf(ba + r_a, (ba + bd) + r_b);
@@ -806,7 +700,7 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
   }
   if (wave == 4 * HPB - 1) {
     // _create_phase_shift (generators.py:54-56): fl(fl(u * rand_phase) - fl32(pi)) for harmonic c = slot c
-    auto shift_of = [&](int c) { return (DBG == 6 || DBG == 9) ? 0.01f * (float)c : (c >= 1 && c <= kK ? phase_u[c - 1] * rand_phase[c - 1] - kPi : 0.0f); };
+    auto shift_of = [&](int c) { return c >= 1 && c <= kK ? phase_u[c - 1] * rand_phase[c - 1] - kPi : 0.0f; };
     L.shift[lane] = shift_of(lane);
     L.kf[lane] = (float)lane;
     if (lane < kKPad - 64) {
@@ -840,10 +734,6 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (!hop_live) return;
-  if (DBG == 5) {   // prologue only (timing): what staging + phase + the barrier cost per launch
-    if (half == 0) newt_out[(size_t)b * N + n] = phase + L.shift[lane] + L.bsum[0];
-    return;
-  }
 
   // ---- 101 harmonics -> 64 shapers on the matrix cores (fp16 two-term split, fp32 accumulate) ----
   // K-step ks covers harmonics 16ks+1 .. 16ks+16; lane (col, half) evaluates the 8 sines of harmonics
@@ -887,7 +777,6 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
   auto two_wterms = [](const int ks) { return (OPT & kOptHybridW) ? ks == 0 : true; };
   // sines of one pair of K slots: arg = fl(fl(k*phase) + shift), the reference's own rounding chain, then sin
   auto sine_pair = [&](const f32x2 kfp, const f32x2 shp) -> f32x2 {
-    if (DBG == 1) return (kfp * ph2 + shp) * splat2(0x1p-40f);   // (bounded: the range-proven lookups trust |x| <= X)
     if (small_args) return sin_turns2_fract(kfp * ph2 + shp);
     const f32x2 arg2 = kfp * ph2 + shp;
     return f32x2{nws_sin_wide(arg2.x), nws_sin_wide(arg2.y)};
@@ -904,7 +793,7 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
     const f32x2 sh2[4] = {{sh0.x, sh0.y}, {sh0.z, sh0.w}, {sh1.x, sh1.y}, {sh1.z, sh1.w}};
     const f32x2 kf2[4] = {{kf0.x, kf0.y}, {kf0.z, kf0.w}, {kf1.x, kf1.y}, {kf1.z, kf1.w}};
     f32x2 v2[4];
-    if (kSharedTurns && small_args && DBG != 1) {
+    if (kSharedTurns && small_args) {
       // the lane's 8 consecutive harmonics: turns(k0 + e) = turns(k0) + e P + (shift differences, |.| < 1 turn), so
       // n_e = rint(x_0 C_hi) + rint(e P) is within 2 of every x_e C_hi: one rint per K-step instead of eight, the reduced
       // argument t_e = fma(x_e, C_hi, -n_e) + x_e C_lo is still the exact product minus an integer, now |t_e| < 2 (fp32
@@ -931,7 +820,7 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
         v2[p].y = 2 * p + 1 < rem ? v2[p].y : 0.0f;
       }
     }
-    if (kFirst && DBG != 1) v2[0].x = half == 0 ? 1.0f : v2[0].x;  // slot 0: the bias' constant input
+    if (kFirst) v2[0].x = half == 0 ? 1.0f : v2[0].x;  // slot 0: the bias' constant input
     // v = hi + lo, both fp16 (lo = exact residual rounded to fp16): v_cvt_pk_f16_f32 for hi, one v_fma_mix{lo,hi}_f16 per lo
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
@@ -951,15 +840,9 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
     for (int m = 0; m < 2; ++m) {
       const f16x8 ahi = L.whi[(ks * 2 + m) * 64 + frag_lane];
       f32x16& acc = m == 0 ? acc0 : acc1;
-      if (DBG == 4) {
-        const f16x8 alo = L.wlo[(ks * 2 + m) * 64 + frag_lane];
-        if (kFirst) acc = f32x16{};
-        acc[ks] += (float)ahi[0] * (float)vhi[0] + (float)alo[1] * (float)vlo[1];
-      } else {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, vhi, kFirst ? f32x16{} : acc, 0, 0, 0);
-        if (two_terms(ks)) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, vlo, acc, 0, 0, 0);
-        if (two_wterms(ks)) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(L.wlo[(ks * 2 + m) * 64 + frag_lane], vhi, acc, 0, 0, 0);
-      }
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, vhi, kFirst ? f32x16{} : acc, 0, 0, 0);
+      if (two_terms(ks)) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, vlo, acc, 0, 0, 0);
+      if (two_wterms(ks)) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(L.wlo[(ks * 2 + m) * 64 + frag_lane], vhi, acc, 0, 0, 0);
     }
   };
   // K-step 6 = slots 96..103 (harmonics 96..101): ONE K=8 MFMA per term instead of a K=16 one whose upper half would be
@@ -973,7 +856,7 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
     const float4 sh = *reinterpret_cast<const float4*>(&L.shift[kk0]);
     const float4 kf = *reinterpret_cast<const float4*>(&L.kf[kk0]);
     f32x2 v2[2];
-    if (kSharedTurns && small_args && DBG != 1) {
+    if (kSharedTurns && small_args) {
       const f32x2 c_hi = splat2(0.15915493667125702f), c_lo = splat2(6.4206382432985265e-09f);
       const f32x2 a2[2] = {f32x2{kf.x, kf.y} * ph2 + f32x2{sh.x, sh.y}, f32x2{kf.z, kf.w} * ph2 + f32x2{sh.z, sh.w}};
       const f32x2 n0 = splat2(__builtin_rintf(a2[0].x * 0.15915493667125702f));
@@ -1009,14 +892,10 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
     for (int m = 0; m < 2; ++m) {
       const f16x4 ahi = *reinterpret_cast<const f16x4*>(&L.whi[(ks * 2 + m) * 64 + frag_lane]);   // first 8 bytes of the row
       f32x16& acc = m == 0 ? acc0 : acc1;
-      if (DBG == 4) {
-        acc[ks] += (float)ahi[0] * (float)vhi[0];
-      } else {
-        acc = __builtin_amdgcn_mfma_f32_32x32x8f16(ahi, vhi, acc, 0, 0, 0);
-        if (two_terms(ks)) acc = __builtin_amdgcn_mfma_f32_32x32x8f16(ahi, vlo, acc, 0, 0, 0);
-        if (two_wterms(ks))
-          acc = __builtin_amdgcn_mfma_f32_32x32x8f16(*reinterpret_cast<const f16x4*>(&L.wlo[(ks * 2 + m) * 64 + frag_lane]), vhi, acc, 0, 0, 0);
-      }
+      acc = __builtin_amdgcn_mfma_f32_32x32x8f16(ahi, vhi, acc, 0, 0, 0);
+      if (two_terms(ks)) acc = __builtin_amdgcn_mfma_f32_32x32x8f16(ahi, vlo, acc, 0, 0, 0);
+      if (two_wterms(ks))
+        acc = __builtin_amdgcn_mfma_f32_32x32x8f16(*reinterpret_cast<const f16x4*>(&L.wlo[(ks * 2 + m) * 64 + frag_lane]), vhi, acc, 0, 0, 0);
     }
   };
   // the first step always runs (it carries the bias); k*f0 only grows with k: once a step has no live lane, everything
@@ -1050,14 +929,6 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
     }
   }
   if (MODE == kModeExciterOnly) return;
-  if (DBG == 3) {
-    float t = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t += acc0[r] + acc1[r];
-    t += nws_swap_halves(t);
-    if (half == 0) newt_out[(size_t)b * N + n] = t;
-    return;
-  }
 
   // ---- FiLM -> shaper -> FiLM -> 64->1 mix, all in registers ----
   const int q0 = lc.i0 - (jb - 1);  // slot of the left frame; fd[q0] is zero where the right frame is clamped
@@ -1072,97 +943,33 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
     // accumulator layout of the exciter tile itself, so G[r], Bb[r], Gn[r] pair up with acc[r] register for register.
     typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
     const unsigned w1b = __builtin_bit_cast(unsigned, lc.w1);   // a multiple of 1/256 in [0, 1): exact in bf16
-    uint4 bop;
-    if (kFilmDma) {
-      // half 0 weighs the left frame's three terms with 1 - w, half 1 the right frame's with w (K slots 8 h + 0..2); 1 - w is
-      // a multiple of 1/256 in (0, 1] like w: exact in bf16
-      const unsigned wb = (half == 0 ? __builtin_bit_cast(unsigned, 1.0f - lc.w1) : w1b) >> 16;
-      bop = uint4{wb | (wb << 16), wb, 0u, 0u};
-    } else {
-      bop = half == 0 ? uint4{0x3f803f80u, 0x3f80u | (w1b & 0xffff0000u), (w1b >> 16) | (w1b & 0xffff0000u), 0u}
-                      : uint4{0u, 0u, 0u, 0u};       // K slots 8..15 unused: zero B, whatever A holds there
-    }
+    const uint4 bop = half == 0 ? uint4{0x3f803f80u, 0x3f80u | (w1b & 0xffff0000u), (w1b >> 16) | (w1b & 0xffff0000u), 0u}
+                                : uint4{0u, 0u, 0u, 0u};       // K slots 8..15 unused: zero B, whatever A holds there
     const bf16x8 bfrag = __builtin_bit_cast(bf16x8, bop);
     // A fragment of parameter type ty, M-tile m
     auto ffrag_of = [&](const int ty, const int m) -> bf16x8 {
-      if (kFilmDma) {
-        const uint2 v = *reinterpret_cast<const uint2*>(&L.frec[0][0] + (q0 + half) * NWS_FILM_REC_BYTES + ((ty * 2 + m) * 32 + col) * 8);
-        return __builtin_bit_cast(bf16x8, uint4{v.x, v.y, 0u, 0u});
-      }
       return __builtin_bit_cast(bf16x8, L.ffrag[q0][ty][m][col]);
     };
     float part = 0.0f;
     unsigned ok_tile[2] = {0u, 0u};   // bit k of ok_tile[m]: shaper 32 m + k proven in range for this wave's samples
-    if (OPT & kOptLowReg) {
-      const int q0u = __builtin_amdgcn_readfirstlane(q0);
-      if (__all(q0 == q0u)) {           // (a wave's 32 samples share their frame pair; anything else takes the clamped form)
-        const unsigned long long okm = kFilmDma ? (L.fmask[q0u] & L.fmask[q0u + 1]) : L.okmask[q0u];
-        ok_tile[0] = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)okm);
-        ok_tile[1] = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(okm >> 32));
-      }
+    const int q0u = __builtin_amdgcn_readfirstlane(q0);
+    if (__all(q0 == q0u)) {           // (a wave's 32 samples share their frame pair; anything else takes the clamped form)
+      const unsigned long long okm = L.okmask[q0u];
+      ok_tile[0] = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)okm);
+      ok_tile[1] = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(okm >> 32));
     }
-    if (OPT & kOptLowReg) {
-      // Register diet (93 -> <= 80 VGPRs: a third 8-wave workgroup fits a CU, 6 waves per SIMD instead of 4).  Same arithmetic,
-      // other order: the index FiLM of a whole M-tile first, IN PLACE of the accumulator tile (acc, G, Bb live: 48 + the other
-      // tile's 16), only then the gain tile Gn (its MFMA runs under the first gathers) and the lookups.
-      // Two copies of a tile's sixteen lookups, chosen ONCE per tile by a wave-uniform test behind the tile's three MFMAs (a branch per
-      // group of four lookups cost the register allocator the in-place tiles: 218 spilled registers; a branch around the whole tile
-      // body had the FiLM stage hoisted out of both arms into fresh registers: 12 spilled): `proven` = all 32 shapers of the tile
-      // provably index inside the table for this wave's samples -> floor(idx) is the table cell and idx - floor(idx) = fract(idx)
-      // exactly (below 2^23): v_fract + v_cvt_u32 + v_lshl_add where the clamped form of shaping.py:136-151 needs floor, med3,
-      // cvt, sub, lshl_add.  Same bits wherever both apply.
-      auto lookups = [&](auto m_tag, auto proven_tag, const f32x16& acc, const f32x16& Gn) {
-        constexpr int m = decltype(m_tag)::value;
-        constexpr bool proven = decltype(proven_tag)::value;
-#pragma unroll
-        for (int g = 0; g < 16 / kLutGroup; ++g) {
-          float fr[kLutGroup];
-          float2 tv[kLutGroup];
-#pragma unroll
-          for (int e = 0; e < kLutGroup; ++e) {
-            const int r = kLutGroup * g + e;
-            const float idx = acc[r];
-            unsigned o;
-            if (proven) {
-              o = lane_off_bytes + ((unsigned)idx << 3);
-              fr[e] = __builtin_amdgcn_fractf(idx);
-            } else {
-              const float fl = __builtin_amdgcn_fmed3f(floorf(idx), 0.0f, LF.top);
-              o = lane_off_bytes + ((unsigned)(int)fl << 3);
-              fr[e] = idx - fl;
-            }
-            tv[e] = DBG == 2 ? float2{__builtin_bit_cast(float, o), fr[e]}
-                             : *reinterpret_cast<const float2*>(LF.pairs + (size_t)(32 * m + (r & 3) + 8 * (r >> 2)) * LF.row_bytes + o);
-          }
-#pragma unroll
-          for (int e = 0; e < kLutGroup; ++e) part = fmaf(Gn[kLutGroup * g + e], fmaf(tv[e].y, fr[e], tv[e].x), part);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      };
-      auto tile = [&](auto m_tag) {
-        constexpr int m = decltype(m_tag)::value;
-        f32x16& acc = m == 0 ? acc0 : acc1;
-        {
-          const f32x16 G = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag_of(0, m), bfrag, f32x16{}, 0, 0, 0);
-          const f32x16 Bb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag_of(1, m), bfrag, f32x16{}, 0, 0, 0);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = fmaf(G[r], acc[r], Bb[r]);   // FiLM in table units (bias and origin folded at staging)
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const f32x16 Gn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag_of(2, m), bfrag, f32x16{}, 0, 0, 0);
-        // the tile's sixteen lookups per lane in one of two forms, chosen by ONE wave-uniform branch
-        if (ok_tile[m] == 0xffffffffu) lookups(m_tag, std::true_type{}, acc, Gn);
-        else lookups(m_tag, std::false_type{}, acc, Gn);
-      };
-      tile(std::integral_constant<int, 0>{});
-      tile(std::integral_constant<int, 1>{});
-    } else
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const f32x16& acc = m == 0 ? acc0 : acc1;
-      const f32x16 G = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, L.ffrag[q0][0][m][col]), bfrag, f32x16{}, 0, 0, 0);
-      const f32x16 Bb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, L.ffrag[q0][1][m][col]), bfrag, f32x16{}, 0, 0, 0);
-      const f32x16 Gn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, L.ffrag[q0][2][m][col]), bfrag, f32x16{}, 0, 0, 0);
+    // Register diet (93 -> <= 80 VGPRs: a third 8-wave workgroup fits a CU, 6 waves per SIMD instead of 4).  Same arithmetic,
+    // other order: the index FiLM of a whole M-tile first, IN PLACE of the accumulator tile (acc, G, Bb live: 48 + the other
+    // tile's 16), only then the gain tile Gn (its MFMA runs under the first gathers) and the lookups.
+    // Two copies of a tile's sixteen lookups, chosen ONCE per tile by a wave-uniform test behind the tile's three MFMAs (a branch per
+    // group of four lookups cost the register allocator the in-place tiles: 218 spilled registers; a branch around the whole tile
+    // body had the FiLM stage hoisted out of both arms into fresh registers: 12 spilled): `proven` = all 32 shapers of the tile
+    // provably index inside the table for this wave's samples -> floor(idx) is the table cell and idx - floor(idx) = fract(idx)
+    // exactly (below 2^23): v_fract + v_cvt_u32 + v_lshl_add where the clamped form of shaping.py:136-151 needs floor, med3,
+    // cvt, sub, lshl_add.  Same bits wherever both apply.
+    auto lookups = [&](auto m_tag, auto proven_tag, const f32x16& acc, const f32x16& Gn) {
+      constexpr int m = decltype(m_tag)::value;
+      constexpr bool proven = decltype(proven_tag)::value;
 #pragma unroll
       for (int g = 0; g < 16 / kLutGroup; ++g) {
         float fr[kLutGroup];
@@ -1170,22 +977,40 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
 #pragma unroll
         for (int e = 0; e < kLutGroup; ++e) {
           const int r = kLutGroup * g + e;
-          const float idx = fmaf(G[r], acc[r], Bb[r]);   // FiLM in table units (bias and origin folded at staging)
-          // floor + clamp + integer index without a conversion: idx + (2^23 - 1/2) rounds to 2^23 + floor(idx) (at exact
-          // integers k possibly k - 1 with fraction 1: the same point of the piecewise-linear table up to one rounding of
-          // T), the clamp works on that float, and its low mantissa bits ARE the index
-          // (the add-2^23 trick for floor + index was measured: no faster than floor / med3 / convert, 0.2406 vs 0.2384 ms)
-          const float fl = __builtin_amdgcn_fmed3f(floorf(idx), 0.0f, LF.top);
-          const unsigned o = lane_off_bytes + ((unsigned)(int)fl << 3);
-          fr[e] = idx - fl;
-          tv[e] = DBG == 2 ? float2{idx, 0.0f}
-                           : *reinterpret_cast<const float2*>(LF.pairs + (size_t)(32 * m + (r & 3) + 8 * (r >> 2)) * LF.row_bytes + o);
+          const float idx = acc[r];
+          unsigned o;
+          if (proven) {
+            o = lane_off_bytes + ((unsigned)idx << 3);
+            fr[e] = __builtin_amdgcn_fractf(idx);
+          } else {
+            const float fl = __builtin_amdgcn_fmed3f(floorf(idx), 0.0f, LF.top);
+            o = lane_off_bytes + ((unsigned)(int)fl << 3);
+            fr[e] = idx - fl;
+          }
+          tv[e] = *reinterpret_cast<const float2*>(LF.pairs + (size_t)(32 * m + (r & 3) + 8 * (r >> 2)) * LF.row_bytes + o);
         }
 #pragma unroll
         for (int e = 0; e < kLutGroup; ++e) part = fmaf(Gn[kLutGroup * g + e], fmaf(tv[e].y, fr[e], tv[e].x), part);
         __builtin_amdgcn_sched_barrier(0);
       }
-    }
+    };
+    auto tile = [&](auto m_tag) {
+      constexpr int m = decltype(m_tag)::value;
+      f32x16& acc = m == 0 ? acc0 : acc1;
+      {
+        const f32x16 G = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag_of(0, m), bfrag, f32x16{}, 0, 0, 0);
+        const f32x16 Bb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag_of(1, m), bfrag, f32x16{}, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = fmaf(G[r], acc[r], Bb[r]);   // FiLM in table units (bias and origin folded at staging)
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      const f32x16 Gn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ffrag_of(2, m), bfrag, f32x16{}, 0, 0, 0);
+      // the tile's sixteen lookups per lane in one of two forms, chosen by ONE wave-uniform branch
+      if (ok_tile[m] == 0xffffffffu) lookups(m_tag, std::true_type{}, acc, Gn);
+      else lookups(m_tag, std::false_type{}, acc, Gn);
+    };
+    tile(std::integral_constant<int, 0>{});
+    tile(std::integral_constant<int, 1>{});
     const float bias_n = fmaf(lc.w1, L.bsum[q0 + 1] - L.bsum[q0], L.bsum[q0]);
     const float total = part + nws_swap_halves(part) + (bias_n + w.newt_out_b[0]);
     if (half == 0) newt_out[(size_t)b * N + n] = add_in != nullptr ? add_in[(size_t)b * N + n] + total : total;
@@ -1274,9 +1099,7 @@ __global__ __launch_bounds__(256 * HPB, MODE == kModeExact ? 2 : (is_bank(MODE) 
         const f32x2 g_n = fma2(w1_2, NWS_PAIR(fd[2]), NWS_PAIR(fa[2]));  // already times newt.mixer.weight
         const f32x2 xi = fma2(g_i, x2, b_i);  // FiLM (models/modules/dynamic.py:8)
         f32x2 sh;
-        if (DBG == 2) {
-          sh = xi;
-        } else if (MODE == kModeLutPairsDiv6) {
+        if (MODE == kModeLutPairsDiv6) {
           sh = lut_shaper2_fast(LF, LF.pairs + (size_t)(sb + 2 * h2) * LF.row_bytes, lane_off_bytes, xi);
         } else if (is_lut(MODE)) {
           sh = lut_shaper2<MODE != kModeLut, MODE == kModeLutPairsDiv6>(LP, (sb + 2 * h2) * LP.size + lane_row_off, xi);
@@ -1392,44 +1215,6 @@ __global__ __launch_bounds__(256) void shaper_table_kernel(NwsWeights w, int siz
   for (int i = blockIdx.x * 256 + threadIdx.x; i < size; i += gridDim.x * 256) {
     const float xv = i < halfway ? fmaf(step, (float)i, tmin) : fmaf(-step, (float)(size - 1 - i), tmax);
     table[(size_t)s * size + i] = exact_shaper_precise(SH, s, xv);
-  }
-}
-
-// Candidate cheaper sines, measured on hardware through nws_debug_sin before any of them may replace nws_sinf.
-//  exact-product reduction to turns: p = x*C_hi, e = fma(x, C_hi, -p) (the product's rounding error),
-//  t = (p - rint(p)) + (e + x*C_lo)  in [-0.53, 0.53] turns, good to ~3e-8 turns for |x| <= 6e6.
-__device__ __forceinline__ float turns_reduce(float x) {
-  const float c_hi = 0.15915493667125702f;     // fl32(1/(2 pi))
-  const float c_lo = 6.4206382432985265e-09f;   // 1/(2 pi) - c_hi
-  const float p = x * c_hi;
-  const float e = fmaf(x, c_hi, -p);
-  return (p - rintf(p)) + fmaf(x, c_lo, e);
-}
-__device__ __forceinline__ float sin_hw_turns(float x) { return __builtin_amdgcn_sinf(turns_reduce(x)); }
-__device__ __forceinline__ float sin_poly_turns(float x) {
-  float t = turns_reduce(x);
-  t = t - rintf(t);                                   // [-0.5, 0.5]
-  const float f = copysignf(0.5f, t) - t;             // sin(pi - a) = sin(a)
-  t = fabsf(t) > 0.25f ? f : t;                       // [-0.25, 0.25] turns
-  const float a = t * 6.283185307179586f;             // [-pi/2, pi/2]
-  const float z = a * a;
-  float q = fmaf(-2.4080531346726275e-08f, z, 2.753648004727438e-06f);  // odd degree-11 fit, |err| < 2e-8 on [-pi/2, pi/2]
-  q = fmaf(q, z, -0.00019841086759697646f);
-  q = fmaf(q, z, 0.00833333283662796f);
-  q = fmaf(q, z, -0.1666666716337204f);
-  return fmaf(a * z, q, a);
-}
-
-template <int MODE>
-__global__ void sin_variant_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n, int reps) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float v = x[i];
-    float acc = 0.0f;
-    for (int r = 0; r < reps; ++r) {
-      const float a = v + (float)r * 1.0e-3f * acc;
-      acc += MODE == 0 ? nws_sinf(a) : MODE == 1 ? sin_hw_turns(a) : sin_poly_turns(a);
-    }
-    y[i] = acc;
   }
 }
 
@@ -1555,16 +1340,6 @@ int nws_mixer_frags(const float* mixer_w, const float* mixer_b, void* frags_out,
   return NWS_OK;
 }
 
-int nws_debug_film_frags(const NwsWeights* w, const float* film, int B, int T, void* frags_out, void* stream) {
-  if (!w || !film || !frags_out || B <= 0 || T <= 0 || !w->newt_out_w || w->lut_size < 2) return NWS_ERR_BAD_ARG;
-  const size_t frames = (size_t)B * T;
-  if (frames >= (1ull << 31)) return NWS_ERR_UNSUPPORTED;
-  unsigned char* recs = static_cast<unsigned char*>(frags_out);
-  film_frags_kernel<<<(unsigned)frames, 64, 0, (hipStream_t)stream>>>(*w, film, recs, reinterpret_cast<FilmAux*>(recs + frames * NWS_FILM_REC_BYTES));
-  NWS_CHECK_LAUNCH();
-  return NWS_OK;
-}
-
 int nws_exciter_bound(const float* mixer_w, const float* mixer_b, float* bound_out, void* stream) {
   if (!mixer_w || !mixer_b || !bound_out) return NWS_ERR_BAD_ARG;
   exciter_bound_kernel<<<kS, 64, 0, (hipStream_t)stream>>>(mixer_w, mixer_b, bound_out);
@@ -1585,18 +1360,6 @@ int nws_lut_pairs(const float* table, int table_size, float* pairs_out, void* st
   if (!table || !pairs_out || table_size < 2) return NWS_ERR_BAD_ARG;
   const dim3 grid((table_size + 255) / 256, NWS_N_SHAPERS);
   lut_pairs_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(table, table_size, reinterpret_cast<float2*>(pairs_out));
-  NWS_CHECK_LAUNCH();
-  return NWS_OK;
-}
-
-int nws_debug_sin(int mode, const float* x, float* y, int64_t n, int reps, void* stream) {
-  if (!x || !y || n <= 0 || reps < 1) return NWS_ERR_BAD_ARG;
-  const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-  hipStream_t st = (hipStream_t)stream;
-  if (mode == 0) sin_variant_kernel<0><<<blocks, 256, 0, st>>>(x, y, n, reps);
-  else if (mode == 1) sin_variant_kernel<1><<<blocks, 256, 0, st>>>(x, y, n, reps);
-  else if (mode == 2) sin_variant_kernel<2><<<blocks, 256, 0, st>>>(x, y, n, reps);
-  else return NWS_ERR_BAD_ARG;
   NWS_CHECK_LAUNCH();
   return NWS_OK;
 }
@@ -1635,34 +1398,17 @@ int nws_exciter_newt_add(const NwsWeights* w, const float* f0, const float* f0_u
       if (w->lut_pairs != nullptr && w->lut_max - w->lut_min == 6.0f && pow2) {
         // FastNEWT hot path.  exciter_opts (nws_hip.h): round-1 FiLM interpolation on the VALU / one fp16 term per sine in
         // every K-step / in K-steps 1..6 only
-        // XCD-contiguous hop groups (see the kernel); NWS_EXCITER_XCD=0 restores grid (groups, B) (measurements)
-        static const bool xcd_map = [] { const char* e = getenv("NWS_EXCITER_XCD"); return !(e && e[0] == '0'); }();
+        // XCD-contiguous hop groups (see the kernel) from 64 workgroups up; fewer launch as grid (groups, B)
         const int groups = (T + 1) / 2;
-        const int xcd_groups = xcd_map && (long long)groups * B >= 64 && (long long)groups * B < (1ll << 31) ? groups : 0;
+        const int xcd_groups = (long long)groups * B >= 64 && (long long)groups * B < (1ll << 31) ? groups : 0;
         const dim3 g2 = xcd_groups ? dim3((unsigned)(groups * B), 1) : dim3(groups, B);
         const int opts = w->exciter_opts;
-        // the 80-register tail (kOptLowReg: three workgroups per CU) is the default; NWS_EXCITER_LOWREG=0 keeps the 93-register
-        // one (measurements: same results, 3 % slower alone, 6 % slower on realistic F0)
-        static const bool low_reg = [] { const char* e = getenv("NWS_EXCITER_LOWREG"); return !(e && e[0] == '0'); }();
-        // (measurements: NWS_EXCITER_LDS_PAD=<bytes> of unused LDS per workgroup lowers the occupancy of the hot kernel)
-        static const size_t hot_pad = [] { const char* e = getenv("NWS_EXCITER_LDS_PAD"); return e ? (size_t)atoi(e) : (size_t)0; }();
-#define NWS_HOT(O) exciter_newt_kernel<kModeLutPairsDiv6, 0, 2, O><<<g2, 512, base + hot_pad, st>>>( \
+#define NWS_HOT(O) exciter_newt_kernel<kModeLutPairsDiv6, 2, O><<<g2, 512, base, st>>>( \
             *w, f0, f0_up, carry, phase_u, rand_phase, film, T, sample_rate, exciter_out, newt_out, nullptr, add_in, xcd_groups)
-        // (measurements, VERDICT r4 #4: NWS_EXCITER_HPB=1 launches the default kernel as 4-wave workgroups of one hop - three of them
-        // fit beside a 251-register recurrence wave on a SIMD where one 8-wave workgroup = two waves per SIMD does; alone it is
-        // LDS-bound at four workgroups = four waves per SIMD instead of six.  Same bits.)
-        static const bool one_hop = [] { const char* e = getenv("NWS_EXCITER_HPB"); return e && e[0] == '1'; }();
-        if (one_hop && opts == 0) {
-          const int xg1 = xcd_map && (long long)T * B >= 64 && (long long)T * B < (1ll << 31) ? T : 0;
-          const dim3 g1 = xg1 ? dim3((unsigned)(T * B), 1) : dim3(T, B);
-          exciter_newt_kernel<kModeLutPairsDiv6, 0, 1, kOptFilmMfma | kOptLowReg><<<g1, 256, base + hot_pad, st>>>(
-              *w, f0, f0_up, carry, phase_u, rand_phase, film, T, sample_rate, exciter_out, newt_out, nullptr, add_in, xg1);
-        } else
         if (opts & NWS_EXCITER_VALU_FILM) NWS_HOT(0);
-        else if (opts & NWS_EXCITER_ONE_TERM) NWS_HOT(kOptFilmMfma | kOptOneTerm | kOptLowReg);
-        else if (opts & NWS_EXCITER_HYBRID_W) { if (low_reg) NWS_HOT(kOptFilmMfma | kOptHybrid | kOptHybridW | kOptLowReg); else NWS_HOT(kOptFilmMfma | kOptHybrid | kOptHybridW); }
-        else if (opts & NWS_EXCITER_HYBRID) NWS_HOT(kOptFilmMfma | kOptHybrid | kOptLowReg);
-        else if (low_reg) NWS_HOT(kOptFilmMfma | kOptLowReg);
+        else if (opts & NWS_EXCITER_ONE_TERM) NWS_HOT(kOptFilmMfma | kOptOneTerm);
+        else if (opts & NWS_EXCITER_HYBRID_W) NWS_HOT(kOptFilmMfma | kOptHybrid | kOptHybridW);
+        else if (opts & NWS_EXCITER_HYBRID) NWS_HOT(kOptFilmMfma | kOptHybrid);
         else NWS_HOT(kOptFilmMfma);
 #undef NWS_HOT
       } else if (w->lut_pairs != nullptr)
@@ -1673,96 +1419,17 @@ int nws_exciter_newt_add(const NwsWeights* w, const float* f0, const float* f0_u
                                                                sample_rate, exciter_out, newt_out, nullptr, add_in);
     } else {
       if (!w->shaper_w0 || !w->shaper_w2 || !w->shaper_w4 || !w->shaper_w6) return NWS_ERR_BAD_ARG;
-      // (measurements: NWS_EXCITER_BANK_LDS_PAD=<bytes> of unused LDS per workgroup lowers the bank kernel's occupancy -
-      // 35840 restores the two workgroups per CU it had while the shaper-input planes lived behind ExcLds)
-      static const size_t bank_pad = [] { const char* e = getenv("NWS_EXCITER_BANK_LDS_PAD"); return e ? (size_t)atoi(e) : (size_t)0; }();
       if (w->shaper_turns != nullptr && (w->exciter_opts & NWS_EXCITER_BANK_NOFRACT))
-        exciter_newt_kernel<kModeExactBankNF><<<grid, 256, base + bank_pad, st>>>(
+        exciter_newt_kernel<kModeExactBankNF><<<grid, 256, base, st>>>(
             *w, f0, f0_up, carry, phase_u, rand_phase, film, T, sample_rate, exciter_out, newt_out, w->shaper_turns, add_in);
       else if (w->shaper_turns != nullptr)
-        exciter_newt_kernel<kModeExactBank><<<grid, 256, base + bank_pad, st>>>(
+        exciter_newt_kernel<kModeExactBank><<<grid, 256, base, st>>>(
             *w, f0, f0_up, carry, phase_u, rand_phase, film, T, sample_rate, exciter_out, newt_out, w->shaper_turns, add_in);
       else
         exciter_newt_kernel<kModeExact><<<grid, 256, base + sizeof(ShaperLds), st>>>(
             *w, f0, f0_up, carry, phase_u, rand_phase, film, T, sample_rate, exciter_out, newt_out, nullptr, add_in);
     }
   }
-  NWS_CHECK_LAUNCH();
-  return NWS_OK;
-}
-
-int nws_debug_exciter_newt(int variant, const NwsWeights* w, const float* f0, const double* carry, const float* phase_u,
-                           const float* rand_phase, const float* film, int B, int T, float sample_rate,
-                           float* newt_out, void* stream) {
-  if (!weights_ok(w) || !f0 || !carry || !phase_u || !rand_phase || !film || !newt_out || !w->lut || !w->lut_pairs)
-    return NWS_ERR_BAD_ARG;
-  if (w->lut_max - w->lut_min != 6.0f || (w->lut_size & (w->lut_size - 1)) != 0) return NWS_ERR_UNSUPPORTED;
-  const dim3 grid(T, B);
-  const size_t base = (sizeof(ExcLds) + 15) & ~size_t(15);
-  hipStream_t st = (hipStream_t)stream;
-#define NWS_OPT_LAUNCH(O)                                                                                          \
-  exciter_newt_kernel<kModeLutPairsDiv6, 0, 2, O><<<dim3((T + 1) / 2, B), 512, base, st>>>(*w, f0, nullptr, carry, phase_u, \
-                                                            rand_phase, film, T, sample_rate, nullptr, newt_out)
-  if (variant == 5) {   // prologue only, product configuration
-    exciter_newt_kernel<kModeLutPairsDiv6, 5, 2, kOptFilmMfma | kOptLowReg><<<dim3((T + 1) / 2, B), 512, base, st>>>(
-        *w, f0, nullptr, carry, phase_u, rand_phase, film, T, sample_rate, nullptr, newt_out);
-    NWS_CHECK_LAUNCH();
-    return NWS_OK;
-  }
-  if ((variant >= 21 && variant <= 24) || (variant >= 26 && variant <= 29)) {
-    // timing ablations of the PRODUCT configuration (results wrong by design): 21 no sines, 22 no table gathers, 23 no tail, 24 no mixer MFMAs;
-    // 26 no global load in front of the barrier, 27 / 28 / 29 no FiLM rows / no fragment DMA / no F0, carry, shifts (tools/exciter_ablate_product.py)
-#define NWS_ABL(D) exciter_newt_kernel<kModeLutPairsDiv6, D, 2, kOptFilmMfma | kOptLowReg><<<dim3((T + 1) / 2, B), 512, base, st>>>( \
-        *w, f0, nullptr, carry, phase_u, rand_phase, film, T, sample_rate, nullptr, newt_out)
-    switch (variant) {
-      case 21: NWS_ABL(1); break;
-      case 22: NWS_ABL(2); break;
-      case 23: NWS_ABL(3); break;
-      case 24: NWS_ABL(4); break;
-      case 26: NWS_ABL(6); break;
-      case 27: NWS_ABL(7); break;
-      case 28: NWS_ABL(8); break;
-      default: NWS_ABL(9); break;
-    }
-#undef NWS_ABL
-    NWS_CHECK_LAUNCH();
-    return NWS_OK;
-  }
-  if (variant == 6) {   // prologue only, fragment records by LDS-DMA (`film` = the records + aux entries of nws_debug_film_frags here)
-    exciter_newt_kernel<kModeLutPairsDiv6, 5, 2, kOptFilmMfma | kOptLowReg | kOptFilmDma><<<dim3((T + 1) / 2, B), 512, base, st>>>(
-        *w, f0, nullptr, carry, phase_u, rand_phase, film, T, sample_rate, nullptr, newt_out, film, nullptr, 0, B * T);
-    NWS_CHECK_LAUNCH();
-    return NWS_OK;
-  }
-  if (variant >= 10) {   // 10 + OPT bits: the product kernel's compile-time options (two hops per workgroup)
-    switch (variant - 10) {
-      case 0: NWS_OPT_LAUNCH(0); break;
-      case 2: NWS_OPT_LAUNCH(2); break;
-      case 26: NWS_OPT_LAUNCH(26); break;
-      case 34: NWS_OPT_LAUNCH(34); break;   // kOptFilmMfma | kOptLowReg: the default kernel
-      case 58: NWS_OPT_LAUNCH(58); break;   // ... | kOptHybrid | kOptHybridW | kOptLowReg: the opt-in hybrid-W kernel
-      case 98:                              // kOptFilmMfma | kOptLowReg | kOptFilmDma (`film` = records + aux entries of nws_debug_film_frags)
-        exciter_newt_kernel<kModeLutPairsDiv6, 0, 2, 98><<<dim3((T + 1) / 2, B), 512, base, st>>>(
-            *w, f0, nullptr, carry, phase_u, rand_phase, film, T, sample_rate, nullptr, newt_out, film, nullptr, 0, B * T);
-        break;
-      default: return NWS_ERR_BAD_ARG;
-    }
-    NWS_CHECK_LAUNCH();
-    return NWS_OK;
-  }
-#undef NWS_OPT_LAUNCH
-#define NWS_DBG_LAUNCH(V)                                                                                         \
-  exciter_newt_kernel<kModeLutPairsDiv6, V><<<grid, 256, base, st>>>(*w, f0, nullptr, carry, phase_u, rand_phase, film, T, \
-                                                            sample_rate, nullptr, newt_out)
-  switch (variant) {
-    case 0: NWS_DBG_LAUNCH(0); break;
-    case 1: NWS_DBG_LAUNCH(1); break;
-    case 2: NWS_DBG_LAUNCH(2); break;
-    case 3: NWS_DBG_LAUNCH(3); break;
-    case 4: NWS_DBG_LAUNCH(4); break;
-    default: return NWS_ERR_BAD_ARG;
-  }
-#undef NWS_DBG_LAUNCH
   NWS_CHECK_LAUNCH();
   return NWS_OK;
 }

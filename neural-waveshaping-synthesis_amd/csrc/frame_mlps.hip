@@ -17,7 +17,6 @@
 // Outputs that the sample-rate kernels read frame-major (film, fir) are transposed per wave
 // through a 4 KB LDS patch so every global store is a full 128 B segment.
 #include <cstdlib>
-#include <cstring>
 
 #include "nws_common.h"
 #include "mlp_few.h"
@@ -800,7 +799,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps64_kernel(NwsWeights w, cons
 // Frames are the flattened (b, t) index: every tensor here is frame-major and contiguous, so tiles need not respect
 // utterance boundaries.  6 workgroup barriers per 256 frames (they only guard the reuse of a weight slot).
 // Measured on MI355X at B x T = 64 x 500 (rocprofv3, one stream, inside whole forwards): 41.5 us against 57.7 us for
-// frame_mlps64_kernel; tools/mlp_variants.py, tools/mlp_timeline.py.  What the time is: 1164 MFMAs per SIMD (37 K cycles of the
+// frame_mlps64_kernel; profiles/r04/mlp_variants.txt, mlp_timeline.txt (ablations since retired).  What the time is: 1164 MFMAs per SIMD (37 K cycles of the
 // matrix pipe) and ~2 x 2700 vector instructions that do not overlap them (no MFMAs: 15 us; no LayerNorm arithmetic -3.6, no split
 // -5.8); s_setprio around the MFMA phases -5 %.  Measured and dropped: waves 4..7 half a layer out of phase with waves 0..3 (a SIMD
 // would always have one wave in its MFMA phase and one in its vector phase): same time; the three products of a K-step issued
@@ -870,17 +869,12 @@ __device__ __forceinline__ void wr_dma(const char* __restrict__ src, char* dst, 
 // independent accumulator chains) and the fragments of step s + 2 are requested before the three MFMAs of step s are issued:
 // left to itself hipcc requests each pair right in front of its first use and the matrix pipe idles for an LDS latency per
 // three MFMAs (measured: 34 us of a 49 us kernel in the MFMA phases against 16 us of MFMA time).
-#ifndef NWS_WR_PRIO
-#define NWS_WR_PRIO 1
-#endif
-
-template <int KS, int NMT, bool TRANSPOSED, bool ZERO = false, bool NOLDS = false, bool PRIO = NWS_WR_PRIO>
+template <int KS, int NMT, bool TRANSPOSED, bool ZERO = false>
 __device__ __forceinline__ void wr_layer_mma(const char* slot, int mt0, const WrAct& x, f32x16* acc, int lane) {
   const char* a = slot + (size_t)mt0 * KS * 2048 + lane * 16;
   constexpr int S = KS * NMT;
   f16x8 wh[3], wl[3];
   auto ld = [&](int s2, int b) {
-    if (NOLDS && s2 > 2) return;    // timing ablation: the first three steps' fragments serve every step
     const int mt = s2 % NMT, ks = s2 / NMT;
     wh[b] = *reinterpret_cast<const f16x8*>(a + (mt * KS + ks) * 2048);
     wl[b] = *reinterpret_cast<const f16x8*>(a + (mt * KS + ks) * 2048 + 1024);
@@ -888,7 +882,7 @@ __device__ __forceinline__ void wr_layer_mma(const char* slot, int mt0, const Wr
   ld(0, 0);
   if (S > 1) ld(1, 1);
   __builtin_amdgcn_sched_barrier(0x6);
-  if (PRIO) __builtin_amdgcn_s_setprio(2);
+  __builtin_amdgcn_s_setprio(2);
 #pragma unroll
   for (int s2 = 0; s2 < S; ++s2) {
     const int mt = s2 % NMT, ks = s2 / NMT, b = s2 % 3;
@@ -906,7 +900,7 @@ __device__ __forceinline__ void wr_layer_mma(const char* slot, int mt0, const Wr
     __builtin_amdgcn_sched_barrier(0x6);   // vector / scalar ALU work may move across (the previous layer's split is interleaved
                                            // here by the compiler), LDS reads and MFMAs stay in this order
   }
-  if (PRIO) __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_s_setprio(0);
 }
 
 // the lane's 64 entries of a per-channel vector (channels 32 mt + 8 q + 4 h + i) as four accumulator-shaped tiles
@@ -924,16 +918,7 @@ __device__ __forceinline__ void wr_lane_vec(const float* par, int half, f32x16 (
 }
 
 // four accumulator tiles (128 channels of the lane's frame) -> operand of the next layer
-template <bool CHEAP = false>
 __device__ __forceinline__ void wr_pack(const f32x16 (&v)[4], WrAct& out) {
-  if (CHEAP) {   // timing ablation: no split arithmetic
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      out.hi[ks] = __builtin_bit_cast(f16x8, f32x4{v[ks >> 1][8 * (ks & 1)], v[ks >> 1][8 * (ks & 1) + 1], v[ks >> 1][8 * (ks & 1) + 2], v[ks >> 1][8 * (ks & 1) + 3]});
-      out.lo[ks] = __builtin_bit_cast(f16x8, f32x4{v[ks >> 1][8 * (ks & 1) + 4], v[ks >> 1][8 * (ks & 1) + 5], v[ks >> 1][8 * (ks & 1) + 6], v[ks >> 1][8 * (ks & 1) + 7]});
-    }
-    return;
-  }
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -1000,13 +985,11 @@ __device__ __forceinline__ void wr_store_rows(__amdgpu_buffer_rsrc_t out, const 
                                           lane_off + ((r & 3) * LD + 32 * tile) * 4, 8 * (r >> 2) * LD * 4, 0);
 }
 
-// ABL: timing ablations (results meaningless): 1 no LayerNorm / LeakyReLU arithmetic, 2 no MFMAs (and no weight reads), 3 MFMAs without their weight reads from LDS, 5 no
-// (hi, lo) split arithmetic; 6: product arithmetic + cycle timeline (s_memtime probes, tools/mlp_timeline.py)
-template <bool TAPS, int ABL = 0>
+template <bool TAPS>
 __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, const float* __restrict__ gru_out, int F, int T,
                                                                  float* __restrict__ emb_out, float* __restrict__ film_out,
                                                                  float* __restrict__ H_out, float* __restrict__ fir_out,
-                                                                 const int xcd_blocks = 0, const int only_path = -1) {
+                                                                 const int xcd_blocks = 0) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   WrLds& L = *reinterpret_cast<WrLds*>(smem_raw);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1018,7 +1001,6 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
   const int fb = xcd_blocks > 0 ? (int)(blockIdx.x >> 4) * 8 + (int)(blockIdx.x & 7) : (int)blockIdx.x;
   const int path = xcd_blocks > 0 ? (int)((blockIdx.x >> 3) & 1) : (int)blockIdx.y;   // 0: proj + newt.mlp -> film; 1: proj + h_generator -> H -> fir
   if (xcd_blocks > 0 && fb >= xcd_blocks) return;
-  if (only_path >= 0 && path != only_path) return;   // measurements (tools/mlp_paths_ab.py): one path's workgroups alone
   const int half = lane >> 5, col = lane & 31;
   const int f0 = fb * kWrFrames + 32 * wave;         // first frame of this wave
   const int frame = f0 + col;                        // this lane's frame (standard orientation)
@@ -1080,22 +1062,12 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
   __builtin_amdgcn_sched_barrier(0);
   // barrier k closes interval k: every wave has finished reading slot (k - 1) & 1, and its share of chunk k (requested one
   // interval earlier) has landed; then chunk k + 1 goes into the slot just released
-  // ABL == 6: cycle timeline - s_memtime at numbered points, every wave of workgroup (0, path), into emb_out as long long [path][wave][32]
-  int probe_n = 0;
-  auto probe = [&]() {
-    if (ABL == 6 && fb == 0 && lane == 0 && probe_n < 32)
-      reinterpret_cast<long long*>(emb_out)[(path * 8 + wave) * 32 + probe_n] = (long long)__builtin_readcyclecounter();
-    ++probe_n;
-  };
-  probe();   // 0: prologue done (DMA requested, inputs converted)
   auto sync = [&](int k) {
-    probe();
     if (k == 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // everything but chunk 1
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // (not __syncthreads(): hipcc puts a vmcnt(0) in front of it while LDS-bound loads are in flight, which would wait for
     // chunk 1 as well; the LDS writes of the parameters are drained by the lgkmcnt(0))
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    probe();
     if (k >= 1 && k <= 4) wr_dma(T2 + (size_t)(path ? kT2Kb[1][k + 1] : kT2Kb[0][k + 1]) * 1024, ((k + 1) & 1) ? S1 : S0, (path == 1 && k == 4) ? 72 : 64, wave, lane);
   };
   sync(0);
@@ -1103,8 +1075,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
   f32x16 v[4];
   // ---- layer 0: emb = proj(gru_out) ----
   wr_lane_vec(L.par, half, v);
-  if (ABL != 2) wr_layer_mma<8, 4, false, false, ABL == 3>(S0, 0, X, v, lane);
-  probe();
+  wr_layer_mma<8, 4, false, false>(S0, 0, X, v, lane);
   if (TAPS && path == 0 && emb_out != nullptr && frame < F) {
     const int b = frame / T, t = frame - b * T;
 #pragma unroll
@@ -1112,8 +1083,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
 #pragma unroll
       for (int r = 0; r < 16; ++r) emb_out[((size_t)b * NWS_HIDDEN + 32 * mt + frag_row(r, half)) * T + t] = v[mt][r];
   }
-  wr_pack<ABL == 5>(v, X);
-  probe();
+  wr_pack(v, X);
   sync(1);
 
   // ---- three hidden layers: X = LeakyReLU(LayerNorm(W X + b)) ----
@@ -1123,9 +1093,8 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
     const float* par = L.par + 128 + 384 * l;
     const char* slot = (l & 1) ? S0 : S1;          // chunks 1, 2, 3 -> slots 1, 0, 1
     wr_lane_vec(par, half, v);
-    if (ABL != 2) wr_layer_mma<8, 4, false, false, ABL == 3>(slot, 0, X, v, lane);
-    probe();
-    if (ABL != 1) wr_layer_norm(v, par + 128, par + 256, half);
+    wr_layer_mma<8, 4, false, false>(slot, 0, X, v, lane);
+    wr_layer_norm(v, par + 128, par + 256, half);
     if (l == 2 && path == 1) {
       // band 128 of H: fp32 dot product of the frame's 128 activations with row 128 of the last layer
       f32x16 w128[4];
@@ -1142,8 +1111,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
       d += nws_swap_halves(d);
       h128 = d + L.par[1536];
     }
-    wr_pack<ABL == 5>(v, X);
-    probe();
+    wr_pack(v, X);
     sync(l + 2);
   }
 
@@ -1157,18 +1125,17 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
 #pragma unroll
       for (int pr = 0; pr < 2; ++pr) {           // two tiles at a time: two accumulator chains
         f32x16 acc[2];
-        if (ABL != 2) wr_layer_mma<8, 2, true, true, ABL == 3>(slot, 2 * pr, X, acc, lane);
+        wr_layer_mma<8, 2, true, true>(slot, 2 * pr, X, acc, lane);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           wr_store_rows<NWS_FILM_CH, true>(film_rs, acc[j], lane_off, 4 * c + 2 * pr + j, L.par[1280 + 32 * (4 * c + 2 * pr + j) + col]);
       }
-      probe();
       if (c == 0) sync(5);
     }
   } else {
     // ---- H = last layer of h_generator (bands 0..127 on the matrix pipe, band 128 from above) -> operand of the FIR design ----
     wr_lane_vec(L.par + 1280, half, v);
-    if (ABL != 2) wr_layer_mma<8, 4, false, false, ABL == 3>(S0, 0, X, v, lane);
+    wr_layer_mma<8, 4, false, false>(S0, 0, X, v, lane);
     if (TAPS && H_out != nullptr && frame < F) {
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
@@ -1188,11 +1155,10 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
       f32x16 acc[2];
-      if (ABL != 2) wr_layer_mma<9, 2, true, true, ABL == 3>(S1, 2 * pr, X, acc, lane);
+      wr_layer_mma<9, 2, true, true>(S1, 2 * pr, X, acc, lane);
 #pragma unroll
       for (int j = 0; j < 2; ++j) wr_store_rows<NWS_FIR_HALF, false>(fir_rs, acc[j], lane_off, 2 * pr + j, 0.0f);
     }
-    probe();
   }
 }
 
@@ -1281,13 +1247,13 @@ __global__ void fir_design_kernel(const float* __restrict__ window, float* __res
 template <int NF>
 __global__ __launch_bounds__(256) void frame_mlps_few_kernel(NwsWeights w, const float* __restrict__ gru_out, int T,
                                                              float* __restrict__ film_out, float* __restrict__ fir_out, int out_T,
-                                                             int out_off, NwsStreamNoiseWin win, long long* probe) {
+                                                             int out_off, NwsStreamNoiseWin win) {
   if (win.nzwin != nullptr && blockIdx.y == gridDim.y - 1) {
     if (blockIdx.x == 0) nws_stream_noise_window_block<256>(win, threadIdx.x);
     return;
   }
   __shared__ __attribute__((aligned(16))) NwsFewLds L;
-  nws_mlp_few_path<NF>(L, w, gru_out, T, blockIdx.y, blockIdx.x, film_out, fir_out, out_T, out_off, threadIdx.x, [] { return true; }, probe);
+  nws_mlp_few_path<NF>(L, w, gru_out, T, blockIdx.y, blockIdx.x, film_out, fir_out, out_T, out_off, threadIdx.x, [] { return true; });
 }
 
 }  // namespace
@@ -1314,17 +1280,11 @@ int nws_mlp_frags(const NwsWeights* w, const float* fir_design, void* frags_out,
   return NWS_OK;
 }
 
-// measurements / tests: 0 automatic (by frame count, NWS_MLP_KERNEL), 1 tile kernels (frame_mlps16 / 64), 2 wave-resident frames
-static int g_mlp_kernel_mode = 0, g_mlp_dbg = 0;
-static void* g_mlp_probe = nullptr;
-int nws_debug_frame_mlps_probe(void* buf) {
-  g_mlp_probe = buf;   // 2 x 8 x 32 long long: s_memtime timeline of workgroups (0, path), ablation 6
-  return NWS_OK;
-}
+// tests: 0 automatic (by frame count), 1 tile kernels (frame_mlps16 / 64), 2 wave-resident frames
+static int g_mlp_kernel_mode = 0;
 int nws_debug_frame_mlps_kernel(int mode) {
-  if (mode < 0 || (mode & 15) > 2) return NWS_ERR_BAD_ARG;
-  g_mlp_kernel_mode = mode & 15;
-  g_mlp_dbg = mode >> 4;     // bits 8..10: timing ablation
+  if (mode < 0 || mode > 2) return NWS_ERR_BAD_ARG;
+  g_mlp_kernel_mode = mode;
   return NWS_OK;
 }
 
@@ -1358,12 +1318,8 @@ int nws_frame_mlps(const NwsWeights* w, const float* gru_out, const float* fir_d
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(MlpLds16));
     if (e != hipSuccess) return (int)e;
   }
-  // enough frames to give most CUs a 256-frame workgroup: wave-resident frames (NWS_MLP_KERNEL=tiles keeps the kernels below)
-  static const int env_mode = [] {
-    const char* e = getenv("NWS_MLP_KERNEL");
-    return e == nullptr ? 0 : strcmp(e, "tiles") == 0 ? 1 : strcmp(e, "frames") == 0 ? 2 : 0;
-  }();
-  const int mode = g_mlp_kernel_mode ? g_mlp_kernel_mode : env_mode;
+  // enough frames to give most CUs a 256-frame workgroup: wave-resident frames
+  const int mode = g_mlp_kernel_mode;
   const long long F = (long long)B * T;
   // (from the point where the 64-frame tile kernel needs a second round of workgroups: 256 tiles)
   const bool many = (long long)B * ((T + kFT2 - 1) / kFT2) > 256;
@@ -1380,37 +1336,22 @@ int nws_frame_mlps(const NwsWeights* w, const float* gru_out, const float* fir_d
                               (int)sizeof(WrLds));
       if (e != hipSuccess) return (int)e;
     }
-    // both paths of a frame block on one XCD (see the kernel); NWS_MLP_XCD=0 restores grid (blocks, 2) (measurements)
-    static const bool xcd_map = [] { const char* e = getenv("NWS_MLP_XCD"); return !(e && e[0] == '0'); }();
+    // both paths of a frame block on one XCD (see the kernel)
     const unsigned nblk = (unsigned)((F + kWrFrames - 1) / kWrFrames);
-    const int xcd_blocks = xcd_map ? (int)nblk : 0;
-    const dim3 gridw = xcd_map ? dim3(16 * ((nblk + 7) / 8), 1) : dim3(nblk, 2);
-    const int abl = g_mlp_dbg >> 4;
-    if (abl == 6 && g_mlp_probe) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(frame_mlps_wr_kernel<false, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WrLds));
-      frame_mlps_wr_kernel<false, 6><<<gridw, 512, sizeof(WrLds), (hipStream_t)stream>>>(*w, gru_out, (int)F, T, static_cast<float*>(g_mlp_probe), film_out, nullptr, fir_out, xcd_blocks);
-    } else if (abl == 1 || abl == 2 || abl == 3 || abl == 5) {
-      auto fn = abl == 1 ? frame_mlps_wr_kernel<false, 1> : abl == 2 ? frame_mlps_wr_kernel<false, 2> : abl == 3 ? frame_mlps_wr_kernel<false, 3> : frame_mlps_wr_kernel<false, 5>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WrLds));
-      fn<<<gridw, 512, sizeof(WrLds), (hipStream_t)stream>>>(*w, gru_out, (int)F, T, nullptr, film_out, nullptr, fir_out, xcd_blocks, -1);
-    } else if (abl == 7 || abl == 8) {   // one path's workgroups alone (the other path's outputs are not written)
-      frame_mlps_wr_kernel<false><<<gridw, 512, sizeof(WrLds), (hipStream_t)stream>>>(*w, gru_out, (int)F, T, nullptr, film_out, nullptr, fir_out, xcd_blocks, abl - 7);
-    } else if (!emb_out && !H_out)
+    const int xcd_blocks = (int)nblk;
+    const dim3 gridw(16 * ((nblk + 7) / 8), 1);
+    if (!emb_out && !H_out)
       frame_mlps_wr_kernel<false><<<gridw, 512, sizeof(WrLds), (hipStream_t)stream>>>(*w, gru_out, (int)F, T, nullptr, film_out, nullptr, fir_out, xcd_blocks);
     else
       frame_mlps_wr_kernel<true><<<gridw, 512, sizeof(WrLds), (hipStream_t)stream>>>(*w, gru_out, (int)F, T, emb_out, film_out, H_out, fir_out, xcd_blocks);
     NWS_CHECK_LAUNCH();
     return NWS_OK;
   }
-  // more than one 32-frame tile per utterance: 64-frame tiles.  NWS_MLP_TILE=32 keeps the 32-frame kernel for A/B timing
+  // more than one 32-frame tile per utterance: 64-frame tiles
   // (same box, back to back at B=64, T=500: 66.4 us per call with 32-frame tiles, 62.5 with 64-frame tiles)
-  static const bool tile64 = [] {
-    const char* e = getenv("NWS_MLP_TILE");
-    return e == nullptr || atoi(e) != 32;
-  }();
   // (only when the 64-frame grid still gives every CU a workgroup: at B = 1 the 16 workgroups of the 32-frame kernel finish
   // a 4 s clip sooner than 8 twice as long ones - batch-1 latency 0.305 against 0.32 ms)
-  if (w->mlp_frags != nullptr && T > kFT && tile64 && (long long)B * ((T + kFT2 - 1) / kFT2) >= 256) {
+  if (w->mlp_frags != nullptr && T > kFT && (long long)B * ((T + kFT2 - 1) / kFT2) >= 256) {
     static unsigned long long attr64 = 0;
     if (nws_first_use_on_device(attr64)) {
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(frame_mlps64_kernel<false>),
@@ -1431,8 +1372,7 @@ int nws_frame_mlps(const NwsWeights* w, const float* gru_out, const float* fir_d
   // one or two frames per utterance (256-sample streaming buffers, scripts/time_buffer_sizes.py): the matrix-vector form of mlp_few.h
   // (four frames through the NF = 4 instantiation measured no faster than the tile kernel: 65.5 against 64.8 us per 512-sample buffer)
   if (w->mlp_frags != nullptr && !emb_out && !H_out && T <= 2 && mode == 0 && few_frames_enabled()) {
-    frame_mlps_few_kernel<2><<<dim3(2, B), 256, 0, (hipStream_t)stream>>>(*w, gru_out, T, film_out, fir_out, T, 0, NwsStreamNoiseWin{},
-                                                                          static_cast<long long*>(g_mlp_probe));
+    frame_mlps_few_kernel<2><<<dim3(2, B), 256, 0, (hipStream_t)stream>>>(*w, gru_out, T, film_out, fir_out, T, 0, NwsStreamNoiseWin{});
     NWS_CHECK_LAUNCH();
     return NWS_OK;
   }
@@ -1466,7 +1406,7 @@ int nws_frame_mlps_stream(const NwsWeights* w, const float* gru_out, int B, int 
   }
   // one or two frames: the matrix-vector form (NWS_MLP_FEW=0 keeps the tile kernel: measurements, bit-identity tests)
   if (few_frames_enabled() && T <= 2) {
-    frame_mlps_few_kernel<2><<<dim3(2, B + 1), 256, 0, (hipStream_t)stream>>>(*w, gru_out, T, film_w, fir_w, out_T, out_off, *win, nullptr);
+    frame_mlps_few_kernel<2><<<dim3(2, B + 1), 256, 0, (hipStream_t)stream>>>(*w, gru_out, T, film_w, fir_w, out_T, out_off, *win);
     NWS_CHECK_LAUNCH();
     return NWS_OK;
   }

@@ -1226,10 +1226,7 @@ int nws_g_gru(const float* w_ih, const float* w_hh, const float* b_ih, const flo
   const size_t lds = ((size_t)2 * hidden + C_in) * sizeof(float);
   if (lds > 160 * 1024) return NWS_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  // (measurement switches, read once: NWS_G_GRU_RUNTIME keeps the runtime-size recurrence for the default shape, NWS_G_GRU_L2 the
-  // form that reads W_hh from L2 every step)
-  static const bool env_runtime = getenv("NWS_G_GRU_RUNTIME") != nullptr, env_l2 = getenv("NWS_G_GRU_L2") != nullptr;
-  if (hidden == 128 && C_in == 2 && !env_runtime) {
+  if (hidden == 128 && C_in == 2) {
     // the reference's default recurrence (GRU(2 -> 128)) inside an otherwise non-default configuration: the fused path's
     // kernel (control_gru.hip: 0.44 us per step against 0.8 for the runtime-size recurrence below), same layouts
     NwsWeights w{};
@@ -1239,7 +1236,7 @@ int nws_g_gru(const float* w_ih, const float* w_hh, const float* b_ih, const flo
     w.gru_b_hh = b_hh;
     return nws_control_gru_state(&w, control, B, C_total, T, h0, out, hT, stream);
   }
-  if (hidden <= 128 && !env_l2) {
+  if (hidden <= 128) {
     // W_hh in registers: four lanes per hidden unit (whole waves: units rounded up to 16)
     const int threads = 4 * ((hidden + 15) & ~15);
     const int kq = hidden <= 32 ? 8 : hidden <= 64 ? 16 : 32;
@@ -1390,10 +1387,9 @@ static int g_fir_design_impl(const float* H, const float* window, int fir_len, i
   if (!H || !window || !fir_out || B <= 0 || T <= 0 || fir_len < 2 || (fir_len & 1)) return NWS_ERR_BAD_ARG;
   if (B > 65535) return NWS_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  static const bool valu_only = [] { const char* e = getenv("NWS_G_FIR"); return e && !strcmp(e, "valu"); }();
   const int nb = fir_len / 2 + 1;
   const size_t lds_mfma = (size_t)(nb + 1) * 33 * sizeof(float);
-  if (!valu_only && lds_mfma <= 160 * 1024) {
+  if (lds_mfma <= 160 * 1024) {
     float* D = dmat;
     if (!D && (hipMallocAsync(reinterpret_cast<void**>(&D), (size_t)nb * fir_len * sizeof(float), st) != hipSuccess || !D))
       return NWS_ERR_WORKSPACE;
@@ -1428,10 +1424,9 @@ int nws_g_fir_noise(const float* fir, const float* noise, int fir_len, int hop, 
   const long long N = (long long)T * hop;
   if (fir_len < hop || fir_len / 2 >= N - 1 || B > 65535) return NWS_ERR_UNSUPPORTED;
   // matrix-pipe form (rows = utterances, shared noise circulant) when the tap tile fits LDS and a wave's column tiles its
-  // registers; NWS_G_FIR=valu keeps the per-sample kernel
-  static const bool valu_only = [] { const char* e = getenv("NWS_G_FIR"); return e && !strcmp(e, "valu"); }();
+  // registers, else the per-sample kernel
   const size_t lds = ((size_t)32 * (fir_len + 1) + 2 * (size_t)fir_len) * sizeof(float);
-  if (!valu_only && lds <= 160 * 1024 && hop <= 128 * kFirTilesPerWave) {
+  if (lds <= 160 * 1024 && hop <= 128 * kFirTilesPerWave) {
     static unsigned long long attr = 0;
     if (int rc = ensure_lds(reinterpret_cast<const void*>(g_fir_noise_mfma_kernel), attr)) return rc;
     g_fir_noise_mfma_kernel<<<dim3(T, (B + 31) / 32), 256, lds, (hipStream_t)stream>>>(fir, noise, (int)N - 1, fir_len, hop, T, B,
@@ -1549,15 +1544,14 @@ static int g_exciter_newt_fused(const NwsGenericModel* m, const float* f0_up, co
                                 const float* rand_phase, const float* film, int B, int T, int N, float sample_rate, float* scratch,
                                 float* newt_out, float* exciter_out, float* shaped, void* stream) {
   const int S = m->n_shapers, K = m->n_harmonics, OC = m->out_channels;
-  if (S > 64 || OC > 4 || B > 65535 || getenv("NWS_G_STAGES")) return NWS_ERR_UNSUPPORTED;
+  if (S > 64 || OC > 4 || B > 65535) return NWS_ERR_UNSUPPORTED;
   const bool exc_only = m->shaper.lut == nullptr;     // sin-MLP shapers: see EXC_ONLY
   hipStream_t st = (hipStream_t)stream;
   const float scale = (float)T / (float)N;
   const NwsShaperDesc* d = &m->shaper;
   const GShaper P = to_dev(d);
-  static const bool valu_mixer = [] { const char* e = getenv("NWS_G_EXCITER"); return e && !strcmp(e, "valu"); }();
-  if (!valu_mixer) {
-    // matrix-pipe mixer: tiles of 32 samples, `tpw` per wave as long as the launch keeps >= 1024 workgroups
+  {
+    // matrix-pipe mixer (the thread-per-sample kernel below when its LDS does not fit): tiles of 32 samples, `tpw` per wave as long as the launch keeps >= 1024 workgroups
     const int MT = S <= 32 ? 1 : 2, SBM = 32 * MT, K16 = (K + 15) / 16;
     int tpw = 4;
     while (tpw > 1 && (long long)((N + 128 * tpw - 1) / (128 * tpw)) * B < 1024) tpw >>= 1;
@@ -1567,9 +1561,8 @@ static int g_exciter_newt_fused(const NwsGenericModel* m, const float* f0_up, co
       return ((size_t)K16 * MT * 512 + 16 * K16 + 5 * (size_t)SBM + (exc_only ? 0 : (size_t)8 * SBM * frames)) * sizeof(float);
     };
     // FOUR workgroups per CU when fewer tiles per wave allow it (120 registers permit 4 waves per SIMD; the fragments alone
-    // are 28 KB at the default sizes: 44.7 KB = 3 workgroups with four tiles per wave, 40.6 KB = 4 with two), else two.
-    // NWS_G_TILE_LDS=<bytes> moves the first limit (measurements; 81920 = the rule before)
-    static const size_t lds_goal = [] { const char* e = getenv("NWS_G_TILE_LDS"); return e ? (size_t)atoi(e) : (size_t)40960; }();
+    // are 28 KB at the default sizes: 44.7 KB = 3 workgroups with four tiles per wave, 40.6 KB = 4 with two), else two
+    constexpr size_t lds_goal = 40960;
     {
       int t4 = tpw;
       while (t4 > 1 && lds_of(t4) > lds_goal) t4 >>= 1;

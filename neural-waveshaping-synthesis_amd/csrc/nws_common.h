@@ -109,7 +109,7 @@ __device__ __forceinline__ float nws_sinf(float x) {
 // ---------------------------------------------------------------------------------------------
 // Fast sine for the 6.5 M oscillator evaluations per utterance: the hardware v_sin_f32 (argument in turns)
 // behind an exact-product reduction  p = x*C_hi, e = fma(x, C_hi, -p) (the rounding error of p, exact),
-// t = (p - rint(p)) + (e + x*C_lo).  Measured on MI355X against float64 (tools/measure_sin.py): max abs
+// t = (p - rint(p)) + (e + x*C_lo).  Measured on MI355X against float64 (a since retired probe): max abs
 // error 2.4e-7 for |x| <= 5e6 (rms 4.6e-8), 2.2x the throughput of nws_sinf.  The oscillator needs ~1e-6.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float nws_sin_turns(float x) {  // caller guarantees |x| <= 6e6

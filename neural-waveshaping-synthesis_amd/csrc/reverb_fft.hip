@@ -789,18 +789,16 @@ int nws_reverb_plan(int N, int ir_len_plus1, NwsReverbPlan* plan) {
   for (int m = n2; m >= 32; m >>= 1)
     if (Lc / m == 125 && Lc % m == 0) n2 = m;
   const int n1 = n2 >= 32 ? Lc / n2 : 0;
-  int dense_max = kDenseMaxN1;
-  // (the two NWS_REVERB_* switches are re-read per call on purpose: tests and tools/reverb_lengths.py flip them in-process; the
-  // plan is host-only and the Python engine caches it per length, so this is not on a per-forward path)
-  if (const char* e = getenv("NWS_REVERB_DENSE_MAX")) dense_max = atoi(e);   // measurements only
-  if (n2 >= 32 && (n1 == 125 || n1 <= dense_max)) {
+  if (n2 >= 32 && (n1 == 125 || n1 <= kDenseMaxN1)) {
     plan->L = Lc;
     plan->N1 = n1;
     plan->N2 = n2;
     plan->nblk = 1;
     return NWS_OK;
   }
-  // overlap-save on 125 x 2^k transforms; NWS_REVERB_OLS_N2 pins the row size (measurements)
+  // overlap-save on 125 x 2^k transforms; NWS_REVERB_OLS_N2 pins the row size (measurements).  (It is re-read per call on
+  // purpose: tests and tools/reverb_lengths.py flip it in-process; the plan is host-only and the Python engine caches it per
+  // length, so this is not on a per-forward path)
   if ((Lc & 1) == 0) {
     const int hist = ir_len_plus1 - 1;
     int forced = 0;

@@ -381,9 +381,7 @@ class Engine:
         """Exact sin-MLP shapers: may the sines of the hidden and output layers go to v_sin_f32 without a v_fract in front?
         Their inputs are sines, so a row's pre-activation is bounded by sum |W| + |b| whatever the signal; v_sin_f32 reduces
         arguments inside +-256 turns itself.  One-time host check from the weights (the shipped checkpoints: 0.6 turns; the bound
-        is held to half the domain).  NWS_BANK_FRACT=1 keeps the v_fract for A/B timing."""
-        if os.environ.get("NWS_BANK_FRACT"):
-            return False
+        is held to half the domain)."""
         sh = self._model_ref.newt._modules.get("shaping_fn")
         if sh is None or getattr(sh, "depth", 0) != 4:
             return False

@@ -15,8 +15,6 @@ NWS_BENCH_FORCE_DIST=1 python bench.py --full --no-cpu-baseline --pmc off --legs
 bash tools/world1_check.sh > gpurun_out/ev/world1_ab.txt 2>&1
 bash tools/scale_check.sh --dry-run --out gpurun_out/ev/scale_dry > gpurun_out/ev/scale_check_dry_run.txt 2>&1
 bash tools/range_check.sh > gpurun_out/ev/range_proven_ab.txt 2>&1
-VARIANTS=12,44,36,68 python tools/exciter_variants.py > gpurun_out/ev/exciter_variants.txt 2>&1
-python tools/gru_variants.py > gpurun_out/ev/gru_variants.txt 2>&1
 python scripts/time_buffer_sizes.py --use-fast-newt --checkpoint tests/golden/weights_vn.npz 2>/dev/null | grep '^buffer' > gpurun_out/ev/buffer_fast.txt
 python scripts/time_buffer_sizes.py --checkpoint tests/golden/weights_vn.npz 2>/dev/null | grep '^buffer' > gpurun_out/ev/buffer_exact.txt
 rm -f gpurun_out/ev/streaming.jsonl
@@ -25,22 +23,18 @@ for b in 1 16; do
   python scripts/time_streaming.py --batch-size $b --num-hops 2000 --static-io --json-out gpurun_out/ev/streaming.jsonl 2>/dev/null | grep '^stateful' >> gpurun_out/ev/streaming_stateful.txt
   python scripts/time_streaming.py --batch-size $b --num-hops 500 --no-graph --json-out gpurun_out/ev/streaming.jsonl 2>/dev/null | grep '^stateful' >> gpurun_out/ev/streaming_stateful.txt
 done
-# round 4: the reverb at every length, the two frame-MLP kernel families (+ ablations, cycle timeline), the runtime-size path
+# round 4: the reverb at every length, the two frame-MLP kernel families, the runtime-size path
 python tools/reverb_lengths.py > gpurun_out/ev/reverb_lengths.txt 2>&1
 MODES=1,2 python tools/mlp_variants.py 64 500 48 500 32 500 128 500 > gpurun_out/ev/mlp_variants.txt 2>&1
-python tools/mlp_timeline.py > gpurun_out/ev/mlp_timeline.txt 2>&1
 python tools/generic_profile.py > gpurun_out/ev/generic_path.txt 2>&1
 bash tools/generic_kernels.sh 64 500 > gpurun_out/ev/generic_kernels.txt 2>&1
-# round 6: queue placement by measurement, the 8-rank queue population on one GPU, CU pressure, the two measured-as-nothing kernel items
+# round 6: queue placement by measurement, the 8-rank queue population on one GPU, CU pressure
 python tools/queue_pipe_map.py --layout nnnnhhhh --repeat 2 > gpurun_out/ev/queue_pipe_map_final.txt 2>&1
 bash tools/placement_ab.sh > /dev/null 2>&1; cp gpurun_out/placement_ab.txt gpurun_out/ev/placement_ab.txt
 bash tools/fake_peers_ab.sh > /dev/null 2>&1; cp gpurun_out/fake_peers_ab.txt gpurun_out/ev/fake_peers_ab.txt
 python tools/cu_pressure.py > gpurun_out/ev/cu_pressure.txt 2>&1
-python tools/film_dma_ab.py > gpurun_out/ev/film_dma_ab.txt 2>&1
-python tools/mlp_paths_ab.py > gpurun_out/ev/mlp_paths_ab.txt 2>&1
-# round 6, last session: the streaming hop's launch structures (bit-identity + p50 per form), the few-frame MLP kernel's cycle timeline
+# round 6, last session: the streaming hop's launch structures (bit-identity + p50 per form)
 bash tools/stream_hop_ab.sh 2>&1 | grep -E "p50|outputs" > gpurun_out/ev/stream_hop_ab.txt
-python tools/mlp_few_timeline.py 2>&1 | grep -E "^rep [345]" > gpurun_out/ev/mlp_few_timeline.txt
 bash tools/collect_profiles.sh ${ROUND:-r06} > gpurun_out/ev/collect.log 2>&1
 ls gpurun_out/prof_${ROUND:-r06} | head -30
 du -sh gpurun_out

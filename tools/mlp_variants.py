@@ -22,7 +22,7 @@ def main():
     # only the product kernel families are compared (1 tile kernels, 2 wave-resident frames): an ablation mode's output is
     # meaningless by construction and used to print `nan` into the one correctness column of profiles/r0x/mlp_variants.txt
     if not set(MODES) <= {1, 2}:
-        raise SystemExit("MODES: 1 (tile kernels) and / or 2 (wave-resident frames); timing ablations live in tools/mlp_timeline.py")
+        raise SystemExit("MODES: 1 (tile kernels) and / or 2 (wave-resident frames)")
     for B, T in shapes:
         gru = torch.tanh(torch.randn(B, T, 128, device="cuda"))
         res = {}

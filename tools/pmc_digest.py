@@ -59,7 +59,7 @@ def main(root):
     kernels = {}
     opt_bits = None
     for k in out:
-        mm = re.match(r"exciter_newt_kernel<4, 0, 2, (\d+)", k)
+        mm = re.match(r"exciter_newt_kernel<4, 2, (\d+)", k)
         if mm:
             opt_bits = int(mm.group(1))
     # template OPT bits of the hot-path kernel -> NwsWeights.exciter_opts value that selects it (csrc/exciter_newt.hip)
