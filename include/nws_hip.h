@@ -284,6 +284,37 @@ int nws_stream_reverb_tail(const NwsReverbPlan* plan, const void* reverb_tables,
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Slot mode of the stateful stream: B independent voice slots that start and stop on their own, one hop of K <= 16 frames per
+ * call, (B, 128 K) out every hop.  `events` is a (B) int32 array in DEVICE memory with this hop's word per slot, read by the
+ * hop's launches (a captured hop stays valid whatever the events):
+ *   NWS_SLOT_ACTIVE             the slot's voice covers this hop's frames (set together with START on the voice's first hop)
+ *   NWS_SLOT_START              this hop's frames are the voice's first frames (its recurrence, phase and noise start here)
+ *   NWS_SLOT_STOP               this hop's frames are the voice's last frames
+ *   NWS_SLOT_RELEASE            (alone) the hop after the stop hop: the voice's last 64 samples come out
+ *   0                           idle: inputs are not read into any output; the slot emits its dry signal 0 and its reverb tail
+ * Voice v of slot b, starting at stream frame a with T frames, is the one-shot pre-reverb signal of its own (f0, control) with the
+ * stream's phase draw and the noise samples [128 a, 128 (a + T) - 1) of the stream's noise, placed at output samples
+ * [128 a + 64, 128 (a + T) + 64); out = dry + linear reverb of the slot's dry signal.  The first call (frames_seen == 0) is an
+ * all-idle pre-roll whose output the caller drops.  NWS_ERR_UNSUPPORTED for K > 16.  State: nws_stream_slot_state_bytes.  Hops of
+ * one or two frames take the four-launch form up to B = 512 slots, everything else the seven-launch form.
+ */
+/* byte offset of the stream's position counters (int64 [8]) in the state blob; counters[5] != 0: a frame-MLP workgroup of a
+ * four-launch hop gave up waiting for its recurrence rows (that hop's rows are NaN) */
+size_t nws_stream_counters_offset(int B, int max_frames, int ir_len);
+/* state blob of a slot-mode stream (hops of at most max_frames <= 16 frames: no FFT reverb buffers) */
+size_t nws_stream_slot_state_bytes(int B, int max_frames, int ir_len);
+#define NWS_SLOT_START 1
+#define NWS_SLOT_STOP 2
+#define NWS_SLOT_RELEASE 4
+#define NWS_SLOT_ACTIVE 8
+int nws_stream_step_slots(const NwsWeights* w, const float* fir_design, void* state, size_t state_bytes, int B, int max_frames,
+                          const float* f0 /* (B,K) */, const float* control /* (B,C,K) */, int C, int K, long long frames_seen,
+                          long long nz_prev_start, float sample_rate, const float* phase_u, const float* rand_phase,
+                          const float* noise_new, const float* noise_all, int noise_all_len, const float* ir, int ir_len,
+                          const int* events /* (B) device */, float* out /* (B, 128 K) */, float* pre_out /* optional */,
+                          void* stream);
+
+/*
  * Stand-alone forms of the reference's sub-modules ("the seven module classes" are public interface).  Inside
  * nws_forward the same arithmetic is fused; these entry points serve callers that invoke a sub-module on its own
  * (model.osc(f0), model.newt(exciter, emb), model.h_generator(emb), model.noise_synth(H), ...).

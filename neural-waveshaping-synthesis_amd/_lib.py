@@ -181,6 +181,11 @@ _PROTOTYPES = {
     "nws_stream_step": (C.c_int, [C.POINTER(NwsWeights), _fp, C.POINTER(NwsReverbPlan), _fp, _fp, _fp, C.c_size_t, C.c_int, C.c_int,
                                   _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_float, _fp, _fp,
                                   _fp, _fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp]),
+    "nws_stream_counters_offset": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nws_stream_slot_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nws_stream_step_slots": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, C.c_size_t, C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int,
+                                        C.c_longlong, C.c_longlong, C.c_float, _fp, _fp, _fp, _fp, C.c_int, _fp, C.c_int, _fp, _fp,
+                                        _fp, _fp]),
     "nws_stream_reverb_tail": (C.c_int, [C.POINTER(NwsReverbPlan), _fp, _fp, _fp, C.c_size_t, C.c_int, C.c_int, C.c_int, _fp, _fp,
                                          C.c_size_t, _fp]),
     "nws_profile_begin": (C.c_int, [C.c_int, C.c_uint]),

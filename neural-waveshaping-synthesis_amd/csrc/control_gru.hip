@@ -81,7 +81,11 @@ __global__ __launch_bounds__(256, 1) void control_gru_kernel(NwsWeights w, const
         const int mb = idx >> 1;
         const long long target = side.counters[1] + side.counters[3] + side.K;
         __shared__ int gave_up;
-        nws_mlp_few_path<2>(FL, w, side.gru_out, side.K, mb, idx & 1, side.film_w, side.fir_w, side.out_T, side.out_off, tid, [&] {
+        // (slot mode: a row without a voice in this hop writes into the junk rows - the head fills its window rows)
+        const int ev = side.ev != nullptr ? side.ev[mb] : NWS_SLOT_ACTIVE;
+        const bool voiced = (ev & NWS_SLOT_ACTIVE) != 0;
+        nws_mlp_few_path<2>(FL, w, side.gru_out, side.K, mb, idx & 1, voiced ? side.film_w : side.film_junk,
+                            voiced ? side.fir_w : side.fir_junk, side.out_T, side.out_off, tid, [&] {
           if (tid == 0) {
             int spins = 0, lost = 0;
             while (__hip_atomic_load(&side.gru_flag[mb], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != target) {
@@ -98,6 +102,13 @@ __global__ __launch_bounds__(256, 1) void control_gru_kernel(NwsWeights w, const
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // gru_out as the recurrence workgroup left it
           return gave_up == 0;
         });
+        if (ev & NWS_SLOT_START) {
+          // a starting voice: its first new frame's row is also window row 0 (the duplicate the left clamp needs)
+          __syncthreads();   // this workgroup's rows are complete (its global writes are visible to it)
+          const int n = (idx & 1) ? NWS_FIR_HALF : NWS_FILM_CH;
+          float* win = (idx & 1) ? side.fir_w : side.film_w;
+          for (int c = tid; c < n; c += 256) win[(size_t)mb * side.out_T * n + c] = win[((size_t)mb * side.out_T + side.out_off) * n + c];
+        }
         return;
       }
       idx -= 2 * side.B;
@@ -153,8 +164,10 @@ __global__ __launch_bounds__(256, 1) void control_gru_kernel(NwsWeights w, const
   const float b_r = kSig * (w.gru_b_ih[unit] + w.gru_b_hh[unit]), b_z = kSig * (w.gru_b_ih[kH + unit] + w.gru_b_hh[kH + unit]);
   const float bi_n = kTanh * w.gru_b_ih[2 * kH + unit], bh_n = kTanh * w.gru_b_hh[2 * kH + unit];
 
-  float h_prev = h0 != nullptr ? h0[(size_t)b * kH + unit] : 0.0f;
-  if (tid < kH) h_lds[0][tid] = h0 != nullptr ? h0[(size_t)b * kH + tid] : 0.0f;
+  // (slot mode: a row whose voice starts in this hop begins from h = 0 - a select, its carried state may be anything)
+  const bool h_live = h0 != nullptr && !(side.ev != nullptr && (side.ev[b] & NWS_SLOT_START));
+  float h_prev = h_live ? h0[(size_t)b * kH + unit] : 0.0f;
+  if (tid < kH) h_lds[0][tid] = h_live ? h0[(size_t)b * kH + tid] : 0.0f;
   const float* x0p = control + ((size_t)b * C + 0) * T;
   const float* x1p = control + ((size_t)b * C + 1) * T;
 

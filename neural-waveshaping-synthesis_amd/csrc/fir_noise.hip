@@ -39,28 +39,45 @@ __device__ __forceinline__ float padded_noise(const float* __restrict__ noise, i
   return noise[s];
 }
 
+// slot mode of a streaming window (ROWS): row b's noise reflects about its own bounds rows[b].x (first) and rows[b].y (last
+// sample) instead of 0 and len - 1, and its frames start at window frame rows[b].z: earlier frames are silent and the first
+// one's left hop is that frame alone (overlap count 1), as at the start of a one-shot signal
+__device__ __forceinline__ float row_noise(const float* __restrict__ noise, int lo, int hi, int origin, int i) {
+  int s = i - origin;
+  if (s < lo) s = 2 * lo - s;
+  if (s > hi) s = 2 * hi - s;
+  s = s < 0 ? 0 : s;
+  return noise[s];
+}
+
+template <bool ROWS>
 __global__ __launch_bounds__(256) void fir_noise_kernel(const float* __restrict__ fir, const float* __restrict__ noise,
                                                         const float* __restrict__ add_in, int T, int len, int origin,
-                                                        float* __restrict__ out) {
+                                                        float* __restrict__ out, const int4* __restrict__ rows) {
   __shared__ __attribute__((aligned(16))) NoiseLds L;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int half = lane >> 5, q = lane & 31;
   const int b = blockIdx.y;
   const int t0 = blockIdx.x * kHopsPerBlock;
   const int N = T * kHop;
+  int4 rb = make_int4(0, 0, 0, 0);
+  if constexpr (ROWS) rb = rows[b];
+  const int t_lo = ROWS ? rb.z : 0;
 
   // fir holds the upper half-taps u[d] = h[128 + d]; the row is symmetric about tap 128 and h[0] = 0 (include/nws_hip.h)
   for (int e = tid; e < (kHopsPerBlock + 1) * kL; e += 256) {
     const int fr = e >> 8, k = e & 255;
     const int t = t0 - 1 + fr;
     const int d = k >= kHalf ? k - kHalf : kHalf - k;      // k = 0 -> d = 128: the zero tap
-    const float v = (t >= 0 && t < T && d < kHalf) ? fir[((size_t)b * T + t) * kHalf + d] : 0.0f;
+    const float v = (t >= t_lo && t < T && d < kHalf) ? fir[((size_t)b * T + t) * kHalf + d] : 0.0f;
     L.taps[fr][k] = v;
     L.taps1[fr][(k + 1) & 255] = v;
   }
   for (int e = tid; e < (kHopsPerBlock + 1) * kHop + kHop; e += 256) {
     const int i = (t0 - 1) * kHop + e;  // index into the padded noise, valid range [0, N+255)
-    L.sig[e] = (i >= 0 && i < N + kL - 1) ? padded_noise(noise, len, origin, i) : 0.0f;
+    float v = 0.0f;
+    if (i >= 0 && i < N + kL - 1) v = ROWS ? row_noise(noise, rb.x, rb.y, origin, i) : padded_noise(noise, len, origin, i);
+    L.sig[e] = v;
   }
   __syncthreads();
 
@@ -108,7 +125,7 @@ __global__ __launch_bounds__(256) void fir_noise_kernel(const float* __restrict_
   const float o2 = y2 + nws_swap_halves(y2);
   const float o3 = y3 + nws_swap_halves(y3);
   if (half == 0) {
-    const float inv = t == 0 ? 1.0f : 0.5f;
+    const float inv = t == t_lo ? 1.0f : 0.5f;
     const size_t o = (size_t)b * N + (size_t)t * kHop + 4 * q;
     float4 r = make_float4(o0 * inv, o1 * inv, o2 * inv, o3 * inv);
     if (add_in != nullptr) {
@@ -402,7 +419,19 @@ extern "C" int nws_fir_noise_window(const float* fir, const float* noise, int no
     return NWS_OK;
   }
   const dim3 grid((T + kHopsPerBlock - 1) / kHopsPerBlock, B);
-  fir_noise_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(fir, noise, add_in, T, noise_len, origin, out);
+  fir_noise_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(fir, noise, add_in, T, noise_len, origin, out, nullptr);
+  NWS_CHECK_LAUNCH();
+  return NWS_OK;
+}
+
+// slot mode of a streaming window (stream.hip): per-row reflection bounds and first frames, every B on the per-utterance kernel
+// (the B >= 16 circulant GEMM shares one noise frame over 32 rows; per-row edges would have to be a fix-up beside it)
+extern "C" int nws_fir_noise_window_rows(const float* fir, const float* noise, int origin, const int4* rows, int B, int T,
+                                         float* out, void* stream) {
+  if (!fir || !noise || !out || !rows || B <= 0 || T <= 0 || origin < 0) return NWS_ERR_BAD_ARG;
+  if (B > 65535) return NWS_ERR_UNSUPPORTED;
+  const dim3 grid((T + kHopsPerBlock - 1) / kHopsPerBlock, B);
+  fir_noise_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(fir, noise, nullptr, T, 0, origin, out, rows);
   NWS_CHECK_LAUNCH();
   return NWS_OK;
 }

@@ -254,18 +254,34 @@ __device__ __forceinline__ float nws_leaky_relu(float x) { return x > 0.0f ? x :
 // launch of their own behind the oscillator and noise kernels.
 // ---------------------------------------------------------------------------------------------
 #define NWS_STREAM_RING 65536   // reverb-input ring per utterance (>= 31 999 samples of history + the longest chunk)
+// slot mode: per-row event word of a hop (include/nws_hip.h NWS_SLOT_*)
+#ifndef NWS_SLOT_START
+#define NWS_SLOT_START 1
+#define NWS_SLOT_STOP 2
+#define NWS_SLOT_RELEASE 4
+#define NWS_SLOT_ACTIVE 8
+#endif
 
 // pre-reverb value of emitted sample i of this step: oscillator branch [lo, hi) + noise branch (64 samples of residue first,
-// then this window's hops)
+// then this window's hops).  Slot mode (ev != NULL, nws_stream_step_slots): each row's event word of the hop decides which of its
+// emitted samples belong to a voice; every other sample is exactly 0, by a select (an idle row's window may hold anything)
 struct NwsPreSrc {
   const float* newt_w;
   const float* noise_w;
   const float* residue;
   int Nw, lo, R0, noise_off;
+  const int* ev;
 };
+// a voice starting in this hop begins at emitted sample 64 (window sample 128: the hop's first new frame); a releasing voice
+// ends there (its last 64 samples, the right half of its last frame)
+__device__ __forceinline__ bool nws_slot_emits(int e, int i) {
+  return (e & NWS_SLOT_ACTIVE) ? (!(e & NWS_SLOT_START) || i >= 64) : ((e & NWS_SLOT_RELEASE) && i < 64);
+}
 __device__ __forceinline__ float nws_pre_value(const NwsPreSrc& P, int b, int i) {
   const float nz = i < P.R0 ? P.residue[(size_t)b * 64 + i] : P.noise_w[(size_t)b * P.Nw + P.noise_off + i - P.R0];
-  return P.newt_w[(size_t)b * P.Nw + P.lo + i] + nz;
+  const float v = P.newt_w[(size_t)b * P.Nw + P.lo + i] + nz;
+  if (P.ev != nullptr) return nws_slot_emits(P.ev[b], i) ? v : 0.0f;
+  return v;
 }
 
 // sum_{i < 256} ir[256 p + i] * x[pos + j0 + tid - 1 - 256 p - i]  (tap m = 1 + 256 p + i, ir_[m] = ir[m-1]) for output
@@ -378,10 +394,72 @@ struct NwsStreamSide {
   const float* gru_out;         // (B, K, 128)
   int out_T, out_off;           // rows per utterance of film_w / fir_w, row of the first new frame
   NwsStreamNoiseWin win;
+  // slot mode: the hop's per-row event words (NULL: none); a row with NWS_SLOT_START begins its recurrence from h = 0.  In the
+  // four-launch hop the head also leaves each row's noise bounds (nzrows, from vage and n_len), and the frame-MLP workgroups of a
+  // row without a voice write into mlp_junk instead of the windows (the head fills those rows)
+  const int* ev;
+  int* vage;
+  int4* nzrows;
+  float* film_junk;
+  float* fir_junk;
+  int n_len;
 };
+
+// slot mode of the head (ev != NULL): window frame t of row b from the previous frame, a new frame or nothing (zeros), as in
+// stream_prep_kernel; rows of the FiLM / tap windows that no frame-MLP workgroup writes (all of an idle or releasing row, row 0 of
+// a continuing voice); carries re-based at a starting voice's sample 0; the row's noise bounds
+__device__ __forceinline__ void nws_stream_head_block_slots(const NwsStreamSide& H, int b, int tid, double* wave_tot) {
+  const int K = H.K, Tw = H.first ? K : K + 1, off = H.first ? 0 : 1;
+  const int e = H.ev[b];
+  for (int i = tid; i < Tw; i += 256) {
+    int s;
+    if (e & NWS_SLOT_RELEASE) s = -1;
+    else if (!(e & NWS_SLOT_ACTIVE)) s = -2;
+    else if (e & NWS_SLOT_START) s = i < off ? 0 : i - off;
+    else s = i < off ? -1 : i - off;
+    H.f0_w[(size_t)b * Tw + i] = s >= 0 ? H.f0_new[(size_t)b * K + s] : (s == -1 ? H.prev_f0[b] : 0.0f);
+  }
+  const bool hold = (e & NWS_SLOT_RELEASE) != 0;
+  const int rows = !(e & NWS_SLOT_ACTIVE) ? Tw : ((e & NWS_SLOT_START) ? 0 : off);
+  for (int i = tid; i < rows * NWS_FILM_CH; i += 256) {
+    const int c = i % NWS_FILM_CH;
+    H.film_w[(size_t)b * Tw * NWS_FILM_CH + i] = (hold || (e & NWS_SLOT_ACTIVE)) ? H.prev_film[(size_t)b * NWS_FILM_CH + c] : 0.0f;
+  }
+  for (int i = tid; i < rows * NWS_FIR_HALF; i += 256) {
+    const int c = i % NWS_FIR_HALF;
+    H.fir_w[(size_t)b * Tw * NWS_FIR_HALF + i] = (hold || (e & NWS_SLOT_ACTIVE)) ? H.prev_fir[(size_t)b * NWS_FIR_HALF + c] : 0.0f;
+  }
+  if (tid == 0) {
+    const int age = (e & NWS_SLOT_START) ? 0 : H.vage[b];
+    const int lo = 256 - 128 * (age < 2 ? age : 2);
+    const int hi = (e & NWS_SLOT_STOP) ? 128 * (Tw + 1) - 2 : H.n_len - 1;
+    const bool live = !H.first && (e & NWS_SLOT_ACTIVE);
+    H.nzrows[b] = make_int4(live ? lo : 0, live ? hi : H.n_len - 1, (!H.first && (e & NWS_SLOT_START)) ? 1 : 0, 0);
+    H.vage[b] = (e & NWS_SLOT_ACTIVE) ? (age + K < (1 << 20) ? age + K : (1 << 20)) : 0;
+  }
+  __syncthreads();   // the F0 window is complete and prev_f0 has been consumed: the next hop's previous frame is the window's last
+  if (tid == 0) H.prev_f0[b] = H.f0_w[(size_t)b * Tw + Tw - 1];
+  nws_phase_carry_block<4>(H.f0_w, nullptr, Tw, H.carry, b, tid, wave_tot);
+  __syncthreads();
+  const int nch = 4 * Tw;
+  double* cb = H.carry + (size_t)b * nch;
+  if (!H.first) {
+    // a starting voice: exclusive sum 0 at its sample 0 (window sample 128); otherwise spliced with the carried sum
+    const bool start = (e & NWS_SLOT_START) != 0;
+    const double base = start ? cb[4] : cb[2], s0 = start ? 0.0 : H.S[b];
+    __syncthreads();
+    for (int c = tid; c < nch; c += 256) cb[c] = start ? cb[c] - base : s0 + (cb[c] - base);
+    __syncthreads();
+  }
+  if (!H.final && tid == 0) H.S[b] = cb[nch - 2];
+}
 
 // 256 threads; wave_tot: 4 doubles of LDS
 __device__ __forceinline__ void nws_stream_head_block(const NwsStreamSide& H, int b, int tid, double* wave_tot) {
+  if (H.ev != nullptr) {
+    nws_stream_head_block_slots(H, b, tid, wave_tot);
+    return;
+  }
   const int K = H.K, Tw = H.first ? K : K + 1, off = H.first ? 0 : 1;
   for (int i = tid; i < Tw; i += 256) H.f0_w[(size_t)b * Tw + i] = (i < off) ? H.prev_f0[b] : H.f0_new[(size_t)b * K + i - off];
   if (off) {
@@ -407,6 +485,11 @@ __device__ __forceinline__ void nws_stream_head_block(const NwsStreamSide& H, in
   if (!H.final && tid == 0) H.S[b] = cb[nch - 2];    // through the last emitted sample (128 Tw - 64)
 }
 
+// fir_noise.hip: nws_fir_noise_window with per-row reflection bounds (x: first, y: last noise-window index of the row's voice) and
+// first window frame (z) - the slot mode of a streaming hop.  Internal to the library.
+extern "C" __attribute__((visibility("hidden"))) int nws_fir_noise_window_rows(const float* fir, const float* noise, int origin,
+                                                                               const int4* rows, int B, int T, float* out,
+                                                                               void* stream);
 // control_gru.hip: nws_control_gru_state with the extra workgroups `side` asks for (NULL: none).  Internal to the library.
 extern "C" __attribute__((visibility("hidden"))) int nws_control_gru_stream(const NwsWeights* w, const float* control, int B, int C,
                                                                             int T, const float* h0, float* gru_out, float* hT,

@@ -21,17 +21,20 @@ namespace {
 constexpr int kRing = NWS_STREAM_RING; // reverb-input ring per utterance (>= 31 999 history + the longest chunk)
 constexpr int kTapsPerPart = 256;
 constexpr int kMaxDirect = 2048;      // samples per step the time-domain reverb serves
+constexpr int kSlotFusedMaxB = 512;   // slot mode: rows of a four-launch hop (its in-launch wait needs every recurrence resident)
 
 size_t al(size_t b) { return (b + 255) & ~size_t(255); }
 
 struct Layout {
-  size_t h, h_next, prev_f0, prev_film, prev_fir, S, residue, ring, counters, gru_flag, nzwin;  // state
+  size_t h, h_next, prev_f0, prev_film, prev_fir, S, residue, ring, counters, gru_flag, nzwin, vage, nzrows;  // state
   size_t gru_out, film_new, fir_new, f0_w, film_w, fir_w, carry, newt_w, noise_w, pre, partial, x_lin, y_lin, rv_ws;   // scratch
+  size_t film_junk, fir_junk;   // slot mode, four-launch hop: frame-MLP rows of slots without a voice
   size_t rv_ws_bytes, total;
   int parts;
 };
 
-Layout layout(int B, int max_frames, int ir_len, size_t fft_ws_bytes) {
+// fft: reserve the FFT reverb's buffers when a chunk can exceed 2048 samples (slot mode never takes that path)
+Layout layout(int B, int max_frames, int ir_len, size_t fft_ws_bytes, bool fft = true) {
   Layout L{};
   size_t o = 0;
   auto take = [&](size_t bytes) {
@@ -51,6 +54,8 @@ Layout layout(int B, int max_frames, int ir_len, size_t fft_ws_bytes) {
   L.counters = take(64);
   L.gru_flag = take((size_t)B * 8);
   L.nzwin = take((Nw + 128 + 8) * 4);
+  L.vage = take((size_t)B * 4);          // slot mode: frames of each row's voice before this hop
+  L.nzrows = take((size_t)B * 16);       // slot mode: each row's noise bounds in this hop's window (int4)
   L.gru_out = take((size_t)B * K * NWS_HIDDEN * 4);
   L.film_new = take((size_t)B * K * NWS_FILM_CH * 4);
   L.fir_new = take((size_t)B * K * NWS_FIR_HALF * 4);
@@ -63,7 +68,12 @@ Layout layout(int B, int max_frames, int ir_len, size_t fft_ws_bytes) {
   L.pre = take((size_t)B * Nw * 4);
   L.parts = (ir_len + kTapsPerPart - 1) / kTapsPerPart;
   L.partial = take((size_t)L.parts * B * (Nw < (size_t)kMaxDirect ? Nw : (size_t)kMaxDirect) * 4);
-  if (Nw > (size_t)kMaxDirect) {
+  if (!fft) {
+    const size_t Tw2 = Tw < 3 ? Tw : 3;       // the four-launch hop: one or two new frames
+    L.film_junk = take((size_t)B * Tw2 * NWS_FILM_CH * 4);
+    L.fir_junk = take((size_t)B * Tw2 * NWS_FIR_HALF * 4);
+  }
+  if (fft && Nw > (size_t)kMaxDirect) {
     L.x_lin = take((size_t)B * (ir_len + Nw) * 4);
     L.y_lin = take((size_t)B * (ir_len + Nw) * 4);
     L.rv_ws_bytes = fft_ws_bytes;
@@ -84,7 +94,9 @@ __global__ __launch_bounds__(256) void stream_prep_kernel(const float* __restric
                                                           float* __restrict__ fir_w, double* __restrict__ carry,
                                                           float* __restrict__ nzwin, const float* __restrict__ noise_new,
                                                           int nz_shift, int nz_keep, int n_new, const float* __restrict__ noise_all,
-                                                          int noise_all_len, long long* __restrict__ counters) {
+                                                          int noise_all_len, long long* __restrict__ counters,
+                                                          const int* __restrict__ ev, int* __restrict__ vage,
+                                                          int4* __restrict__ nzrows, int n_len) {
   __shared__ double wave_tot[4];
   const int tid = threadIdx.x;
   const int b = blockIdx.x;
@@ -98,6 +110,48 @@ __global__ __launch_bounds__(256) void stream_prep_kernel(const float* __restric
   }
   // window = [previous frame] + new frames
   const int off = first ? 0 : 1;
+  if (ev != nullptr) {
+    // slot mode: window frame t of row b comes from src(t) = previous frame (-1), new frame (>= 0) or nothing (-2, zeros: an idle
+    // row's inputs are never read).  A starting row duplicates its first new frame into frame 0 (the lerp of window samples
+    // 128 .. 191 is then the one-shot's left clamp), a releasing row repeats its last frame (the right clamp)
+    const int e = ev[b];
+    auto src = [&](int t) {
+      if (e & NWS_SLOT_RELEASE) return -1;
+      if (!(e & NWS_SLOT_ACTIVE)) return -2;
+      if (e & NWS_SLOT_START) return t < off ? 0 : t - off;
+      return t < off ? -1 : t - off;
+    };
+    for (int i = tid; i < Tw; i += 256) {
+      const int s = src(i);
+      f0_w[(size_t)b * Tw + i] = s >= 0 ? f0_new[(size_t)b * K + s] : (s == -1 ? prev_f0[b] : 0.0f);
+    }
+    for (int i = tid; i < Tw * NWS_FILM_CH; i += 256) {
+      const int t = i / NWS_FILM_CH, c = i - t * NWS_FILM_CH, s = src(t);
+      film_w[(size_t)b * Tw * NWS_FILM_CH + i] = s >= 0 ? film_new[((size_t)b * K + s) * NWS_FILM_CH + c]
+                                                        : (s == -1 ? prev_film[(size_t)b * NWS_FILM_CH + c] : 0.0f);
+    }
+    for (int i = tid; i < Tw * NWS_FIR_HALF; i += 256) {
+      const int t = i / NWS_FIR_HALF, c = i - t * NWS_FIR_HALF, s = src(t);
+      fir_w[(size_t)b * Tw * NWS_FIR_HALF + i] = s >= 0 ? fir_new[((size_t)b * K + s) * NWS_FIR_HALF + c]
+                                                       : (s == -1 ? prev_fir[(size_t)b * NWS_FIR_HALF + c] : 0.0f);
+    }
+    if (tid < NWS_HIDDEN) h[(size_t)b * NWS_HIDDEN + tid] = h_next[(size_t)b * NWS_HIDDEN + tid];
+    if (tid == 0) {
+      // noise bounds in this window's noise index space (origin 0 after the first hop): the voice's first sample sits at
+      // 256 - 128 age (it reaches back into the window while its first frame is one of the window's frames), its last one, in a
+      // stopping hop, at 128 (Tw + 1) - 2 (the voice's noise has 128 T - 1 samples, like a one-shot draw)
+      const int age = (e & NWS_SLOT_START) ? 0 : vage[b];
+      const int lo = 256 - 128 * (age < 2 ? age : 2);
+      const int hi = (e & NWS_SLOT_STOP) ? 128 * (Tw + 1) - 2 : n_len - 1;
+      const bool live = !first && (e & NWS_SLOT_ACTIVE);
+      nzrows[b] = make_int4(live ? lo : 0, live ? hi : n_len - 1, (!first && (e & NWS_SLOT_START)) ? 1 : 0, 0);
+      vage[b] = (e & NWS_SLOT_ACTIVE) ? (age + K < (1 << 20) ? age + K : (1 << 20)) : 0;
+    }
+    __syncthreads();   // the window is complete and prev_* has been consumed: the next hop's previous frame is the window's last
+    if (tid == 0) prev_f0[b] = f0_w[(size_t)b * Tw + Tw - 1];
+    for (int c = tid; c < NWS_FILM_CH; c += 256) prev_film[(size_t)b * NWS_FILM_CH + c] = film_w[((size_t)b * Tw + Tw - 1) * NWS_FILM_CH + c];
+    for (int c = tid; c < NWS_FIR_HALF; c += 256) prev_fir[(size_t)b * NWS_FIR_HALF + c] = fir_w[((size_t)b * Tw + Tw - 1) * NWS_FIR_HALF + c];
+  } else {
   for (int i = tid; i < Tw; i += 256) f0_w[(size_t)b * Tw + i] = (i < off) ? prev_f0[b] : f0_new[(size_t)b * K + i - off];
   for (int i = tid; i < Tw * NWS_FILM_CH; i += 256) {
     const int t = i / NWS_FILM_CH, c = i - t * NWS_FILM_CH;
@@ -112,13 +166,21 @@ __global__ __launch_bounds__(256) void stream_prep_kernel(const float* __restric
   if (tid == 0) prev_f0[b] = f0_new[(size_t)b * K + K - 1];
   for (int c = tid; c < NWS_FILM_CH; c += 256) prev_film[(size_t)b * NWS_FILM_CH + c] = film_new[((size_t)b * K + K - 1) * NWS_FILM_CH + c];
   for (int c = tid; c < NWS_FIR_HALF; c += 256) prev_fir[(size_t)b * NWS_FIR_HALF + c] = fir_new[((size_t)b * K + K - 1) * NWS_FIR_HALF + c];
+  }
   // exclusive float64 prefix sums of the window's upsampled F0 at 32-sample granularity (the lerp clamps at the window edges;
   // those 64 + 64 samples are only emitted at the true ends of the stream)
   nws_phase_carry_block<4>(f0_w, nullptr, Tw, carry, b, tid, wave_tot);
   __syncthreads();
   const int nch = 4 * Tw;
   double* cb = carry + (size_t)b * nch;
-  if (!first) {
+  if (ev != nullptr && !first && (ev[b] & NWS_SLOT_START)) {
+    // slot mode, a voice starting in this hop: re-based so that the exclusive sum at its sample 0 (window sample 128) is exactly 0;
+    // differences of exact fp64 sums are exact, so they equal the one-shot forward's carries of the voice
+    const double base = cb[4];
+    __syncthreads();
+    for (int c = tid; c < nch; c += 256) cb[c] = cb[c] - base;
+    __syncthreads();
+  } else if (!first) {
     // sample 64 of the window is the first one not yet emitted: its running sum must continue the carried one.  Sums of
     // fp32 values in fp64 are exact, so the spliced carries are bit-identical to the one-shot forward's
     const double base = cb[2], s0 = S[b];
@@ -288,6 +350,16 @@ size_t nws_stream_state_bytes(int B, int max_frames, int ir_len, const NwsReverb
   return layout(B, max_frames, ir_len, plan ? nws_reverb_workspace_bytes(plan, B) : 0).total;
 }
 
+size_t nws_stream_slot_state_bytes(int B, int max_frames, int ir_len) {
+  if (B <= 0 || max_frames <= 0 || max_frames > kMaxDirect / 128 || ir_len <= 0) return 0;
+  return layout(B, max_frames, ir_len, 0, false).total;
+}
+
+size_t nws_stream_counters_offset(int B, int max_frames, int ir_len) {
+  if (B <= 0 || max_frames <= 0 || ir_len <= 0) return 0;
+  return layout(B, max_frames, ir_len, 0).counters;
+}
+
 int nws_stream_reset(void* state, size_t state_bytes, void* stream) {
   if (!state || state_bytes == 0) return NWS_ERR_BAD_ARG;
   stream_reset_kernel<<<512, 256, 0, (hipStream_t)stream>>>(static_cast<char*>(state), state_bytes);
@@ -321,18 +393,24 @@ int nws_stream_noise_draws(int K, int first, long long frames_seen) {
   return (int)(need_upto - have);
 }
 
-int nws_stream_step(const NwsWeights* w, const float* fir_design, const NwsReverbPlan* plan, const void* reverb_tables,
-                    const void* reverb_spectrum, void* state, size_t state_bytes, int B, int max_frames, const float* f0,
-                    const float* control, int C, int K, int first, int final, long long frames_seen, long long nz_prev_start,
-                    float sample_rate, const float* phase_u, const float* rand_phase, const float* noise_new,
-                    const float* noise_all, int noise_all_len, const float* ir, int ir_len, float* out, float* pre_out,
-                    void* stream) {
+}  // extern "C"
+
+namespace {
+
+// ev != NULL: slot mode (nws_stream_step_slots) - the seven-launch form whatever K, with the per-row events in the windows, the
+// recurrence's start state, the noise bounds and the emitted-sample mask
+int stream_step(const NwsWeights* w, const float* fir_design, const NwsReverbPlan* plan, const void* reverb_tables,
+                const void* reverb_spectrum, void* state, size_t state_bytes, int B, int max_frames, const float* f0,
+                const float* control, int C, int K, int first, int final, long long frames_seen, long long nz_prev_start,
+                float sample_rate, const float* phase_u, const float* rand_phase, const float* noise_new,
+                const float* noise_all, int noise_all_len, const float* ir, int ir_len, float* out, float* pre_out,
+                const int* ev, void* stream) {
   if (!w || !fir_design || !state || !f0 || !control || !phase_u || !rand_phase || !ir || !out) return NWS_ERR_BAD_ARG;
   if (B <= 0 || K <= 0 || K > max_frames || C < 2 || ir_len <= 0 || ir_len >= kRing / 2) return NWS_ERR_BAD_ARG;
   if ((noise_new == nullptr) == (noise_all == nullptr)) return NWS_ERR_BAD_ARG;
   if ((first != 0) != (frames_seen == 0)) return NWS_ERR_BAD_ARG;
   if (B > 65535) return NWS_ERR_UNSUPPORTED;
-  const Layout L = layout(B, max_frames, ir_len, plan ? nws_reverb_workspace_bytes(plan, B) : 0);
+  const Layout L = layout(B, max_frames, ir_len, plan ? nws_reverb_workspace_bytes(plan, B) : 0, ev == nullptr);
   if (L.total > state_bytes) return NWS_ERR_WORKSPACE;
   char* base = static_cast<char*>(state);
   auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
@@ -349,7 +427,7 @@ int nws_stream_step(const NwsWeights* w, const float* fir_design, const NwsRever
     const char* e = getenv("NWS_STREAM_SPLIT_REVERB");
     return e == nullptr || e[0] != '0';
   }();
-  const bool split_reverb = split_env && M <= 256 && L.parts >= 2;
+  bool split_reverb = split_env && M <= 256 && L.parts >= 2;
   // ... and then nothing is left for a prep launch either (NWS_STREAM_FUSE_HEAD=0 keeps it): the per-utterance head (F0 window, first
   // rows of the FiLM / tap windows, spliced carries) depends on nothing the hop computes - more workgroups of the recurrence launch;
   // the frame-MLP kernel writes its rows straight into the windows and carries one workgroup for the shared noise window and the
@@ -358,7 +436,7 @@ int nws_stream_step(const NwsWeights* w, const float* fir_design, const NwsRever
     const char* e = getenv("NWS_STREAM_FUSE_HEAD");
     return e == nullptr || e[0] != '0';
   }();
-  const bool fuse_head = head_env && split_reverb && K <= 32 && w->mlp_frags != nullptr;
+  bool fuse_head = head_env && split_reverb && K <= 32 && w->mlp_frags != nullptr;
   // ... and with one or two new frames the frame MLPs join the recurrence launch as well (two workgroups per utterance that fetch
   // their first weights while the recurrence runs and wait for its rows; NWS_STREAM_FUSE_MLP=0 keeps their launch).  Four launches.
   static const bool mlp_env = [] {
@@ -366,13 +444,23 @@ int nws_stream_step(const NwsWeights* w, const float* fir_design, const NwsRever
     const char* f = getenv("NWS_MLP_FEW");
     return (e == nullptr || e[0] != '0') && (f == nullptr || f[0] != '0');
   }();
-  const bool fuse_mlp = mlp_env && fuse_head && K <= 2;
+  bool fuse_mlp = mlp_env && fuse_head && K <= 2;
+  // slot mode: the four-launch hop carries the events (head, frame-MLP roles); every other form of a hop is the seven-launch one,
+  // and so is every hop of more than kSlotFusedMaxB rows - the frame-MLP roles wait inside the launch for their recurrence
+  // workgroups, which only works while all of them can be resident at once
+  if (ev != nullptr && !(fuse_mlp && B <= kSlotFusedMaxB)) split_reverb = fuse_head = fuse_mlp = false;
   const long long nz_start = nws_stream_noise_start(first, frames_seen);
   const long long have = first ? 0 : 128 * (frames_seen - 1) + 129;       // absolute end of what the window holds now
   const int n_new = noise_new ? nws_stream_noise_draws(K, first, frames_seen) : 0;
   const int nz_keep = first ? 0 : (int)(have - nz_start);
   const int nz_shift = first ? 0 : (int)(nz_start - nz_prev_start);
   if (nz_shift < 0 || nz_keep < 0) return NWS_ERR_BAD_ARG;
+  // frame t of the window covers nzwin[128 t - origin, +256): the stream's first frame reaches 128 samples before its start
+  // (reflected like torch.stft, generators.py:31); the one-shot draw has 128 F - 1 samples: its end reflects in the final chunk
+  const long long A0 = first ? 0 : frames_seen - 1;
+  const int origin = A0 == 0 ? 128 : 0;
+  const int n_have = (int)(128 * (A0 + Tw - 1) + 129 - nz_start);
+  const int n_len = final ? (int)(128 * (A0 + Tw) - 1 - nz_start) : n_have;
   NwsStreamSide side{};
   side.B = B;
   if (split_reverb) {
@@ -406,9 +494,17 @@ int nws_stream_step(const NwsWeights* w, const float* fir_design, const NwsRever
     side.out_T = Tw;
     side.out_off = first ? 0 : 1;
     side.win = NwsStreamNoiseWin{F(L.nzwin), noise_new, noise_all, counters, nz_shift, nz_keep, n_new, noise_all_len, first, K};
+    if (ev != nullptr) {
+      side.vage = reinterpret_cast<int*>(base + L.vage);
+      side.nzrows = reinterpret_cast<int4*>(base + L.nzrows);
+      side.film_junk = F(L.film_junk);
+      side.fir_junk = F(L.fir_junk);
+      side.n_len = n_len;
+    }
   }
-  rc = nws_control_gru_stream(w, control, B, C, K, first ? nullptr : F(L.h), F(L.gru_out), F(L.h_next), split_reverb ? &side : nullptr,
-                              stream);
+  side.ev = ev;
+  rc = nws_control_gru_stream(w, control, B, C, K, first ? nullptr : F(L.h), F(L.gru_out), F(L.h_next),
+                              (split_reverb || ev != nullptr) ? &side : nullptr, stream);
   if (rc != NWS_OK) return rc;
   if (fuse_mlp) {
     // (nothing: the frame MLPs, the noise window and the windows' rows were part of the first launch)
@@ -423,25 +519,22 @@ int nws_stream_step(const NwsWeights* w, const float* fir_design, const NwsRever
     stream_prep_kernel<<<B + 1, 256, 0, st>>>(f0, F(L.film_new), F(L.fir_new), K, first, final, B, F(L.prev_f0), F(L.prev_film),
                                              F(L.prev_fir), reinterpret_cast<double*>(base + L.S), F(L.h), F(L.h_next), F(L.f0_w),
                                              F(L.film_w), F(L.fir_w), reinterpret_cast<double*>(base + L.carry), F(L.nzwin), noise_new,
-                                             nz_shift, nz_keep, n_new, noise_all, noise_all_len, counters);
+                                             nz_shift, nz_keep, n_new, noise_all, noise_all_len, counters, ev,
+                                             reinterpret_cast<int*>(base + L.vage), reinterpret_cast<int4*>(base + L.nzrows), n_len);
     NWS_CHECK_LAUNCH();
   }
   // 4. oscillator + waveshapers on the window   5. noise branch on the same window
   rc = nws_exciter_newt(w, F(L.f0_w), nullptr, reinterpret_cast<double*>(base + L.carry), phase_u, rand_phase, F(L.film_w), B, Tw,
                         sample_rate, nullptr, F(L.newt_w), stream);
   if (rc != NWS_OK) return rc;
-  // frame t of the window covers nzwin[128 t - origin, +256): the stream's first frame reaches 128 samples before its start
-  // (reflected like torch.stft, generators.py:31); the one-shot draw has 128 F - 1 samples: its end reflects in the final chunk
-  const long long A0 = first ? 0 : frames_seen - 1;
-  const int origin = A0 == 0 ? 128 : 0;
-  const int n_have = (int)(128 * (A0 + Tw - 1) + 129 - nz_start);
-  const int n_len = final ? (int)(128 * (A0 + Tw) - 1 - nz_start) : n_have;
-  rc = nws_fir_noise_window(F(L.fir_w), F(L.nzwin), n_len, origin, nullptr, B, Tw, F(L.noise_w), stream);
+  rc = ev != nullptr ? nws_fir_noise_window_rows(F(L.fir_w), F(L.nzwin), origin, reinterpret_cast<const int4*>(base + L.nzrows), B, Tw,
+                                                 F(L.noise_w), stream)
+                     : nws_fir_noise_window(F(L.fir_w), F(L.nzwin), n_len, origin, nullptr, B, Tw, F(L.noise_w), stream);
   if (rc != NWS_OK) return rc;
   // 6./7. emitted samples (oscillator branch [lo, hi) + noise branch: 64 samples of residue first, then this window's hops)
   // and the linear reverb of the stream
   const int R0 = first ? 0 : 64, noise_off = first ? 0 : 128;
-  const PreSrc P{F(L.newt_w), F(L.noise_w), F(L.residue), Nw, lo, R0, noise_off};
+  const PreSrc P{F(L.newt_w), F(L.noise_w), F(L.residue), Nw, lo, R0, noise_off, ev};
   float* pre = pre_out ? pre_out : F(L.pre);
   const int tail_from = noise_off + M - R0;
   if (split_reverb) {
@@ -475,6 +568,37 @@ int nws_stream_step(const NwsWeights* w, const float* fir_design, const NwsRever
     NWS_CHECK_LAUNCH();
   }
   return NWS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nws_stream_step(const NwsWeights* w, const float* fir_design, const NwsReverbPlan* plan, const void* reverb_tables,
+                    const void* reverb_spectrum, void* state, size_t state_bytes, int B, int max_frames, const float* f0,
+                    const float* control, int C, int K, int first, int final, long long frames_seen, long long nz_prev_start,
+                    float sample_rate, const float* phase_u, const float* rand_phase, const float* noise_new,
+                    const float* noise_all, int noise_all_len, const float* ir, int ir_len, float* out, float* pre_out,
+                    void* stream) {
+  return stream_step(w, fir_design, plan, reverb_tables, reverb_spectrum, state, state_bytes, B, max_frames, f0, control, C, K, first,
+                     final, frames_seen, nz_prev_start, sample_rate, phase_u, rand_phase, noise_new, noise_all, noise_all_len, ir,
+                     ir_len, out, pre_out, nullptr, stream);
+}
+
+// Slot mode: B independent voice slots, one hop of K <= 16 frames (M = 128 K samples out, every hop).  events: (B) int32 in DEVICE
+// memory, NWS_SLOT_* per row for this hop - read by the launches, so a captured hop stays valid whatever the events.  The first
+// step (frames_seen == 0) is the stream's internal pre-roll: every row idle.  The caller keeps the slot state machine
+// (streaming.VoiceStream); rows without a voice emit exact zeros and their inputs are never read into an output.
+int nws_stream_step_slots(const NwsWeights* w, const float* fir_design, void* state, size_t state_bytes, int B, int max_frames,
+                          const float* f0, const float* control, int C, int K, long long frames_seen, long long nz_prev_start,
+                          float sample_rate, const float* phase_u, const float* rand_phase, const float* noise_new,
+                          const float* noise_all, int noise_all_len, const float* ir, int ir_len, const int* events, float* out,
+                          float* pre_out, void* stream) {
+  if (!events) return NWS_ERR_BAD_ARG;
+  if (K < 1 || 128 * K > kMaxDirect) return NWS_ERR_UNSUPPORTED;     // the time-domain reverb's hops only
+  return stream_step(w, fir_design, nullptr, nullptr, nullptr, state, state_bytes, B, max_frames, f0, control, C, K,
+                     frames_seen == 0 ? 1 : 0, 0, frames_seen, nz_prev_start, sample_rate, phase_u, rand_phase, noise_new, noise_all,
+                     noise_all_len, ir, ir_len, out, pre_out, events, stream);
 }
 
 // What a linear reverb still rings out after the last chunk: tail[k] = sum_m ir_[m] x[end + k - m], k < ir_len + 1, from the

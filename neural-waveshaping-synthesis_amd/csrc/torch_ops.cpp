@@ -860,6 +860,59 @@ void stream_step(const Tensor& wdesc, const Tensor& fir_design, const OptTensor&
             "nws_stream_step");
 }
 
+// ---- slot mode of the stateful stream (csrc/stream.hip nws_stream_step_slots): per-slot events in a device int32 (B) buffer ----
+void stream_step_slots(const Tensor& wdesc, const Tensor& fir_design, Tensor& state, int64_t max_frames, const Tensor& f0,
+                       const Tensor& control, int64_t frames_seen, int64_t nz_prev_start, double sample_rate, const Tensor& phase_u,
+                       const Tensor& rand_phase, const OptTensor& noise_new, const OptTensor& noise_all, const Tensor& ir,
+                       const Tensor& events, Tensor& out, const OptTensor& pre_out) {
+  const NwsWeights* w = weights_of(wdesc);
+  check_dev(f0, "f0");
+  check_dev(control, "control");
+  check_dev(fir_design, "fir_design");
+  check_dev(state, "state", at::kByte);
+  check_dev(phase_u, "phase_u");
+  check_dev(rand_phase, "rand_phase");
+  check_dev(ir, "reverb.ir");
+  check_dev(out, "out");
+  check_dev(events, "events", at::kInt);
+  check_same_device(f0, "f0", control, "control");
+  check_same_device(f0, "f0", state, "state");
+  check_same_device(f0, "f0", out, "out");
+  check_same_device(f0, "f0", ir, "reverb.ir");
+  check_same_device(f0, "f0", events, "events");
+  TORCH_CHECK(f0.dim() == 2 && control.dim() == 3 && control.size(0) == f0.size(0) && control.size(2) == f0.size(1) && control.size(1) >= 2,
+              "stream_step_slots: f0 (B, K), control (B, C>=2, K); got ", f0.sizes(), " / ", control.sizes());
+  const int64_t B = f0.size(0), K = f0.size(1), C = control.size(1);
+  TORCH_CHECK(K >= 1 && K <= 16 && K <= max_frames, "stream_step_slots: hops of 1 .. 16 frames (sized for ", max_frames, "), got ", K);
+  TORCH_CHECK(events.numel() == B, "stream_step_slots: events: one int32 word per slot, expected ", B, ", got ", events.numel());
+  TORCH_CHECK(phase_u.numel() == NWS_N_HARMONICS && rand_phase.numel() == NWS_N_HARMONICS, "phase_u / rand_phase: 101 elements each");
+  TORCH_CHECK(noise_new.has_value() != noise_all.has_value(), "stream_step_slots: give exactly one of noise_new and noise_all");
+  const int first = frames_seen == 0 ? 1 : 0;
+  const int M = nws_stream_out_samples((int)K, first, 0);
+  TORCH_CHECK(out.numel() == B * M, "out: expected (", B, ", ", M, "), got ", out.sizes());
+  if (pre_out.has_value()) {
+    check_dev(*pre_out, "pre_out");
+    TORCH_CHECK(pre_out->numel() == B * M, "pre_out: expected (", B, ", ", M, ")");
+  }
+  if (noise_new.has_value()) {
+    check_dev(*noise_new, "noise_new");
+    TORCH_CHECK(noise_new->numel() >= nws_stream_noise_draws((int)K, first, frames_seen), "noise_new: expected ",
+                nws_stream_noise_draws((int)K, first, frames_seen), " fresh samples");
+  } else {
+    check_dev(*noise_all, "noise_all");
+  }
+  TORCH_CHECK((size_t)state.numel() >= nws_stream_slot_state_bytes((int)B, (int)max_frames, (int)ir.numel()),
+              "stream_step_slots: state blob too small");
+  Launch L(f0);
+  nws_check(nws_stream_step_slots(w, fir_design.data_ptr<float>(), state.data_ptr(), (size_t)state.numel(), (int)B, (int)max_frames,
+                                  f0.data_ptr<float>(), control.data_ptr<float>(), (int)C, (int)K, (long long)frames_seen,
+                                  (long long)nz_prev_start, (float)sample_rate, phase_u.data_ptr<float>(), rand_phase.data_ptr<float>(),
+                                  fptr(noise_new), fptr(noise_all), noise_all.has_value() ? (int)noise_all->numel() : 0,
+                                  ir.data_ptr<float>(), (int)ir.numel(), events.data_ptr<int>(), out.data_ptr<float>(),
+                                  pre_out.has_value() ? pre_out->data_ptr<float>() : nullptr, L.stream),
+            "nws_stream_step_slots");
+}
+
 int64_t abi_version() { return nws_abi_version(); }
 
 }  // namespace
@@ -914,5 +967,9 @@ TORCH_LIBRARY(newt_hip, m) {
         "int max_frames, Tensor f0, Tensor control, bool first, bool final, int frames_seen, int nz_prev_start, float sample_rate, "
         "Tensor phase_u, Tensor rand_phase, Tensor? noise_new, Tensor? noise_all, Tensor ir, Tensor(b!) out, Tensor(c!)? pre_out) -> ()",
         &stream_step);
+  m.def("stream_step_slots(Tensor wdesc, Tensor fir_design, Tensor(a!) state, int max_frames, Tensor f0, Tensor control, int frames_seen, "
+        "int nz_prev_start, float sample_rate, Tensor phase_u, Tensor rand_phase, Tensor? noise_new, Tensor? noise_all, Tensor ir, "
+        "Tensor events, Tensor(b!) out, Tensor(c!)? pre_out) -> ()",
+        &stream_step_slots);
   m.def("loudness(Tensor audio, Tensor dft, int n_fft, int hop, float amin, float top_db, bool normalise) -> Tensor", &loudness);
 }

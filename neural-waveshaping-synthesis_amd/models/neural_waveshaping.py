@@ -270,10 +270,13 @@ def ensure_default_config():
         gin.parse_config_file(_DEFAULT_GIN)
 
 
-def _stream(self, batch_size: int = 1, *, phase_u=None, noise=None, **kw):
-    """Stateful streaming synthesiser bound to this model (see streaming.NewtStream; kw: max_chunk_frames, graph)."""
-    from ..streaming import NewtStream
+def _stream(self, batch_size: int = 1, *, phase_u=None, noise=None, slots: bool = False, **kw):
+    """Stateful streaming synthesiser bound to this model (see streaming.NewtStream; kw: max_chunk_frames, graph).
+    slots=True: B voice slots that start and stop on their own (streaming.VoiceStream; kw: graph)."""
+    from ..streaming import NewtStream, VoiceStream
 
+    if slots:
+        return VoiceStream(self, batch_size, phase_u=phase_u, noise=noise, **kw)
     return NewtStream(self, batch_size, phase_u=phase_u, noise=noise, **kw)
 
 

@@ -18,6 +18,9 @@ hipGraph and replayed (`graph=True`, the default): a 256-sample hop is then one 
     ahead); `push(..., final=True)` releases the remainder exactly like the one-shot forward's right edge;
   * the phase offsets are drawn once per stream and the noise chunk by chunk from the device generator (or both are
     injected for parity testing), mirroring the reference's two hidden draws.
+
+`VoiceStream` (`model.stream(B, slots=True)`, `nws_stream_step_slots`) is the slot mode: B voices that start and stop on their
+own in one batched stream, with per-slot events as device data; its docstring states the contract.
 """
 from __future__ import annotations
 
@@ -255,3 +258,336 @@ class NewtStream:
                                                 self._state.numel(), self.B, self.max_frames, self._ir_len, tail.data_ptr(),
                                                 ws.data_ptr(), nb, stream_ptr(self.dev)), "nws_stream_reverb_tail")
         return tail
+
+
+# ---- slot mode: B voices with their own lifetimes in one batched stream ------------------------------------------------
+SLOT_START, SLOT_STOP, SLOT_RELEASE, SLOT_ACTIVE = 1, 2, 4, 8   # include/nws_hip.h NWS_SLOT_*
+IDLE, ACTIVE, RELEASING = "idle", "active", "releasing"
+_SLOT_MAX_FRAMES = 16     # hops of up to 2048 samples: the time-domain reverb
+_PREROLL = 2              # internal all-idle frames in front of the first hop (the first user hop is then an ordinary one)
+
+
+def _slot_set(sel, B: int, what: str) -> set:
+    """A bool mask of B entries or a list of slot indices -> set of slot indices."""
+    if sel is None:
+        return set()
+    if isinstance(sel, torch.Tensor):
+        sel = sel.detach().cpu()
+        if sel.dtype == torch.bool:
+            if sel.numel() != B:
+                raise RuntimeError(f"{what}: a bool mask needs {B} entries, got {sel.numel()}")
+            return set(int(i) for i in torch.nonzero(sel.reshape(-1)).reshape(-1).tolist())
+        sel = sel.reshape(-1).tolist()
+    elif hasattr(sel, "dtype") and str(getattr(sel, "dtype")) == "bool":     # numpy bool mask
+        sel = list(sel)
+        if len(sel) != B:
+            raise RuntimeError(f"{what}: a bool mask needs {B} entries, got {len(sel)}")
+        return {i for i, v in enumerate(sel) if v}
+    sel = list(sel)
+    if sel and all(isinstance(v, bool) for v in sel):
+        if len(sel) != B:
+            raise RuntimeError(f"{what}: a bool mask needs {B} entries, got {len(sel)}")
+        return {i for i, v in enumerate(sel) if v}
+    out = set()
+    for v in sel:
+        i = int(v)
+        if not 0 <= i < B:
+            raise RuntimeError(f"{what}: slot {i} outside 0 .. {B - 1}")
+        out.add(i)
+    return out
+
+
+class SlotBook:
+    """Host-side slot state machine of a VoiceStream (no GPU): idle -> active on start, active -> releasing for the one hop after
+    the stop hop, releasing -> idle after it.  `plan` validates one hop's events and returns the per-slot event words without
+    changing anything; `commit` applies them once the hop has been issued."""
+
+    def __init__(self, B: int):
+        self.B = int(B)
+        self.states = [IDLE] * self.B
+
+    def plan(self, start=None, stop=None) -> list:
+        st, sp = _slot_set(start, self.B, "start"), _slot_set(stop, self.B, "stop")
+        for i in sorted(st):
+            if self.states[i] != IDLE:
+                raise RuntimeError(f"start on slot {i}: it is {self.states[i]} (a start is accepted on an idle slot only)")
+        for i in sorted(sp - st):
+            if self.states[i] != ACTIVE:
+                raise RuntimeError(f"stop on slot {i}: it is {self.states[i]} (a stop is accepted on an active slot, or with a start)")
+        words = []
+        for i, s in enumerate(self.states):
+            if i in st:
+                w = SLOT_ACTIVE | SLOT_START | (SLOT_STOP if i in sp else 0)
+            elif s == ACTIVE:
+                w = SLOT_ACTIVE | (SLOT_STOP if i in sp else 0)
+            elif s == RELEASING:
+                w = SLOT_RELEASE
+            else:
+                w = 0
+            words.append(w)
+        return words
+
+    def commit(self, words) -> None:
+        for i, w in enumerate(words):
+            if w & SLOT_STOP:
+                self.states[i] = RELEASING
+            elif w & SLOT_ACTIVE:
+                self.states[i] = ACTIVE
+            else:
+                self.states[i] = IDLE
+
+
+class VoiceStream:
+    """B voice slots in one batched stream, each starting and stopping on its own (`model.stream(B, slots=True)`).
+
+    One hop = K frames (1 <= K <= 16) for every slot, `push(f0, control, start=, stop=)` -> (B, 128 K), every hop the same shape.
+    Events per slot and hop (`start` / `stop`: bool masks of B entries or lists of slot indices):
+      * start: this hop's frames are a new voice's first frames; accepted on an IDLE slot only;
+      * stop: this hop's frames are the voice's last frames; accepted on an ACTIVE slot, or together with a start;
+      * a slot is RELEASING for the one hop after its stop hop (its voice's last 64 samples come out), then IDLE again.
+    A violation raises RuntimeError before anything is launched; the stream stays usable.
+
+    Output: slot b's output is one continuous signal o_b; the hop covering frames [a, a+K) (a = 0 for the first hop) returns
+    o_b[128 a : 128 a + 128 K].  A voice v of slot b starting at frame a_v with T_v frames has the dry signal pre_v = the
+    one-shot forward's `pre_reverb` of its own (f0, control), with the stream's single phase draw (shared by all voices, as the
+    reference shares it over a batch) and the noise samples noise[128 a_v : 128 a_v + 128 T_v - 1] of the stream's noise sequence
+    (reflect-padded at both ends exactly like the one-shot).  pre_v sits at o-indices [128 a_v + 64, 128 (a_v + T_v) + 64) - the
+    64-sample latency of every stream.  The slot's dry signal is the sum of its placed voices and exactly 0 everywhere else, and
+    o_b = dry_b + linear_conv(dry_b, [0, ir]): reverb tails of ended voices keep ringing, also under a later voice of the slot.
+    Idle and releasing slots' f0 / control are never read into an output (NaN there is harmless).
+
+    Draws: phase_u once per stream; in drawn mode every hop draws 128 K noise samples whatever its events, so one captured hop per
+    K stays valid.  Parity mode (`noise=`): the stream's whole noise sequence, at least 128 F - 1 samples for F frames pushed in
+    all (samples past its end read as 0).
+
+    `static_io(K)` -> (f0_in, control_in, events, out): the captured hop's own buffers; `hop(K, start=, stop=)` writes the
+    events and replays ONE graph per K whatever they are.  `check()` raises if the device reported a hop it had to give up on.
+    """
+
+    def __init__(self, model, batch_size: int, phase_u: torch.Tensor | None = None, noise: torch.Tensor | None = None,
+                 graph: bool = True):
+        if not model._engine.specialised():
+            raise RuntimeError("stateful streaming runs on the fused kernels: the model must have the architecture of "
+                               "gin/models/newt.gin")
+        self.model = model
+        self.eng = model._engine
+        _, _, dev = self.eng.weights()
+        self.dev = dev
+        self.B = int(batch_size)
+        if self.B < 1:
+            raise RuntimeError("VoiceStream: at least one slot")
+        self._ir_len = int(self.eng.ir().numel())
+        self.tail_len = self._ir_len + 1
+        if self._ir_len >= _RING // 2:
+            raise RuntimeError(f"stateful streaming keeps {_RING // 2 - 1} samples of reverb history per slot; this model's impulse "
+                               f"response has {self._ir_len} taps - render it with the one-shot forward")
+        self._plan_n = next(n for n in (32000, 64000, 128000, 256000) if n >= 2 * self.tail_len)
+        self.max_frames = _SLOT_MAX_FRAMES
+        self.phase_u = _req((phase_u if phase_u is not None else torch.rand_like(model.osc.rand_phase)).reshape(-1),
+                            "phase_u", _lib.N_HARMONICS)
+        self._noise_all = None
+        if noise is not None:
+            nz = _req(noise, "noise").reshape(-1)
+            # the pre-roll's frames come first in the device's noise positions: its samples are never read into an output
+            self._noise_all = torch.cat([torch.zeros(HOP * _PREROLL, dtype=nz.dtype, device=nz.device), nz])
+        L = _lib.lib()
+        nbytes = L.nws_stream_slot_state_bytes(self.B, self.max_frames, self._ir_len)
+        self._counters_at = int(L.nws_stream_counters_offset(self.B, self.max_frames, self._ir_len))
+        with torch.cuda.device(dev):
+            self._state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.check(L.nws_stream_reset(self._state.data_ptr(), nbytes, stream_ptr(dev)), "nws_stream_reset")
+            self._ev = torch.zeros(self.B, dtype=torch.int32, device=dev)     # the hop's event words, read by its launches
+        self._ev_words = [0] * self.B
+        self.book = SlotBook(self.B)
+        self._use_graph = bool(graph)
+        self._graphs = {}          # (K, channels) -> (graph, f0_in, control_in, noise_new, out, pre)
+        self._steady_runs = {}
+        self.frames_seen = 0       # device frames, pre-roll included
+        self.hops = 0
+        self._nz_prev_start = 0
+        self._last_K = None
+        self._last_pre = None
+        self.finished = False
+        # pre-roll: every slot idle, output dropped; afterwards each hop is an ordinary (not first) one of the same shape
+        with torch.cuda.device(dev):
+            f0 = torch.zeros((self.B, _PREROLL), dtype=torch.float32, device=dev)
+            c = torch.zeros((self.B, 2, _PREROLL), dtype=torch.float32, device=dev)
+            M = L.nws_stream_out_samples(_PREROLL, 1, 0)
+            out = torch.empty((self.B, M), dtype=torch.float32, device=dev)
+            nz = torch.rand(L.nws_stream_noise_draws(_PREROLL, 1, 0), device=dev) if self._noise_all is None else None
+            self._step(f0, c, nz, out, None)
+        self._advance(_PREROLL)
+        self._last_K = None
+
+    # ---- one C-ABI call ---------------------------------------------------------------------------------------------
+    def _step(self, f0_2d, control, noise_new, out, pre):
+        eng = self.eng
+        w, keep, dev, wdesc = eng._wd()
+        B, K = f0_2d.shape
+        sr = eng.osc_sample_rate()
+        rp, ir = keep[-2], keep[-1]
+        o = ops()
+        if o is not None:
+            o.stream_step_slots(wdesc, eng._fir_design, self._state, self.max_frames, f0_2d, control, int(self.frames_seen),
+                                int(self._nz_prev_start), sr, self.phase_u, rp, noise_new, self._noise_all, ir.reshape(-1), self._ev,
+                                out, pre)
+            return
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().nws_stream_step_slots(
+                C.byref(w), eng._fir_design.data_ptr(), self._state.data_ptr(), self._state.numel(), B, self.max_frames,
+                f0_2d.data_ptr(), control.data_ptr(), control.shape[1], K, int(self.frames_seen), int(self._nz_prev_start), sr,
+                self.phase_u.data_ptr(), rp.data_ptr(), noise_new.data_ptr() if noise_new is not None else None,
+                self._noise_all.data_ptr() if self._noise_all is not None else None,
+                self._noise_all.numel() if self._noise_all is not None else 0, ir.data_ptr(), ir.numel(), self._ev.data_ptr(),
+                out.data_ptr(), pre.data_ptr() if pre is not None else None, stream_ptr(dev)), "nws_stream_step_slots")
+
+    def _capture(self, K, C_in):
+        dev = self.dev
+        with torch.cuda.device(dev):
+            f0_in = torch.zeros((self.B, K), dtype=torch.float32, device=dev)
+            c_in = torch.zeros((self.B, C_in, K), dtype=torch.float32, device=dev)
+            nz = torch.empty(HOP * K, dtype=torch.float32, device=dev) if self._noise_all is None else None
+            out = torch.empty((self.B, HOP * K), dtype=torch.float32, device=dev)
+            pre = torch.empty((self.B, HOP * K), dtype=torch.float32, device=dev)
+            g = torch.cuda.CUDAGraph()
+            torch.cuda.synchronize(dev)
+            with torch.cuda.graph(g):
+                if nz is not None:
+                    nz.uniform_()
+                self._step(f0_in, c_in, nz, out, pre)
+        return g, f0_in, c_in, nz, out, pre
+
+    def _set_events(self, words):
+        # one host-to-device copy per hop whose words differ from the last ones written (a copy costs a few us of the hop's
+        # latency; a hop without events and without a release repeats the previous words)
+        if words == self._ev_words:
+            return
+        host = torch.tensor(words, dtype=torch.int32).pin_memory()
+        self._ev.copy_(host, non_blocking=True)
+        self._ev_words = list(words)
+
+    def _steady(self, K):
+        return self._last_K == K and self.hops >= 1
+
+    def _check_shape(self, f0, control):
+        f0 = _req(f0 if f0.is_contiguous() else f0.contiguous(), "f0")
+        control = _req(control if control.is_contiguous() else control.contiguous(), "control")
+        if f0.dim() != 3 or control.dim() != 3:
+            raise RuntimeError(f"expected f0 ({self.B},1,K) and control ({self.B},C>=2,K)")
+        B, one, K = f0.shape
+        if B != self.B or one != 1 or control.shape[0] != B or control.shape[2] != K or control.shape[1] < 2:
+            raise RuntimeError(f"expected f0 ({self.B},1,K) and control ({self.B},C>=2,K), got {tuple(f0.shape)} / {tuple(control.shape)}")
+        if not 1 <= K <= _SLOT_MAX_FRAMES:
+            raise RuntimeError(f"slot mode serves hops of 1 .. {_SLOT_MAX_FRAMES} frames (up to 2048 samples); got {K}")
+        return f0, control, K
+
+    # ---- one hop ---------------------------------------------------------------------------------------------------------
+    def push(self, f0: torch.Tensor, control: torch.Tensor, start=None, stop=None) -> torch.Tensor:
+        """f0 (B,1,K) Hz, control (B,C>=2,K) normalised, this hop's events -> (B, 128 K) audio."""
+        if self.finished:
+            raise RuntimeError("VoiceStream: closed")
+        f0, control, K = self._check_shape(f0, control)
+        words = self.book.plan(start, stop)        # raises before anything is launched
+        self._check_weights()
+        f0_2d = f0[:, 0, :]
+        self._set_events(words)
+        key = (K, control.shape[1])
+        if self._use_graph and self._steady(K) and not torch.cuda.is_current_stream_capturing():
+            hit = self._graphs.get(key)
+            if hit is None:
+                try:
+                    hit = self._graphs[key] = self._capture(K, control.shape[1])
+                except Exception as e:
+                    import warnings
+                    warnings.warn(f"VoiceStream: hipGraph capture of the {K}-frame hop failed ({type(e).__name__}: {e}); this stream "
+                                  f"continues with eager pushes", RuntimeWarning, stacklevel=2)
+                    self._use_graph = False
+                    hit = None
+            if hit is not None:
+                g, f0_in, c_in, _, out, pre = hit
+                torch._foreach_copy_([f0_in, c_in], [f0_2d, control])
+                g.replay()
+                self._done(words, K, pre)
+                return out.clone()
+        L = _lib.lib()
+        with torch.cuda.device(self.dev):
+            out = torch.empty((self.B, HOP * K), dtype=torch.float32, device=self.dev)
+            pre = torch.empty((self.B, HOP * K), dtype=torch.float32, device=self.dev)
+            nz = torch.rand(L.nws_stream_noise_draws(K, 0, self.frames_seen), device=self.dev) if self._noise_all is None else None
+            self._step(f0_2d.contiguous(), control, nz, out, pre)
+        self._done(words, K, pre)
+        return out
+
+    def _done(self, words, K, pre):
+        self.book.commit(words)
+        self._advance(K)
+        self.hops += 1
+        self._last_pre = pre
+
+    def _advance(self, K):
+        self._nz_prev_start = int(_lib.lib().nws_stream_noise_start(int(self.frames_seen == 0), self.frames_seen))
+        self.frames_seen += K
+        self._last_K = K
+
+    # ---- zero-copy hops ----------------------------------------------------------------------------------------------
+    def static_io(self, K: int, channels: int = 2):
+        """(f0_in (B, K), control_in (B, channels, K), events (B) int32, out (B, 128 K)) of the captured hop of K frames: the
+        buffers `hop()` consumes and fills (`hop` writes `events` from its start / stop arguments).  Needs one push of K frames
+        behind it."""
+        if self.finished:
+            raise RuntimeError("VoiceStream: closed")
+        if not self._steady(K):
+            raise RuntimeError(f"static_io({K}): push a hop of {K} frames first")
+        if not 1 <= K <= _SLOT_MAX_FRAMES:
+            raise RuntimeError(f"slot mode serves hops of 1 .. {_SLOT_MAX_FRAMES} frames; got {K}")
+        hit = self._graphs.get((K, channels))
+        if hit is None:
+            hit = self._graphs[(K, channels)] = self._capture(K, channels)
+        return hit[1], hit[2], self._ev, hit[4]
+
+    def hop(self, K: int, start=None, stop=None, channels: int = 2) -> torch.Tensor:
+        """Replay the captured hop on static_io(K)'s inputs with this hop's events; returns the static output buffer (overwritten
+        by the next hop)."""
+        if self.finished:
+            raise RuntimeError("VoiceStream: closed")
+        self._check_weights()
+        hit = self._graphs.get((K, channels))
+        if hit is None or not self._steady(K):
+            raise RuntimeError("hop(): call static_io(K) first (again after a weight update), and do not interleave other hop sizes")
+        words = self.book.plan(start, stop)
+        self._set_events(words)
+        hit[0].replay()
+        self._done(words, K, hit[5])
+        return hit[4]
+
+    # ---- state ---------------------------------------------------------------------------------------------------------
+    def slot_states(self) -> list:
+        """'idle' / 'active' / 'releasing' per slot, as of the next hop."""
+        return list(self.book.states)
+
+    def idle_slots(self) -> list:
+        return [i for i, s in enumerate(self.book.states) if s == IDLE]
+
+    def check(self) -> None:
+        """Raise if a hop's device work reported that it gave up waiting (counters[5]; synchronises).  The flag belongs to the
+        four-launch hop (K <= 2 frames, at most 512 slots), whose frame-MLP workgroups wait inside the launch for their slot's
+        recurrence with a bounded wait; the seven-launch form of every other hop has no such wait and never sets it."""
+        flag = int(self._state[self._counters_at + 40: self._counters_at + 48].cpu().view(torch.int64)[0])
+        if flag != 0:
+            raise RuntimeError("VoiceStream: a hop's frame-MLP work gave up waiting for its recurrence rows (its output is NaN)")
+
+    def close(self) -> None:
+        """check(), then release the captured hops; push / hop / static_io raise afterwards."""
+        self.check()
+        self._graphs.clear()
+        self.finished = True
+
+    def refresh(self):
+        NewtStream.refresh(self)
+
+    def _check_weights(self):
+        NewtStream._check_weights(self)
+
+    def reverb_tail(self) -> torch.Tensor:
+        """The remaining (B, ir_len + 1) reverb tail of every slot after the last hop."""
+        return NewtStream.reverb_tail(self)

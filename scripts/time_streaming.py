@@ -3,7 +3,9 @@
 16 ms of audio) pushed back to back, HIP-event timed per push.  Unlike scripts/time_buffer_sizes.py (stateless, hipGraph)
 every push carries GRU / phase / noise / reverb state and applies the 2 s reverb as a linear convolution of the stream
 (csrc/stream.hip); steady-state hops replay a hipGraph unless --no-graph.  Host wall-clock per push is reported beside the
-HIP-event latency (a push returns a fresh tensor: input copy + graph launch + output copy)."""
+HIP-event latency (a push returns a fresh tensor: input copy + graph launch + output copy).
+--slots: the slot mode (model.stream(B, slots=True)) under a random note-on / note-off schedule (every hop each idle slot starts
+with probability --note-on, each active one stops with probability --note-off); same timing, events written every hop."""
 import importlib
 import os
 import sys
@@ -26,9 +28,14 @@ sys.path.insert(0, ROOT)
 @click.option("--static-io/--copy-io", default=False, help="time NewtStream.hop(): the caller fills the captured hop's own "
               "input buffers and reads its output buffer (no input / output copies), like an audio callback would")
 @click.option("--json-out", default=None)
+@click.option("--slots", is_flag=True, default=False, help="time the slot mode (VoiceStream) under a random note-on/off schedule")
+@click.option("--note-on", default=0.2, help="--slots: per-hop start probability of an idle slot")
+@click.option("--note-off", default=0.1, help="--slots: per-hop stop probability of an active slot")
+@click.option("--seed", default=0)
 @click.option("--gc/--no-gc", "keep_gc", default=True, help="--no-gc: Python's cyclic garbage collector off during the timed hops "
               "(what a host with a real-time audio callback does); reported in the result")
-def main(checkpoint, batch_size, hop_frames, num_hops, use_fast_newt, graph, static_io, json_out, keep_gc):
+def main(checkpoint, batch_size, hop_frames, num_hops, use_fast_newt, graph, static_io, json_out, slots, note_on, note_off, seed,
+         keep_gc):
     nws = importlib.import_module("neural-waveshaping-synthesis_amd")
     nws.ensure_default_config()
     model = nws.NeuralWaveshaping.load_from_checkpoint(checkpoint).cuda().eval()
@@ -37,12 +44,23 @@ def main(checkpoint, batch_size, hop_frames, num_hops, use_fast_newt, graph, sta
     K = hop_frames
     f0 = 220 + 20 * torch.rand(batch_size, 1, K, device="cuda")
     control = torch.randn(batch_size, 2, K, device="cuda")
+    rng = np.random.default_rng(seed)
+
+    def events():
+        """this hop's (start, stop) slot lists: random note-ons on idle slots, note-offs on active ones"""
+        if not slots:
+            return {}
+        st = s.slot_states()
+        start = [b for b, x in enumerate(st) if x == "idle" and rng.random() < note_on]
+        stop = [b for b, x in enumerate(st) if x == "active" and rng.random() < note_off]
+        return {"start": start, "stop": stop}
+
     with torch.no_grad():
-        s = model.stream(batch_size, graph=graph)
+        s = model.stream(batch_size, graph=graph, slots=True) if slots else model.stream(batch_size, graph=graph)
         for _ in range(20):
-            s.push(f0, control)
+            s.push(f0, control, **events())
         if static_io:
-            f0_in, c_in, _ = s.static_io(K)
+            f0_in, c_in = s.static_io(K)[:2]
             f0_in.copy_(f0[:, 0])
             c_in.copy_(control)
         torch.cuda.synchronize()
@@ -52,14 +70,17 @@ def main(checkpoint, batch_size, hop_frames, num_hops, use_fast_newt, graph, sta
         if not keep_gc:
             gc.collect()
             gc.disable()
+        n_events = 0
         for _ in range(num_hops):
+            ev = events()
+            n_events += len(ev.get("start", ())) + len(ev.get("stop", ()))
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0 = time.perf_counter()
             e0.record()
             if static_io:
-                s.hop(K)
+                s.hop(K, **ev)
             else:
-                s.push(f0, control)
+                s.push(f0, control, **ev)
             e1.record()
             e1.synchronize()
             wall.append((time.perf_counter() - t0) * 1e6)
@@ -68,10 +89,11 @@ def main(checkpoint, batch_size, hop_frames, num_hops, use_fast_newt, graph, sta
     lat, wall = np.array(lat), np.array(wall)
     period = K * 128 / 16000.0 * 1e6
     res = {"batch": batch_size, "hop_samples": K * 128, "graph": bool(graph), "static_io": bool(static_io), "hops": num_hops, "python_gc": bool(keep_gc),
+           "slots": bool(slots), "events": n_events,
            "p50_us": float(np.percentile(lat, 50)), "p99_us": float(np.percentile(lat, 99)), "max_us": float(lat.max()),
            "wall_p50_us": float(np.percentile(wall, 50)), "wall_p99_us": float(np.percentile(wall, 99)),
            "x_realtime_p50": period / float(np.percentile(lat, 50))}
-    print(f"stateful streaming, batch {batch_size}, hop {K * 128} samples ({period / 1e3:.1f} ms), graph={graph}, static_io={static_io}, gc={keep_gc}: p50 {res['p50_us']:.1f} us  "
+    print(f"stateful streaming{' (slots, %d events)' % n_events if slots else ''}, batch {batch_size}, hop {K * 128} samples ({period / 1e3:.1f} ms), graph={graph}, static_io={static_io}, gc={keep_gc}: p50 {res['p50_us']:.1f} us  "
           f"p99 {res['p99_us']:.1f} us  (host wall p50 {res['wall_p50_us']:.1f} / p99 {res['wall_p99_us']:.1f} us)  -> "
           f"{res['x_realtime_p50']:.1f}x real-time")
     if json_out:
