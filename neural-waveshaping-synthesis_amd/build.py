@@ -23,11 +23,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
          "-Wall", "-Wno-unused-function", "-Wno-pass-failed", "-Rpass-analysis=kernel-resource-usage"]
 # -fno-slp-vectorize: the SLP vectoriser turns scalar fp32 code into packed instructions with operand swizzles of its own
 # choosing, among them the form that misbehaves beside another kernel's f16 MFMAs (see check_packed_swizzles below);
-# packed arithmetic is written explicitly (f32x2) where it pays.  Two files keep the vectoriser (the guard checks every
-# file anyway) because an MFMA kernel in each sits at its register budget and spills without it: fir_noise.hip (only
-# receives the harmless low-broadcast form) and control_gru.hip (batched kernel; the per-utterance kernel's horizontal
-# sums are scalar by hand).
-KEEP_SLP = ("fir_noise.hip", "control_gru.hip")
+# packed arithmetic is written explicitly (f32x2) where it pays.  One file keeps the vectoriser (the guard checks every
+# file anyway) because an MFMA kernel in it sits at its register budget and spills without it: control_gru.hip (batched
+# kernel; the per-utterance kernel's horizontal sums are scalar by hand).  fir_noise.hip left the list with its MFMA
+# kernel: hand-written complex butterflies are exactly what the vectoriser turns into swizzled packed operations.
+KEEP_SLP = ("control_gru.hip",)
 EXTRA_FLAGS = {src: ["-fno-slp-vectorize"] for src in SOURCES + PROBE_SOURCES if src not in KEEP_SLP}
 # experiments: extra hipcc flags for every file (e.g. NWS_EXTRA_HIPCC_FLAGS="-DNWS_EXCITER_PRIO_MIX=1"); part of the build stamp
 FLAGS += [f for f in os.environ.get("NWS_EXTRA_HIPCC_FLAGS", "").split() if f]

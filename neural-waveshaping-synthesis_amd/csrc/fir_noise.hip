@@ -12,9 +12,16 @@
 // 8-tap register window of the taps and of a copy delayed by one sample (so that tap PAIRS are
 // even-aligned for both output parities): two ds_read_b128 of taps + one broadcast ds_read_b128 of
 // noise feed 8 v_pk_fma_f32 = 16 MACs.  The NEWT branch is added here (cat + sum(1), models/neural_waveshaping.py:85-86).
-#include <type_traits>
-
 #include "nws_common.h"
+#include "fir_spectral_fft.h"
+
+// the two-float value type of fir_spectral_fft.h's templates
+template <>
+struct SpOps<f32x2> {
+  static __device__ __forceinline__ f32x2 fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+  static __device__ __forceinline__ f32x2 of(float v) { return f32x2{v, v}; }
+  static __device__ __forceinline__ f32x2 at(const float* p) { return *reinterpret_cast<const f32x2*>(p); }
+};
 
 namespace {
 
@@ -140,268 +147,249 @@ __global__ __launch_bounds__(256) void fir_noise_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Batched form on the matrix cores (B >= 16).  All utterances share ONE noise vector (generators.py:30), so for frame t
-// the 256x256 circulant C_t[n][k] = f_t[(n-k) & 255] of the noise frame is the same GEMM operand for every utterance:
-//     Y_t (B x 256) = H_t (B x 256 taps) * C_t^T .
-// One workgroup = one output hop x 32 utterances; the hop needs rows 0..127 of frame t's circulant and rows 128..255 of
-// frame t-1's, i.e. ONE accumulation over K = 512: D[b][j] = sum_k h_t[b][k] f_t[(j-k)&255] + sum_k h_{t-1}[b][k] f_{t-1}[(128+j-k)&255].
-// fp32 accuracy from fp16 MFMAs by the two-term split (x = hi + lo, three products); taps are pre-scaled by a per-utterance
-// power of two and the noise by 2^10 so that the lo parts stay out of the fp16 subnormal range.
-//  * A operand (utterance rows): taps as fp16 hi/lo half rows in LDS, row stride 272 B (bank-conflict-free b128 reads);
-//    HBM holds the upper 128 taps of every frame only (mirror-symmetric rows, include/nws_hip.h).
-//  * B operand (sample columns): lane (j, khalf) needs 8 CONSECUTIVE entries of the reversed noise frame starting at
-//    (k0 + 8 khalf - j) & 255 -- an arbitrary offset, but its low three bits are (-j) & 7, fixed per lane: eight copies of
-//    the reversed frame, copy c shifted by c, make every read an aligned ds_read_b128 of one 16-byte block of its copy.
-//    Round 5: a ds_read_b128 is served in four NON-contiguous 16-lane groups ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ...;
-//    MI355X_MICROARCH, LDS), not in runs of 16 lanes: the padded copy stride of rounds 3-4 (544 B, "conflict-free") put two
-//    lanes of every group on one bank (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.283, the only hot kernel above 0.06).  Every
-//    plain stride leaves a 2-way conflict (exhaustive check, tools/lds_groups_fir.py); rotating the 32 blocks of copy c by
-//    kRot[c] = {0, 1, 5, 9, 13, 5, 9, 13} blocks makes all four groups hit 16 distinct 16-byte slots for every k0 and wave.
-//    Copies are exactly 512 B now (a read never straddles a block, so the 32 wrap-around bytes per copy are gone).
-//  * D rows are utterances, columns samples: each accumulator register stores 2 x 128 B contiguous segments.
-constexpr int kUtt = 32;
-constexpr int kCopyHalfs = 256;      // one copy = the 256 entries of the reversed frame = 32 blocks of 16 B
-// block rotation of copy c (in blocks of 8 halfs), packed one nibble per copy: {0, 1, 5, 9, 13, 5, 9, 13}
-constexpr unsigned kCopyRot = 0xD95D9510u;
-__device__ __forceinline__ int copy_rot_halfs(int c) { return (int)((kCopyRot >> (4 * c)) & 15u) * 8; }
-constexpr int kRowHalfs = 136;       // half a tap row (128 taps) + pad: 272 B stride, conflict-free ds_read_b128
-constexpr float kNoiseScale = 1024.0f;  // noise (U[0,1) in the reference; anything within +-32 is fine) times 2^10
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+// Batched form (B >= 16): the per-frame circular convolution as the reference does it, a product of spectra, in fp32 on the
+// vector pipe.  Per frame: Y_t = X_t H_t, y_t = IDFT(Y_t), then the overlap-add above.
+//  * The stored tap row is the upper half u[d] = h[128 + d] of a row mirror-symmetric about tap 128 with h[0] = 0: rolled
+//    back by 128 it is real and even, e[n] = u[min(n, 256 - n)] (u[128] := 0), so its DFT G is REAL and H[k] = (-1)^k G[k].
+//  * Two frames of ONE utterance share a complex transform in both directions: DFT(e_a + i e_b) = G_a + i G_b needs no split
+//    because both spectra are real, and IDFT(X_a H_a + i X_b H_b) = y_a + i y_b.  Frames of different utterances never share a
+//    transform: an Inf / NaN in one utterance's taps leaves every other row bit-for-bit alone.  Inside an utterance a bad
+//    frame reaches its pair partner too, i.e. one hop further than the two hops the frame itself covers.
+//  * One transform = 16 lanes x 16 points (fir_spectral_fft.h).  A wave runs four of them side by side, the four consecutive
+//    frame pairs (t0-1, t0) .. (t0+5, t0+6), and does so for TWO utterances at once: every value is a two-float vector
+//    (.x = utterance b0, .y = utterance b0 + 1), so the butterflies are v_pk_add / v_pk_mul / v_pk_fma_f32 with no operand
+//    swizzle - the two halves of a packed instruction are independent IEEE operations, an utterance's bits do not depend on
+//    which half it rides in or on its neighbour.  (Packing re with im instead would need the swizzle the build refuses.)
+//  * The wave writes the seven hops t0 .. t0+6.  Hop t = first half of y_t + second half of y_t-1: inside a lane for the odd
+//    member of a pair, one 16-lane shift for the even one; the run's first frame only supplies the second half (recomputed by
+//    this run, written by nobody: no atomics, no dependence on launch order or on the batch).
+//  * The noise spectra are shared by every utterance: wave 0 of the workgroup (4 waves = 8 utterances on the same run)
+//    transforms the four noise frame pairs, separates each pair with the k <-> -k mirror through LDS and leaves, per bin,
+//    S = (-1)^k X_a / 256 and D = (-1)^k i X_b / 256; the product of a bin is then P = G_a S + G_b D (two FMAs per part).
+//    THE FILTER SPECTRUM IS ONE STEP (sp_filter_spectrum): a forward path that hands over spectra instead of taps replaces it.
+//  * Frames outside [0, T) are silent by a select on the loaded taps (and on their half of the result: the partner's rounding
+//    residue does not leak into a silent frame); rows >= B compute on a clamped row and store nothing.
+// Memory: every tap row is read once by its run (the run's first frame a second time by the run before, on the same L2: the
+// block order below); lane l of a transform reads u[16 j + l], 64 contiguous bytes per 16 lanes.
+constexpr int kSpWaves = 4;          // waves per workgroup, two utterances each
+constexpr int kSpUtt = 2 * kSpWaves; // utterances per workgroup
+constexpr int kSpPairs = 4;          // frame pairs per wave = transforms running side by side
+constexpr int kSpHops = 2 * kSpPairs - 1;
 
-struct NoiseMfmaLds {
-  _Float16 rhi[2][8][kCopyHalfs];  // [frame t | frame t-1 advanced by 128][shift c][v] = R[(v + c) & 255]
-  _Float16 rlo[2][8][kCopyHalfs];
-  _Float16 hhi[kUtt][kRowHalfs];   // HALF the taps (128) of the frame being accumulated, times the utterance's scale:
-  _Float16 hlo[kUtt][kRowHalfs];   // staging half rows keeps the block at 36 KB of LDS = 4 workgroups per CU
-  __attribute__((aligned(16))) float unscale[kUtt];   // 1 / (tap scale * noise scale) per utterance
-  float win[4 * kHop];             // padded noise [128 (t-1), 128 (t-1) + 384), times the noise scale: frames t-1 and t (+ 128 of
-                                   // padding: every thread stores two entries, so both loads are requested up front)
+struct SpectralLds {
+  float4 sd[kSpPairs][9][16];                  // [pair][k2][k1] = (S.re, S.im, D.re, D.im) of bin k1 + 16 k2 <= 143; the bins
+                                               // above 128 are read at their mirror image (sp_product)
+  float4 tw[256];                              // (cos, cos, sin, sin)(2 pi l k / 256) at [k][l]
+  f32x2 x[kSpWaves][kSpPairs * kSpPlane];      // the 16 x 16 transposes of a wave's four transforms, re then im through the
+                                               // same plane (47 KB per workgroup: three of them on a CU)
 };
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-// (hi, lo) fp16 split of two values: v_cvt_pk_f16_f32 for hi, one v_fma_mix{lo,hi}_f16 per lo (exact residual rounded once)
-__device__ __forceinline__ void split16x2(float a, float b, f16x2& hi, f16x2& lo) {
-  hi = __builtin_convertvector(f32x2{a, b}, f16x2);
-  const unsigned hp = __builtin_bit_cast(unsigned, hi);
-  unsigned lp;
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lp) : "v"(hp), "v"(a));
-  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lp) : "v"(hp), "v"(b));
-  lo = __builtin_bit_cast(f16x2, lp);
+// a wave's LDS traffic is ordered by itself; this keeps the compiler from moving accesses across an exchange
+__device__ __forceinline__ void sp_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f32(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false));
+// the 16 x 16 transpose: (register k, lane l) -> (lane k, register l).  Rows of 17 entries: 8-byte entries of 16 lanes x 4
+// transforms fall on distinct bank pairs both ways (fir_spectral_fft.h)
+template <class T>
+__device__ __forceinline__ void sp_transpose(T (&v)[16], T* x, int l) {
+#pragma unroll
+  for (int k = 0; k < 16; ++k) x[k * kSpRow + l] = v[k];
+  sp_wave_sync();
+#pragma unroll
+  for (int j = 0; j < 16; ++j) v[j] = x[l * kSpRow + j];
+  sp_wave_sync();
 }
-// maximum of non-negative values over each 32-lane half of the wave, in every lane of the half
-__device__ __forceinline__ float half_max(float v) {
-  v = fmaxf(v, dpp_f32<0xb1, 0xf>(v));   // quad_perm [1,0,3,2]
-  v = fmaxf(v, dpp_f32<0x4e, 0xf>(v));   // quad_perm [2,3,0,1]
-  v = fmaxf(v, dpp_f32<0x141, 0xf>(v));  // row_half_mirror
-  v = fmaxf(v, dpp_f32<0x140, 0xf>(v));  // row_mirror: every lane holds its 16-lane row's maximum
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));   // rows 0|1 and 2|3 exchanged: the half's maximum
+// 256-point transform of (lane l, register j) = x[16 j + l] into (lane k1, register k2) = X[k1 + 16 k2]; INV: the same with
+// conjugate twiddles, (lane k1, register k2) -> (lane l, register j), no scaling.  x: this transform's LDS plane.
+template <bool INV, class T>
+__device__ __forceinline__ void sp_fft256(C16T<T>& z, const float* tw, T* x, int l) {
+  sp_pass1<INV>(z, tw);
+  sp_transpose(z.re, x, l);
+  sp_transpose(z.im, x, l);
+  sp_dft16<INV>(z);
 }
-__global__ __launch_bounds__(256, 4) void fir_noise_mfma_kernel(const float* __restrict__ fir, const float* __restrict__ noise,
-                                                                const float* __restrict__ add_in, int B, int T, int len,
-                                                                int origin, float* __restrict__ out) {
-  __shared__ __attribute__((aligned(16))) NoiseMfmaLds L;
+
+__device__ __forceinline__ f32x2 sp_shfl(f32x2 v, int src) { return f32x2{__shfl(v.x, src, 64), __shfl(v.y, src, 64)}; }
+__device__ __forceinline__ f32x2 sp_select(bool c, f32x2 a, f32x2 b) { return f32x2{c ? a.x : b.x, c ? a.y : b.y}; }
+
+// Spectrum of the filters of a frame pair from their stored half rows: on return (lane k1, register k2) holds
+// (G_a, G_b)[k1 + 16 k2] as (re, im).  ua / ub: u[16 j + l] of the two rows, already zero for a silent frame.
+__device__ __forceinline__ void sp_filter_spectrum(C16T<f32x2>& z, const f32x2 (&ua)[8], const f32x2 (&ub)[8], const float* tw,
+                                                   f32x2* x, int lane, int l) {
+  // e[16 j + l] for j >= 8 is u[16 (16 - j) - l]: register 15 - j of lane 16 - l, or for l = 0 the lane's own register 16 - j
+  const int src = (lane & 48) | ((16 - l) & 15);
+  const f32x2 zero = {0.0f, 0.0f};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    z.re[j] = ua[j];
+    z.im[j] = ub[j];
+  }
+#pragma unroll
+  for (int j = 8; j < 16; ++j) {
+    const f32x2 ma = sp_shfl(ua[15 - j], src), mb = sp_shfl(ub[15 - j], src);
+    const f32x2 oa = j == 8 ? zero : ua[(16 - j) & 7], ob = j == 8 ? zero : ub[(16 - j) & 7];   // u[128] := 0 (h[0] = 0)
+    z.re[j] = sp_select(l == 0, oa, ma);
+    z.im[j] = sp_select(l == 0, ob, mb);
+  }
+  sp_fft256<false>(z, tw, x, l);
+}
+
+__global__ __launch_bounds__(64 * kSpWaves, 3) void fir_noise_spectral_kernel(const float* __restrict__ fir,
+                                                                             const float* __restrict__ noise,
+                                                                             const float* __restrict__ add_in, int B, int T, int len,
+                                                                             int origin, float* __restrict__ out, int nruns, int total) {
+  __shared__ __attribute__((aligned(16))) SpectralLds L;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int kh = lane >> 5, col = lane & 31;
-  // Hop t stages the tap rows of frames t and t-1, so every row is wanted by two workgroups.  Workgroups are dealt to the eight
-  // XCDs round-robin (block b -> XCD b % 8, MI355X_MICROARCH; placement only matters for speed): with t = blockIdx.x the two
-  // always sat on different XCDs and both fetched the row from HBM (32.8 MB per launch instead of 16.4, L2 hit 0.24).  The hop
-  // range is cut into eight contiguous chunks, one per XCD; neighbours in t are then neighbours in launch order on ONE L2.
-  const int per_xcd = gridDim.x >> 3;                         // gridDim.x = 8 ceil(T / 8)
-  const int t = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-  if (t >= T) return;
-  const int b0 = blockIdx.y * kUtt;
+  const int g = lane >> 4, l = lane & 15;
+  // Workgroups are dealt to the eight XCDs round-robin (block i -> XCD i % 8; placement only matters for speed).  The list of
+  // (utterance block, run) with the run fastest is cut into eight contiguous chunks, one per XCD, so that the tap row two
+  // neighbouring runs both read (frame t0 - 1 of one = frame t0 + 6 of the other) comes from one L2.
+  const int per_xcd = gridDim.x >> 3;                           // gridDim.x = 8 ceil(total / 8)
+  const int id = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  if (id >= total) return;
+  const int run = id % nruns;
+  const int b0 = (id / nruns) * kSpUtt + 2 * wave, b1 = b0 + 1; // .x | .y
+  const int t0 = run * kSpHops;
+  const int ta = t0 - 1 + 2 * g, tb = ta + 1;                   // this transform's frames (Re | Im)
   const int N = T * kHop;
+  const bool oka = ta >= 0 && ta < T, okb = tb < T;
+  const int tac = ta < 0 ? 0 : (ta < T ? ta : T - 1), tbc = tb < T ? tb : T - 1;
 
-  // taps: wave w covers rows r = w + 4 q (q = 0..7).  One load instruction fetches HALF rows of TWO rows: lanes 0..31 the
-  // taps [128 h + 4 p, +4) of row w + 4 (2 it), lanes 32..63 the same taps of row w + 4 (2 it + 1); v[it] holds the first
-  // halves (h = 0), v[it + 4] the second.  Staging a half frame then has all 64 lanes busy (a row per instruction left 32
-  // idle in every one of the 416 staging instructions), and the per-row scale search runs on two rows at once.
-  const int p32 = lane & 31;
-  const int my_row = wave + 4 * kh;   // this lane's row of it = 0; row(it) = wave + 4 (2 it + kh) = my_row + 8 it
-  // The stored row is the upper half u[d] = h[128 + d] (include/nws_hip.h); the lower half is its mirror image:
-  // h[4p + i] = u[128 - 4p - i] with u[128] := 0 (h[0] = 0).  Lane p fetches the aligned quad A = u[124 - 4p .. 127 - 4p] and takes
-  // u[128 - 4p] = the first element of lane p-1's quad (one DPP lane shift): both halves
-  // of a row come out of the SAME 512 B of HBM.
-  auto load_rows = [&](int frame, float4 (&v)[8]) {
+  // tap rows first: they fly under the twiddle set-up and, in wave 0, under the noise transform.  Always-in-bounds addresses
+  // and a select afterwards (never a multiplication: 0 * Inf = NaN would leak a clamped row into a silent frame).
+  const int bc0 = b0 < B ? b0 : B - 1, bc1 = b1 < B ? b1 : B - 1;
+  const float* rowa0 = &fir[((size_t)bc0 * T + tac) * kHalf + l];
+  const float* rowb0 = &fir[((size_t)bc0 * T + tbc) * kHalf + l];
+  const float* rowa1 = &fir[((size_t)bc1 * T + tac) * kHalf + l];
+  const float* rowb1 = &fir[((size_t)bc1 * T + tbc) * kHalf + l];
+  f32x2 ua[8], ub[8];
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int b = b0 + my_row + 8 * it;
-      const bool ok = frame >= 0 && frame < T && b < B;
-      // always-in-bounds addresses and a select afterwards: as `ok ? *ptr : zero` hipcc predicated every COMPONENT on its own
-      // (64 global_load_dword per lane instead of 16 global_load_dwordx4: four instructions over the same cache lines)
-      const int bc = b < B ? b : B - 1, fc = frame < 0 ? 0 : (frame < T ? frame : T - 1);
-      // (two index expressions off the same row start: written as `src + 124 - 4 p` hipcc put a temporary on the stack)
-      const float* src = &fir[((size_t)bc * T + fc) * kHalf + 4 * p32];
-      const float* src_lo = &fir[((size_t)bc * T + fc) * kHalf + 4 * (31 - p32)];
-      const float4 hi4 = *reinterpret_cast<const float4*>(src), lo4 = *reinterpret_cast<const float4*>(src_lo);
-      // zeroed by a select on the loaded values (not by a multiplication: 0 * Inf = NaN would leak a clamped row's Inf / NaN into
-      // a frame that has to be silent, and into the utterance's scale search)
-      const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      v[it + 4] = ok ? hi4 : zero4;
-      v[it] = ok ? lo4 : zero4;     // the raw quad A; mirrored when staged
-    }
-  };
-  // the 384 noise samples both frames are cut from, once (reflect padding resolved here), pre-scaled.  Requested BEFORE the
-  // tap rows: the vector-memory counter retires in order, so waiting for these two leaves the 16 row loads in flight
-  float wv[2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int e = tid + 256 * q, i = kHop * (t - 1) + e;
-    const bool in = e < 3 * kHop && i >= 0 && i < N + kL - 1;
-    const float nv = padded_noise(noise, len, origin, in ? i : origin);   // unconditional: both loads issue back to back
-    wv[q] = in ? nv * kNoiseScale : 0.0f;
+  for (int j = 0; j < 8; ++j) {
+    ua[j] = f32x2{rowa0[16 * j], rowa1[16 * j]};
+    ub[j] = f32x2{rowb0[16 * j], rowb1[16 * j]};
   }
-  float4 cur[8], prv[8];
-  load_rows(t, cur);
-  load_rows(t - 1, prv);
-  L.win[tid] = wv[0];
-  L.win[tid + 256] = wv[1];
-
-  // (LDS-only barrier: __syncthreads() would also wait for the tap rows requested above, and the staging of the noise copies
-  // below - LDS and vector work only - is what their latency is there to hide)
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // win complete
-
-  // reversed noise frames, eight shifted copies each: frame 0: R[u] = f_t[(-u) & 255] = win[128 + ((-u) & 255)];
-  // frame 1: R[u] = f_{t-1}[(128 - u) & 255] = win[(128 - u) & 255].  One thread fills 8 consecutive v (one 16-byte chunk).
-  // (lane -> chunk with the shift c fastest: the 8 lanes of one v0 read 15 CONSECUTIVE win entries between them and the next
-  // group continues 8 further on, so a half-wave's ds_read_b32 touch 32 distinct banks; with v0 fastest the lanes were 8
-  // dwords apart - 4 banks, 8-way conflicts - which is where the 0.37 LDS bank-conflict rate of round 2 came from)
-#pragma unroll
-  for (int fr = 0; fr < 2; ++fr) {           // 2 x 8 copies x 32 blocks = two chunks per thread
-    // thread -> (copy c, block): c fastest, the block skewed by sigma(c) = (c - kRot[c]) mod 8 = {0, 0, 5, 2, 7, 0, 5, 2}: the 8 lanes
-    // of a ds_write_b128 group then land on 8 distinct 16-byte slots ((block + kRot[c]) mod 8 = (tid / 8 + c) mod 8), and the
-    // 32 lanes of a ds_read_b32 group still read 32 distinct banks of `win` (offsets 8 sigma(c) + c mod 32 are distinct within a
-    // set of eight, the four sets sit 8 apart)
-    const int c = tid & 7, v0 = 8 * (((tid >> 3) + (int)((0x25072500u >> (4 * c)) & 15u)) & 31);
-    f16x8 h8, l8;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int u0 = (v0 + 2 * q + c) & 255, u1 = (v0 + 2 * q + 1 + c) & 255;
-      const float a = fr == 0 ? L.win[kHop + ((-u0) & 255)] : L.win[(kHop - u0) & 255];
-      const float bb = fr == 0 ? L.win[kHop + ((-u1) & 255)] : L.win[(kHop - u1) & 255];
-      f16x2 hi, lo;
-      split16x2(a, bb, hi, lo);
-      h8[2 * q] = hi.x;
-      h8[2 * q + 1] = hi.y;
-      l8[2 * q] = lo.x;
-      l8[2 * q + 1] = lo.y;
-    }
-    const int vp = (v0 + copy_rot_halfs(c)) & 255;       // the block's rotated place inside its copy
-    *reinterpret_cast<f16x8*>(&L.rhi[fr][c][vp]) = h8;
-    *reinterpret_cast<f16x8*>(&L.rlo[fr][c][vp]) = l8;
+  // W256^(l k): the twiddle between the two passes, the same table in both directions, (cos, sin) at [k][l] (a wave's four
+  // transforms read the same 256 B per k: broadcast; each value twice, see SpOps); in LDS because 30 registers of them per lane cost a wave per SIMD
+  {
+    float c, s;
+    sp_twiddle((tid & 15) * (tid >> 4), c, s);
+    L.tw[tid] = make_float4(c, c, s, s);
   }
-  // one power-of-two scale per utterance (both frames): largest |tap| -> [2^14, 2^15).  Keeps hi AND lo of every tap that
-  // matters clear of the fp16 subnormals whatever the filter gain (-120 dB noise floors included); exact to undo.
-  float scale[4];   // of row my_row + 8 it (each 32-lane half has its own rows)
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    auto amax4 = [](const float4& a) { return fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))); };
-    float mx = fmaxf(amax4(cur[it + 4]), amax4(prv[it + 4]));     // the upper halves hold every distinct tap of the two rows
-    mx = half_max(mx);   // over the 32 lanes that hold this row
-    int ex = (int)((__float_as_uint(mx) >> 23) & 0xff);  // biased exponent of the row maximum
-    ex = ex < 16 ? 16 : (ex > 250 ? 250 : ex);
-    scale[it] = __uint_as_float((unsigned)(268 - ex) << 23);          // 2^(14 - e)
-    if (p32 == 0) L.unscale[my_row + 8 * it] = __uint_as_float((unsigned)(ex - 14) << 23) * (1.0f / kNoiseScale);  // 2^(e - 14) / 2^10
-  }
-  auto stage_rows = [&](const float4 (&v)[8], const int khalf) {  // taps [128 khalf, 128 khalf + 128) of all 32 rows
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int r = my_row + 8 * it;
-      float4 t4 = v[it + 4 * khalf];
-      if (khalf == 0) {   // lower half: h[4p + i] = u[128 - 4p - i] from the quad A = u[124 - 4p .. 127 - 4p] (see load_rows)
-        float up = dpp_f32<0x138, 0xf>(t4.x);      // wave_shr:1: lane l <- lane l-1 (lane 0 keeps the 0 of `old`)
-        up = p32 == 0 ? 0.0f : up;                 // u[128] := 0 (h[0] = 0); also cuts the shift across the two rows of a wave
-        t4 = make_float4(up, t4.w, t4.z, t4.y);
-      }
-      f16x2 h01, l01, h23, l23;
-      split16x2(t4.x * scale[it], t4.y * scale[it], h01, l01);
-      split16x2(t4.z * scale[it], t4.w * scale[it], h23, l23);
-      const f16x4 h = {h01.x, h01.y, h23.x, h23.y}, l = {l01.x, l01.y, l23.x, l23.y};
-      *reinterpret_cast<f16x4*>(&L.hhi[r][4 * p32]) = h;
-      *reinterpret_cast<f16x4*>(&L.hlo[r][4 * p32]) = l;
-    }
-  };
-  stage_rows(cur, 0);
+  const float* tw = reinterpret_cast<const float*>(&L.tw[l]);
   __syncthreads();
 
-  f32x16 acc;
-  const int j = 32 * wave + col;  // output sample inside the hop
-  const int c = (-j) & 7;
-  const int jr = j - copy_rot_halfs(c);   // the copy's block rotation folded into the lane's offset (a multiple of 8: the & ~7 commutes)
-  auto accumulate = [&](const int fr, const int khalf, auto first_tag) {
-    constexpr bool kFirst = decltype(first_tag)::value;
-    const _Float16* rh = &L.rhi[fr][c][0];
-    const _Float16* rl = &L.rlo[fr][c][0];
-#pragma unroll 4
-    for (int ks = 0; ks < kL / 32; ++ks) {
-      const int k = 16 * ks + 8 * kh;                       // tap inside the staged half
-      const int s8 = ((kL / 2 * khalf + k - jr) & 255) & ~7;
-      const f16x8 ahi = *reinterpret_cast<const f16x8*>(&L.hhi[col][k]);
-      const f16x8 alo = *reinterpret_cast<const f16x8*>(&L.hlo[col][k]);
-      const f16x8 bhi = *reinterpret_cast<const f16x8*>(&rh[s8]);
-      const f16x8 blo = *reinterpret_cast<const f16x8*>(&rl[s8]);
-      if (kFirst && ks == 0) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, bhi, f32x16{}, 0, 0, 0);
-      else acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, bhi, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, blo, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(alo, bhi, acc, 0, 0, 0);
+  f32x2* x = &L.x[wave][g * kSpPlane];
+  if (wave == 0) {
+    // noise frames ta | tb (reflect padding resolved here; a frame position outside the padded signal reads as 0)
+    C16 z;
+    float* xs = reinterpret_cast<float*>(x);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int i0 = kHop * ta + 16 * j + l, i1 = i0 + kHop;
+      const bool in0 = i0 >= 0 && i0 < N + kL - 1, in1 = i1 >= 0 && i1 < N + kL - 1;
+      const float v0 = padded_noise(noise, len, origin, in0 ? i0 : origin);
+      const float v1 = padded_noise(noise, len, origin, in1 ? i1 : origin);
+      z.re[j] = in0 ? v0 : 0.0f;
+      z.im[j] = in1 ? v1 : 0.0f;
     }
-  };
-  accumulate(0, 0, std::true_type{});
-  __syncthreads();
-  stage_rows(cur, 1);
-  __syncthreads();
-  accumulate(0, 1, std::false_type{});
-  __syncthreads();
-  stage_rows(prv, 0);
-  __syncthreads();
-  accumulate(1, 0, std::false_type{});
-  __syncthreads();
-  stage_rows(prv, 1);
-  // the 16 values of the other branch this lane adds (cat + sum(1)): requested here, all at once, so that they arrive under
-  // the last 24 MFMAs (as "if (b < B) out = add_in[o] + v" per row hipcc serialised 16 load -> wait -> store round trips to
-  // memory at the end of every wave: 40 % of the kernel's time)
-  float addv[16];
+    sp_fft256<false>(z, tw, xs, l);
+    // Z = X_a + i X_b in (lane k1, register k2).  X_a = (Z[k] + conj Z[-k]) / 2, i X_b = (Z[k] - conj Z[-k]) / 2: the
+    // mirror through this transform's own LDS plane, in natural order
+    float mr[16], mi[16];
+    auto mirror = [&](const float (&v)[16], float (&m)[16]) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) xs[l + 16 * j] = v[j];
+      sp_wave_sync();
+#pragma unroll
+      for (int j = 0; j < 16; ++j) m[j] = xs[(256 - (l + 16 * j)) & 255];
+      sp_wave_sync();
+    };
+    mirror(z.re, mr);
+    mirror(z.im, mi);
+    const float c = (l & 1) ? -(1.0f / 512.0f) : (1.0f / 512.0f);   // (-1)^k / 2 / 256, exact
+#pragma unroll
+    for (int j = 0; j < 9; ++j)      // bins 0 .. 143; S[-k] = conj S[k] and D[-k] = -conj D[k] give the rest
+      L.sd[g][j][l] = make_float4(c * (z.re[j] + mr[j]), c * (z.im[j] - mi[j]), c * (z.re[j] - mr[j]), c * (z.im[j] + mi[j]));
+  }
+  const f32x2 zero = {0.0f, 0.0f};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    ua[j] = sp_select(oka, ua[j], zero);
+    ub[j] = sp_select(okb, ub[j], zero);
+  }
+  C16T<f32x2> z;
+  sp_filter_spectrum(z, ua, ub, tw, x, lane, l);
+  __syncthreads();                                               // the noise spectra are in place
+
+  // the other branch's samples of the hops this lane stores (cat + sum(1)): requested before the inverse transform
   const bool has_add = add_in != nullptr;
+  const bool sta = g > 0 && ta < T, stb = tb < T;
+  const size_t oa0 = (size_t)bc0 * N + (size_t)tac * kHop + l, ob0 = (size_t)bc0 * N + (size_t)tbc * kHop + l;
+  const size_t oa1 = (size_t)bc1 * N + (size_t)tac * kHop + l, ob1 = (size_t)bc1 * N + (size_t)tbc * kHop + l;
+  f32x2 adda[8], addb[8];
+  if (has_add) {
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
-    const int b = b0 + row < B ? b0 + row : B - 1;          // clamped: the load is always in bounds, the store is masked
-    addv[r] = has_add ? add_in[(size_t)b * N + (size_t)t * kHop + j] : 0.0f;
-  }
-  __syncthreads();
-  accumulate(1, 1, std::false_type{});
-
-  const float ola = t == 0 ? 1.0f : 0.5f;  // overlap-add count: 1 in the first hop, else 2
-  float vout[16];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const float4 us = *reinterpret_cast<const float4*>(&L.unscale[8 * g + 4 * kh]);   // rows 8 g + 4 kh + (0..3)
-    const float u4[4] = {us.x, us.y, us.z, us.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float v = acc[4 * g + i] * (ola * u4[i]);
-      vout[4 * g + i] = has_add ? addv[4 * g + i] + v : v;
+    for (int j = 0; j < 8; ++j) {
+      adda[j] = f32x2{add_in[oa0 + 16 * j], add_in[oa1 + 16 * j]};
+      addb[j] = f32x2{add_in[ob0 + 16 * j], add_in[ob1 + 16 * j]};
     }
   }
-  // every value is final before the first store: 16 stores back to back, nothing to wait for in between (with the load, or
-  // a per-row branch, next to each store hipcc put an s_waitcnt vmcnt(0) - the previous store's acknowledgement - in front of it)
-  float* o = out + (size_t)(b0 + 4 * kh) * N + (size_t)t * kHop + j;
-  if (b0 + kUtt <= B) {
+  // P = G_a S + G_b D per bin, element by element: S and D are one float each for both utterances, and a packed instruction
+  // would have to broadcast the upper register of a loaded pair.  Bin k = l + 16 j > 143 reads its mirror image 256 - k =
+  // (lane 16 - l, register 15 - j), for l = 0 (lane 0, register 16 - j): S[k] = conj S[-k], D[k] = -conj D[-k].
+  const float4* sdm = &L.sd[g][l == 0 ? 1 : 0][(16 - l) & 15];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) o[(size_t)((r & 3) + 8 * (r >> 2)) * N] = vout[r];
-  } else {
+  for (int j = 0; j < 16; ++j) {
+    const f32x2 ga = z.re[j], gb = z.im[j];
+    if (j < 9) {
+      const float4 sd = L.sd[g][j][l];
+      z.re[j] = f32x2{fmaf(ga.x, sd.x, gb.x * sd.z), fmaf(ga.y, sd.x, gb.y * sd.z)};
+      z.im[j] = f32x2{fmaf(ga.x, sd.y, gb.x * sd.w), fmaf(ga.y, sd.y, gb.y * sd.w)};
+    } else {
+      const float4 sd = sdm[(15 - j) * 16];
+      z.re[j] = f32x2{fmaf(ga.x, sd.x, -(gb.x * sd.z)), fmaf(ga.y, sd.x, -(gb.y * sd.z))};
+      z.im[j] = f32x2{fmaf(gb.x, sd.w, -(ga.x * sd.y)), fmaf(gb.y, sd.w, -(ga.y * sd.y))};
+    }
+  }
+  sp_fft256<true>(z, tw, x, l);
+  // (lane l, register j) = y_a[l + 16 j] + i y_b[l + 16 j]; overlap-add, divided by the overlap count (1 in the signal's
+  // first hop, else 2; a stored hop ta is never the first)
+  const float invb = tb == 0 ? 1.0f : 0.5f;
+  f32x2 ha[8], hb[8];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2);
-      if (b0 + 4 * kh + row < B) o[(size_t)row * N] = vout[r];
+  for (int j = 0; j < 8; ++j) {
+    const f32x2 ya0 = sp_select(oka, z.re[j], zero), ya1 = sp_select(oka, z.re[j + 8], zero);
+    const f32x2 yb0 = sp_select(okb, z.im[j], zero), yb1 = sp_select(okb, z.im[j + 8], zero);
+    // second half of frame ta - 1: the pair to the left (pair 0 wraps to pair 3; its hop ta belongs to the run before, sta = false)
+    const f32x2 prev = sp_shfl(yb1, (lane - 16) & 63);
+    ha[j] = (ya0 + prev) * 0.5f;
+    hb[j] = (yb0 + ya1) * invb;
+    if (has_add) {
+      ha[j] = adda[j] + ha[j];
+      hb[j] = addb[j] + hb[j];
+    }
+  }
+  if (sta) {
+    if (b0 < B) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) out[oa0 + 16 * j] = ha[j].x;
+    }
+    if (b1 < B) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) out[oa1 + 16 * j] = ha[j].y;
+    }
+  }
+  if (stb) {
+    if (b0 < B) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) out[ob0 + 16 * j] = hb[j].x;
+    }
+    if (b1 < B) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) out[ob1 + 16 * j] = hb[j].y;
     }
   }
 }
@@ -412,9 +400,12 @@ extern "C" int nws_fir_noise_window(const float* fir, const float* noise, int no
                                     int B, int T, float* out, void* stream) {
   if (!fir || !noise || !out || B <= 0 || T <= 0 || noise_len < 2 || origin < 0) return NWS_ERR_BAD_ARG;
   if (B > 65535) return NWS_ERR_UNSUPPORTED;
-  if (B >= 16) {  // shared-noise circulant GEMM on the matrix cores
-    const dim3 grid(8 * ((T + 7) / 8), (B + kUtt - 1) / kUtt);    // see the XCD note in the kernel
-    fir_noise_mfma_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(fir, noise, add_in, B, T, noise_len, origin, out);
+  if (B >= 16) {  // shared noise spectra, one wave per two utterances and run of seven hops
+    const long long nruns = (T + kSpHops - 1) / kSpHops, total = nruns * ((B + kSpUtt - 1) / kSpUtt);
+    if (total > (1ll << 30)) return NWS_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)(8 * ((total + 7) / 8)));           // see the XCD note in the kernel
+    fir_noise_spectral_kernel<<<grid, 64 * kSpWaves, 0, (hipStream_t)stream>>>(fir, noise, add_in, B, T, noise_len, origin, out,
+                                                                             (int)nruns, (int)total);
     NWS_CHECK_LAUNCH();
     return NWS_OK;
   }
@@ -425,7 +416,7 @@ extern "C" int nws_fir_noise_window(const float* fir, const float* noise, int no
 }
 
 // slot mode of a streaming window (stream.hip): per-row reflection bounds and first frames, every B on the per-utterance kernel
-// (the B >= 16 circulant GEMM shares one noise frame over 32 rows; per-row edges would have to be a fix-up beside it)
+// (the B >= 16 spectral kernel shares one set of noise spectra over eight rows; per-row edges would need their own)
 extern "C" int nws_fir_noise_window_rows(const float* fir, const float* noise, int origin, const int4* rows, int B, int T,
                                          float* out, void* stream) {
   if (!fir || !noise || !out || !rows || B <= 0 || T <= 0 || origin < 0) return NWS_ERR_BAD_ARG;

@@ -51,7 +51,7 @@ def run(blocks=4096, iters=2000, rounds=5, product_kernels=True):
                     fn()
             return go
         loads["product: frame_mlps16_kernel x3"] = with_stream(lambda: [eng.frame_mlps(gru) for _ in range(3)])
-        loads["product: fir_noise_mfma_kernel x4"] = with_stream(lambda: [eng.fir_noise(fir, nz, add_in=newt) for _ in range(4)])
+        loads["product: fir_noise_spectral_kernel x4"] = with_stream(lambda: [eng.fir_noise(fir, nz, add_in=newt) for _ in range(4)])
         loads["product: control_gru_kernel"] = with_stream(lambda: eng.control_gru(c))
     out, out2 = {}, {}
     for probe, dst in ((L.nws_coexec_pk_probe, out), (L.nws_coexec_pk_probe2, out2)):
