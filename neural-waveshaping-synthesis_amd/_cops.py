@@ -1,0 +1,400 @@
+"""The ctypes binding with the op layer's surface: `CtypesOps` has one method per operator of the TORCH_LIBRARY(newt_hip)
+block of csrc/torch_ops.cpp - same name, same positional parameters, same return arity - and each method is the call of
+the `extern "C"` launcher(s) of libnws_hip.so that the op of that name makes (tests/test_cpu_cops_surface.py holds the two
+surfaces together).  `engine.binding()` hands out either this object or `torch.ops.newt_hip`, so a call site is written once.
+
+Like the ops, every method takes contiguous fp32 CUDA tensors, allocates its outputs on the tensors' device, enqueues on
+torch's current stream of that device and raises (`_lib.check`) when the launcher reports an error.  `wdesc` / `gdesc` /
+`sdesc` arrive as the CPU uint8 tensor of the struct, `plan` as the CPU int32 tensor of `NwsReverbPlan.as_tensor()`, event
+handles as ints.  This module is the only place in the package that marshals a launcher call through ctypes.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+from ._lib import NwsForwardAux, NwsGenericModel, NwsReverbPlan, NwsShaperDesc, NwsWeights, check, ptr
+
+HOP = _lib.HOP
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _struct(desc: torch.Tensor, cls):
+    """the CPU uint8 tensor of a struct (engine.py / generic.desc_bytes) back as the ctypes struct"""
+    return cls.from_buffer_copy(desc.numpy())
+
+
+def _plan(plan: torch.Tensor | None):
+    return NwsReverbPlan(*plan.tolist()[:6]) if plan is not None else None
+
+
+def _ref(struct):
+    return C.byref(struct) if struct is not None else None
+
+
+def _aux(fir_design, plan, tables, spectrum) -> NwsForwardAux:
+    aux = NwsForwardAux()
+    aux.fir_design = ptr(fir_design)
+    aux.plan = C.pointer(_plan(plan))
+    aux.reverb_tables = ptr(tables)
+    aux.reverb_spectrum = ptr(spectrum)
+    return aux
+
+
+def _new(like: torch.Tensor, *shape, dtype=torch.float32):
+    return torch.empty(shape, dtype=dtype, device=like.device)
+
+
+def _ptrs(tensors):
+    return (C.c_void_p * max(1, len(tensors)))(*[t.data_ptr() for t in tensors])
+
+
+class CtypesOps:
+    def abi_version(self):
+        return int(_lib.lib().nws_abi_version())
+
+    # ---- whole forward and its halves ----------------------------------------------------------------------------------
+    def forward(self, wdesc, f0, control, phase_u, rand_phase, noise, fir_design, plan, reverb_tables, reverb_spectrum,
+                workspace, sample_rate):
+        B, Cc, T = control.shape
+        aux = _aux(fir_design, plan, reverb_tables, reverb_spectrum)
+        with torch.cuda.device(f0.device):
+            out = _new(f0, B, T * HOP)
+            check(_lib.lib().nws_forward(C.byref(_struct(wdesc, NwsWeights)), C.byref(aux), ptr(f0), ptr(control), B, Cc, T,
+                                         sample_rate, ptr(phase_u), ptr(rand_phase), ptr(noise), ptr(out), ptr(workspace),
+                                         workspace.numel(), _stream(f0.device)), "nws_forward")
+        return out
+
+    def forward_control(self, wdesc, f0, control, workspace, batched_gru):
+        B, Cc, T = control.shape
+        with torch.cuda.device(f0.device):
+            check(_lib.lib().nws_forward_control(C.byref(_struct(wdesc, NwsWeights)), ptr(f0), ptr(control), B, Cc, T,
+                                                 1 if batched_gru else 0, ptr(workspace), workspace.numel(), _stream(f0.device)),
+                  "nws_forward_control")
+
+    def forward_audio(self, wdesc, f0, phase_u, rand_phase, noise, fir_design, plan, reverb_tables, reverb_spectrum, workspace,
+                      sample_rate, out, wait_event, record_event):
+        B, _, T = f0.shape
+        aux = _aux(fir_design, plan, reverb_tables, reverb_spectrum)
+        with torch.cuda.device(f0.device):
+            if out is None:
+                out = _new(f0, B, T * HOP)
+            check(_lib.lib().nws_forward_audio_ev(C.byref(_struct(wdesc, NwsWeights)), C.byref(aux), ptr(f0), B, T, sample_rate,
+                                                  ptr(phase_u), ptr(rand_phase), ptr(noise), ptr(out), ptr(workspace),
+                                                  workspace.numel(), _stream(f0.device), wait_event or None, record_event or None),
+                  "nws_forward_audio_ev")
+        return out
+
+    def forward_audio_pre(self, wdesc, f0, phase_u, rand_phase, noise, fir_design, plan, reverb_tables, reverb_spectrum,
+                          workspace, sample_rate):
+        B, _, T = f0.shape
+        aux = _aux(fir_design, plan, reverb_tables, reverb_spectrum)
+        with torch.cuda.device(f0.device):
+            check(_lib.lib().nws_forward_audio_pre(C.byref(_struct(wdesc, NwsWeights)), C.byref(aux), ptr(f0), B, T, sample_rate,
+                                                   ptr(phase_u), ptr(rand_phase), ptr(noise), ptr(workspace), workspace.numel(),
+                                                   _stream(f0.device)), "nws_forward_audio_pre")
+
+    def forward_audio_blocks(self, wdesc, f0, phase_u, rand_phase, noise, fir_design, plan, reverb_tables, reverb_spectrum,
+                             workspace, sample_rate, out, row0, nrows, events):
+        B, _, T = f0.shape
+        n = len(row0)
+        aux = _aux(fir_design, plan, reverb_tables, reverb_spectrum)
+        with torch.cuda.device(f0.device):
+            check(_lib.lib().nws_forward_audio_blocks(C.byref(_struct(wdesc, NwsWeights)), C.byref(aux), ptr(f0), B, T, sample_rate,
+                                                      ptr(phase_u), ptr(rand_phase), ptr(noise), ptr(out), ptr(workspace),
+                                                      workspace.numel(), _stream(f0.device), (C.c_int32 * n)(*row0),
+                                                      (C.c_int32 * n)(*nrows), (C.c_void_p * n)(*events) if events else None, n),
+                  "nws_forward_audio_blocks")
+
+    def forward_reverb_rows(self, fir_design, plan, reverb_tables, reverb_spectrum, workspace, T, row0, nrows, out):
+        aux = _aux(fir_design, plan, reverb_tables, reverb_spectrum)
+        with torch.cuda.device(out.device):
+            check(_lib.lib().nws_forward_reverb_rows(C.byref(aux), out.shape[0], T, row0, nrows, ptr(out), ptr(workspace),
+                                                     workspace.numel(), _stream(out.device)), "nws_forward_reverb_rows")
+
+    # ---- stages of the fused path ----------------------------------------------------------------------------------------
+    def phase_carry(self, f0, f0_up):
+        src = f0 if f0 is not None else f0_up
+        B = src.shape[0]
+        T = src.shape[-1] if f0 is not None else src.shape[-1] // HOP
+        with torch.cuda.device(src.device):
+            carry = _new(src, B, T * HOP // 32, dtype=torch.float64)
+            check(_lib.lib().nws_phase_carry(ptr(f0), ptr(f0_up), B, T, ptr(carry), _stream(src.device)), "nws_phase_carry")
+        return carry
+
+    def exciter_newt(self, wdesc, f0, f0_up, carry, phase_u, rand_phase, film, sample_rate, want_exciter, want_newt):
+        src = f0 if f0 is not None else f0_up
+        B = src.shape[0]
+        T = src.shape[-1] if f0 is not None else src.shape[-1] // HOP
+        with torch.cuda.device(src.device):
+            exc = _new(src, B, _lib.N_SHAPERS, T * HOP) if want_exciter else None
+            out = _new(src, B, T * HOP) if want_newt else None
+            check(_lib.lib().nws_exciter_newt(C.byref(_struct(wdesc, NwsWeights)), ptr(f0), ptr(f0_up), ptr(carry), ptr(phase_u),
+                                              ptr(rand_phase), ptr(film), B, T, sample_rate, ptr(exc), ptr(out),
+                                              _stream(src.device)), "nws_exciter_newt")
+        return exc, out
+
+    def oscillator(self, f0_up, phase_u, rand_phase, sample_rate):
+        B, N = f0_up.shape
+        with torch.cuda.device(f0_up.device):
+            st = _stream(f0_up.device)
+            carry = _new(f0_up, B, N // 32, dtype=torch.float64)
+            out = _new(f0_up, B, _lib.N_HARMONICS, N)
+            check(_lib.lib().nws_phase_carry(None, ptr(f0_up), B, N // HOP, ptr(carry), st), "nws_phase_carry")
+            check(_lib.lib().nws_oscillator(ptr(f0_up), ptr(carry), ptr(phase_u), ptr(rand_phase), B, N, sample_rate, ptr(out), st),
+                  "nws_oscillator")
+        return out
+
+    def control_gru(self, wdesc, control, h0, batched):
+        B, Cc, T = control.shape
+        fn = _lib.lib().nws_control_gru_batched if batched else _lib.lib().nws_control_gru_state
+        with torch.cuda.device(control.device):
+            out = _new(control, B, T, _lib.HIDDEN)
+            hT = _new(control, B, _lib.HIDDEN)
+            check(fn(C.byref(_struct(wdesc, NwsWeights)), ptr(control), B, Cc, T, ptr(h0), ptr(out), ptr(hT),
+                     _stream(control.device)), "nws_control_gru")
+        return out, hT
+
+    def frame_mlps(self, wdesc, gru_out, fir_design, want_emb, want_H):
+        B, T, _ = gru_out.shape
+        with torch.cuda.device(gru_out.device):
+            emb = _new(gru_out, B, _lib.HIDDEN, T) if want_emb else None
+            film = _new(gru_out, B, T, _lib.FILM_CH)
+            H = _new(gru_out, B, T, _lib.N_BANDS) if want_H else None
+            fir = _new(gru_out, B, T, _lib.FIR_HALF)
+            check(_lib.lib().nws_frame_mlps(C.byref(_struct(wdesc, NwsWeights)), ptr(gru_out), ptr(fir_design), B, T, ptr(emb),
+                                            ptr(film), ptr(H), ptr(fir), _stream(gru_out.device)), "nws_frame_mlps")
+        return emb, film, H, fir
+
+    def fir_noise(self, fir, noise, add_in, origin):
+        B, T, _ = fir.shape
+        with torch.cuda.device(fir.device):
+            out = _new(fir, B, T * HOP)
+            if origin < 0:
+                check(_lib.lib().nws_fir_noise(ptr(fir), ptr(noise), ptr(add_in), B, T, ptr(out), _stream(fir.device)), "nws_fir_noise")
+            else:
+                check(_lib.lib().nws_fir_noise_window(ptr(fir), ptr(noise), noise.numel(), origin, ptr(add_in), B, T, ptr(out),
+                                                      _stream(fir.device)), "nws_fir_noise_window")
+        return out
+
+    def fir_from_h(self, H, fir_design):
+        B, _, T = H.shape
+        with torch.cuda.device(H.device):
+            fir = _new(H, B, T, _lib.FIR_HALF)
+            check(_lib.lib().nws_fir_from_h(ptr(H), ptr(fir_design), B, T, ptr(fir), _stream(H.device)), "nws_fir_from_h")
+        return fir
+
+    def reverb(self, plan, tables, spectrum, x):
+        B, N = x.shape
+        p = _plan(plan)
+        with torch.cuda.device(x.device):
+            nbytes = _lib.lib().nws_reverb_workspace_bytes(C.byref(p), B)
+            ws = _new(x, nbytes, dtype=torch.uint8)
+            y = torch.empty_like(x)
+            check(_lib.lib().nws_reverb(C.byref(p), ptr(tables), ptr(spectrum), ptr(x), B, N, ptr(y), ptr(ws), nbytes,
+                                        _stream(x.device)), "nws_reverb")
+        return y
+
+    def reverb_linear_chunk(self, plan, tables, spectrum, x, tail_in):
+        B, M = x.shape
+        p = _plan(plan)
+        with torch.cuda.device(x.device):
+            nfl = (2 * ((B + 1) // 2) + B) * p.L
+            ws = _new(x, nfl)
+            y, tail_out = torch.empty_like(x), torch.empty_like(tail_in)
+            check(_lib.lib().nws_reverb_linear_chunk(C.byref(p), ptr(tables), ptr(spectrum), ptr(x), B, M, ptr(tail_in),
+                                                     ptr(tail_out), tail_in.shape[1], ptr(y), ptr(ws), nfl * 4, _stream(x.device)),
+                  "nws_reverb_linear_chunk")
+        return y, tail_out
+
+    def shaper_apply(self, wdesc, x):
+        with torch.cuda.device(x.device):
+            y = torch.empty_like(x)
+            check(_lib.lib().nws_shaper_apply(C.byref(_struct(wdesc, NwsWeights)), ptr(x), x.shape[0], x.shape[2], ptr(y),
+                                              _stream(x.device)), "nws_shaper_apply")
+        return y
+
+    def shaper_table(self, wdesc, like, size, tmin, tmax):
+        with torch.cuda.device(like.device):
+            table = _new(like, _lib.N_SHAPERS, size)
+            check(_lib.lib().nws_shaper_table(C.byref(_struct(wdesc, NwsWeights)), size, tmin, tmax, ptr(table), _stream(like.device)),
+                  "nws_shaper_table")
+        return table
+
+    def newt_apply(self, wdesc, exciter, film):
+        B, _, N = exciter.shape
+        T = film.shape[2]
+        if film.shape[1] != _lib.FILM_CH or N != T * HOP:
+            raise RuntimeError(f"NEWT: exciter {tuple(exciter.shape)} and FiLM parameters {tuple(film.shape)} disagree")
+        with torch.cuda.device(exciter.device):
+            out = _new(exciter, B, 1, N)
+            check(_lib.lib().nws_newt_apply(C.byref(_struct(wdesc, NwsWeights)), ptr(exciter), ptr(film), B, T, ptr(out),
+                                            _stream(exciter.device)), "nws_newt_apply")
+        return out
+
+    # ---- stand-alone stage kernels (csrc/stages.hip) ---------------------------------------------------------------------
+    def td_mlp(self, x, weights, biases, ln_w, ln_b, eps, slope):
+        B, in_size, T = x.shape
+        hidden, out_size = weights[0].shape[0], weights[-1].shape[0]
+        with torch.cuda.device(x.device):
+            y = _new(x, B, out_size, T)
+            check(_lib.lib().nws_td_mlp(ptr(x), B, in_size, hidden, out_size, len(weights), T, _ptrs(weights), _ptrs(biases),
+                                        _ptrs(ln_w), _ptrs(ln_b), eps, slope, ptr(y), _stream(x.device)), "nws_td_mlp")
+        return y
+
+    def td_layer_norm(self, x, weight, bias, eps):
+        with torch.cuda.device(x.device):
+            y = torch.empty_like(x)
+            check(_lib.lib().nws_td_layer_norm(ptr(x), ptr(weight), ptr(bias), x.shape[0], x.shape[1], x.shape[2], eps, ptr(y),
+                                               _stream(x.device)), "nws_td_layer_norm")
+        return y
+
+    def film(self, x, gamma, beta):
+        with torch.cuda.device(x.device):
+            y = torch.empty_like(x)
+            check(_lib.lib().nws_film(ptr(x), ptr(gamma), ptr(beta), x.numel(), ptr(y), _stream(x.device)), "nws_film")
+        return y
+
+    def sine(self, x):
+        with torch.cuda.device(x.device):
+            y = torch.empty_like(x)
+            check(_lib.lib().nws_sin(ptr(x), ptr(y), x.numel(), _stream(x.device)), "nws_sin")
+        return y
+
+    def loudness(self, audio, dft, n_fft, hop, amin, top_db, normalise):
+        B, N = audio.shape
+        L = _lib.lib()
+        with torch.cuda.device(audio.device):
+            ws = _new(audio, L.nws_loudness_workspace_bytes(B, N, n_fft, hop), dtype=torch.uint8)
+            out = _new(audio, B, L.nws_loudness_frames(N, hop))
+            check(L.nws_loudness(ptr(audio), B, N, n_fft, hop, ptr(dft), amin, top_db, 1 if normalise else 0, ptr(out), ptr(ws),
+                                 ws.numel(), _stream(audio.device)), "nws_loudness")
+        return out
+
+    # ---- runtime-size path (csrc/generic.hip) ----------------------------------------------------------------------------
+    def forward_generic(self, gdesc, f0, control, phase_u, rand_phase, noise, plan, reverb_tables, reverb_spectrum,
+                        reverb_workspace, workspace, sample_rate):
+        B, Cc, T = control.shape
+        g = _struct(gdesc, NwsGenericModel)
+        p = _plan(plan)
+        with torch.cuda.device(f0.device):
+            out = _new(f0, B, T * g.hop)
+            check(_lib.lib().nws_forward_generic(C.byref(g), ptr(f0), ptr(control), B, Cc, T, sample_rate, ptr(phase_u),
+                                                 ptr(rand_phase), ptr(noise), _ref(p), ptr(reverb_tables), ptr(reverb_spectrum),
+                                                 ptr(reverb_workspace) if p is not None else None,
+                                                 reverb_workspace.numel() if p is not None else 0, ptr(out), ptr(workspace),
+                                                 workspace.numel(), _stream(f0.device)), "nws_forward_generic")
+        return out
+
+    def g_gru(self, w_ih, w_hh, b_ih, b_hh, control, h0):
+        B, Ct, T = control.shape
+        H, Cin = w_hh.shape[1], w_ih.shape[1]
+        L = _lib.lib()
+        with torch.cuda.device(control.device):
+            out = _new(control, B, T, H)
+            hT = _new(control, B, H)
+            nb = L.nws_g_gru_workspace_bytes(H)
+            ws = _new(control, nb, dtype=torch.uint8)
+            check(L.nws_g_gru(ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(control), B, Ct, Cin, H, T, ptr(h0), ptr(out), ptr(hT),
+                              ptr(ws), nb, _stream(control.device)), "nws_g_gru")
+        return out, hT
+
+    def g_oscillator(self, f0_up, phase_u, rand_phase, sample_rate):
+        B, N = f0_up.shape
+        K = phase_u.numel()
+        with torch.cuda.device(f0_up.device):
+            st = _stream(f0_up.device)
+            phase = torch.empty_like(f0_up)
+            out = _new(f0_up, B, K, N)
+            check(_lib.lib().nws_g_phase(None, ptr(f0_up), B, N, 1, sample_rate, None, ptr(phase), st), "nws_g_phase")
+            check(_lib.lib().nws_g_oscillator(ptr(f0_up), ptr(phase), ptr(phase_u), ptr(rand_phase), K, B, N, sample_rate, ptr(out),
+                                              st), "nws_g_oscillator")
+        return out
+
+    def g_conv1x1(self, x, weight, bias):
+        B, Cin, N = x.shape
+        Cout = weight.shape[0]
+        with torch.cuda.device(x.device):
+            y = _new(x, B, Cout, N)
+            check(_lib.lib().nws_g_conv1x1(ptr(x), ptr(weight), ptr(bias), B, Cin, Cout, N, ptr(y), _stream(x.device)),
+                  "nws_g_conv1x1")
+        return y
+
+    def g_upsample(self, x, hop):
+        T = x.shape[-1]
+        with torch.cuda.device(x.device):
+            y = _new(x, *x.shape[:-1], T * hop)
+            check(_lib.lib().nws_g_upsample(ptr(x), x.numel() // T, T, hop, ptr(y), _stream(x.device)), "nws_g_upsample")
+        return y
+
+    def g_shaper_apply(self, sdesc, x):
+        with torch.cuda.device(x.device):
+            y = torch.empty_like(x)
+            check(_lib.lib().nws_g_shaper_apply(C.byref(_struct(sdesc, NwsShaperDesc)), ptr(x), x.shape[0] * x.shape[1], x.shape[2],
+                                                ptr(y), _stream(x.device)), "nws_g_shaper_apply")
+        return y
+
+    def g_shaper_table(self, sdesc, like, size, tmin, tmax):
+        d = _struct(sdesc, NwsShaperDesc)
+        with torch.cuda.device(like.device):
+            table = _new(like, d.n_shapers, size)
+            check(_lib.lib().nws_g_shaper_table(C.byref(d), size, tmin, tmax, ptr(table), _stream(like.device)), "nws_g_shaper_table")
+        return table
+
+    def g_newt_apply(self, sdesc, exciter, film, mix_w, mix_b):
+        B, S, N = exciter.shape
+        T = film.shape[2]
+        O = mix_w.numel() // S
+        with torch.cuda.device(exciter.device):
+            st = _stream(exciter.device)
+            shaped = torch.empty_like(exciter)
+            out = _new(exciter, B, O, N)
+            check(_lib.lib().nws_g_film_shaper(C.byref(_struct(sdesc, NwsShaperDesc)), ptr(exciter), ptr(film), B, T, N // T,
+                                               ptr(shaped), st), "nws_g_film_shaper")
+            check(_lib.lib().nws_g_conv1x1(ptr(shaped), ptr(mix_w), ptr(mix_b), B, S, O, N, ptr(out), st), "nws_g_conv1x1")
+        return out
+
+    def g_fir_noise(self, H, window, noise, hop):
+        B, _, T = H.shape
+        Lf = window.numel()
+        with torch.cuda.device(H.device):
+            st = _stream(H.device)
+            fir = _new(H, B, T, Lf)
+            out = _new(H, B, T * hop)
+            check(_lib.lib().nws_g_fir_design(ptr(H), ptr(window), Lf, B, T, ptr(fir), st), "nws_g_fir_design")
+            check(_lib.lib().nws_g_fir_noise(ptr(fir), ptr(noise), Lf, hop, B, T, None, 0, ptr(out), st), "nws_g_fir_noise")
+        return out
+
+    def g_reverb_direct(self, x, ir):
+        with torch.cuda.device(x.device):
+            y = torch.empty_like(x)
+            check(_lib.lib().nws_g_reverb_direct(ptr(x), ptr(ir), ir.numel(), x.shape[0], x.shape[1], ptr(y), _stream(x.device)),
+                  "nws_g_reverb_direct")
+        return y
+
+    # ---- stateful streaming step (csrc/stream.hip) -----------------------------------------------------------------------
+    def stream_step(self, wdesc, fir_design, plan, reverb_tables, reverb_spectrum, state, max_frames, f0, control, first, final,
+                    frames_seen, nz_prev_start, sample_rate, phase_u, rand_phase, noise_new, noise_all, ir, out, pre_out):
+        B, K = f0.shape
+        with torch.cuda.device(f0.device):
+            check(_lib.lib().nws_stream_step(
+                C.byref(_struct(wdesc, NwsWeights)), ptr(fir_design), _ref(_plan(plan)), ptr(reverb_tables), ptr(reverb_spectrum),
+                ptr(state), state.numel(), B, max_frames, ptr(f0), ptr(control), control.shape[1], K, int(first), int(final),
+                frames_seen, nz_prev_start, sample_rate, ptr(phase_u), ptr(rand_phase), ptr(noise_new), ptr(noise_all),
+                noise_all.numel() if noise_all is not None else 0, ptr(ir), ir.numel(), ptr(out), ptr(pre_out),
+                _stream(f0.device)), "nws_stream_step")
+
+    def stream_step_slots(self, wdesc, fir_design, state, max_frames, f0, control, frames_seen, nz_prev_start, sample_rate, phase_u,
+                          rand_phase, noise_new, noise_all, ir, events, out, pre_out):
+        B, K = f0.shape
+        with torch.cuda.device(f0.device):
+            check(_lib.lib().nws_stream_step_slots(
+                C.byref(_struct(wdesc, NwsWeights)), ptr(fir_design), ptr(state), state.numel(), B, max_frames, ptr(f0),
+                ptr(control), control.shape[1], K, frames_seen, nz_prev_start, sample_rate, ptr(phase_u), ptr(rand_phase),
+                ptr(noise_new), ptr(noise_all), noise_all.numel() if noise_all is not None else 0, ptr(ir), ir.numel(),
+                ptr(events), ptr(out), ptr(pre_out), _stream(f0.device)), "nws_stream_step_slots")

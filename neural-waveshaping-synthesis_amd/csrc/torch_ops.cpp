@@ -120,6 +120,27 @@ void check_draws(const Tensor& phase_u, const Tensor& rand_phase, const Tensor& 
   TORCH_CHECK(noise.numel() == NWS_HOP * T - 1, "noise: expected ", NWS_HOP * T - 1, " elements, got ", noise.sizes());
 }
 
+// what forward_audio, forward_audio_pre and forward_audio_blocks check before anything else: f0's shape, the two draws and the
+// workspace, then (Aux) the model's tables as the launchers' NwsForwardAux
+struct AudioShape {
+  int64_t B, T;
+  AudioShape(const Tensor& f0, const Tensor& phase_u, const Tensor& rand_phase, const Tensor& noise, const Tensor& workspace) {
+    check_dev(f0, "f0");
+    TORCH_CHECK(f0.dim() == 3 && f0.size(1) == 1 && f0.size(2) >= 2, "f0: expected (B, 1, T>=2), got ", f0.sizes());
+    B = f0.size(0);
+    T = f0.size(2);
+    check_draws(phase_u, rand_phase, noise, T, f0);
+    check_dev(workspace, "workspace", at::kByte);
+    check_same_device(f0, "f0", workspace, "workspace");
+  }
+};
+
+struct AudioArgs : AudioShape, Aux {      // (bases are built in this order: the checks above run first, as they always did)
+  AudioArgs(const Tensor& f0, const Tensor& phase_u, const Tensor& rand_phase, const Tensor& noise, const Tensor& fir_design,
+            const Tensor& plan_t, const Tensor& tables, const Tensor& spectrum, const Tensor& workspace)
+      : AudioShape(f0, phase_u, rand_phase, noise, workspace), Aux(fir_design, plan_t, tables, spectrum) {}
+};
+
 // ---- whole forward: models/neural_waveshaping.py:74-90 ---------------------------------------------------------------
 Tensor forward(const Tensor& wdesc, const Tensor& f0, const Tensor& control, const Tensor& phase_u, const Tensor& rand_phase,
                const Tensor& noise, const Tensor& fir_design, const Tensor& plan, const Tensor& reverb_tables,
@@ -157,13 +178,8 @@ Tensor forward_audio(const Tensor& wdesc, const Tensor& f0, const Tensor& phase_
                      const Tensor& fir_design, const Tensor& plan, const Tensor& reverb_tables, const Tensor& reverb_spectrum,
                      Tensor& workspace, double sample_rate, const OptTensor& out_opt, int64_t wait_event, int64_t record_event) {
   const NwsWeights* w = weights_of(wdesc);
-  check_dev(f0, "f0");
-  TORCH_CHECK(f0.dim() == 3 && f0.size(1) == 1 && f0.size(2) >= 2, "f0: expected (B, 1, T>=2), got ", f0.sizes());
-  const int64_t B = f0.size(0), T = f0.size(2);
-  check_draws(phase_u, rand_phase, noise, T, f0);
-  check_dev(workspace, "workspace", at::kByte);
-  check_same_device(f0, "f0", workspace, "workspace");
-  Aux a(fir_design, plan, reverb_tables, reverb_spectrum);
+  AudioArgs a(f0, phase_u, rand_phase, noise, fir_design, plan, reverb_tables, reverb_spectrum, workspace);
+  const int64_t B = a.B, T = a.T;
   Launch L(f0);
   Tensor out;
   if (out_opt.has_value()) {
@@ -188,13 +204,8 @@ void forward_audio_pre(const Tensor& wdesc, const Tensor& f0, const Tensor& phas
                        const Tensor& fir_design, const Tensor& plan, const Tensor& reverb_tables, const Tensor& reverb_spectrum,
                        Tensor& workspace, double sample_rate) {
   const NwsWeights* w = weights_of(wdesc);
-  check_dev(f0, "f0");
-  TORCH_CHECK(f0.dim() == 3 && f0.size(1) == 1 && f0.size(2) >= 2, "f0: expected (B, 1, T>=2), got ", f0.sizes());
-  const int64_t B = f0.size(0), T = f0.size(2);
-  check_draws(phase_u, rand_phase, noise, T, f0);
-  check_dev(workspace, "workspace", at::kByte);
-  check_same_device(f0, "f0", workspace, "workspace");
-  Aux a(fir_design, plan, reverb_tables, reverb_spectrum);
+  AudioArgs a(f0, phase_u, rand_phase, noise, fir_design, plan, reverb_tables, reverb_spectrum, workspace);
+  const int64_t B = a.B, T = a.T;
   Launch L(f0);
   nws_check(nws_forward_audio_pre(w, &a.aux, f0.data_ptr<float>(), (int)B, (int)T, (float)sample_rate, phase_u.data_ptr<float>(),
                                   rand_phase.data_ptr<float>(), noise.data_ptr<float>(), workspace.data_ptr(),
@@ -220,13 +231,9 @@ void forward_audio_blocks(const Tensor& wdesc, const Tensor& f0, const Tensor& p
                           Tensor& workspace, double sample_rate, Tensor& out, at::IntArrayRef row0, at::IntArrayRef nrows,
                           at::IntArrayRef events) {
   const NwsWeights* w = weights_of(wdesc);
-  check_dev(f0, "f0");
-  TORCH_CHECK(f0.dim() == 3 && f0.size(1) == 1 && f0.size(2) >= 2, "f0: expected (B, 1, T>=2), got ", f0.sizes());
-  const int64_t B = f0.size(0), T = f0.size(2);
-  check_draws(phase_u, rand_phase, noise, T, f0);
-  check_dev(workspace, "workspace", at::kByte);
+  AudioArgs a(f0, phase_u, rand_phase, noise, fir_design, plan, reverb_tables, reverb_spectrum, workspace);
+  const int64_t B = a.B, T = a.T;
   check_dev(out, "out");
-  check_same_device(f0, "f0", workspace, "workspace");
   check_same_device(f0, "f0", out, "out");
   TORCH_CHECK(out.dim() == 2 && out.size(0) == B && out.size(1) == T * NWS_HOP && out.is_contiguous(), "out: expected a contiguous (", B, ", ",
               T * NWS_HOP, "), got ", out.sizes());
@@ -235,7 +242,6 @@ void forward_audio_blocks(const Tensor& wdesc, const Tensor& f0, const Tensor& p
   std::vector<int32_t> r0(row0.begin(), row0.end()), nr(nrows.begin(), nrows.end());
   std::vector<void*> ev(events.size());
   for (size_t q = 0; q < events.size(); ++q) ev[q] = reinterpret_cast<void*>(static_cast<uintptr_t>(events[q]));
-  Aux a(fir_design, plan, reverb_tables, reverb_spectrum);
   Launch L(f0);
   nws_check(nws_forward_audio_blocks(w, &a.aux, f0.data_ptr<float>(), (int)B, (int)T, (float)sample_rate, phase_u.data_ptr<float>(),
                                      rand_phase.data_ptr<float>(), noise.data_ptr<float>(), out.data_ptr<float>(), workspace.data_ptr(),
@@ -800,13 +806,13 @@ Tensor g_reverb_direct(const Tensor& x, const Tensor& ir) {
   return y;
 }
 
-// ---- stateful streaming step (csrc/stream.hip): K new frames of B streams -> out (B, M); all state in `state` ----------
-void stream_step(const Tensor& wdesc, const Tensor& fir_design, const OptTensor& plan_t, const OptTensor& tables,
-                 const OptTensor& spectrum, Tensor& state, int64_t max_frames, const Tensor& f0, const Tensor& control, bool first,
-                 bool final, int64_t frames_seen, int64_t nz_prev_start, double sample_rate, const Tensor& phase_u,
-                 const Tensor& rand_phase, const OptTensor& noise_new, const OptTensor& noise_all, const Tensor& ir, Tensor& out,
-                 const OptTensor& pre_out) {
-  const NwsWeights* w = weights_of(wdesc);
+// ---- what stream_step and stream_step_slots check alike; `op` is the name their messages carry -----------------------------
+struct StepDims {
+  int64_t B, K, C;
+};
+
+StepDims check_step_tensors(const char* op, const Tensor& f0, const Tensor& control, const Tensor& fir_design, const Tensor& state,
+                            const Tensor& phase_u, const Tensor& rand_phase, const Tensor& ir, const Tensor& out) {
   check_dev(f0, "f0");
   check_dev(control, "control");
   check_dev(fir_design, "fir_design");
@@ -820,24 +826,41 @@ void stream_step(const Tensor& wdesc, const Tensor& fir_design, const OptTensor&
   check_same_device(f0, "f0", out, "out");
   check_same_device(f0, "f0", ir, "reverb.ir");
   TORCH_CHECK(f0.dim() == 2 && control.dim() == 3 && control.size(0) == f0.size(0) && control.size(2) == f0.size(1) && control.size(1) >= 2,
-              "stream_step: f0 (B, K), control (B, C>=2, K); got ", f0.sizes(), " / ", control.sizes());
-  const int64_t B = f0.size(0), K = f0.size(1), C = control.size(1);
-  TORCH_CHECK(K >= 1 && K <= max_frames, "stream_step: chunk of ", K, " frames, the stream was sized for ", max_frames);
+              op, ": f0 (B, K), control (B, C>=2, K); got ", f0.sizes(), " / ", control.sizes());
+  return {f0.size(0), f0.size(1), control.size(1)};
+}
+
+void check_step_io(const char* op, const StepDims& d, bool first, bool final, int64_t frames_seen, const Tensor& phase_u,
+                   const Tensor& rand_phase, const OptTensor& noise_new, const OptTensor& noise_all, const Tensor& out,
+                   const OptTensor& pre_out) {
   TORCH_CHECK(phase_u.numel() == NWS_N_HARMONICS && rand_phase.numel() == NWS_N_HARMONICS, "phase_u / rand_phase: 101 elements each");
-  TORCH_CHECK(noise_new.has_value() != noise_all.has_value(), "stream_step: give exactly one of noise_new and noise_all");
-  const int M = nws_stream_out_samples((int)K, first, final);
-  TORCH_CHECK(out.numel() == B * M, "out: expected (", B, ", ", M, "), got ", out.sizes());
+  TORCH_CHECK(noise_new.has_value() != noise_all.has_value(), op, ": give exactly one of noise_new and noise_all");
+  const int M = nws_stream_out_samples((int)d.K, first, final);
+  TORCH_CHECK(out.numel() == d.B * M, "out: expected (", d.B, ", ", M, "), got ", out.sizes());
   if (pre_out.has_value()) {
     check_dev(*pre_out, "pre_out");
-    TORCH_CHECK(pre_out->numel() == B * M, "pre_out: expected (", B, ", ", M, ")");
+    TORCH_CHECK(pre_out->numel() == d.B * M, "pre_out: expected (", d.B, ", ", M, ")");
   }
   if (noise_new.has_value()) {
     check_dev(*noise_new, "noise_new");
-    TORCH_CHECK(noise_new->numel() >= nws_stream_noise_draws((int)K, first, frames_seen), "noise_new: expected ",
-                nws_stream_noise_draws((int)K, first, frames_seen), " fresh samples");
+    TORCH_CHECK(noise_new->numel() >= nws_stream_noise_draws((int)d.K, first, frames_seen), "noise_new: expected ",
+                nws_stream_noise_draws((int)d.K, first, frames_seen), " fresh samples");
   } else {
     check_dev(*noise_all, "noise_all");
   }
+}
+
+// ---- stateful streaming step (csrc/stream.hip): K new frames of B streams -> out (B, M); all state in `state` ----------
+void stream_step(const Tensor& wdesc, const Tensor& fir_design, const OptTensor& plan_t, const OptTensor& tables,
+                 const OptTensor& spectrum, Tensor& state, int64_t max_frames, const Tensor& f0, const Tensor& control, bool first,
+                 bool final, int64_t frames_seen, int64_t nz_prev_start, double sample_rate, const Tensor& phase_u,
+                 const Tensor& rand_phase, const OptTensor& noise_new, const OptTensor& noise_all, const Tensor& ir, Tensor& out,
+                 const OptTensor& pre_out) {
+  const NwsWeights* w = weights_of(wdesc);
+  const StepDims d = check_step_tensors("stream_step", f0, control, fir_design, state, phase_u, rand_phase, ir, out);
+  const int64_t B = d.B, K = d.K, C = d.C;
+  TORCH_CHECK(K >= 1 && K <= max_frames, "stream_step: chunk of ", K, " frames, the stream was sized for ", max_frames);
+  check_step_io("stream_step", d, first, final, frames_seen, phase_u, rand_phase, noise_new, noise_all, out, pre_out);
   NwsReverbPlan plan{};
   const bool fft = plan_t.has_value();
   if (fft) {
@@ -866,41 +889,13 @@ void stream_step_slots(const Tensor& wdesc, const Tensor& fir_design, Tensor& st
                        const Tensor& rand_phase, const OptTensor& noise_new, const OptTensor& noise_all, const Tensor& ir,
                        const Tensor& events, Tensor& out, const OptTensor& pre_out) {
   const NwsWeights* w = weights_of(wdesc);
-  check_dev(f0, "f0");
-  check_dev(control, "control");
-  check_dev(fir_design, "fir_design");
-  check_dev(state, "state", at::kByte);
-  check_dev(phase_u, "phase_u");
-  check_dev(rand_phase, "rand_phase");
-  check_dev(ir, "reverb.ir");
-  check_dev(out, "out");
+  const StepDims d = check_step_tensors("stream_step_slots", f0, control, fir_design, state, phase_u, rand_phase, ir, out);
+  const int64_t B = d.B, K = d.K, C = d.C;
   check_dev(events, "events", at::kInt);
-  check_same_device(f0, "f0", control, "control");
-  check_same_device(f0, "f0", state, "state");
-  check_same_device(f0, "f0", out, "out");
-  check_same_device(f0, "f0", ir, "reverb.ir");
   check_same_device(f0, "f0", events, "events");
-  TORCH_CHECK(f0.dim() == 2 && control.dim() == 3 && control.size(0) == f0.size(0) && control.size(2) == f0.size(1) && control.size(1) >= 2,
-              "stream_step_slots: f0 (B, K), control (B, C>=2, K); got ", f0.sizes(), " / ", control.sizes());
-  const int64_t B = f0.size(0), K = f0.size(1), C = control.size(1);
   TORCH_CHECK(K >= 1 && K <= 16 && K <= max_frames, "stream_step_slots: hops of 1 .. 16 frames (sized for ", max_frames, "), got ", K);
   TORCH_CHECK(events.numel() == B, "stream_step_slots: events: one int32 word per slot, expected ", B, ", got ", events.numel());
-  TORCH_CHECK(phase_u.numel() == NWS_N_HARMONICS && rand_phase.numel() == NWS_N_HARMONICS, "phase_u / rand_phase: 101 elements each");
-  TORCH_CHECK(noise_new.has_value() != noise_all.has_value(), "stream_step_slots: give exactly one of noise_new and noise_all");
-  const int first = frames_seen == 0 ? 1 : 0;
-  const int M = nws_stream_out_samples((int)K, first, 0);
-  TORCH_CHECK(out.numel() == B * M, "out: expected (", B, ", ", M, "), got ", out.sizes());
-  if (pre_out.has_value()) {
-    check_dev(*pre_out, "pre_out");
-    TORCH_CHECK(pre_out->numel() == B * M, "pre_out: expected (", B, ", ", M, ")");
-  }
-  if (noise_new.has_value()) {
-    check_dev(*noise_new, "noise_new");
-    TORCH_CHECK(noise_new->numel() >= nws_stream_noise_draws((int)K, first, frames_seen), "noise_new: expected ",
-                nws_stream_noise_draws((int)K, first, frames_seen), " fresh samples");
-  } else {
-    check_dev(*noise_all, "noise_all");
-  }
+  check_step_io("stream_step_slots", d, frames_seen == 0, false, frames_seen, phase_u, rand_phase, noise_new, noise_all, out, pre_out);
   TORCH_CHECK((size_t)state.numel() >= nws_stream_slot_state_bytes((int)B, (int)max_frames, (int)ir.numel()),
               "stream_step_slots: state blob too small");
   Launch L(f0);

@@ -8,7 +8,6 @@ or a (N,) / (B, N) CUDA tensor (returns a tensor per row).  No CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Callable, Optional
 
 import numpy as np
@@ -17,7 +16,7 @@ import torch
 from ... import _lib
 from ... import ginlite as gin
 from ..._lib import check, ptr
-from ...engine import ops, stream_ptr
+from ...engine import binding, stream_ptr
 from .upsampling import linear_interpolation
 
 _DFT_CACHE: dict = {}
@@ -46,22 +45,13 @@ def loudness_frames(audio: torch.Tensor, n_fft: int, hop_length: int, epsilon: f
     audio = audio.contiguous()
     B, N = audio.shape
     L = _lib.lib()
-    frames = L.nws_loudness_frames(N, hop_length)
     nbytes = L.nws_loudness_workspace_bytes(B, N, n_fft, hop_length)
     if nbytes == 0 or N <= n_fft // 2:
         raise RuntimeError(f"unsupported loudness configuration: N={N}, n_fft={n_fft}, hop_length={hop_length} (n_fft: a power "
                            "of two in [64, 2048]; 1 <= hop_length <= n_fft; the 31 * hop_length + n_fft samples one workgroup "
                            "stages must fit 160 KB of LDS, e.g. hop_length <= 1250 at n_fft 2048; N > n_fft / 2)")
     dft = _dft_operand(n_fft, audio.device)
-    o = ops()
-    if o is not None:
-        return o.loudness(audio, dft, int(n_fft), int(hop_length), float(epsilon), float(top_db), bool(normalise))
-    with torch.cuda.device(audio.device):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=audio.device)
-        out = torch.empty((B, frames), dtype=torch.float32, device=audio.device)
-        check(L.nws_loudness(ptr(audio), B, N, n_fft, hop_length, ptr(dft), float(epsilon), float(top_db), 1 if normalise else 0,
-                             ptr(out), ptr(ws), ws.numel(), stream_ptr(audio.device)), "nws_loudness")
-    return out
+    return binding().loudness(audio, dft, int(n_fft), int(hop_length), float(epsilon), float(top_db), bool(normalise))
 
 
 @gin.configurable

@@ -7,7 +7,9 @@ Two bindings of the same C-ABI (include/nws_hip.h):
     argument validation, device guard and current-stream lookup in C++ - the default;
   * ctypes on libnws_hip.so directly (`NWS_BACKEND=ctypes`): the torch-free binding a foreign host would write
     (INTEGRATION.md), kept as a second test path.
-Both end in the same `extern "C"` launchers; there is no CPU or PyTorch fallback behind either.
+Both end in the same `extern "C"` launchers; there is no CPU or PyTorch fallback behind either.  The choice is made in ONE
+place, `binding()`: it returns `torch.ops.newt_hip` or the `_cops.CtypesOps` object that has the same methods, and every call
+site in the package is `binding().X(...)`.
 
 PyTorch is used here only as plumbing: device memory (tensors), the current HIP stream and the
 device RNG that the reference itself draws from inside forward().
@@ -18,11 +20,12 @@ import ctypes as C
 import itertools
 import math
 import os
+from typing import NamedTuple
 
 import torch
 
 from . import _lib
-from ._lib import NwsForwardAux, NwsReverbPlan, NwsWeights, check, ptr
+from ._lib import NwsReverbPlan, NwsWeights, check, ptr
 
 
 def _req(t: torch.Tensor, name: str, numel: int | None = None) -> torch.Tensor:
@@ -74,6 +77,22 @@ def ops():
             _OPS = torch.ops.newt_hip
         _OPS_TRIED = True
     return _OPS
+
+
+_BINDING = None
+
+
+def binding():
+    """The object every launcher call goes through: torch.ops.newt_hip, or the ctypes object with the same surface
+    (_cops.CtypesOps) when NWS_BACKEND=ctypes."""
+    global _BINDING
+    if _BINDING is None:
+        _BINDING = ops()
+        if _BINDING is None:
+            from ._cops import CtypesOps
+
+            _BINDING = CtypesOps()
+    return _BINDING
 
 
 def stream_ptr(dev: torch.device):
@@ -130,15 +149,26 @@ def reverb_plan_and_tables(device: torch.device, n_samples: int, ir_len_plus1: i
     return hit
 
 
+class Weights(NamedTuple):
+    """What Engine caches per weights version: the pointer struct, the same struct as the bytes tensor the binding takes, and
+    the tensors the launchers pass beside it.  `keep` holds every tensor the struct points into."""
+    struct: NwsWeights
+    wdesc: torch.Tensor
+    device: torch.device
+    rand_phase: torch.Tensor
+    ir: torch.Tensor
+    fir_design: torch.Tensor
+    keep: list
+
+
 class Engine:
     """Per-model launcher.  ``model`` is a NeuralWaveshaping module (see models/neural_waveshaping.py)."""
 
     def __init__(self, model):
         self._model_ref = model
-        self._w = None          # (NwsWeights, keep-alive list, device, wdesc tensor)
+        self._w = None          # the current Weights record, replaced on rebuild
         self._fp = None         # what the cache was built from: ((data_ptr, version) per tensor, registry epoch, options)
         self._tensors = None    # the parameter / buffer objects the fingerprint walks
-        self._fir_design = None
         self._spectra = {}      # L -> spectrum tensor
         self._workspaces = {}   # (B, T, stream) -> tensor
 
@@ -216,7 +246,6 @@ class Engine:
         self._w = None
         self._fp = None
         self._tensors = None
-        self._fir_design = None
         self._spectra.clear()
         self._workspaces.clear()
 
@@ -236,7 +265,8 @@ class Engine:
     # ---- weights -----------------------------------------------------------------------------
     def weights(self):
         """(NwsWeights struct, keep-alive list, device) - rebuilt when the parameters' fingerprint changed"""
-        return self._wd()[:3]
+        r = self._wd()
+        return r.struct, r.keep, r.device
 
     def _wd(self):
         fp = self._fingerprint()
@@ -251,7 +281,7 @@ class Engine:
             # Other streams (ForwardPipeline, NewtStream, the caller's own) may still have kernels enqueued that read the
             # fragment tables / spectra / workspaces dropped below; the caching allocator only orders re-use on the stream a
             # block was allocated on.  A rebuild is rare (weights changed): drain the device first.
-            torch.cuda.synchronize(self._w[2])
+            torch.cuda.synchronize(self._w.device)
             self.invalidate()
             fp = self._fingerprint()
         m = self._model_ref
@@ -272,7 +302,7 @@ class Engine:
         w.proj_b = P(m.embedding.proj.bias, "embedding.proj.bias", 128)
         w.mixer_w = P(m.harmonic_mixer.weight, "harmonic_mixer.weight", 64 * 101)
         w.mixer_b = P(m.harmonic_mixer.bias, "harmonic_mixer.bias", 64)
-        dev = keep[-1].device
+        dev = m.harmonic_mixer.bias.device
         L = _lib.lib()
         with torch.cuda.device(dev):
             st = stream_ptr(dev)
@@ -339,7 +369,6 @@ class Engine:
             # stays inside fp16 range, the pre-split fp16 fragment table that moves the frame MLPs to the fp16 matrix pipe
             fd = torch.empty(_lib.FIR_LEN * _lib.FIR_DESIGN_COLS, dtype=torch.float32, device=dev)
             check(L.nws_fir_design_matrix(w.noise_window, ptr(fd), st), "nws_fir_design_matrix")
-            self._fir_design = fd
             keep.append(fd)
             w.mlp_frags = None
             if self.fp16_mlp_safe():
@@ -347,14 +376,15 @@ class Engine:
                 check(L.nws_mlp_frags(C.byref(w), ptr(fd), ptr(frags), st), "nws_mlp_frags")
                 keep.append(frags)
                 w.mlp_frags = frags.data_ptr()
-            keep.append(_req(m.osc.rand_phase.detach(), "osc.rand_phase", 101))
-            keep.append(_req(m.reverb.ir.detach(), "reverb.ir"))
+            rand_phase = _req(m.osc.rand_phase.detach(), "osc.rand_phase", 101)
+            ir = _req(m.reverb.ir.detach(), "reverb.ir")
+            keep += [rand_phase, ir]
             devs = {t.device for t in keep}
             if len(devs) != 1:
                 raise RuntimeError(f"model parameters are spread over several devices: {devs}")
             torch.cuda.current_stream(dev).synchronize()   # derived tables complete before any other stream can use them
         wdesc = torch.frombuffer(bytearray(bytes(w)), dtype=torch.uint8)      # the struct as the op layer takes it
-        self._w = (w, keep, dev, wdesc)
+        self._w = Weights(w, wdesc, dev, rand_phase, ir, fd, keep)
         self._fp = fp
         return self._w
 
@@ -424,18 +454,17 @@ class Engine:
 
     @property
     def device(self):
-        return self.weights()[2]
+        return self._wd().device
 
     def rand_phase(self):
-        return self.weights()[1][-2]
+        return self._wd().rand_phase
 
     def ir(self):
-        return self.weights()[1][-1]
+        return self._wd().ir
 
     # ---- weight-independent / cached tables ----------------------------------------------------
     def fir_design(self):
-        self.weights()
-        return self._fir_design
+        return self._wd().fir_design
 
     def osc_sample_rate(self) -> float:
         """The rate the oscillator divides by: HarmonicOscillator's own gin binding (generators.py:41,59), which a configuration
@@ -449,8 +478,7 @@ class Engine:
         return self._reverb_aux(n_samples)
 
     def _reverb_aux(self, n_samples: int):     # after _wd(): no second fingerprint walk
-        ir = self._w[1][-1]
-        dev = self._w[2]
+        ir, dev = self._w.ir, self._w.device
         plan, tables, plan_t = reverb_plan_and_tables(dev, n_samples, ir.numel() + 1)
         skey = (plan.L, plan.N1, plan.N2)      # stored in the transform's own (k1, k2) order: one spectrum per factorisation
         spec = self._spectra.get(skey)
@@ -465,180 +493,73 @@ class Engine:
             self._spectra[skey] = spec
         return plan, tables, spec, plan_t
 
-    # ---- stage launchers (public for the parity tests; each is one C-ABI call / one torch op) ------------------
+    # ---- stage launchers (public for the parity tests; each is one call of the binding) ------------------------------------
     def phase_carry(self, f0=None, f0_up=None):
-        src = f0 if f0 is not None else f0_up
-        o = ops()
-        if o is not None:
-            return o.phase_carry(f0, f0_up)
-        B = src.shape[0]
-        T = f0.shape[-1] if f0 is not None else f0_up.shape[-1] // _lib.HOP
-        with torch.cuda.device(src.device):
-            carry = torch.empty((B, T * _lib.HOP // 32), dtype=torch.float64, device=src.device)
-            check(_lib.lib().nws_phase_carry(ptr(f0), ptr(f0_up), B, T, ptr(carry), stream_ptr(src.device)), "nws_phase_carry")
-        return carry
+        return binding().phase_carry(f0, f0_up)
 
     def exciter_newt(self, f0, f0_up, carry, phase_u, film, want_exciter=False, want_newt=True):
-        w, _, dev, wdesc = self._wd()
-        src = f0 if f0 is not None else f0_up
-        same_device(dev, f0=src, carry=carry, phase_u=phase_u, film=film)
-        sr = self.osc_sample_rate()
-        o = ops()
-        if o is not None:
-            exc, out = o.exciter_newt(wdesc, f0, f0_up, carry, phase_u, self._w[1][-2], film, sr, want_exciter, want_newt)
-            return (exc if want_exciter else None), (out if want_newt else None)
-        B = src.shape[0]
-        T = f0.shape[-1] if f0 is not None else f0_up.shape[-1] // _lib.HOP
-        N = T * _lib.HOP
-        with torch.cuda.device(dev):
-            exc = torch.empty((B, _lib.N_SHAPERS, N), dtype=torch.float32, device=dev) if want_exciter else None
-            out = torch.empty((B, N), dtype=torch.float32, device=dev) if want_newt else None
-            check(_lib.lib().nws_exciter_newt(C.byref(w), ptr(f0), ptr(f0_up), ptr(carry), ptr(phase_u), ptr(self._w[1][-2]),
-                                              ptr(film), B, T, sr, ptr(exc), ptr(out), stream_ptr(dev)), "nws_exciter_newt")
-        return exc, out
+        r = self._wd()
+        same_device(r.device, f0=f0 if f0 is not None else f0_up, carry=carry, phase_u=phase_u, film=film)
+        exc, out = binding().exciter_newt(r.wdesc, f0, f0_up, carry, phase_u, r.rand_phase, film, self.osc_sample_rate(),
+                                          want_exciter, want_newt)
+        return (exc if want_exciter else None), (out if want_newt else None)
 
     def control_gru(self, control, batched=False, h0=None, return_state=False):
-        w, _, dev, wdesc = self._wd()
-        same_device(dev, control=control, h0=h0)
-        B, Cc, T = control.shape
-        o = ops()
-        if o is not None:
-            out, hT = o.control_gru(wdesc, control, h0, bool(batched))
-            return (out, hT) if return_state else out
-        with torch.cuda.device(dev):
-            out = torch.empty((B, T, _lib.HIDDEN), dtype=torch.float32, device=dev)
-            hT = torch.empty((B, _lib.HIDDEN), dtype=torch.float32, device=dev) if return_state else None
-            fn = _lib.lib().nws_control_gru_batched if batched else _lib.lib().nws_control_gru_state
-            check(fn(C.byref(w), ptr(control), B, Cc, T, ptr(h0), ptr(out), ptr(hT), stream_ptr(dev)), "nws_control_gru")
+        r = self._wd()
+        same_device(r.device, control=control, h0=h0)
+        out, hT = binding().control_gru(r.wdesc, control, h0, bool(batched))
         return (out, hT) if return_state else out
 
     def frame_mlps(self, gru_out, want_emb=False, want_H=False):
-        w, _, dev, wdesc = self._wd()
-        same_device(dev, gru_out=gru_out)
-        B, T, _ = gru_out.shape
-        o = ops()
-        if o is not None:
-            emb, film, H, fir = o.frame_mlps(wdesc, gru_out, self._fir_design, want_emb, want_H)
-            return (emb if want_emb else None), film, (H if want_H else None), fir
-        with torch.cuda.device(dev):
-            emb = torch.empty((B, _lib.HIDDEN, T), dtype=torch.float32, device=dev) if want_emb else None
-            film = torch.empty((B, T, _lib.FILM_CH), dtype=torch.float32, device=dev)
-            H = torch.empty((B, T, _lib.N_BANDS), dtype=torch.float32, device=dev) if want_H else None
-            fir = torch.empty((B, T, _lib.FIR_HALF), dtype=torch.float32, device=dev)
-            check(_lib.lib().nws_frame_mlps(C.byref(w), ptr(gru_out), ptr(self._fir_design), B, T, ptr(emb), ptr(film),
-                                            ptr(H), ptr(fir), stream_ptr(dev)), "nws_frame_mlps")
-        return emb, film, H, fir
+        r = self._wd()
+        same_device(r.device, gru_out=gru_out)
+        emb, film, H, fir = binding().frame_mlps(r.wdesc, gru_out, r.fir_design, want_emb, want_H)
+        return (emb if want_emb else None), film, (H if want_H else None), fir
 
     def fir_noise(self, fir, noise, add_in=None, origin=None, noise_len=None):
         """origin None: the reference's framing (N-1 noise samples, reflect padding); else a streaming window whose frame t
         covers noise[128 t - origin, +256) of the first `noise_len` samples (nws_fir_noise_window)"""
-        B, T, _ = fir.shape
         same_device(fir.device, noise=noise, add_in=add_in)
-        o = ops()
-        if o is not None:
-            nz = noise if noise_len is None or noise_len == noise.numel() else noise[:noise_len]
-            return o.fir_noise(fir, nz, add_in, -1 if origin is None else int(origin))
-        with torch.cuda.device(fir.device):
-            out = torch.empty((B, T * _lib.HOP), dtype=torch.float32, device=fir.device)
-            if origin is None:
-                check(_lib.lib().nws_fir_noise(ptr(fir), ptr(noise), ptr(add_in), B, T, ptr(out), stream_ptr(fir.device)),
-                      "nws_fir_noise")
-            else:
-                n_len = noise.numel() if noise_len is None else int(noise_len)
-                check(_lib.lib().nws_fir_noise_window(ptr(fir), ptr(noise), n_len, int(origin), ptr(add_in), B, T, ptr(out),
-                                                      stream_ptr(fir.device)), "nws_fir_noise_window")
-        return out
+        nz = noise if noise_len is None or noise_len == noise.numel() else noise[:noise_len]
+        return binding().fir_noise(fir, nz, add_in, -1 if origin is None else int(origin))
 
     def reverb(self, x):
-        B, N = x.shape
-        _, _, dev, _ = self._wd()
-        same_device(dev, x=x)
-        plan, tables, spec, plan_t = self._reverb_aux(N)
-        o = ops()
-        if o is not None:
-            return o.reverb(plan_t, tables, spec, x)
-        with torch.cuda.device(x.device):
-            nbytes = _lib.lib().nws_reverb_workspace_bytes(C.byref(plan), B)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            y = torch.empty_like(x)
-            check(_lib.lib().nws_reverb(C.byref(plan), ptr(tables), ptr(spec), ptr(x), B, N, ptr(y), ptr(ws), nbytes,
-                                        stream_ptr(x.device)), "nws_reverb")
-        return y
+        same_device(self._wd().device, x=x)
+        _, tables, spec, plan_t = self._reverb_aux(x.shape[1])
+        return binding().reverb(plan_t, tables, spec, x)
 
     def reverb_linear_chunk(self, plan_aux, x, tail_in):
         """streaming: y = x + wet[:M] + tail_in[:M]; returns (y, tail_out)"""
-        plan, tables, spec, plan_t = plan_aux
+        _, tables, spec, plan_t = plan_aux
         same_device(tables.device, x=x, tail_in=tail_in)
-        o = ops()
-        if o is not None:
-            return o.reverb_linear_chunk(plan_t, tables, spec, x, tail_in)
-        B, M = x.shape
-        with torch.cuda.device(x.device):
-            nfl = (2 * ((B + 1) // 2) + B) * plan.L
-            ws = torch.empty(nfl, dtype=torch.float32, device=x.device)
-            y, tail_out = torch.empty_like(x), torch.empty_like(tail_in)
-            check(_lib.lib().nws_reverb_linear_chunk(C.byref(plan), ptr(tables), ptr(spec), ptr(x), B, M, ptr(tail_in),
-                                                     ptr(tail_out), tail_in.shape[1], ptr(y), ptr(ws), nfl * 4,
-                                                     stream_ptr(x.device)), "nws_reverb_linear_chunk")
-        return y, tail_out
+        return binding().reverb_linear_chunk(plan_t, tables, spec, x, tail_in)
 
     def shaper_table(self, size, tmin, tmax):
-        w, _, dev, wdesc = self._wd()
-        o = ops()
-        if o is not None:
-            return o.shaper_table(wdesc, self._w[1][-2], int(size), float(tmin), float(tmax))
-        with torch.cuda.device(dev):
-            t = torch.empty((_lib.N_SHAPERS, size), dtype=torch.float32, device=dev)
-            check(_lib.lib().nws_shaper_table(C.byref(w), int(size), float(tmin), float(tmax), ptr(t), stream_ptr(dev)),
-                  "nws_shaper_table")
-        return t
+        r = self._wd()
+        return binding().shaper_table(r.wdesc, r.rand_phase, int(size), float(tmin), float(tmax))
 
     def shaper_apply(self, x):
-        w, _, dev, wdesc = self._wd()
-        same_device(dev, x=x)
-        o = ops()
-        if o is not None:
-            return o.shaper_apply(wdesc, x)
-        B, S, N = x.shape
-        with torch.cuda.device(dev):
-            y = torch.empty_like(x)
-            check(_lib.lib().nws_shaper_apply(C.byref(w), ptr(x), B, N, ptr(y), stream_ptr(dev)), "nws_shaper_apply")
-        return y
+        r = self._wd()
+        same_device(r.device, x=x)
+        return binding().shaper_apply(r.wdesc, x)
 
     def newt_apply(self, exciter, film):
         """NEWT.forward on a materialised exciter: exciter (B, 64, N), film (B, 256, T) channel-major -> (B, 1, N)"""
-        w, _, dev, wdesc = self._wd()
-        same_device(dev, exciter=exciter, film=film)
-        o = ops()
-        if o is not None:
-            return o.newt_apply(wdesc, exciter, film)
-        B, _, N = exciter.shape
-        T = film.shape[2]
-        if film.shape[1] != _lib.FILM_CH or N != T * _lib.HOP:
-            raise RuntimeError(f"NEWT: exciter {tuple(exciter.shape)} and FiLM parameters {tuple(film.shape)} disagree")
-        with torch.cuda.device(dev):
-            out = torch.empty((B, 1, N), dtype=torch.float32, device=dev)
-            check(_lib.lib().nws_newt_apply(C.byref(w), ptr(exciter), ptr(film), B, T, ptr(out), stream_ptr(dev)), "nws_newt_apply")
-        return out
+        r = self._wd()
+        same_device(r.device, exciter=exciter, film=film)
+        return binding().newt_apply(r.wdesc, exciter, film)
 
     # ---- the forward in two halves (throughput pipeline, pipeline.py) ------------------------------------------------
     def new_workspace(self, B, T):
-        _, _, dev, _ = self._wd()
+        dev = self._wd().device
         plan, _, _, _ = self._reverb_aux(T * _lib.HOP)
         return torch.empty(_lib.lib().nws_forward_workspace_bytes(C.byref(plan), B, T), dtype=torch.uint8, device=dev)
 
     def forward_control(self, f0, control, ws, batched_gru=True):
         """phase carries + GRU into the head of `ws`, on the current stream"""
-        w, _, dev, wdesc = self._wd()
-        same_device(dev, f0=f0, control=control, workspace=ws)
-        o = ops()
-        if o is not None:
-            o.forward_control(wdesc, f0, control, ws, bool(batched_gru))
-            return
-        B, Cc, T = control.shape
-        with torch.cuda.device(dev):
-            check(_lib.lib().nws_forward_control(C.byref(w), ptr(f0), ptr(control), B, Cc, T, 1 if batched_gru else 0, ptr(ws),
-                                                 ws.numel(), stream_ptr(dev)), "nws_forward_control")
+        r = self._wd()
+        same_device(r.device, f0=f0, control=control, workspace=ws)
+        binding().forward_control(r.wdesc, f0, control, ws, bool(batched_gru))
 
     def forward_audio(self, f0, B, T, phase_u, noise, ws, out=None, wait_event=None, record_event=None, row_blocks=None,
                       on_block=None, block_events=None):
@@ -647,7 +568,8 @@ class Engine:
         row_blocks = [(row0, nrows), ...] (even row0, nrows >= 4): the reverb runs block by block and `on_block(row0, nrows,
         out)` is called after each block has been enqueued - a multi-GPU caller pushes that sub-batch to its peers while the
         next block's reverb runs.  Same bits as the single call."""
-        w, _, dev, wdesc = self._wd()
+        r = self._wd()
+        dev = r.device
         same_device(dev, f0=f0, phase_u=phase_u, noise=noise, workspace=ws, out=out)
         if block_events is not None and (row_blocks is None or len(row_blocks) < 2 or on_block is not None):
             # never silently ignored: synchronize() on a never-recorded event returns at once, and whoever waits on these events
@@ -655,103 +577,55 @@ class Engine:
             raise RuntimeError("block_events are recorded by the one-call block path only: pass row_blocks of two or more blocks and "
                                "no on_block callback")
         N = T * _lib.HOP
-        plan, tables, spec, plan_t = self._reverb_aux(N)
-        sr = self.osc_sample_rate()
-        o = ops()
-        if row_blocks is not None and len(row_blocks) > 1:
-            # the blocks must tile [0, B) with even sizes (two utterances share one transform; ForwardPipeline.row_blocks' rule):
-            # anything else would leave rows of `out` unwritten or pair the wrong utterances
-            nxt = 0
-            for k, (row0, nrows) in enumerate(row_blocks):
-                # every block but the last has an even size (so that every row0 is even: nws_forward_reverb_rows' own rule; an odd
-                # last block pads its last pair like an odd batch does)
-                if int(row0) != nxt or int(nrows) <= 0 or (int(nrows) % 2 and k != len(row_blocks) - 1):
-                    raise RuntimeError(f"row_blocks must tile [0, {B}) in order, even sizes except the last, got {list(row_blocks)}")
-                nxt += int(nrows)
-            if nxt != B:
-                raise RuntimeError(f"row_blocks cover {nxt} of {B} rows: {list(row_blocks)}")
-            if wait_event is not None or record_event is not None:
-                raise RuntimeError("wait_event / record_event hook the single-call form; they cannot be combined with row_blocks")
-            if block_events is not None and on_block is None:
-                # ONE call: audio_pre + every block's reverb, block q's torch.cuda.Event recorded behind it by the library itself
-                # (nws_forward_audio_blocks; a helper thread waits on the events and pushes each sub-batch as it completes)
-                if len(block_events) != len(row_blocks):
-                    raise RuntimeError("block_events: one torch.cuda.Event per row block")
-                with torch.cuda.device(dev):
-                    if out is None:
-                        out = torch.empty((B, N), dtype=torch.float32, device=dev)
-                    for ev in block_events:         # (a never-recorded torch event has no handle yet: record() creates it lazily)
-                        if not ev.cuda_event:
-                            ev.record()
-                    r0 = [int(r) for r, _ in row_blocks]
-                    nr = [int(n) for _, n in row_blocks]
-                    evs = [int(ev.cuda_event) for ev in block_events]
-                    if o is not None:
-                        o.forward_audio_blocks(wdesc, f0, phase_u, self._w[1][-2], noise, self._fir_design, plan_t, tables, spec, ws, sr, out,
-                                               r0, nr, evs)
-                    else:
-                        aux = NwsForwardAux()
-                        aux.fir_design = ptr(self._fir_design)
-                        aux.plan = C.pointer(plan)
-                        aux.reverb_tables = ptr(tables)
-                        aux.reverb_spectrum = ptr(spec)
-                        n = len(r0)
-                        check(_lib.lib().nws_forward_audio_blocks(C.byref(w), C.byref(aux), ptr(f0), B, T, sr, ptr(phase_u), ptr(self._w[1][-2]),
-                                                                  ptr(noise), ptr(out), ptr(ws), ws.numel(), stream_ptr(dev),
-                                                                  (C.c_int32 * n)(*r0), (C.c_int32 * n)(*nr), (C.c_void_p * n)(*evs), n),
-                              "nws_forward_audio_blocks")
-                return out
-            with torch.cuda.device(dev):
-                if out is None:
-                    out = torch.empty((B, N), dtype=torch.float32, device=dev)
-                aux = None
-                if o is not None:
-                    o.forward_audio_pre(wdesc, f0, phase_u, self._w[1][-2], noise, self._fir_design, plan_t, tables, spec, ws, sr)
-                else:
-                    aux = NwsForwardAux()
-                    aux.fir_design = ptr(self._fir_design)
-                    aux.plan = C.pointer(plan)
-                    aux.reverb_tables = ptr(tables)
-                    aux.reverb_spectrum = ptr(spec)
-                    check(_lib.lib().nws_forward_audio_pre(C.byref(w), C.byref(aux), ptr(f0), B, T, sr, ptr(phase_u), ptr(self._w[1][-2]),
-                                                           ptr(noise), ptr(ws), ws.numel(), stream_ptr(dev)), "nws_forward_audio_pre")
-                for row0, nrows in row_blocks:
-                    if o is not None:
-                        o.forward_reverb_rows(self._fir_design, plan_t, tables, spec, ws, T, int(row0), int(nrows), out)
-                    else:
-                        check(_lib.lib().nws_forward_reverb_rows(C.byref(aux), B, T, int(row0), int(nrows), ptr(out), ptr(ws), ws.numel(),
-                                                                 stream_ptr(dev)), "nws_forward_reverb_rows")
-                    if on_block is not None:
-                        on_block(int(row0), int(nrows), out)
-            return out
-        if o is not None:
-            return o.forward_audio(wdesc, f0, phase_u, self._w[1][-2], noise, self._fir_design, plan_t, tables, spec, ws, sr, out,
-                                   wait_event.cuda_event if wait_event is not None else 0,
+        _, tables, spec, plan_t = self._reverb_aux(N)
+        b = binding()
+        audio = (r.wdesc, f0, phase_u, r.rand_phase, noise, r.fir_design, plan_t, tables, spec, ws, self.osc_sample_rate())
+        if row_blocks is None or len(row_blocks) < 2:
+            return b.forward_audio(*audio, out, wait_event.cuda_event if wait_event is not None else 0,
                                    record_event.cuda_event if record_event is not None else 0)
+        # the blocks must tile [0, B) with even sizes (two utterances share one transform; ForwardPipeline.row_blocks' rule):
+        # anything else would leave rows of `out` unwritten or pair the wrong utterances
+        nxt = 0
+        for k, (row0, nrows) in enumerate(row_blocks):
+            # every block but the last has an even size (so that every row0 is even: nws_forward_reverb_rows' own rule; an odd
+            # last block pads its last pair like an odd batch does)
+            if int(row0) != nxt or int(nrows) <= 0 or (int(nrows) % 2 and k != len(row_blocks) - 1):
+                raise RuntimeError(f"row_blocks must tile [0, {B}) in order, even sizes except the last, got {list(row_blocks)}")
+            nxt += int(nrows)
+        if nxt != B:
+            raise RuntimeError(f"row_blocks cover {nxt} of {B} rows: {list(row_blocks)}")
+        if wait_event is not None or record_event is not None:
+            raise RuntimeError("wait_event / record_event hook the single-call form; they cannot be combined with row_blocks")
+        if block_events is not None and len(block_events) != len(row_blocks):
+            raise RuntimeError("block_events: one torch.cuda.Event per row block")
         with torch.cuda.device(dev):
             if out is None:
                 out = torch.empty((B, N), dtype=torch.float32, device=dev)
-            aux = NwsForwardAux()
-            aux.fir_design = ptr(self._fir_design)
-            aux.plan = C.pointer(plan)
-            aux.reverb_tables = ptr(tables)
-            aux.reverb_spectrum = ptr(spec)
-            check(_lib.lib().nws_forward_audio_ev(C.byref(w), C.byref(aux), ptr(f0), B, T, sr, ptr(phase_u), ptr(self._w[1][-2]),
-                                                  ptr(noise), ptr(out), ptr(ws), ws.numel(), stream_ptr(dev),
-                                                  wait_event.cuda_event if wait_event is not None else None,
-                                                  record_event.cuda_event if record_event is not None else None),
-                  "nws_forward_audio_ev")
+            if block_events is not None:
+                # ONE call: audio_pre + every block's reverb, block q's torch.cuda.Event recorded behind it by the library itself
+                # (nws_forward_audio_blocks; a helper thread waits on the events and pushes each sub-batch as it completes)
+                for ev in block_events:         # (a never-recorded torch event has no handle yet: record() creates it lazily)
+                    if not ev.cuda_event:
+                        ev.record()
+                b.forward_audio_blocks(*audio, out, [int(r0) for r0, _ in row_blocks], [int(n) for _, n in row_blocks],
+                                       [int(ev.cuda_event) for ev in block_events])
+                return out
+            b.forward_audio_pre(*audio)
+            for row0, nrows in row_blocks:
+                b.forward_reverb_rows(r.fir_design, plan_t, tables, spec, ws, T, int(row0), int(nrows), out)
+                if on_block is not None:
+                    on_block(int(row0), int(nrows), out)
         return out
 
-    # ---- the whole forward: ONE op / ONE C-ABI call --------------------------------------------------------
+    # ---- the whole forward: ONE call of the binding ----------------------------------------------------------------
     def forward(self, f0, control, phase_u, noise):
         if not self.specialised():
             return self.generic.forward(f0, control, phase_u, noise)
-        w, _, dev, wdesc = self._wd()
+        r = self._wd()
+        dev = r.device
         same_device(dev, f0=f0, control=control, phase_u=phase_u, noise=noise)
-        B, Cc, T = control.shape
-        N = T * _lib.HOP
-        plan, tables, spec, plan_t = self._reverb_aux(N)
+        B, _, T = control.shape
+        plan, tables, spec, plan_t = self._reverb_aux(T * _lib.HOP)
         key = (B, T, stream_ptr(dev))   # one scratch arena per stream: forwards on different streams may overlap
         ws = self._workspaces.get(key)
         if ws is None:
@@ -762,18 +636,5 @@ class Engine:
                 # is handed back to the caching allocator, which re-issues a block only in the stream order it was used in)
                 self._workspaces.pop(next(iter(self._workspaces)))
             self._workspaces[key] = ws
-        sr = self.osc_sample_rate()
-        o = ops()
-        if o is not None:
-            return o.forward(wdesc, f0, control, phase_u, self._w[1][-2], noise, self._fir_design, plan_t, tables, spec, ws, sr)
-        with torch.cuda.device(dev):
-            out = torch.empty((B, N), dtype=torch.float32, device=dev)
-            aux = NwsForwardAux()
-            aux.fir_design = ptr(self._fir_design)
-            aux.plan = C.pointer(plan)
-            aux.reverb_tables = ptr(tables)
-            aux.reverb_spectrum = ptr(spec)
-            check(_lib.lib().nws_forward(C.byref(w), C.byref(aux), ptr(f0), ptr(control), B, Cc, T, sr, ptr(phase_u),
-                                         ptr(self._w[1][-2]), ptr(noise), ptr(out), ptr(ws), ws.numel(), stream_ptr(dev)),
-                  "nws_forward")
-        return out
+        return binding().forward(r.wdesc, f0, control, phase_u, r.rand_phase, noise, r.fir_design, plan_t, tables, spec, ws,
+                                 self.osc_sample_rate())

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import itertools
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -64,12 +65,23 @@ def desc_bytes(struct) -> torch.Tensor:
     return torch.frombuffer(bytearray(bytes(struct)), dtype=torch.uint8)
 
 
+class GenericModel(NamedTuple):
+    """What GenericEngine caches per weights version (engine.Weights' counterpart for the runtime-size path)."""
+    fingerprint: tuple
+    struct: NwsGenericModel
+    gdesc: torch.Tensor
+    device: torch.device
+    rand_phase: torch.Tensor
+    ir: torch.Tensor
+    keep: list
+
+
 class GenericEngine:
     """Launcher of the runtime-size forward for one NeuralWaveshaping module (any gin configuration)."""
 
     def __init__(self, model):
         self._model_ref = model
-        self._cache = None      # (fingerprint, NwsGenericModel, keep-alive list, device, gdesc tensor)
+        self._cache = None      # the current GenericModel record, replaced on rebuild
         self._reverb = {}       # N -> (plan | None, tables, spectrum, plan tensor)
         self._workspaces = {}
 
@@ -84,10 +96,10 @@ class GenericEngine:
 
     def model_desc(self):
         fp = self._fingerprint()
-        if self._cache is not None and self._cache[0] == fp:
-            return self._cache[1:]
+        if self._cache is not None and self._cache.fingerprint == fp:
+            return self._cache
         if self._cache is not None:
-            torch.cuda.synchronize(self._cache[3])
+            torch.cuda.synchronize(self._cache.device)
             self.invalidate()
         m = self._model_ref
         keep = []
@@ -173,8 +185,8 @@ class GenericEngine:
         devs = {t.device for t in keep}
         if len(devs) != 1:
             raise RuntimeError(f"model parameters are spread over several devices: {devs}")
-        self._cache = (fp, g, keep, keep[0].device, desc_bytes(g))
-        return self._cache[1:]
+        self._cache = GenericModel(fp, g, desc_bytes(g), rp.device, rp, ir, keep)
+        return self._cache
 
     def _reverb_aux(self, N, dev, ir):
         hit = self._reverb.get(N)
@@ -200,14 +212,13 @@ class GenericEngine:
         return hit
 
     def forward(self, f0, control, phase_u, noise):
-        from .engine import ops, same_device, stream_ptr
+        from .engine import binding, same_device, stream_ptr
 
-        g, keep, dev, gdesc = self.model_desc()
+        r = self.model_desc()
+        g, dev = r.struct, r.device
         same_device(dev, f0=f0, control=control, phase_u=phase_u, noise=noise)
-        B, Cc, T = control.shape
-        N = T * g.hop
-        ir, rp = keep[-1], keep[-2]
-        plan, tables, spec, plan_t = self._reverb_aux(N, dev, ir)
+        B, _, T = control.shape
+        plan, tables, spec, plan_t = self._reverb_aux(T * g.hop, dev, r.ir)
         L = _lib.lib()
         key = (B, T, stream_ptr(dev))
         ws = self._workspaces.get(key)
@@ -219,13 +230,4 @@ class GenericEngine:
                 self._workspaces.pop(next(iter(self._workspaces)))
             self._workspaces[key] = ws
         sr = float(getattr(getattr(self._model_ref, 'osc', None), 'sample_rate', self._model_ref.sample_rate))   # the oscillator's own binding (generators.py:41)
-        o = ops()
-        if o is not None:
-            return o.forward_generic(gdesc, f0, control, phase_u, rp, noise, plan_t, tables, spec, ws[1], ws[0], sr)
-        with torch.cuda.device(dev):
-            out = torch.empty((B, N), dtype=torch.float32, device=dev)
-            check(L.nws_forward_generic(C.byref(g), ptr(f0), ptr(control), B, Cc, T, sr, ptr(phase_u), ptr(rp), ptr(noise),
-                                        C.byref(plan) if plan is not None else None, ptr(tables), ptr(spec),
-                                        ptr(ws[1]) if plan is not None else None, ws[1].numel() if plan is not None else 0,
-                                        ptr(out), ptr(ws[0]), ws[0].numel(), stream_ptr(dev)), "nws_forward_generic")
-        return out
+        return binding().forward_generic(r.gdesc, f0, control, phase_u, r.rand_phase, noise, plan_t, tables, spec, ws[1], ws[0], sr)

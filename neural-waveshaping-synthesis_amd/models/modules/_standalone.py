@@ -1,16 +1,14 @@
 """Plumbing for sub-modules called on their own (model.osc(f0), model.newt(exciter, emb), model.h_generator(emb), ...).
 
 Inside NeuralWaveshaping.forward these modules never run as separate launches (everything is fused into five kernels);
-called stand-alone each one maps to ONE stage kernel through torch.ops.newt_hip.* (or the ctypes binding of the same
-C-ABI entry point with NWS_BACKEND=ctypes).  No PyTorch arithmetic fallback: CPU tensors raise."""
+called stand-alone each one maps to ONE stage kernel through `engine.binding()`: torch.ops.newt_hip.*, or the ctypes object
+with the same surface when NWS_BACKEND=ctypes.  No PyTorch arithmetic fallback: CPU tensors raise."""
 from __future__ import annotations
-
-import ctypes as C
 
 import torch
 
 from ... import _lib
-from ...engine import _req, ops, stream_ptr
+from ...engine import _req, binding, stream_ptr
 
 
 def contiguous(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -18,7 +16,8 @@ def contiguous(t: torch.Tensor, name: str) -> torch.Tensor:
 
 
 class Desc:
-    """A partial NwsWeights descriptor for one sub-module, cached until one of its tensors changes."""
+    """A partial NwsWeights descriptor for one sub-module as the byte tensor the binding takes (`wdesc`), cached until one of its
+    tensors changes."""
 
     def __init__(self):
         self._key = None
@@ -36,9 +35,9 @@ class Desc:
                 setattr(w, field, t.data_ptr())
             for field, v in (scalars or {}).items():
                 setattr(w, field, v)
-            self._val = (w, keep, torch.frombuffer(bytearray(bytes(w)), dtype=torch.uint8))
+            self._val = (torch.frombuffer(bytearray(bytes(w)), dtype=torch.uint8), keep)
             self._key = key
-        return self._val
+        return self._val[0]
 
 
 def shaper_fields(sh) -> dict:
@@ -79,19 +78,12 @@ def sum_channels(x: torch.Tensor) -> torch.Tensor:
     """(B, C, N) -> (B, N): the `x.sum(1)` of models/neural_waveshaping.py:86 as a 1x1 convolution with unit weights
     (g_conv1x1_kernel: sequential adds in channel order)"""
     x = contiguous(x, "x")
-    B, Cc, N = x.shape
+    Cc = x.shape[1]
     key = (x.device, Cc)
     ones = _ONES.get(key)
     if ones is None:
         ones = _ONES[key] = torch.ones((1, Cc), dtype=torch.float32, device=x.device)
-
-    def c_call(L):
-        with torch.cuda.device(x.device):
-            y = torch.empty((B, 1, N), dtype=torch.float32, device=x.device)
-            checked(L.nws_g_conv1x1(x.data_ptr(), ones.data_ptr(), None, B, Cc, 1, N, y.data_ptr(), stream_ptr(x.device)), "nws_g_conv1x1")
-        return y
-
-    return call("g_conv1x1", "nws_g_conv1x1", (x, ones, None), c_call)[:, 0].contiguous()
+    return call("g_conv1x1", x, ones, None)[:, 0].contiguous()
 
 
 def has_hooks(*modules) -> bool:
@@ -99,20 +91,17 @@ def has_hooks(*modules) -> bool:
     return any(m is not None and (m._forward_hooks or m._forward_pre_hooks) for m in modules)
 
 
-def call(op_name: str, c_name: str, op_args: tuple, c_call):
-    """Run `torch.ops.newt_hip.<op_name>(*op_args)` or, on the ctypes binding, `c_call(lib)` (which returns the result)."""
+def call(op_name: str, *op_args):
+    """`engine.binding().<op_name>(*op_args)` after the inference-only check of its tensor arguments."""
     flat = []
     for a in op_args:
         flat.extend(a if isinstance(a, (list, tuple)) else (a,))
     no_autograd(inputs=flat)
-    o = ops()
-    if o is not None:
-        return getattr(o, op_name)(*op_args)
-    return c_call(_lib.lib())
+    return getattr(binding(), op_name)(*op_args)
 
 
 def checked(rc: int, what: str):
     _lib.check(rc, what)
 
 
-__all__ = ["C", "Desc", "call", "has_hooks", "no_autograd", "sum_channels", "checked", "contiguous", "shaper_fields", "stream_ptr", "_req", "_lib", "ops"]
+__all__ = ["Desc", "call", "has_hooks", "no_autograd", "sum_channels", "checked", "contiguous", "shaper_fields", "stream_ptr", "_req", "_lib", "binding"]

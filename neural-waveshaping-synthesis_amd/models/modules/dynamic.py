@@ -18,15 +18,7 @@ class FiLM(nn.Module):
     def forward(self, x, gamma, beta):
         x, gamma, beta = torch.broadcast_tensors(x, gamma, beta)
         x, gamma, beta = sa.contiguous(x, "x"), sa.contiguous(gamma, "gamma"), sa.contiguous(beta, "beta")
-
-        def c_call(L):
-            y = torch.empty_like(x)
-            with torch.cuda.device(x.device):
-                sa.checked(L.nws_film(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), x.numel(), y.data_ptr(),
-                                      sa.stream_ptr(x.device)), "nws_film")
-            return y
-
-        return sa.call("film", "nws_film", (x, gamma, beta), c_call)
+        return sa.call("film", x, gamma, beta)
 
 
 class Conv1x1(nn.Conv1d):
@@ -46,30 +38,13 @@ class Conv1x1(nn.Conv1d):
         wt = sa._req(self.weight.detach(), "weight")
         bt = sa._req(self.bias.detach(), "bias") if self.bias is not None else None
         sa.no_autograd(params=[self.weight])
-        B, Cin, N = x.shape
-
-        def c_call(L):
-            with torch.cuda.device(x.device):
-                y = torch.empty((B, self.out_channels, N), dtype=torch.float32, device=x.device)
-                sa.checked(L.nws_g_conv1x1(x.data_ptr(), wt.data_ptr(), bt.data_ptr() if bt is not None else None, B, Cin,
-                                           self.out_channels, N, y.data_ptr(), sa.stream_ptr(x.device)), "nws_g_conv1x1")
-            return y
-
-        return sa.call("g_conv1x1", "nws_g_conv1x1", (x, wt, bt), c_call)
+        return sa.call("g_conv1x1", x, wt, bt)
 
 
 def upsample_linear(x, hop: int):
     """F.upsample(x, T * hop, mode="linear") on the last axis of a CUDA tensor (neural_waveshaping.py:75, shaping.py:69)."""
     x = sa.contiguous(x, "x")
-    T = x.shape[-1]
-
-    def c_call(L):
-        with torch.cuda.device(x.device):
-            y = torch.empty(tuple(x.shape[:-1]) + (T * hop,), dtype=torch.float32, device=x.device)
-            sa.checked(L.nws_g_upsample(x.data_ptr(), x.numel() // T, T, int(hop), y.data_ptr(), sa.stream_ptr(x.device)), "nws_g_upsample")
-        return y
-
-    return sa.call("g_upsample", "nws_g_upsample", (x, int(hop)), c_call)
+    return sa.call("g_upsample", x, int(hop))
 
 
 class TimeDistributedLayerNorm(nn.Module):
@@ -85,15 +60,7 @@ class TimeDistributedLayerNorm(nn.Module):
         if x.dim() != 3 or x.shape[1] != ln.weight.numel():
             raise RuntimeError(f"TimeDistributedLayerNorm({ln.weight.numel()}): expected (B, {ln.weight.numel()}, T), got {tuple(x.shape)}")
         g, b = sa._req(ln.weight.detach(), "layer_norm.weight"), sa._req(ln.bias.detach(), "layer_norm.bias")
-
-        def c_call(L):
-            y = torch.empty_like(x)
-            with torch.cuda.device(x.device):
-                sa.checked(L.nws_td_layer_norm(x.data_ptr(), g.data_ptr(), b.data_ptr(), x.shape[0], x.shape[1], x.shape[2],
-                                               float(ln.eps), y.data_ptr(), sa.stream_ptr(x.device)), "nws_td_layer_norm")
-            return y
-
-        return sa.call("td_layer_norm", "nws_td_layer_norm", (x, g, b, float(ln.eps)), c_call)
+        return sa.call("td_layer_norm", x, g, b, float(ln.eps))
 
 
 @gin.configurable
@@ -139,16 +106,4 @@ def td_mlp_forward(x, net):
     if len(acts) != len(norms) or any(not n.layer_norm.elementwise_affine for n in norms):
         raise RuntimeError("TimeDistributedMLP: expected Conv1d -> LayerNorm(affine) -> LeakyReLU blocks")
     sa.no_autograd(params=[p for c in convs for p in (c.weight, c.bias)])
-    depth = len(convs)
-    hidden = ws[0].shape[0]
-    out_size = ws[-1].shape[0]
-
-    def c_call(L):
-        arr = lambda ts: (sa.C.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])  # noqa: E731
-        y = torch.empty((x.shape[0], out_size, x.shape[2]), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            sa.checked(L.nws_td_mlp(x.data_ptr(), x.shape[0], x.shape[1], hidden, out_size, depth, x.shape[2], arr(ws), arr(bs),
-                                    arr(gs), arr(ls), eps, slope, y.data_ptr(), sa.stream_ptr(x.device)), "nws_td_mlp")
-        return y
-
-    return sa.call("td_mlp", "nws_td_mlp", (x, ws, bs, gs, ls, eps, slope), c_call)
+    return sa.call("td_mlp", x, ws, bs, gs, ls, eps, slope)

@@ -59,20 +59,8 @@ class FIRNoiseSynth(nn.Module):
         if noise is None:
             noise = torch.rand(self.hop_length * T - 1, device=H.device)          # the reference's draw (generators.py:30)
         noise = sa._req(noise, "noise", self.hop_length * T - 1)
-
-        def c_call(L):
-            with torch.cuda.device(H.device):
-                fir = torch.empty((B, T, sa._lib.FIR_HALF), dtype=torch.float32, device=H.device)
-                out = torch.empty((B, T * sa._lib.HOP), dtype=torch.float32, device=H.device)
-                sa.checked(L.nws_fir_from_h(H.data_ptr(), D.data_ptr(), B, T, fir.data_ptr(), sa.stream_ptr(H.device)), "nws_fir_from_h")
-                sa.checked(L.nws_fir_noise(fir.data_ptr(), noise.data_ptr(), None, B, T, out.data_ptr(), sa.stream_ptr(H.device)),
-                           "nws_fir_noise")
-            return out
-
-        o = sa.ops()
-        out = o.fir_noise(o.fir_from_h(H, D), noise, None, -1) if o is not None else c_call(sa._lib.lib())
-        return out.unsqueeze(1)
-
+        b = sa.binding()
+        return b.fir_noise(b.fir_from_h(H, D), noise, None, -1).unsqueeze(1)
 
     def _window_symmetric(self):
         """the specialised kernels pass half rows of taps (include/nws_hip.h, nws_frame_mlps): needs a window that is symmetric
@@ -101,18 +89,7 @@ class FIRNoiseSynth(nn.Module):
         if noise is None:
             noise = torch.rand(hop * T - 1, device=H.device)                      # the reference's draw (generators.py:30)
         noise = sa._req(noise, "noise", hop * T - 1)
-
-        def c_call(lib):
-            with torch.cuda.device(H.device):
-                fir = torch.empty((B, T, L), dtype=torch.float32, device=H.device)
-                out = torch.empty((B, T * hop), dtype=torch.float32, device=H.device)
-                st = sa.stream_ptr(H.device)
-                sa.checked(lib.nws_g_fir_design(H.data_ptr(), win.data_ptr(), L, B, T, fir.data_ptr(), st), "nws_g_fir_design")
-                sa.checked(lib.nws_g_fir_noise(fir.data_ptr(), noise.data_ptr(), L, hop, B, T, None, 0, out.data_ptr(), st),
-                           "nws_g_fir_noise")
-            return out
-
-        return sa.call("g_fir_noise", "nws_g_fir_noise", (H, win, noise, hop), c_call).unsqueeze(1)
+        return sa.call("g_fir_noise", H, win, noise, hop).unsqueeze(1)
 
 
 @gin.configurable
@@ -136,30 +113,7 @@ class HarmonicOscillator(nn.Module):
         rp = sa._req(self.rand_phase.detach().reshape(-1), "osc.rand_phase", K)
         u = torch.rand_like(self.rand_phase) if phase_u is None else phase_u            # the reference's draw (generators.py:55)
         u = sa._req(u.reshape(-1), "phase_u", K)
-        B, N = f0.shape
-        if K != sa._lib.N_HARMONICS or N % sa._lib.HOP:
-            # any harmonic count / length: runtime-size stage kernels (csrc/generic.hip: g_phase_kernel, g_oscillator_kernel)
-            def g_call(lib):
-                with torch.cuda.device(f0.device):
-                    phase = torch.empty_like(f0)
-                    out = torch.empty((B, K, N), dtype=torch.float32, device=f0.device)
-                    st = sa.stream_ptr(f0.device)
-                    sa.checked(lib.nws_g_phase(None, f0.data_ptr(), B, N, 1, float(self.sample_rate), None, phase.data_ptr(), st),
-                               "nws_g_phase")
-                    sa.checked(lib.nws_g_oscillator(f0.data_ptr(), phase.data_ptr(), u.data_ptr(), rp.data_ptr(), K, B, N,
-                                                    float(self.sample_rate), out.data_ptr(), st), "nws_g_oscillator")
-                return out
-
-            return sa.call("g_oscillator", "nws_g_oscillator", (f0, u, rp, float(self.sample_rate)), g_call)
-
-        def c_call(L):
-            with torch.cuda.device(f0.device):
-                carry = torch.empty((B, N // 32), dtype=torch.float64, device=f0.device)
-                out = torch.empty((B, sa._lib.N_HARMONICS, N), dtype=torch.float32, device=f0.device)
-                st = sa.stream_ptr(f0.device)
-                sa.checked(L.nws_phase_carry(None, f0.data_ptr(), B, N // sa._lib.HOP, carry.data_ptr(), st), "nws_phase_carry")
-                sa.checked(L.nws_oscillator(f0.data_ptr(), carry.data_ptr(), u.data_ptr(), rp.data_ptr(), B, N,
-                                            float(self.sample_rate), out.data_ptr(), st), "nws_oscillator")
-            return out
-
-        return sa.call("oscillator", "nws_oscillator", (f0, u, rp, float(self.sample_rate)), c_call)
+        # 101 harmonics on a whole number of hops: the specialised stage kernel; any other harmonic count / length: the
+        # runtime-size stage kernels (csrc/generic.hip: g_phase_kernel, g_oscillator_kernel)
+        generic = K != sa._lib.N_HARMONICS or f0.shape[1] % sa._lib.HOP
+        return sa.call("g_oscillator" if generic else "oscillator", f0, u, rp, float(self.sample_rate))

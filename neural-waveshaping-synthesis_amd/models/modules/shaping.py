@@ -21,31 +21,11 @@ class Sine(nn.Module):
     def forward(self, x):
         """sin(x) on a CUDA tensor with the engine's full-range sine (nws_sin: <= 1.5e-7 absolute)."""
         x = sa.contiguous(x, "x")
-
-        def c_call(L):
-            y = torch.empty_like(x)
-            with torch.cuda.device(x.device):
-                sa.checked(L.nws_sin(x.data_ptr(), y.data_ptr(), x.numel(), sa.stream_ptr(x.device)), "nws_sin")
-            return y
-
-        return sa.call("sine", "nws_sin", (x,), c_call)
-
-
-def _shaper_apply(x, wdesc_tuple):
-    w, _, wdesc = wdesc_tuple
-
-    def c_call(L):
-        y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            sa.checked(L.nws_shaper_apply(C.byref(w), x.data_ptr(), x.shape[0], x.shape[2], y.data_ptr(), sa.stream_ptr(x.device)),
-                       "nws_shaper_apply")
-        return y
-
-    return sa.call("shaper_apply", "nws_shaper_apply", (wdesc, x), c_call)
+        return sa.call("sine", x)
 
 
 class _GShaperCache:
-    """NwsShaperDesc (+ its byte tensor for the op layer) of a TrainableNonlinearity or a FastNEWT table, cached until a
+    """NwsShaperDesc of a TrainableNonlinearity or a FastNEWT table as the byte tensor the binding takes (`sdesc`), cached until a
     tensor changes"""
 
     def __init__(self):
@@ -61,20 +41,9 @@ class _GShaperCache:
             sa.no_autograd(params=ts)
             keep = []
             d = shaper_desc(sh, lut=lut, lut_min=lut_min, lut_max=lut_max, keep=keep)
-            self._val = (d, desc_bytes(d), keep)
+            self._val = (desc_bytes(d), keep)
             self._key = key
-        return self._val[0], self._val[1]
-
-
-def _g_shaper_apply(x, d, sdesc):
-    def c_call(lib):
-        y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            sa.checked(lib.nws_g_shaper_apply(C.byref(d), x.data_ptr(), x.shape[0] * x.shape[1], x.shape[2], y.data_ptr(),
-                                              sa.stream_ptr(x.device)), "nws_g_shaper_apply")
-        return y
-
-    return sa.call("g_shaper_apply", "nws_g_shaper_apply", (sdesc, x), c_call)
+        return self._val[0]
 
 
 @gin.configurable
@@ -109,8 +78,8 @@ class TrainableNonlinearity(nn.Module):
         if not all(isinstance(m, Sine) for m in list(self.net)[1::2]):
             raise RuntimeError("kernels implement the sine activations NEWT configures (nonlinearity=Sine)")
         if (self.channels, self.width, self.depth) != (sa._lib.N_SHAPERS, sa._lib.SHAPER_WIDTH, 4):
-            return _g_shaper_apply(x, *self._gdesc.get(self))          # any channels / width / depth (csrc/generic.hip)
-        return _shaper_apply(x, self._desc.get(sa.shaper_fields(self)))
+            return sa.call("g_shaper_apply", self._gdesc.get(self), x)          # any channels / width / depth (csrc/generic.hip)
+        return sa.call("shaper_apply", self._desc.get(sa.shaper_fields(self)), x)
 
 
 @gin.configurable
@@ -147,25 +116,9 @@ class NEWT(nn.Module):
     def _forward_generic(self, exciter, film):
         """any n_waveshapers / shaping_fn_size / depth / out_channels / hop: FiLM -> shaper -> FiLM (g_film_shaper_kernel) then
         the Conv1d(S -> out_channels) mixer (g_conv1x1_kernel), csrc/generic.hip"""
-        d, sdesc = self._g_shaper()
-        B, S, N = exciter.shape
-        T = film.shape[2]
         mw = sa._req(self.mixer[0].weight.detach(), "newt.mixer.0.weight")
         mb = sa._req(self.mixer[0].bias.detach(), "newt.mixer.0.bias")
-        O = mw.shape[0]
-
-        def c_call(lib):
-            with torch.cuda.device(exciter.device):
-                shaped = torch.empty_like(exciter)
-                out = torch.empty((B, O, N), dtype=torch.float32, device=exciter.device)
-                st = sa.stream_ptr(exciter.device)
-                sa.checked(lib.nws_g_film_shaper(C.byref(d), exciter.data_ptr(), film.data_ptr(), B, T, N // T, shaped.data_ptr(), st),
-                           "nws_g_film_shaper")
-                sa.checked(lib.nws_g_conv1x1(shaped.data_ptr(), mw.data_ptr(), mb.data_ptr(), B, S, O, N, out.data_ptr(), st),
-                           "nws_g_conv1x1")
-            return out
-
-        return sa.call("g_newt_apply", "nws_g_film_shaper", (sdesc, exciter, film, mw, mb), c_call)
+        return sa.call("g_newt_apply", self._g_shaper(), exciter, film, mw, mb)
 
     def forward(self, exciter, control_embedding):
         """(B, 64, N) exciter, (B, 128, T) control embedding -> (B, 1, N) (reference shaping.py:67-79): the FiLM-parameter
@@ -189,16 +142,7 @@ class NEWT(nn.Module):
             return self._forward_generic(exciter, film)
         tensors, scalars = self._apply_fields()
         tensors = dict(tensors, newt_out_w=self.mixer[0].weight, newt_out_b=self.mixer[0].bias)
-        w, _, wdesc = self._newt_desc.get(tensors, scalars)
-
-        def c_call(L):
-            with torch.cuda.device(exciter.device):
-                out = torch.empty((exciter.shape[0], 1, exciter.shape[2]), dtype=torch.float32, device=exciter.device)
-                sa.checked(L.nws_newt_apply(C.byref(w), exciter.data_ptr(), film.data_ptr(), exciter.shape[0], T, out.data_ptr(),
-                                            sa.stream_ptr(exciter.device)), "nws_newt_apply")
-            return out
-
-        return sa.call("newt_apply", "nws_newt_apply", (wdesc, exciter, film), c_call)
+        return sa.call("newt_apply", self._newt_desc.get(tensors, scalars), exciter, film)
 
 
 class FastNEWT(NEWT):
@@ -258,31 +202,12 @@ class FastNEWT(NEWT):
             sh_dev = sh if home == dev else copy.deepcopy(sh).to(dev)
             keep = []
             d = shaper_desc(sh_dev, keep=keep)
-
-            def g_call(lib):
-                with torch.cuda.device(dev):
-                    table = torch.empty((n_waveshapers, table_size), dtype=torch.float32, device=dev)
-                    sa.checked(lib.nws_g_shaper_table(C.byref(d), int(table_size), float(table_min), float(table_max), table.data_ptr(),
-                                                      sa.stream_ptr(dev)), "nws_g_shaper_table")
-                return table
-
             with torch.no_grad():
-                table = sa.call("g_shaper_table", "nws_g_shaper_table",
-                                (desc_bytes(d), keep[0], int(table_size), float(table_min), float(table_max)), g_call)
+                table = sa.call("g_shaper_table", desc_bytes(d), keep[0], int(table_size), float(table_min), float(table_max))
             torch.cuda.current_stream(dev).synchronize()
             return nn.Parameter(table.to(home))
         fields = {k: v.detach().to(dev).contiguous() for k, v in sa.shaper_fields(sh).items()}
-        w, keep, wdesc = sa.Desc().get(fields)
-        like = keep[0]
-
-        def c_call(L):
-            with torch.cuda.device(dev):
-                table = torch.empty((n_waveshapers, table_size), dtype=torch.float32, device=dev)
-                sa.checked(L.nws_shaper_table(C.byref(w), int(table_size), float(table_min), float(table_max), table.data_ptr(),
-                                              sa.stream_ptr(dev)), "nws_shaper_table")
-            return table
-
-        table = sa.call("shaper_table", "nws_shaper_table", (wdesc, like, int(table_size), float(table_min), float(table_max)), c_call)
+        table = sa.call("shaper_table", sa.Desc().get(fields), fields["shaper_in_scale"], int(table_size), float(table_min), float(table_max))
         torch.cuda.current_stream(dev).synchronize()
         return nn.Parameter(table.to(home))
 
@@ -301,8 +226,8 @@ class FastNEWT(NEWT):
         if self.lookup_table.numel() != self.n_waveshapers * self.table_size:
             raise RuntimeError("lookup_table does not match table_size")
         if self.n_waveshapers != sa._lib.N_SHAPERS:
-            return _g_shaper_apply(x, *self._g_shaper())
-        return _shaper_apply(x, self._lut_desc.get(*self._lut_fields()))
+            return sa.call("g_shaper_apply", self._g_shaper(), x)
+        return sa.call("shaper_apply", self._lut_desc.get(*self._lut_fields()), x)
 
 
 @gin.configurable
@@ -330,20 +255,13 @@ class Reverb(nn.Module):
         ir = sa._req(self.ir.detach(), "reverb.ir")
         if ir.device != x.device:
             raise RuntimeError(f"x is on {x.device} but reverb.ir is on {ir.device}")
-        B, N = x.shape
+        N = x.shape[1]
         from ..._lib import NwsReverbPlan
 
         probe = NwsReverbPlan()
         if sa._lib.lib().nws_reverb_plan(int(N), int(ir.numel()) + 1, C.byref(probe)) != 0:
             # odd circular length (every even one has a plan): the reference's own rfft / irfft expression (csrc/generic.hip)
-            def d_call(lib):
-                y = torch.empty_like(x)
-                with torch.cuda.device(x.device):
-                    sa.checked(lib.nws_g_reverb_direct(x.data_ptr(), ir.data_ptr(), ir.numel(), B, N, y.data_ptr(),
-                                                       sa.stream_ptr(x.device)), "nws_g_reverb_direct")
-                return y
-
-            return sa.call("g_reverb_direct", "nws_g_reverb_direct", (x, ir.reshape(-1)), d_call)
+            return sa.call("g_reverb_direct", x, ir.reshape(-1))
         plan, tables, plan_t = reverb_plan_and_tables(x.device, N, ir.numel() + 1)
         L = sa._lib.lib()
         key = (plan.L, ir.data_ptr(), ir._version)
@@ -358,14 +276,4 @@ class Reverb(nn.Module):
                                                     spec.data_ptr(), ws1.data_ptr(), nb, sa.stream_ptr(x.device)),
                            "nws_reverb_ir_spectrum")
             self._tables[key] = spec
-
-        def c_call(L):
-            with torch.cuda.device(x.device):
-                nb = L.nws_reverb_workspace_bytes(C.byref(plan), B)
-                ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
-                y = torch.empty_like(x)
-                sa.checked(L.nws_reverb(C.byref(plan), tables.data_ptr(), spec.data_ptr(), x.data_ptr(), B, N, y.data_ptr(),
-                                        ws.data_ptr(), nb, sa.stream_ptr(x.device)), "nws_reverb")
-            return y
-
-        return sa.call("reverb", "nws_reverb", (plan_t, tables, spec, x), c_call)
+        return sa.call("reverb", plan_t, tables, spec, x)

@@ -49,8 +49,6 @@ class ControlModule(nn.Module):
     def forward(self, x):
         """(B, control_size, T) -> (B, embedding_size, T): persistent GRU kernel (csrc/control_gru.hip) + Conv1d(k=1).
         Stand-alone form of what NeuralWaveshaping.forward runs fused (GRU, then proj inside frame_mlps16_kernel)."""
-        import ctypes as C
-
         x = sa.contiguous(x, "x")
         g = self.gru
         if g.num_layers != 1 or g.bidirectional or not g.batch_first:
@@ -61,35 +59,11 @@ class ControlModule(nn.Module):
             # any control_size / hidden_size: runtime-size recurrence (csrc/generic.hip: g_gru_kernel)
             ps = [sa._req(p.detach(), "gru parameter") for p in (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)]
             sa.no_autograd(params=[g.weight_ih_l0])
-            B, Cin, T = x.shape
-            H = g.hidden_size
-
-            def g_call(lib):
-                with torch.cuda.device(x.device):
-                    out = torch.empty((B, T, H), dtype=torch.float32, device=x.device)
-                    nb = lib.nws_g_gru_workspace_bytes(H)
-                    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
-                    sa.checked(lib.nws_g_gru(ps[0].data_ptr(), ps[1].data_ptr(), ps[2].data_ptr(), ps[3].data_ptr(), x.data_ptr(), B,
-                                             Cin, Cin, H, T, None, out.data_ptr(), None, ws.data_ptr(), nb, sa.stream_ptr(x.device)),
-                               "nws_g_gru")
-                return out
-
-            o = sa.ops()
-            sa.no_autograd(inputs=(x,))
-            h = o.g_gru(ps[0], ps[1], ps[2], ps[3], x, None)[0] if o is not None else g_call(sa._lib.lib())
-            return td_mlp_forward(h.transpose(1, 2).contiguous(), self.proj)
-        w, _, wdesc = self._desc.get({"gru_w_ih": g.weight_ih_l0, "gru_w_hh": g.weight_hh_l0, "gru_b_ih": g.bias_ih_l0,
-                                      "gru_b_hh": g.bias_hh_l0})
-
-        def c_call(L):
-            with torch.cuda.device(x.device):
-                out = torch.empty((x.shape[0], x.shape[2], sa._lib.HIDDEN), dtype=torch.float32, device=x.device)
-                sa.checked(L.nws_control_gru(C.byref(w), x.data_ptr(), x.shape[0], x.shape[1], x.shape[2], out.data_ptr(),
-                                             sa.stream_ptr(x.device)), "nws_control_gru")
-            return out
-
-        o = sa.ops()
-        h = o.control_gru(wdesc, x, None, False)[0] if o is not None else c_call(sa._lib.lib())      # (B, T, 128)
+            h = sa.call("g_gru", ps[0], ps[1], ps[2], ps[3], x, None)[0]
+        else:
+            wdesc = self._desc.get({"gru_w_ih": g.weight_ih_l0, "gru_w_hh": g.weight_hh_l0, "gru_b_ih": g.bias_ih_l0,
+                                    "gru_b_hh": g.bias_hh_l0})
+            h = sa.binding().control_gru(wdesc, x, None, False)[0]      # (B, T, 128)
         return td_mlp_forward(h.transpose(1, 2).contiguous(), self.proj)
 
 
@@ -162,17 +136,7 @@ class NeuralWaveshaping(nn.Module):
                 osc = self.osc(f0[:, 0])
                 mw = _req(self.harmonic_mixer.weight.detach(), "harmonic_mixer.weight")
                 mb = _req(self.harmonic_mixer.bias.detach(), "harmonic_mixer.bias")
-                B, K, N = osc.shape
-                S = mw.shape[0]
-
-                def c_call(lib):
-                    with torch.cuda.device(osc.device):
-                        out = torch.empty((B, S, N), dtype=torch.float32, device=osc.device)
-                        sa.checked(lib.nws_g_conv1x1(osc.data_ptr(), mw.data_ptr(), mb.data_ptr(), B, K, S, N, out.data_ptr(),
-                                                     sa.stream_ptr(osc.device)), "nws_g_conv1x1")
-                    return out
-
-                return sa.call("g_conv1x1", "nws_g_conv1x1", (osc, mw, mb), c_call)
+                return sa.call("g_conv1x1", osc, mw, mb)
         eng = self._engine
         f0_up = f0[:, 0]
         u = torch.rand_like(self.osc.rand_phase).reshape(-1)

@@ -5,7 +5,7 @@ oscillator phase and the reverb.  `NewtStream` carries that state so that the co
 equals the reference's ONE-SHOT forward over the whole signal up to the reverb input (`pre_reverb`), and applies the
 learned reverb as a linear convolution of the stream instead of the one-shot path's wrap-around.
 
-One `push` = ONE C-ABI call (`nws_stream_step` / `torch.ops.newt_hip.stream_step`): the one-shot kernels plus small streaming
+One `push` = ONE call of the binding (`engine.binding().stream_step` -> `nws_stream_step`): the one-shot kernels plus small streaming
 kernels on a window = [last frame of the previous chunk] + [K new frames] - four launches for a hop of <= 256 samples (whatever
 depends on nothing the hop computes, and the frame MLPs of its one or two frames, ride on the recurrence launch: DESIGN.md 3.8),
 seven for longer chunks; every piece of state
@@ -26,11 +26,12 @@ from __future__ import annotations
 
 import ctypes as C
 import time
+import warnings
 
 import torch
 
 from . import _lib
-from .engine import _req, ops, stream_ptr
+from .engine import _req, binding, stream_ptr
 
 HOP = _lib.HOP
 _MAX_CHUNK_FRAMES = 249   # 16 kHz: (K+1) * 128 + 31999 <= 64000, the FFT reverb of a long chunk inside the L = 64000 plan
@@ -38,7 +39,87 @@ _RING = 65536             # kRing of csrc/stream.hip: reverb-input ring per utte
 _GRAPH_AFTER = 2          # consecutive steady-state pushes of one (K, channels) before that hop is captured
 
 
-class NewtStream:
+class _StreamBase:
+    """What NewtStream and VoiceStream share: the captured steady-state hop and its fall-back to eager pushes, the watch on the
+    engine's weights record, and the reverb tail.  A subclass provides `_steady_step(f0_2d, control, noise_new, out, pre)`: one
+    steady-state hop through the binding."""
+
+    def _capture(self, K, C_in):
+        """hipGraph of one steady-state hop of K frames: static input / output buffers, the fresh noise draws inside."""
+        dev = self.dev
+        with torch.cuda.device(dev):
+            f0_in = torch.zeros((self.B, K), dtype=torch.float32, device=dev)
+            c_in = torch.zeros((self.B, C_in, K), dtype=torch.float32, device=dev)
+            nz = torch.empty(HOP * K, dtype=torch.float32, device=dev) if self._noise_all is None else None
+            out = torch.empty((self.B, HOP * K), dtype=torch.float32, device=dev)
+            pre = torch.empty((self.B, HOP * K), dtype=torch.float32, device=dev)
+            g = torch.cuda.CUDAGraph()
+            torch.cuda.synchronize(dev)
+            with torch.cuda.graph(g):
+                if nz is not None:
+                    nz.uniform_()                                  # the reference's torch.rand draw, chunk by chunk
+                self._steady_step(f0_in, c_in, nz, out, pre)
+        # capture records, it does not run: the state has not advanced
+        return g, f0_in, c_in, nz, out, pre
+
+    def _captured_hop(self, key, may_capture):
+        """The captured hop of key = (K, channels), or None.  With `may_capture` a missing one is captured now; where that is not
+        possible (e.g. a foreign capture in progress) the stream stays eager from now on, and says so."""
+        hit = self._graphs.get(key)
+        if hit is None and may_capture:
+            try:
+                hit = self._graphs[key] = self._capture(*key)
+            except Exception as e:
+                warnings.warn(f"{type(self).__name__}: hipGraph capture of the {key[0]}-frame hop failed ({type(e).__name__}: {e}); this "
+                              f"stream continues with eager pushes", RuntimeWarning, stacklevel=3)
+                self._use_graph = False
+        return hit
+
+    def refresh(self):
+        """Pick up a weight update NOW: re-derive the engine's tables if any parameter changed and drop the captured hops that
+        point into the old ones.  Call it after an optimizer step / load_state_dict / in-place edit when the very next hop must
+        see the new weights; without it a captured hop (`graph=True`) keeps replaying the old tables for up to 250 ms (eager
+        pushes notice at once), see _check_weights."""
+        self.__dict__["_last_walk"] = 0.0
+        self._check_weights()
+
+    def _check_weights(self):
+        """A captured hop holds raw pointers into the engine's derived tables (fragment tables, LUT pairs, FIR design, IR
+        spectrum).  If the engine has rebuilt them (somebody ran a forward after a weight update, `.to()`, `invalidate_cache`)
+        the graphs are dropped and re-captured; in-place updates nobody has told the engine about are looked for at most every
+        250 ms of wall-clock (a full fingerprint walk costs ~12 us of host time: too much for every 256-sample hop, nothing once
+        per sixteen 16 ms hops).  So for up to 250 ms after such an update graph=True and graph=False streams differ; `refresh()`
+        closes that window on demand."""
+        eng = self.eng
+        now = time.monotonic()
+        if now - self.__dict__.get("_last_walk", 0.0) >= 0.25:
+            self._last_walk = now
+            if eng._w is not None and eng._fingerprint() != eng._fp:
+                eng._wd()                              # rebuilds (drains the device first)
+        if eng._w is not self.__dict__.get("_w_seen"):
+            if self._graphs:
+                torch.cuda.synchronize(self.dev)
+                self._graphs.clear()
+                self._steady_runs.clear()
+            self._w_seen = eng._w
+
+    def reverb_tail(self) -> torch.Tensor:
+        """The remaining (B, ir_len + 1) reverb tail of every row after the last chunk (what a linear reverb still rings out)."""
+        eng = self.eng
+        eng._wd()
+        plan, tables, spec, _ = eng._reverb_aux(self._plan_n)
+        L = _lib.lib()
+        with torch.cuda.device(self.dev):
+            tail = torch.empty((self.B, self.tail_len), dtype=torch.float32, device=self.dev)
+            nb = 2 * ((self.B * (2 * self._ir_len + 1) * 4 + 255) // 256 * 256) + L.nws_reverb_workspace_bytes(C.byref(plan), self.B)
+            ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
+            _lib.check(L.nws_stream_reverb_tail(C.byref(plan), tables.data_ptr(), spec.data_ptr(), self._state.data_ptr(),
+                                                self._state.numel(), self.B, self.max_frames, self._ir_len, tail.data_ptr(),
+                                                ws.data_ptr(), nb, stream_ptr(self.dev)), "nws_stream_reverb_tail")
+        return tail
+
+
+class NewtStream(_StreamBase):
     def __init__(self, model, batch_size: int, phase_u: torch.Tensor | None = None, noise: torch.Tensor | None = None,
                  max_chunk_frames: int = _MAX_CHUNK_FRAMES, graph: bool = True):
         if not model._engine.specialised():
@@ -80,49 +161,17 @@ class NewtStream:
         self._last_K = None
         self._last_pre = None
 
-    # ---- one C-ABI call ---------------------------------------------------------------------------------------------
+    # ---- one call of the binding ------------------------------------------------------------------------------------
     def _step(self, f0_2d, control, first, final, noise_new, out, pre):
         eng = self.eng
-        w, keep, dev, wdesc = eng._wd()
-        B, K = f0_2d.shape
-        fft = self._need_fft
-        plan, tables, spec, plan_t = eng._reverb_aux(self._plan_n) if fft else (None, None, None, None)
-        sr = eng.osc_sample_rate()
-        rp, ir = keep[-2], keep[-1]
-        o = ops()
-        if o is not None:
-            o.stream_step(wdesc, eng._fir_design, plan_t, tables, spec, self._state, self.max_frames, f0_2d, control, bool(first),
-                          bool(final), int(self.frames_seen), int(self._nz_prev_start), sr, self.phase_u, rp, noise_new,
-                          self._noise_all, ir.reshape(-1), out, pre)
-            return
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nws_stream_step(
-                C.byref(w), eng._fir_design.data_ptr(), C.byref(plan) if fft else None, tables.data_ptr() if fft else None,
-                spec.data_ptr() if fft else None, self._state.data_ptr(), self._state.numel(), B, self.max_frames,
-                f0_2d.data_ptr(), control.data_ptr(), control.shape[1], K, int(first), int(final), int(self.frames_seen),
-                int(self._nz_prev_start), sr, self.phase_u.data_ptr(), rp.data_ptr(),
-                noise_new.data_ptr() if noise_new is not None else None,
-                self._noise_all.data_ptr() if self._noise_all is not None else None,
-                self._noise_all.numel() if self._noise_all is not None else 0, ir.data_ptr(), ir.numel(), out.data_ptr(),
-                pre.data_ptr() if pre is not None else None, stream_ptr(dev)), "nws_stream_step")
+        r = eng._wd()
+        _, tables, spec, plan_t = eng._reverb_aux(self._plan_n) if self._need_fft else (None, None, None, None)
+        binding().stream_step(r.wdesc, r.fir_design, plan_t, tables, spec, self._state, self.max_frames, f0_2d, control, bool(first),
+                              bool(final), int(self.frames_seen), int(self._nz_prev_start), eng.osc_sample_rate(), self.phase_u,
+                              r.rand_phase, noise_new, self._noise_all, r.ir.reshape(-1), out, pre)
 
-    def _capture(self, K, C_in):
-        """hipGraph of one steady-state hop of K frames: static input / output buffers, the fresh noise draws inside."""
-        dev = self.dev
-        with torch.cuda.device(dev):
-            f0_in = torch.zeros((self.B, K), dtype=torch.float32, device=dev)
-            c_in = torch.zeros((self.B, C_in, K), dtype=torch.float32, device=dev)
-            nz = torch.empty(HOP * K, dtype=torch.float32, device=dev) if self._noise_all is None else None
-            out = torch.empty((self.B, HOP * K), dtype=torch.float32, device=dev)
-            pre = torch.empty((self.B, HOP * K), dtype=torch.float32, device=dev)
-            g = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize(dev)
-            with torch.cuda.graph(g):
-                if nz is not None:
-                    nz.uniform_()                                  # the reference's torch.rand draw, chunk by chunk
-                self._step(f0_in, c_in, False, False, nz, out, pre)
-        # capture records, it does not run: the state has not advanced
-        return g, f0_in, c_in, nz, out, pre
+    def _steady_step(self, f0_2d, control, noise_new, out, pre):
+        self._step(f0_2d, control, False, False, noise_new, out, pre)
 
     # ---- one chunk ----------------------------------------------------------------------------------------------------
     def push(self, f0: torch.Tensor, control: torch.Tensor, final: bool = False) -> torch.Tensor:
@@ -155,18 +204,9 @@ class NewtStream:
         if not steady:
             self._steady_runs.clear()      # the count is of CONSECUTIVE steady hops of one shape
         if steady and self._use_graph:
-            hit = self._graphs.get(key)
             runs = self._steady_runs.get(key, 0) + 1
             self._steady_runs = {key: runs}
-            if hit is None and runs > _GRAPH_AFTER and not torch.cuda.is_current_stream_capturing():
-                try:
-                    hit = self._graphs[key] = self._capture(K, control.shape[1])
-                except Exception as e:     # capture not possible here (e.g. foreign capture in progress): stay eager, and say so
-                    import warnings
-                    warnings.warn(f"NewtStream: hipGraph capture of the {K}-frame hop failed ({type(e).__name__}: {e}); this stream "
-                                  f"continues with eager pushes", RuntimeWarning, stacklevel=2)
-                    self._use_graph = False
-                    hit = None
+            hit = self._captured_hop(key, runs > _GRAPH_AFTER and not torch.cuda.is_current_stream_capturing())
             if hit is not None:
                 g, f0_in, c_in, _, out, pre = hit
                 torch._foreach_copy_([f0_in, c_in], [f0_2d, control])      # one multi-tensor launch for both inputs
@@ -184,34 +224,6 @@ class NewtStream:
         self._advance(K, M, first, final)
         self._last_pre = pre
         return out
-
-    def refresh(self):
-        """Pick up a weight update NOW: re-derive the engine's tables if any parameter changed and drop the captured hops that
-        point into the old ones.  Call it after an optimizer step / load_state_dict / in-place edit when the very next hop must
-        see the new weights; without it a captured hop (`graph=True`) keeps replaying the old tables for up to 250 ms (eager
-        pushes notice at once), see _check_weights."""
-        self.__dict__["_last_walk"] = 0.0
-        self._check_weights()
-
-    def _check_weights(self):
-        """A captured hop holds raw pointers into the engine's derived tables (fragment tables, LUT pairs, FIR design, IR
-        spectrum).  If the engine has rebuilt them (somebody ran a forward after a weight update, `.to()`, `invalidate_cache`)
-        the graphs are dropped and re-captured; in-place updates nobody has told the engine about are looked for at most every
-        250 ms of wall-clock (a full fingerprint walk costs ~12 us of host time: too much for every 256-sample hop, nothing once
-        per sixteen 16 ms hops).  So for up to 250 ms after such an update graph=True and graph=False streams differ; `refresh()`
-        closes that window on demand."""
-        eng = self.eng
-        now = time.monotonic()
-        if now - self.__dict__.get("_last_walk", 0.0) >= 0.25:
-            self._last_walk = now
-            if eng._w is not None and eng._fingerprint() != eng._fp:
-                eng._wd()                              # rebuilds (drains the device first)
-        if eng._w is not self.__dict__.get("_w_seen"):
-            if self._graphs:
-                torch.cuda.synchronize(self.dev)
-                self._graphs.clear()
-                self._steady_runs.clear()
-            self._w_seen = eng._w
 
     # ---- zero-copy hops: the caller writes into the captured hop's own input buffers and reads its output buffer ----------
     def static_io(self, K: int, channels: int = 2):
@@ -243,22 +255,6 @@ class NewtStream:
         self.samples_emitted += M
         self._last_K = K
         self.finished = bool(final)
-
-    def reverb_tail(self) -> torch.Tensor:
-        """The remaining (B, 32000) reverb tail after the last chunk (what a linear reverb still rings out)."""
-        eng = self.eng
-        eng._wd()
-        plan, tables, spec, _ = eng._reverb_aux(self._plan_n)
-        L = _lib.lib()
-        with torch.cuda.device(self.dev):
-            tail = torch.empty((self.B, self.tail_len), dtype=torch.float32, device=self.dev)
-            nb = 2 * ((self.B * (2 * self._ir_len + 1) * 4 + 255) // 256 * 256) + L.nws_reverb_workspace_bytes(C.byref(plan), self.B)
-            ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
-            _lib.check(L.nws_stream_reverb_tail(C.byref(plan), tables.data_ptr(), spec.data_ptr(), self._state.data_ptr(),
-                                                self._state.numel(), self.B, self.max_frames, self._ir_len, tail.data_ptr(),
-                                                ws.data_ptr(), nb, stream_ptr(self.dev)), "nws_stream_reverb_tail")
-        return tail
-
 
 # ---- slot mode: B voices with their own lifetimes in one batched stream ------------------------------------------------
 SLOT_START, SLOT_STOP, SLOT_RELEASE, SLOT_ACTIVE = 1, 2, 4, 8   # include/nws_hip.h NWS_SLOT_*
@@ -337,7 +333,7 @@ class SlotBook:
                 self.states[i] = IDLE
 
 
-class VoiceStream:
+class VoiceStream(_StreamBase):
     """B voice slots in one batched stream, each starting and stopping on its own (`model.stream(B, slots=True)`).
 
     One hop = K frames (1 <= K <= 16) for every slot, `push(f0, control, start=, stop=)` -> (B, 128 K), every hop the same shape.
@@ -419,43 +415,15 @@ class VoiceStream:
         self._advance(_PREROLL)
         self._last_K = None
 
-    # ---- one C-ABI call ---------------------------------------------------------------------------------------------
+    # ---- one call of the binding ------------------------------------------------------------------------------------
     def _step(self, f0_2d, control, noise_new, out, pre):
         eng = self.eng
-        w, keep, dev, wdesc = eng._wd()
-        B, K = f0_2d.shape
-        sr = eng.osc_sample_rate()
-        rp, ir = keep[-2], keep[-1]
-        o = ops()
-        if o is not None:
-            o.stream_step_slots(wdesc, eng._fir_design, self._state, self.max_frames, f0_2d, control, int(self.frames_seen),
-                                int(self._nz_prev_start), sr, self.phase_u, rp, noise_new, self._noise_all, ir.reshape(-1), self._ev,
-                                out, pre)
-            return
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nws_stream_step_slots(
-                C.byref(w), eng._fir_design.data_ptr(), self._state.data_ptr(), self._state.numel(), B, self.max_frames,
-                f0_2d.data_ptr(), control.data_ptr(), control.shape[1], K, int(self.frames_seen), int(self._nz_prev_start), sr,
-                self.phase_u.data_ptr(), rp.data_ptr(), noise_new.data_ptr() if noise_new is not None else None,
-                self._noise_all.data_ptr() if self._noise_all is not None else None,
-                self._noise_all.numel() if self._noise_all is not None else 0, ir.data_ptr(), ir.numel(), self._ev.data_ptr(),
-                out.data_ptr(), pre.data_ptr() if pre is not None else None, stream_ptr(dev)), "nws_stream_step_slots")
+        r = eng._wd()
+        binding().stream_step_slots(r.wdesc, r.fir_design, self._state, self.max_frames, f0_2d, control, int(self.frames_seen),
+                                    int(self._nz_prev_start), eng.osc_sample_rate(), self.phase_u, r.rand_phase, noise_new,
+                                    self._noise_all, r.ir.reshape(-1), self._ev, out, pre)
 
-    def _capture(self, K, C_in):
-        dev = self.dev
-        with torch.cuda.device(dev):
-            f0_in = torch.zeros((self.B, K), dtype=torch.float32, device=dev)
-            c_in = torch.zeros((self.B, C_in, K), dtype=torch.float32, device=dev)
-            nz = torch.empty(HOP * K, dtype=torch.float32, device=dev) if self._noise_all is None else None
-            out = torch.empty((self.B, HOP * K), dtype=torch.float32, device=dev)
-            pre = torch.empty((self.B, HOP * K), dtype=torch.float32, device=dev)
-            g = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize(dev)
-            with torch.cuda.graph(g):
-                if nz is not None:
-                    nz.uniform_()
-                self._step(f0_in, c_in, nz, out, pre)
-        return g, f0_in, c_in, nz, out, pre
+    _steady_step = _step
 
     def _set_events(self, words):
         # one host-to-device copy per hop whose words differ from the last ones written (a copy costs a few us of the hop's
@@ -493,16 +461,7 @@ class VoiceStream:
         self._set_events(words)
         key = (K, control.shape[1])
         if self._use_graph and self._steady(K) and not torch.cuda.is_current_stream_capturing():
-            hit = self._graphs.get(key)
-            if hit is None:
-                try:
-                    hit = self._graphs[key] = self._capture(K, control.shape[1])
-                except Exception as e:
-                    import warnings
-                    warnings.warn(f"VoiceStream: hipGraph capture of the {K}-frame hop failed ({type(e).__name__}: {e}); this stream "
-                                  f"continues with eager pushes", RuntimeWarning, stacklevel=2)
-                    self._use_graph = False
-                    hit = None
+            hit = self._captured_hop(key, True)
             if hit is not None:
                 g, f0_in, c_in, _, out, pre = hit
                 torch._foreach_copy_([f0_in, c_in], [f0_2d, control])
@@ -581,13 +540,3 @@ class VoiceStream:
         self.check()
         self._graphs.clear()
         self.finished = True
-
-    def refresh(self):
-        NewtStream.refresh(self)
-
-    def _check_weights(self):
-        NewtStream._check_weights(self)
-
-    def reverb_tail(self) -> torch.Tensor:
-        """The remaining (B, ir_len + 1) reverb tail of every slot after the last hop."""
-        return NewtStream.reverb_tail(self)
