@@ -438,6 +438,44 @@ int nws_loudness(const float* audio, int B, int N, int n_fft, int hop, const flo
                  int normalise, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * pYIN F0 extractor, the other analysis feature in front of the synthesis path:
+ * neural_waveshaping_synthesis/data/utils/f0_extraction.py:61-92 (extract_f0_with_pyin -> librosa.pyin) with librosa's own
+ * constants (100 thresholds, beta(2, 18) prior, Boltzmann parameter 2, resolution 0.1, max_transition_rate 35.92, switch_prob
+ * 0.01, no_trough_prob 0.01, centre / reflect padding).  DESIGN.md 3.9 is the definition; parity with librosa is unpinned.
+ * A configuration is (sample_rate, fmin, fmax, frame_length, hop); nws_pyin_dims gives its derived sizes
+ * dims[8] = {min_period, max_period, lags, n_bins_per_semitone, n_pitch_bins, transition window, W = frame_length / 2,
+ * hop blocks per frame in the shared-sum form of the difference kernel (0: plain form)}.
+ * Limits (NWS_ERR_UNSUPPORTED, 0 bytes): lags <= 512 (frame_length <= 1024), n_pitch_bins <= 1024 (2048 states), transition
+ * window <= 127, hop <= frame_length, B <= 65535, 31 hop + frame_length + 32 (max_period + 1) floats <= 160 KB of LDS.
+ * N > frame_length / 2 (reflect padding), T = 1 + N / hop frames.
+ *   nws_pyin_table   fills a HOST buffer of nws_pyin_table_bytes with the fp64 constants of a configuration (threshold prior,
+ *                    Boltzmann terms, log transition window, log row sums, F0 of every bin); copy it to the device once.
+ *   nws_pyin_cmnd    audio (B, N) -> yin (B, T, lags) fp32: squared-difference YIN + cumulative-mean normalisation.
+ *   nws_pyin_observe yin -> sparse observations per frame: cand_bin / cand_prob (B, T, lags) in lag order (entries beyond
+ *                    count are -1 / 0), count (B, T), voiced_prob (B, T) fp64.
+ *   nws_pyin_viterbi observations -> states (B, T) int32 in [0, 2 n_pitch_bins) (voiced bins, then unvoiced bins) and
+ *                    f0 (B, T) = fmin 2^(bin / (12 n_bps)); fill_unvoiced != 0 writes fill_value on unvoiced frames.
+ *                    Workspace: the first part of nws_pyin_workspace_bytes (one byte per state and frame + one word per frame).
+ *   nws_pyin         the three stages on one stream.
+ */
+int nws_pyin_frames(int N, int hop);
+int nws_pyin_dims(double sample_rate, double fmin, double fmax, int frame_length, int hop, int32_t* dims);
+size_t nws_pyin_table_bytes(double sample_rate, double fmin, double fmax, int frame_length, int hop);
+int nws_pyin_table(double sample_rate, double fmin, double fmax, int frame_length, int hop, double* table_host);
+size_t nws_pyin_workspace_bytes(int B, int N, double sample_rate, double fmin, double fmax, int frame_length, int hop);
+int nws_pyin_cmnd(const float* audio, int B, int N, double sample_rate, double fmin, double fmax, int frame_length, int hop,
+                  float* yin, void* stream);
+int nws_pyin_observe(const float* yin, int B, int T, double sample_rate, double fmin, double fmax, int frame_length, int hop,
+                     const double* table, int* cand_bin, double* cand_prob, int* count, double* voiced_prob, void* stream);
+int nws_pyin_viterbi(const int* cand_bin, const double* cand_prob, const int* count, const double* voiced_prob, int B, int T,
+                     double sample_rate, double fmin, double fmax, int frame_length, int hop, const double* table,
+                     int fill_unvoiced, float fill_value, int* states, float* f0, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int nws_pyin(const float* audio, int B, int N, double sample_rate, double fmin, double fmax, int frame_length, int hop,
+             const double* table, int fill_unvoiced, float fill_value, float* f0, double* voiced_prob, int* states,
+             void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * ---- Runtime-size path (csrc/generic.hip): every gin-configurable size of the reference ------------------------------
  * The fused kernels above are compiled for gin/models/newt.gin.  These entry points take the sizes as arguments and run
  * one plain-fp32 stage kernel each (correct first, stage boundaries materialised); nws_forward_generic chains them into

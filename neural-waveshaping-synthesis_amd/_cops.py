@@ -54,6 +54,19 @@ def _ptrs(tensors):
     return (C.c_void_p * max(1, len(tensors)))(*[t.data_ptr() for t in tensors])
 
 
+def _pyin_dims(cfg, table=None):
+    """nws_pyin_dims of a configuration + the table's length in doubles; `table`: a device table to check against it"""
+    dims = (C.c_int32 * 8)()
+    L = _lib.lib()
+    if L.nws_pyin_dims(*cfg, dims) != 0:
+        raise RuntimeError(f"pyin: unsupported configuration (sample_rate, fmin, fmax, frame_length, hop) = {cfg}: at most 512 "
+                           "lags (frame_length <= 1024), 1024 pitch bins and a transition window of 127; hop <= frame_length")
+    n = L.nws_pyin_table_bytes(*cfg) // 8
+    if isinstance(table, torch.Tensor) and (not table.is_cuda or table.dtype != torch.float64 or table.numel() != n):
+        raise RuntimeError("pyin: table does not belong to this configuration (expected a float64 CUDA tensor of nws_pyin_table)")
+    return (*dims, n)
+
+
 class CtypesOps:
     def abi_version(self):
         return int(_lib.lib().nws_abi_version())
@@ -275,6 +288,71 @@ class CtypesOps:
             check(L.nws_loudness(ptr(audio), B, N, n_fft, hop, ptr(dft), amin, top_db, 1 if normalise else 0, ptr(out), ptr(ws),
                                  ws.numel(), _stream(audio.device)), "nws_loudness")
         return out
+
+    # ---- pYIN F0 extractor (csrc/pyin.hip) -------------------------------------------------------------------------------
+    def pyin_table(self, sample_rate, fmin, fmax, frame_length, hop):
+        cfg = (sample_rate, fmin, fmax, frame_length, hop)
+        table = torch.empty(_pyin_dims(cfg)[8], dtype=torch.float64)
+        check(_lib.lib().nws_pyin_table(*cfg, table.data_ptr()), "nws_pyin_table")
+        return table
+
+    def pyin_cmnd(self, audio, sample_rate, fmin, fmax, frame_length, hop):
+        cfg = (sample_rate, fmin, fmax, frame_length, hop)
+        B, N = audio.shape
+        L = _lib.lib()
+        with torch.cuda.device(audio.device):
+            yin = _new(audio, B, L.nws_pyin_frames(N, hop), _pyin_dims(cfg)[2])
+            check(L.nws_pyin_cmnd(ptr(audio), B, N, *cfg, ptr(yin), _stream(audio.device)), "nws_pyin_cmnd")
+        return yin
+
+    def pyin_observe(self, yin, table, sample_rate, fmin, fmax, frame_length, hop):
+        cfg = (sample_rate, fmin, fmax, frame_length, hop)
+        B, T, lags = yin.shape
+        if lags != _pyin_dims(cfg, table)[2]:
+            raise RuntimeError(f"pyin_observe: yin {tuple(yin.shape)} does not belong to this configuration")
+        with torch.cuda.device(yin.device):
+            cand_bin = _new(yin, B, T, lags, dtype=torch.int32)
+            cand_prob = _new(yin, B, T, lags, dtype=torch.float64)
+            count = _new(yin, B, T, dtype=torch.int32)
+            voiced_prob = _new(yin, B, T, dtype=torch.float64)
+            check(_lib.lib().nws_pyin_observe(ptr(yin), B, T, *cfg, ptr(table), ptr(cand_bin), ptr(cand_prob), ptr(count),
+                                              ptr(voiced_prob), _stream(yin.device)), "nws_pyin_observe")
+        return cand_bin, cand_prob, count, voiced_prob
+
+    def pyin_viterbi(self, cand_bin, cand_prob, count, voiced_prob, table, sample_rate, fmin, fmax, frame_length, hop,
+                     fill_unvoiced, fill_value):
+        cfg = (sample_rate, fmin, fmax, frame_length, hop)
+        B, T, lags = cand_bin.shape
+        if lags != _pyin_dims(cfg, table)[2] or cand_prob.shape != cand_bin.shape or count.shape != (B, T) or voiced_prob.shape != (B, T):
+            raise RuntimeError("pyin_viterbi: observation tensors disagree on (B, T, lags)")
+        L = _lib.lib()
+        with torch.cuda.device(cand_bin.device):
+            nbytes = L.nws_pyin_workspace_bytes(B, (T - 1) * hop + 1, *cfg)
+            ws = _new(cand_bin, nbytes, dtype=torch.uint8)
+            states = _new(cand_bin, B, T, dtype=torch.int32)
+            f0 = _new(cand_bin, B, T)
+            check(L.nws_pyin_viterbi(ptr(cand_bin), ptr(cand_prob), ptr(count), ptr(voiced_prob), B, T, *cfg, ptr(table),
+                                     1 if fill_unvoiced else 0, fill_value, ptr(states), ptr(f0), ptr(ws), nbytes,
+                                     _stream(cand_bin.device)), "nws_pyin_viterbi")
+        return states, f0
+
+    def pyin(self, audio, table, sample_rate, fmin, fmax, frame_length, hop, fill_unvoiced, fill_value):
+        cfg = (sample_rate, fmin, fmax, frame_length, hop)
+        B, N = audio.shape
+        _pyin_dims(cfg, table)
+        L = _lib.lib()
+        with torch.cuda.device(audio.device):
+            nbytes = L.nws_pyin_workspace_bytes(B, N, *cfg)
+            if nbytes == 0:
+                raise RuntimeError("pyin: unsupported size")
+            T = L.nws_pyin_frames(N, hop)
+            ws = _new(audio, nbytes, dtype=torch.uint8)
+            f0 = _new(audio, B, T)
+            voiced_prob = _new(audio, B, T, dtype=torch.float64)
+            states = _new(audio, B, T, dtype=torch.int32)
+            check(L.nws_pyin(ptr(audio), B, N, *cfg, ptr(table), 1 if fill_unvoiced else 0, fill_value, ptr(f0), ptr(voiced_prob),
+                             ptr(states), ptr(ws), nbytes, _stream(audio.device)), "nws_pyin")
+        return f0, voiced_prob, states
 
     # ---- runtime-size path (csrc/generic.hip) ----------------------------------------------------------------------------
     def forward_generic(self, gdesc, f0, control, phase_u, rand_phase, noise, plan, reverb_tables, reverb_spectrum,

@@ -87,6 +87,8 @@ class NwsGenericModel(C.Structure):
                 ("shaper", NwsShaperDesc)]
 
 
+_PYIN_CFG = (C.c_double, C.c_double, C.c_double, C.c_int, C.c_int)     # sample_rate, fmin, fmax, frame_length, hop
+
 _PROTOTYPES = {
     "nws_abi_version": (C.c_int, []),
     "nws_sizeof": (C.c_size_t, [C.c_int]),
@@ -149,6 +151,16 @@ _PROTOTYPES = {
     "nws_loudness_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "nws_loudness": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_float, C.c_float, C.c_int, _fp, _fp,
                                C.c_size_t, _fp]),
+    "nws_pyin_frames": (C.c_int, [C.c_int, C.c_int]),
+    "nws_pyin_dims": (C.c_int, [*_PYIN_CFG, C.POINTER(C.c_int32)]),
+    "nws_pyin_table_bytes": (C.c_size_t, [*_PYIN_CFG]),
+    "nws_pyin_table": (C.c_int, [*_PYIN_CFG, C.c_void_p]),          # a HOST buffer of doubles
+    "nws_pyin_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, *_PYIN_CFG]),
+    "nws_pyin_cmnd": (C.c_int, [_fp, C.c_int, C.c_int, *_PYIN_CFG, _fp, _fp]),
+    "nws_pyin_observe": (C.c_int, [_fp, C.c_int, C.c_int, *_PYIN_CFG, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "nws_pyin_viterbi": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, *_PYIN_CFG, _fp, C.c_int, C.c_float, _fp, _fp, _fp,
+                                   C.c_size_t, _fp]),
+    "nws_pyin": (C.c_int, [_fp, C.c_int, C.c_int, *_PYIN_CFG, _fp, C.c_int, C.c_float, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
     "nws_oscillator": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_float, _fp, _fp]),
     "nws_newt_apply": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "nws_td_mlp": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),

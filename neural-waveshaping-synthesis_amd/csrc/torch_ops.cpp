@@ -597,6 +597,118 @@ Tensor loudness(const Tensor& audio, const Tensor& dft, int64_t n_fft, int64_t h
   return out;
 }
 
+// ---- pYIN F0 extractor (csrc/pyin.hip; data/utils/f0_extraction.py:61-92) ------------------------------------------------
+struct PyinCfg {
+  double sr, fmin, fmax;
+  int fl, hop;
+  int32_t dims[8];   // min_period, max_period, lags, n_bps, n_pitch_bins, window, W, shared blocks
+  PyinCfg(double sample_rate, double fmin_, double fmax_, int64_t frame_length, int64_t hop_)
+      : sr(sample_rate), fmin(fmin_), fmax(fmax_), fl((int)frame_length), hop((int)hop_) {
+    TORCH_CHECK(nws_pyin_dims(sr, fmin, fmax, fl, hop, dims) == NWS_OK, "pyin: unsupported configuration (sample_rate ", sr,
+                ", fmin ", fmin, ", fmax ", fmax, ", frame_length ", fl, ", hop ", hop,
+                "): at most 512 lags (frame_length <= 1024), 1024 pitch bins and a transition window of 127; hop <= frame_length");
+  }
+  int lags() const { return dims[2]; }
+  void check_table(const Tensor& table) const {
+    check_dev(table, "table", at::kDouble);
+    TORCH_CHECK((size_t)table.numel() * sizeof(double) == nws_pyin_table_bytes(sr, fmin, fmax, fl, hop),
+                "pyin: table does not belong to this configuration");
+  }
+};
+
+Tensor pyin_table(double sample_rate, double fmin, double fmax, int64_t frame_length, int64_t hop) {
+  PyinCfg c(sample_rate, fmin, fmax, frame_length, hop);
+  Tensor t = at::empty({(int64_t)(nws_pyin_table_bytes(c.sr, c.fmin, c.fmax, c.fl, c.hop) / sizeof(double))},
+                       at::TensorOptions().dtype(at::kDouble));
+  nws_check(nws_pyin_table(c.sr, c.fmin, c.fmax, c.fl, c.hop, t.data_ptr<double>()), "nws_pyin_table");
+  return t;
+}
+
+Tensor pyin_cmnd(const Tensor& audio, double sample_rate, double fmin, double fmax, int64_t frame_length, int64_t hop) {
+  check_dev(audio, "audio");
+  TORCH_CHECK(audio.dim() == 2, "pyin_cmnd: expected (B, N), got ", audio.sizes());
+  PyinCfg c(sample_rate, fmin, fmax, frame_length, hop);
+  const int64_t B = audio.size(0), N = audio.size(1);
+  Launch L(audio);
+  Tensor yin = at::empty({B, nws_pyin_frames((int)N, c.hop), c.lags()}, audio.options());
+  nws_check(nws_pyin_cmnd(audio.data_ptr<float>(), (int)B, (int)N, c.sr, c.fmin, c.fmax, c.fl, c.hop, yin.data_ptr<float>(), L.stream),
+            "nws_pyin_cmnd");
+  return yin;
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> pyin_observe(const Tensor& yin, const Tensor& table, double sample_rate, double fmin,
+                                                        double fmax, int64_t frame_length, int64_t hop) {
+  check_dev(yin, "yin");
+  PyinCfg c(sample_rate, fmin, fmax, frame_length, hop);
+  c.check_table(table);
+  check_same_device(yin, "yin", table, "table");
+  TORCH_CHECK(yin.dim() == 3 && yin.size(2) == c.lags(), "pyin_observe: expected (B, T, ", c.lags(), "), got ", yin.sizes());
+  const int64_t B = yin.size(0), T = yin.size(1);
+  Launch L(yin);
+  Tensor cand_bin = at::empty({B, T, c.lags()}, yin.options().dtype(at::kInt));
+  Tensor cand_prob = at::empty({B, T, c.lags()}, yin.options().dtype(at::kDouble));
+  Tensor count = at::empty({B, T}, yin.options().dtype(at::kInt));
+  Tensor voiced_prob = at::empty({B, T}, yin.options().dtype(at::kDouble));
+  nws_check(nws_pyin_observe(yin.data_ptr<float>(), (int)B, (int)T, c.sr, c.fmin, c.fmax, c.fl, c.hop, table.data_ptr<double>(),
+                             cand_bin.data_ptr<int32_t>(), cand_prob.data_ptr<double>(), count.data_ptr<int32_t>(),
+                             voiced_prob.data_ptr<double>(), L.stream), "nws_pyin_observe");
+  return {cand_bin, cand_prob, count, voiced_prob};
+}
+
+std::tuple<Tensor, Tensor> pyin_viterbi(const Tensor& cand_bin, const Tensor& cand_prob, const Tensor& count, const Tensor& voiced_prob,
+                                        const Tensor& table, double sample_rate, double fmin, double fmax, int64_t frame_length,
+                                        int64_t hop, bool fill_unvoiced, double fill_value) {
+  check_dev(cand_bin, "cand_bin", at::kInt);
+  check_dev(cand_prob, "cand_prob", at::kDouble);
+  check_dev(count, "count", at::kInt);
+  check_dev(voiced_prob, "voiced_prob", at::kDouble);
+  PyinCfg c(sample_rate, fmin, fmax, frame_length, hop);
+  c.check_table(table);
+  check_same_device(cand_bin, "cand_bin", table, "table");
+  check_same_device(cand_bin, "cand_bin", cand_prob, "cand_prob");
+  check_same_device(cand_bin, "cand_bin", count, "count");
+  check_same_device(cand_bin, "cand_bin", voiced_prob, "voiced_prob");
+  TORCH_CHECK(cand_bin.dim() == 3 && cand_bin.size(2) == c.lags(), "pyin_viterbi: cand_bin: expected (B, T, ", c.lags(), "), got ",
+              cand_bin.sizes());
+  const int64_t B = cand_bin.size(0), T = cand_bin.size(1);
+  TORCH_CHECK(cand_prob.sizes() == cand_bin.sizes() && count.dim() == 2 && count.size(0) == B && count.size(1) == T &&
+                  voiced_prob.sizes() == count.sizes(), "pyin_viterbi: observation tensors disagree on (B, T, lags)");
+  // the Viterbi part of the workspace does not depend on N beyond T: any N with 1 + N / hop = T
+  const size_t nbytes = nws_pyin_workspace_bytes((int)B, (int)((T - 1) * c.hop + 1), c.sr, c.fmin, c.fmax, c.fl, c.hop);
+  TORCH_CHECK(nbytes > 0, "pyin_viterbi: unsupported size");
+  Launch L(cand_bin);
+  Tensor ws = at::empty({(int64_t)nbytes}, cand_bin.options().dtype(at::kByte));
+  Tensor states = at::empty({B, T}, cand_bin.options());
+  Tensor f0 = at::empty({B, T}, cand_bin.options().dtype(at::kFloat));
+  nws_check(nws_pyin_viterbi(cand_bin.data_ptr<int32_t>(), cand_prob.data_ptr<double>(), count.data_ptr<int32_t>(),
+                             voiced_prob.data_ptr<double>(), (int)B, (int)T, c.sr, c.fmin, c.fmax, c.fl, c.hop,
+                             table.data_ptr<double>(), fill_unvoiced ? 1 : 0, (float)fill_value, states.data_ptr<int32_t>(),
+                             f0.data_ptr<float>(), ws.data_ptr(), nbytes, L.stream), "nws_pyin_viterbi");
+  return {states, f0};
+}
+
+std::tuple<Tensor, Tensor, Tensor> pyin(const Tensor& audio, const Tensor& table, double sample_rate, double fmin, double fmax,
+                                        int64_t frame_length, int64_t hop, bool fill_unvoiced, double fill_value) {
+  check_dev(audio, "audio");
+  TORCH_CHECK(audio.dim() == 2, "pyin: expected (B, N), got ", audio.sizes());
+  PyinCfg c(sample_rate, fmin, fmax, frame_length, hop);
+  c.check_table(table);
+  check_same_device(audio, "audio", table, "table");
+  const int64_t B = audio.size(0), N = audio.size(1);
+  const size_t nbytes = nws_pyin_workspace_bytes((int)B, (int)N, c.sr, c.fmin, c.fmax, c.fl, c.hop);
+  TORCH_CHECK(nbytes > 0, "pyin: unsupported size");
+  const int64_t T = nws_pyin_frames((int)N, c.hop);
+  Launch L(audio);
+  Tensor ws = at::empty({(int64_t)nbytes}, audio.options().dtype(at::kByte));
+  Tensor f0 = at::empty({B, T}, audio.options());
+  Tensor voiced_prob = at::empty({B, T}, audio.options().dtype(at::kDouble));
+  Tensor states = at::empty({B, T}, audio.options().dtype(at::kInt));
+  nws_check(nws_pyin(audio.data_ptr<float>(), (int)B, (int)N, c.sr, c.fmin, c.fmax, c.fl, c.hop, table.data_ptr<double>(),
+                     fill_unvoiced ? 1 : 0, (float)fill_value, f0.data_ptr<float>(), voiced_prob.data_ptr<double>(),
+                     states.data_ptr<int32_t>(), ws.data_ptr(), nbytes, L.stream), "nws_pyin");
+  return {f0, voiced_prob, states};
+}
+
 // ---- runtime-size path (csrc/generic.hip): any gin configuration of the reference --------------------------------------
 template <class T>
 const T* struct_of(const Tensor& desc, const char* name) {
@@ -967,4 +1079,12 @@ TORCH_LIBRARY(newt_hip, m) {
         "Tensor events, Tensor(b!) out, Tensor(c!)? pre_out) -> ()",
         &stream_step_slots);
   m.def("loudness(Tensor audio, Tensor dft, int n_fft, int hop, float amin, float top_db, bool normalise) -> Tensor", &loudness);
+  m.def("pyin_table(float sample_rate, float fmin, float fmax, int frame_length, int hop) -> Tensor", &pyin_table);
+  m.def("pyin_cmnd(Tensor audio, float sample_rate, float fmin, float fmax, int frame_length, int hop) -> Tensor", &pyin_cmnd);
+  m.def("pyin_observe(Tensor yin, Tensor table, float sample_rate, float fmin, float fmax, int frame_length, int hop) -> "
+        "(Tensor, Tensor, Tensor, Tensor)", &pyin_observe);
+  m.def("pyin_viterbi(Tensor cand_bin, Tensor cand_prob, Tensor count, Tensor voiced_prob, Tensor table, float sample_rate, "
+        "float fmin, float fmax, int frame_length, int hop, bool fill_unvoiced, float fill_value) -> (Tensor, Tensor)", &pyin_viterbi);
+  m.def("pyin(Tensor audio, Tensor table, float sample_rate, float fmin, float fmax, int frame_length, int hop, bool fill_unvoiced, "
+        "float fill_value) -> (Tensor, Tensor, Tensor)", &pyin);
 }

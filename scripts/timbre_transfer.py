@@ -1,0 +1,85 @@
+#!/usr/bin/env python
+"""Timbre transfer of one recording on MI355X: wav -> pYIN F0 + perceptual loudness (the two analysis kernels) -> control
+features normalised with the checkpoint's statistics -> the model -> wav.  The chain of the reference's
+data/utils/preprocess_audio.py followed by its inference notebook, on the GPU end to end.
+
+    python scripts/timbre_transfer.py in.wav out.wav --model-checkpoint ckpt [--normalisation-dir dir] [--use-fastnewt]
+
+The wav must already be at the model's sample rate (there is no resampler here) and mono.
+"""
+import importlib
+import os
+import sys
+
+import click
+import numpy as np
+import torch
+from scipy.io import wavfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def read_mono(path, sample_rate):
+    sr, x = wavfile.read(path)
+    if sr != sample_rate:
+        raise click.BadParameter(f"{path} is at {sr} Hz, the model at {sample_rate} Hz: resample it first (no resampler here)")
+    if x.ndim != 1:
+        raise click.BadParameter(f"{path} has {x.shape[1]} channels: expected a mono file")
+    if x.dtype == np.uint8:
+        x = (x.astype(np.float64) - 128.0) / 128.0
+    elif np.issubdtype(x.dtype, np.integer):
+        x = x.astype(np.float64) / (float(np.iinfo(x.dtype).max) + 1.0)
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def normalisation(ck, checkpoint, directory):
+    directory = directory or os.path.dirname(os.path.abspath(checkpoint))
+    if os.path.exists(os.path.join(directory, "data_mean.npy")):
+        return ck.load_normalisation(directory)
+    if str(checkpoint).endswith(".npz"):
+        z = np.load(checkpoint)
+        if "__data_mean__" in z.files:
+            return z["__data_mean__"].astype(np.float64).reshape(-1), z["__data_std__"].astype(np.float64).reshape(-1)
+    raise click.BadParameter(f"no data_mean.npy / data_std.npy in {directory}: pass --normalisation-dir")
+
+
+@click.command()
+@click.argument("input_wav", type=click.Path(exists=True))
+@click.argument("output_wav", type=click.Path())
+@click.option("--model-gin", default=None)
+@click.option("--model-checkpoint", default=os.path.join(ROOT, "tests", "golden", "weights_vn.npz"), show_default=True)
+@click.option("--normalisation-dir", default=None, help="directory of data_mean.npy / data_std.npy (default: the checkpoint's)")
+@click.option("--use-fastnewt", is_flag=True)
+@click.option("--octave-shift", default=0, type=int, help="transpose the extracted F0 by whole octaves")
+def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, use_fastnewt, octave_shift):
+    nws = importlib.import_module("neural-waveshaping-synthesis_amd")
+    ck = importlib.import_module("neural-waveshaping-synthesis_amd.checkpoint")
+    f0x = importlib.import_module("neural-waveshaping-synthesis_amd.data.utils.f0_extraction")
+    ldx = importlib.import_module("neural-waveshaping-synthesis_amd.data.utils.loudness_extraction")
+    if model_gin:
+        nws.gin.parse_config_file(model_gin)
+    else:
+        nws.ensure_default_config()
+    model = nws.NeuralWaveshaping.load_from_checkpoint(model_checkpoint).eval()
+    if use_fastnewt:
+        model.newt = nws.FastNEWT(model.newt)
+    model = model.cuda()
+    sr, hop = int(model.sample_rate), int(model.control_hop)
+    mean, std = normalisation(ck, model_checkpoint, normalisation_dir)
+    audio = read_mono(input_wav, sr)
+    # frame-rate features, one frame per control hop: T = 1 + N // hop for both
+    f0, voiced_prob = f0x.extract_f0_with_pyin(audio, sr, frame_length=1024, hop_length=hop, interpolate_fn=None)
+    loudness = ldx.extract_perceptual_loudness(audio, sr, n_fft=1024, hop_length=hop, interpolate_fn=None)
+    f0 = f0 * 2.0 ** octave_shift
+    f0_t, control = ck.make_control(f0, loudness, mean, std)
+    with torch.no_grad():
+        out = model(f0_t.unsqueeze(0).cuda(), control.unsqueeze(0).cuda())
+    y = out[0, :audio.size].cpu().numpy().astype(np.float32)
+    wavfile.write(output_wav, sr, y)
+    print(f"{input_wav}: {audio.size} samples, {f0.size} frames, {100.0 * float(np.mean(voiced_prob > 0.5)):.0f} % voiced, "
+          f"median F0 {float(np.median(f0)):.1f} Hz -> {output_wav}")
+
+
+if __name__ == "__main__":
+    main()
