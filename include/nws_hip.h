@@ -16,6 +16,9 @@
  *     reference ships): 101 harmonics, 64 waveshapers, hidden/embedding 128, shaper MLP width 8
  *     depth 4, control hop 128, FIR length 256.  Other sizes return NWS_ERR_UNSUPPORTED.
  *   - B = batch, T = control frames, N = 128*T samples.
+ *   - the analysis front end in front of the forward path (data/utils/ of the reference) takes audio (B, N) of any
+ *     length: nws_resample (any integer sample rate to any other), nws_loudness, nws_pyin.  Their constant operands
+ *     (weight bank, DFT matrix, fp64 table) are built once per configuration by the entry points beside them.
  */
 #ifndef NWS_HIP_H
 #define NWS_HIP_H
@@ -474,6 +477,27 @@ int nws_pyin_viterbi(const int* cand_bin, const double* cand_prob, const int* co
 int nws_pyin(const float* audio, int B, int N, double sample_rate, double fmin, double fmax, int frame_length, int hop,
              const double* table, int fill_unvoiced, float fill_value, float* f0, double* voiced_prob, int* states,
              void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Band-limited sample-rate converter, the step in front of the two analysis features:
+ * neural_waveshaping_synthesis/data/utils/preprocess_audio.py:65-66 (resample_audio -> resampy.resample, filter kaiser_best).
+ * DESIGN.md 3.10 is the definition (resampy 0.2.2's interpolation with n_out = (N L) / M in integers and the exact rational
+ * position t M / L of output t); parity with resampy is unpinned.  Rates are integers; L = sr_out / gcd, M = sr_in / gcd.
+ * nws_resample_dims gives dims[6] = {L, M, taps, left, right, window step}: an output is `taps` = left + right weights
+ * against x[n - left + 1 .. n + right], zero outside the row.
+ * Limits (NWS_ERR_UNSUPPORTED, 0 bytes / 0 samples): rates below 1, a bank above 64 MB (every pair of the standard rates
+ * 8000 .. 192000 Hz stays below 1.3 MB), more than 2^31 - 1 outputs a row.  N < 1, B < 1, n_out < 1, NULL: NWS_ERR_BAD_ARG.
+ *   nws_resample_length  n_out = (N L) / M of a row of N samples, in 64-bit arithmetic (0: unsupported rates or N < 1).
+ *   nws_resample_bank    fills a HOST buffer of nws_resample_bank_bytes with the L rows of `taps` weights, row-major by the
+ *                        phase numerator r = (t M) mod L, computed in fp64 and rounded once to fp32; column c weighs
+ *                        x[n + c - (left - 1)], unused columns are 0.  Copy it to the device once.
+ *   nws_resample         x (B, N) -> y (B, n_out) with the device copy of that bank.  A row's result does not depend on B.
+ */
+int nws_resample_dims(int sr_in, int sr_out, int32_t* dims);
+int64_t nws_resample_length(int64_t N, int sr_in, int sr_out);
+size_t nws_resample_bank_bytes(int sr_in, int sr_out);
+int nws_resample_bank(int sr_in, int sr_out, float* bank_host);
+int nws_resample(const float* x, int B, int N, int sr_in, int sr_out, const float* bank_dev, float* y, void* stream);
 
 /*
  * ---- Runtime-size path (csrc/generic.hip): every gin-configurable size of the reference ------------------------------

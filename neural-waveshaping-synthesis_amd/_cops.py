@@ -67,6 +67,15 @@ def _pyin_dims(cfg, table=None):
     return (*dims, n)
 
 
+def _resample_dims(sr_in, sr_out):
+    """nws_resample_dims of a pair of rates: (L, M, taps, left, right, step)"""
+    dims = (C.c_int32 * 6)()
+    if not (1 <= sr_in < 2 ** 31 and 1 <= sr_out < 2 ** 31) or _lib.lib().nws_resample_dims(sr_in, sr_out, dims) != 0:
+        raise RuntimeError(f"resample: unsupported rates {sr_in} -> {sr_out}: integers >= 1 whose weight bank (sr_out / gcd rows) "
+                           "stays below 64 MB")
+    return tuple(dims)
+
+
 class CtypesOps:
     def abi_version(self):
         return int(_lib.lib().nws_abi_version())
@@ -353,6 +362,27 @@ class CtypesOps:
             check(L.nws_pyin(ptr(audio), B, N, *cfg, ptr(table), 1 if fill_unvoiced else 0, fill_value, ptr(f0), ptr(voiced_prob),
                              ptr(states), ptr(ws), nbytes, _stream(audio.device)), "nws_pyin")
         return f0, voiced_prob, states
+
+    # ---- sample-rate converter (csrc/resample.hip) ------------------------------------------------------------------------
+    def resample_bank(self, sr_in, sr_out):
+        L, _, taps = _resample_dims(sr_in, sr_out)[:3]
+        bank = torch.empty(L, taps, dtype=torch.float32)
+        check(_lib.lib().nws_resample_bank(sr_in, sr_out, bank.data_ptr()), "nws_resample_bank")
+        return bank
+
+    def resample(self, audio, bank, sr_in, sr_out):
+        L, _, taps = _resample_dims(sr_in, sr_out)[:3]
+        if not bank.is_cuda or bank.dtype != torch.float32 or tuple(bank.shape) != (L, taps) or bank.device != audio.device:
+            raise RuntimeError(f"resample: bank does not belong to these rates (expected a ({L}, {taps}) float32 tensor on the "
+                               f"audio's device, got {tuple(bank.shape)} {bank.dtype} on {bank.device})")
+        B, N = audio.shape
+        n_out = _lib.lib().nws_resample_length(N, sr_in, sr_out)
+        if n_out < 1 or B < 1:
+            raise RuntimeError(f"resample: {N} samples at {sr_in} Hz give no sample at {sr_out} Hz")
+        with torch.cuda.device(audio.device):
+            y = _new(audio, B, n_out)
+            check(_lib.lib().nws_resample(ptr(audio), B, N, sr_in, sr_out, ptr(bank), ptr(y), _stream(audio.device)), "nws_resample")
+        return y
 
     # ---- runtime-size path (csrc/generic.hip) ----------------------------------------------------------------------------
     def forward_generic(self, gdesc, f0, control, phase_u, rand_phase, noise, plan, reverb_tables, reverb_spectrum,

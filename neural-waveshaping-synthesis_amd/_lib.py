@@ -161,6 +161,11 @@ _PROTOTYPES = {
     "nws_pyin_viterbi": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, *_PYIN_CFG, _fp, C.c_int, C.c_float, _fp, _fp, _fp,
                                    C.c_size_t, _fp]),
     "nws_pyin": (C.c_int, [_fp, C.c_int, C.c_int, *_PYIN_CFG, _fp, C.c_int, C.c_float, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "nws_resample_dims": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "nws_resample_length": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "nws_resample_bank_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "nws_resample_bank": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),          # a HOST buffer of floats
+    "nws_resample": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
     "nws_oscillator": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_float, _fp, _fp]),
     "nws_newt_apply": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "nws_td_mlp": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),

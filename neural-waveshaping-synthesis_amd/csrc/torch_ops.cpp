@@ -709,6 +709,43 @@ std::tuple<Tensor, Tensor, Tensor> pyin(const Tensor& audio, const Tensor& table
   return {f0, voiced_prob, states};
 }
 
+
+// ---- sample-rate converter (csrc/resample.hip; data/utils/preprocess_audio.py:65-66) ---------------------------------------
+struct ResampleCfg {
+  int sr_in, sr_out;
+  int32_t dims[6];   // L, M, taps, left, right, step
+  ResampleCfg(int64_t sr_in_, int64_t sr_out_) : sr_in((int)sr_in_), sr_out((int)sr_out_) {
+    TORCH_CHECK(sr_in_ >= 1 && sr_out_ >= 1 && sr_in_ <= INT32_MAX && sr_out_ <= INT32_MAX &&
+                    nws_resample_dims(sr_in, sr_out, dims) == NWS_OK,
+                "resample: unsupported rates ", sr_in_, " -> ", sr_out_, ": integers >= 1 whose weight bank (sr_out / gcd rows) stays "
+                "below 64 MB");
+  }
+};
+
+Tensor resample_bank(int64_t sr_in, int64_t sr_out) {
+  ResampleCfg c(sr_in, sr_out);
+  Tensor bank = at::empty({(int64_t)c.dims[0], (int64_t)c.dims[2]}, at::TensorOptions().dtype(at::kFloat));
+  nws_check(nws_resample_bank(c.sr_in, c.sr_out, bank.data_ptr<float>()), "nws_resample_bank");
+  return bank;
+}
+
+Tensor resample(const Tensor& audio, const Tensor& bank, int64_t sr_in, int64_t sr_out) {
+  check_dev(audio, "audio");
+  check_dev(bank, "bank");
+  check_same_device(audio, "audio", bank, "bank");
+  ResampleCfg c(sr_in, sr_out);
+  TORCH_CHECK(audio.dim() == 2 && audio.size(0) >= 1 && audio.size(1) <= INT32_MAX, "resample: expected (B, N), got ", audio.sizes());
+  TORCH_CHECK(bank.dim() == 2 && bank.size(0) == c.dims[0] && bank.size(1) == c.dims[2],
+              "resample: bank does not belong to these rates (expected (", c.dims[0], ", ", c.dims[2], "), got ", bank.sizes(), ")");
+  const int64_t B = audio.size(0), N = audio.size(1), n_out = nws_resample_length(N, c.sr_in, c.sr_out);
+  TORCH_CHECK(n_out >= 1 && B <= INT32_MAX, "resample: ", N, " samples at ", sr_in, " Hz give no sample at ", sr_out, " Hz");
+  Launch L(audio);
+  Tensor y = at::empty({B, n_out}, audio.options());
+  nws_check(nws_resample(audio.data_ptr<float>(), (int)B, (int)N, c.sr_in, c.sr_out, bank.data_ptr<float>(), y.data_ptr<float>(),
+                         L.stream), "nws_resample");
+  return y;
+}
+
 // ---- runtime-size path (csrc/generic.hip): any gin configuration of the reference --------------------------------------
 template <class T>
 const T* struct_of(const Tensor& desc, const char* name) {
@@ -1087,4 +1124,6 @@ TORCH_LIBRARY(newt_hip, m) {
         "float fmin, float fmax, int frame_length, int hop, bool fill_unvoiced, float fill_value) -> (Tensor, Tensor)", &pyin_viterbi);
   m.def("pyin(Tensor audio, Tensor table, float sample_rate, float fmin, float fmax, int frame_length, int hop, bool fill_unvoiced, "
         "float fill_value) -> (Tensor, Tensor, Tensor)", &pyin);
+  m.def("resample_bank(int sr_in, int sr_out) -> Tensor", &resample_bank);
+  m.def("resample(Tensor audio, Tensor bank, int sr_in, int sr_out) -> Tensor", &resample);
 }

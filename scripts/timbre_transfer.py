@@ -4,8 +4,11 @@ features normalised with the checkpoint's statistics -> the model -> wav.  The c
 data/utils/preprocess_audio.py followed by its inference notebook, on the GPU end to end.
 
     python scripts/timbre_transfer.py in.wav out.wav --model-checkpoint ckpt [--normalisation-dir dir] [--use-fastnewt]
+                                      [--resample] [--output-rate R]
 
-The wav must already be at the model's sample rate (there is no resampler here) and mono.
+Without --resample the wav must already be at the model's sample rate and mono.  With it the file may be at any rate and
+stereo: the left channel is kept and converted to the model's rate on the GPU (csrc/resample.hip), and the output has the
+converted length.  --output-rate converts the model's output to another rate with the same kernel.
 """
 import importlib
 import os
@@ -23,7 +26,7 @@ sys.path.insert(0, ROOT)
 def read_mono(path, sample_rate):
     sr, x = wavfile.read(path)
     if sr != sample_rate:
-        raise click.BadParameter(f"{path} is at {sr} Hz, the model at {sample_rate} Hz: resample it first (no resampler here)")
+        raise click.BadParameter(f"{path} is at {sr} Hz, the model at {sample_rate} Hz: pass --resample, or resample it first")
     if x.ndim != 1:
         raise click.BadParameter(f"{path} has {x.shape[1]} channels: expected a mono file")
     if x.dtype == np.uint8:
@@ -31,6 +34,17 @@ def read_mono(path, sample_rate):
     elif np.issubdtype(x.dtype, np.integer):
         x = x.astype(np.float64) / (float(np.iinfo(x.dtype).max) + 1.0)
     return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def read_any(path, sample_rate, pre):
+    """--resample: the reference's front end (preprocess_audio.py:109-117): float32, mono (left channel), the model's rate"""
+    sr, x = wavfile.read(path)
+    if x.dtype == np.uint8:
+        x = (x.astype(np.float32) - 128.0) / 128.0
+    elif x.dtype == np.float64:
+        x = x.astype(np.float32)
+    x = np.ascontiguousarray(pre.make_monophonic(pre.convert_to_float32_audio(x)))
+    return x if sr == sample_rate else pre.resample_audio(x, sr, sample_rate)
 
 
 def normalisation(ck, checkpoint, directory):
@@ -52,11 +66,14 @@ def normalisation(ck, checkpoint, directory):
 @click.option("--normalisation-dir", default=None, help="directory of data_mean.npy / data_std.npy (default: the checkpoint's)")
 @click.option("--use-fastnewt", is_flag=True)
 @click.option("--octave-shift", default=0, type=int, help="transpose the extracted F0 by whole octaves")
-def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, use_fastnewt, octave_shift):
+@click.option("--resample", is_flag=True, help="accept any sample rate and stereo: keep the left channel, convert to the model's rate")
+@click.option("--output-rate", default=None, type=int, help="convert the model's output to this sample rate")
+def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, use_fastnewt, octave_shift, resample, output_rate):
     nws = importlib.import_module("neural-waveshaping-synthesis_amd")
     ck = importlib.import_module("neural-waveshaping-synthesis_amd.checkpoint")
     f0x = importlib.import_module("neural-waveshaping-synthesis_amd.data.utils.f0_extraction")
     ldx = importlib.import_module("neural-waveshaping-synthesis_amd.data.utils.loudness_extraction")
+    pre = importlib.import_module("neural-waveshaping-synthesis_amd.data.utils.preprocess_audio")
     if model_gin:
         nws.gin.parse_config_file(model_gin)
     else:
@@ -67,7 +84,7 @@ def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, 
     model = model.cuda()
     sr, hop = int(model.sample_rate), int(model.control_hop)
     mean, std = normalisation(ck, model_checkpoint, normalisation_dir)
-    audio = read_mono(input_wav, sr)
+    audio = read_any(input_wav, sr, pre) if resample else read_mono(input_wav, sr)
     # frame-rate features, one frame per control hop: T = 1 + N // hop for both
     f0, voiced_prob = f0x.extract_f0_with_pyin(audio, sr, frame_length=1024, hop_length=hop, interpolate_fn=None)
     loudness = ldx.extract_perceptual_loudness(audio, sr, n_fft=1024, hop_length=hop, interpolate_fn=None)
@@ -76,6 +93,8 @@ def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, 
     with torch.no_grad():
         out = model(f0_t.unsqueeze(0).cuda(), control.unsqueeze(0).cuda())
     y = out[0, :audio.size].cpu().numpy().astype(np.float32)
+    if output_rate is not None and output_rate != sr:
+        y, sr = pre.resample_audio(y, sr, output_rate), output_rate
     wavfile.write(output_wav, sr, y)
     print(f"{input_wav}: {audio.size} samples, {f0.size} frames, {100.0 * float(np.mean(voiced_prob > 0.5)):.0f} % voiced, "
           f"median F0 {float(np.median(f0)):.1f} Hz -> {output_wav}")
