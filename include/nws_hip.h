@@ -17,8 +17,9 @@
  *     depth 4, control hop 128, FIR length 256.  Other sizes return NWS_ERR_UNSUPPORTED.
  *   - B = batch, T = control frames, N = 128*T samples.
  *   - the analysis front end in front of the forward path (data/utils/ of the reference) takes audio (B, N) of any
- *     length: nws_resample (any integer sample rate to any other), nws_loudness, nws_pyin.  Their constant operands
- *     (weight bank, DFT matrix, fp64 table) are built once per configuration by the entry points beside them.
+ *     length: nws_resample (any integer sample rate to any other), nws_loudness, nws_pyin, nws_mfcc.  Their constant
+ *     operands (weight bank, DFT matrix, fp64 table, filter table) are built once per configuration by the entry points
+ *     beside them.
  */
 #ifndef NWS_HIP_H
 #define NWS_HIP_H
@@ -498,6 +499,30 @@ int64_t nws_resample_length(int64_t N, int sr_in, int sr_out);
 size_t nws_resample_bank_bytes(int sr_in, int sr_out);
 int nws_resample_bank(int sr_in, int sr_out, float* bank_host);
 int nws_resample(const float* x, int B, int N, int sr_in, int sr_out, const float* bank_dev, float* y, void* stream);
+
+/*
+ * MFCC feature, the remaining analysis feature of the reference's control files:
+ * neural_waveshaping_synthesis/data/utils/mfcc_extraction.py:7-13 (extract_mfcc -> librosa.feature.mfcc with librosa 0.8.0's
+ * defaults) = power STFT (the loudness feature's: periodic hann, centre / reflect padding, T = 1 + N / hop frames), Slaney mel
+ * filter bank (fmin 0, fmax sample_rate / 2, Slaney norm), power_to_db (ref 1, amin 1e-10, top_db 80 against the maximum of the
+ * whole utterance), orthonormal DCT-II over the mel axis, first n_mfcc rows.  DESIGN.md 3.11 is the definition; parity with
+ * librosa is unpinned.  audio (B, N) fp32 -> out (B, n_mfcc, T).  An empty filter (low sample_rate, many bands) is amin.
+ * A configuration is (sample_rate, n_fft, n_mfcc, n_mels); nws_mfcc_dims gives dims[8] = {bins, n_mels, n_mfcc, n_mfcc
+ * rounded up to 16 (jpad), non-zero filter weights (nnz), word offset of the weights, word offset of the DCT rows, words}.
+ * Limits (NWS_ERR_UNSUPPORTED, 0 bytes): n_fft and hop as nws_loudness, 1 <= n_mfcc <= n_mels <= 1024, sample_rate > 0,
+ * B <= 65535.  NULL, B < 1, N <= n_fft / 2: NWS_ERR_BAD_ARG, nothing launched.
+ *   nws_mfcc_table  fills a HOST buffer of nws_mfcc_table_bytes, built in fp64 and rounded once to fp32; 4-byte words:
+ *                   n_mels int32 triplets (first bin, count, offset into the weights) | nnz fp32 weights, span after span |
+ *                   DCT entries (n_mels, jpad) fp32, column j scaled by s_j, zero from n_mfcc on.  Copy it to the device once.
+ *   nws_mfcc        the three passes on one stream; `dft` is nws_loudness_dft_matrix of n_fft, `table` the device copy of the
+ *                   table.  Workspace: nws_mfcc_workspace_bytes.  A row's result does not depend on B.
+ */
+int nws_mfcc_dims(double sample_rate, int n_fft, int n_mfcc, int n_mels, int32_t* dims);
+size_t nws_mfcc_table_bytes(double sample_rate, int n_fft, int n_mfcc, int n_mels);
+int nws_mfcc_table(double sample_rate, int n_fft, int n_mfcc, int n_mels, float* table_host);
+size_t nws_mfcc_workspace_bytes(int B, int N, int n_fft, int hop, int n_mels);
+int nws_mfcc(const float* audio, int B, int N, double sample_rate, int n_fft, int hop, int n_mfcc, int n_mels, const float* dft,
+             const float* table, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * ---- Runtime-size path (csrc/generic.hip): every gin-configurable size of the reference ------------------------------

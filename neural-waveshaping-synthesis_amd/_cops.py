@@ -76,6 +76,16 @@ def _resample_dims(sr_in, sr_out):
     return tuple(dims)
 
 
+def _mfcc_dims(sample_rate, n_fft, n_mfcc, n_mels):
+    """nws_mfcc_dims of a configuration: (bins, n_mels, n_mfcc, jpad, nnz, off_w, off_dct, words)"""
+    dims = (C.c_int32 * 8)()
+    ok = all(0 <= v < 2 ** 31 for v in (n_fft, n_mfcc, n_mels))
+    if not ok or _lib.lib().nws_mfcc_dims(sample_rate, n_fft, n_mfcc, n_mels, dims) != 0:
+        raise RuntimeError(f"mfcc: unsupported configuration (sample_rate {sample_rate}, n_fft {n_fft}, n_mfcc {n_mfcc}, n_mels "
+                           f"{n_mels}): sample_rate > 0, n_fft a power of two in [64, 2048], 1 <= n_mfcc <= n_mels <= 1024")
+    return tuple(dims)
+
+
 class CtypesOps:
     def abi_version(self):
         return int(_lib.lib().nws_abi_version())
@@ -383,6 +393,36 @@ class CtypesOps:
             y = _new(audio, B, n_out)
             check(_lib.lib().nws_resample(ptr(audio), B, N, sr_in, sr_out, ptr(bank), ptr(y), _stream(audio.device)), "nws_resample")
         return y
+
+    # ---- MFCC feature (csrc/mfcc.hip) --------------------------------------------------------------------------------------
+    def mfcc_table(self, sample_rate, n_fft, n_mfcc, n_mels):
+        words = _mfcc_dims(sample_rate, n_fft, n_mfcc, n_mels)[7]
+        table = torch.empty(words, dtype=torch.float32)
+        check(_lib.lib().nws_mfcc_table(sample_rate, n_fft, n_mfcc, n_mels, table.data_ptr()), "nws_mfcc_table")
+        return table
+
+    def mfcc(self, audio, dft, table, sample_rate, n_fft, hop, n_mfcc, n_mels):
+        words = _mfcc_dims(sample_rate, n_fft, n_mfcc, n_mels)[7]
+        for name, t in (("dft", dft), ("table", table)):
+            if not t.is_cuda or t.dtype != torch.float32 or t.device != audio.device:
+                raise RuntimeError(f"mfcc: {name}: expected a float32 tensor on the audio's device, got {t.dtype} on {t.device}")
+        if table.numel() != words:
+            raise RuntimeError(f"mfcc: table does not belong to this configuration (expected {words} words of mfcc_table, got "
+                               f"{table.numel()})")
+        B, N = audio.shape
+        L = _lib.lib()
+        if dft.numel() * 4 != L.nws_loudness_dft_bytes(n_fft):
+            raise RuntimeError(f"mfcc: dft does not belong to n_fft = {n_fft}")
+        nbytes = L.nws_mfcc_workspace_bytes(B, N, n_fft, hop, n_mels) if 1 <= B <= 65535 else 0
+        if nbytes == 0 or N <= n_fft // 2:
+            raise RuntimeError(f"mfcc: unsupported size (B {B}, N {N}, n_fft {n_fft}, hop_length {hop}): 1 <= hop <= n_fft, "
+                               "31 hop + n_fft samples must fit 160 KB of LDS, N > n_fft / 2, B <= 65535")
+        with torch.cuda.device(audio.device):
+            ws = _new(audio, nbytes, dtype=torch.uint8)
+            out = _new(audio, B, n_mfcc, L.nws_loudness_frames(N, hop))
+            check(L.nws_mfcc(ptr(audio), B, N, sample_rate, n_fft, hop, n_mfcc, n_mels, ptr(dft), ptr(table), ptr(out), ptr(ws),
+                             nbytes, _stream(audio.device)), "nws_mfcc")
+        return out
 
     # ---- runtime-size path (csrc/generic.hip) ----------------------------------------------------------------------------
     def forward_generic(self, gdesc, f0, control, phase_u, rand_phase, noise, plan, reverb_tables, reverb_spectrum,

@@ -89,6 +89,8 @@ class NwsGenericModel(C.Structure):
 
 _PYIN_CFG = (C.c_double, C.c_double, C.c_double, C.c_int, C.c_int)     # sample_rate, fmin, fmax, frame_length, hop
 
+_MFCC_CFG = (C.c_double, C.c_int, C.c_int, C.c_int)                       # sample_rate, n_fft, n_mfcc, n_mels
+
 _PROTOTYPES = {
     "nws_abi_version": (C.c_int, []),
     "nws_sizeof": (C.c_size_t, [C.c_int]),
@@ -166,6 +168,12 @@ _PROTOTYPES = {
     "nws_resample_bank_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "nws_resample_bank": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),          # a HOST buffer of floats
     "nws_resample": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "nws_mfcc_dims": (C.c_int, [*_MFCC_CFG, C.POINTER(C.c_int32)]),
+    "nws_mfcc_table_bytes": (C.c_size_t, [*_MFCC_CFG]),
+    "nws_mfcc_table": (C.c_int, [*_MFCC_CFG, C.c_void_p]),          # a HOST buffer of 4-byte words
+    "nws_mfcc_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nws_mfcc": (C.c_int, [_fp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t,
+                           _fp]),
     "nws_oscillator": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_float, _fp, _fp]),
     "nws_newt_apply": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "nws_td_mlp": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),

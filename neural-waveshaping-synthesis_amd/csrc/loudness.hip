@@ -148,19 +148,12 @@ size_t nws_loudness_workspace_bytes(int B, int N, int n_fft, int hop) {
   return ((size_t)B * (n_fft / 2 + 1) * frames_pad) * sizeof(float) + (((size_t)B * sizeof(unsigned) + 255) & ~size_t(255));
 }
 
-int nws_loudness(const float* audio, int B, int N, int n_fft, int hop, const float* dft, float amin, float top_db,
-                 int normalise, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!audio || !dft || !out || !workspace || B <= 0 || !fft_ok(n_fft, hop)) return NWS_ERR_BAD_ARG;
-  if (N <= n_fft / 2) return NWS_ERR_BAD_ARG;  // reflect padding needs more than n_fft/2 samples (as in the reference)
-  if (!(amin > 0.0f) || !(top_db >= 0.0f)) return NWS_ERR_BAD_ARG;
-  if (B > 65535) return NWS_ERR_UNSUPPORTED;
-  if (workspace_bytes < nws_loudness_workspace_bytes(B, N, n_fft, hop)) return NWS_ERR_WORKSPACE;
+// The power pass alone: power (B, bins, frames_pad) and the per-utterance maximum of it as float bits (max_bits (B), zeroed
+// here).  The caller has checked the sizes (nws_loudness_workspace_bytes != 0, N > n_fft / 2).  Shared with mfcc.hip.
+int nws_stft_power_pass(const float* audio, int B, int N, int n_fft, int hop, const float* dft, float* power,
+                        unsigned* max_bits, void* stream) {
   const int frames = nws_loudness_frames(N, hop);
   const int frames_pad = (frames + 31) / 32 * 32;
-  const int bins = n_fft / 2 + 1;
-  const size_t max_bytes = ((size_t)B * sizeof(unsigned) + 255) & ~size_t(255);
-  unsigned* max_bits = static_cast<unsigned*>(workspace);
-  float* power = reinterpret_cast<float*>(static_cast<char*>(workspace) + max_bytes);
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(max_bits, 0, (size_t)B * sizeof(unsigned), st);
   if (e != hipSuccess) return (int)e;
@@ -175,6 +168,25 @@ int nws_loudness(const float* audio, int B, int N, int n_fft, int hop, const flo
   const dim3 grid(frames_pad / kFrames, (m_tiles + 3) / 4, B);
   loudness_power_kernel<<<grid, 256, lds, st>>>(audio, N, n_fft, hop, frames, frames_pad, dft, m_tiles, power, max_bits);
   NWS_CHECK_LAUNCH();
+  return NWS_OK;
+}
+
+int nws_loudness(const float* audio, int B, int N, int n_fft, int hop, const float* dft, float amin, float top_db,
+                 int normalise, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!audio || !dft || !out || !workspace || B <= 0 || !fft_ok(n_fft, hop)) return NWS_ERR_BAD_ARG;
+  if (N <= n_fft / 2) return NWS_ERR_BAD_ARG;  // reflect padding needs more than n_fft/2 samples (as in the reference)
+  if (!(amin > 0.0f) || !(top_db >= 0.0f)) return NWS_ERR_BAD_ARG;
+  if (B > 65535) return NWS_ERR_UNSUPPORTED;
+  if (workspace_bytes < nws_loudness_workspace_bytes(B, N, n_fft, hop)) return NWS_ERR_WORKSPACE;
+  const int frames = nws_loudness_frames(N, hop);
+  const int frames_pad = (frames + 31) / 32 * 32;
+  const int bins = n_fft / 2 + 1;
+  const size_t max_bytes = ((size_t)B * sizeof(unsigned) + 255) & ~size_t(255);
+  unsigned* max_bits = static_cast<unsigned*>(workspace);
+  float* power = reinterpret_cast<float*>(static_cast<char*>(workspace) + max_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = nws_stft_power_pass(audio, B, N, n_fft, hop, dft, power, max_bits, stream);
+  if (rc != NWS_OK) return rc;
   const dim3 g2((frames + 255) / 256, B);
   loudness_db_kernel<<<g2, 256, 0, st>>>(power, max_bits, bins, frames, frames_pad, amin, top_db, normalise, out);
   NWS_CHECK_LAUNCH();

@@ -500,3 +500,8 @@ extern "C" __attribute__((visibility("hidden"))) int nws_control_gru_stream(cons
 extern "C" __attribute__((visibility("hidden"))) int nws_frame_mlps_stream(const NwsWeights* w, const float* gru_out, int B, int T,
                                                                            float* film_w, float* fir_w, int out_T, int out_off,
                                                                            const NwsStreamNoiseWin* win, void* stream);
+// loudness.hip: the windowed-DFT power pass of nws_loudness alone (memset of max_bits + loudness_power_kernel), for mfcc.hip.
+// Sizes must have passed nws_loudness_workspace_bytes; N > n_fft / 2.  Internal to the library.
+extern "C" __attribute__((visibility("hidden"))) int nws_stft_power_pass(const float* audio, int B, int N, int n_fft, int hop,
+                                                                         const float* dft, float* power, unsigned* max_bits,
+                                                                         void* stream);

@@ -746,6 +746,52 @@ Tensor resample(const Tensor& audio, const Tensor& bank, int64_t sr_in, int64_t 
   return y;
 }
 
+// ---- MFCC feature (csrc/mfcc.hip; data/utils/mfcc_extraction.py:7-13) ------------------------------------------------------
+struct MfccCfg {
+  double sr;
+  int n_fft, n_mfcc, n_mels;
+  int32_t dims[8];   // bins, n_mels, n_mfcc, jpad, nnz, off_w, off_dct, words
+  MfccCfg(double sample_rate, int64_t n_fft_, int64_t n_mfcc_, int64_t n_mels_)
+      : sr(sample_rate), n_fft((int)n_fft_), n_mfcc((int)n_mfcc_), n_mels((int)n_mels_) {
+    TORCH_CHECK(n_fft_ <= INT32_MAX && n_mfcc_ <= INT32_MAX && n_mels_ <= INT32_MAX &&
+                    nws_mfcc_dims(sr, n_fft, n_mfcc, n_mels, dims) == NWS_OK,
+                "mfcc: unsupported configuration (sample_rate ", sr, ", n_fft ", n_fft_, ", n_mfcc ", n_mfcc_, ", n_mels ", n_mels_,
+                "): sample_rate > 0, n_fft a power of two in [64, 2048], 1 <= n_mfcc <= n_mels <= 1024");
+  }
+};
+
+Tensor mfcc_table(double sample_rate, int64_t n_fft, int64_t n_mfcc, int64_t n_mels) {
+  MfccCfg c(sample_rate, n_fft, n_mfcc, n_mels);
+  Tensor t = at::empty({(int64_t)c.dims[7]}, at::TensorOptions().dtype(at::kFloat));
+  nws_check(nws_mfcc_table(c.sr, c.n_fft, c.n_mfcc, c.n_mels, t.data_ptr<float>()), "nws_mfcc_table");
+  return t;
+}
+
+// extract_mfcc: audio (B, N) -> (B, n_mfcc, 1 + N / hop)
+Tensor mfcc(const Tensor& audio, const Tensor& dft, const Tensor& table, double sample_rate, int64_t n_fft, int64_t hop,
+            int64_t n_mfcc, int64_t n_mels) {
+  check_dev(audio, "audio");
+  check_dev(dft, "dft");
+  check_dev(table, "table");
+  check_same_device(audio, "audio", dft, "dft");
+  check_same_device(audio, "audio", table, "table");
+  MfccCfg c(sample_rate, n_fft, n_mfcc, n_mels);
+  TORCH_CHECK(audio.dim() == 2 && audio.size(0) >= 1 && audio.size(1) <= INT32_MAX, "mfcc: expected (B, N), got ", audio.sizes());
+  const int64_t B = audio.size(0), N = audio.size(1);
+  TORCH_CHECK(table.numel() == c.dims[7], "mfcc: table does not belong to this configuration (expected ", c.dims[7],
+              " words of mfcc_table, got ", table.numel(), ")");
+  TORCH_CHECK((size_t)dft.numel() * sizeof(float) == nws_loudness_dft_bytes(c.n_fft), "mfcc: dft does not belong to n_fft = ", n_fft);
+  const size_t nbytes = B <= 65535 && hop <= INT32_MAX ? nws_mfcc_workspace_bytes((int)B, (int)N, c.n_fft, (int)hop, c.n_mels) : 0;
+  TORCH_CHECK(nbytes > 0 && N > c.n_fft / 2, "mfcc: unsupported size (B ", B, ", N ", N, ", n_fft ", n_fft, ", hop_length ", hop,
+              "): 1 <= hop <= n_fft, 31 hop + n_fft samples must fit 160 KB of LDS, N > n_fft / 2, B <= 65535");
+  Launch L(audio);
+  Tensor ws = at::empty({(int64_t)nbytes}, audio.options().dtype(at::kByte));
+  Tensor out = at::empty({B, (int64_t)c.n_mfcc, (int64_t)nws_loudness_frames((int)N, (int)hop)}, audio.options());
+  nws_check(nws_mfcc(audio.data_ptr<float>(), (int)B, (int)N, c.sr, c.n_fft, (int)hop, c.n_mfcc, c.n_mels, dft.data_ptr<float>(),
+                     table.data_ptr<float>(), out.data_ptr<float>(), ws.data_ptr(), nbytes, L.stream), "nws_mfcc");
+  return out;
+}
+
 // ---- runtime-size path (csrc/generic.hip): any gin configuration of the reference --------------------------------------
 template <class T>
 const T* struct_of(const Tensor& desc, const char* name) {
@@ -1126,4 +1172,6 @@ TORCH_LIBRARY(newt_hip, m) {
         "float fill_value) -> (Tensor, Tensor, Tensor)", &pyin);
   m.def("resample_bank(int sr_in, int sr_out) -> Tensor", &resample_bank);
   m.def("resample(Tensor audio, Tensor bank, int sr_in, int sr_out) -> Tensor", &resample);
+  m.def("mfcc_table(float sample_rate, int n_fft, int n_mfcc, int n_mels) -> Tensor", &mfcc_table);
+  m.def("mfcc(Tensor audio, Tensor dft, Tensor table, float sample_rate, int n_fft, int hop, int n_mfcc, int n_mels) -> Tensor", &mfcc);
 }
