@@ -525,6 +525,34 @@ int nws_mfcc(const float* audio, int B, int N, double sample_rate, int n_fft, in
              const float* table, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Multi-resolution STFT loss (csrc/stft_loss.hip): what the reference logs as val/loss and test/loss,
+ * auraloss.freq.MultiResolutionSTFTLoss()(recon, audio) of auraloss 0.2.1 (models/neural_waveshaping.py:93, 104-112, 136-165).
+ * DESIGN.md 3.12 is the definition; parity with auraloss is unpinned.  x (the reconstruction) and y (the target): (B, N) fp32.
+ * Resolution r = (n_ffts[r], hops[r], win_lengths[r]), R <= NWS_STFT_LOSS_MAX_RES of them:
+ *   STFT      torch.stft: periodic hann of win_length centred in n_fft ((n_fft - win_length) / 2 zeros on the left), centre /
+ *             reflect padding, 1 + N / hop frames, n_fft / 2 + 1 bins
+ *   mag       sqrt(max(re^2 + im^2, eps))
+ *   sc_r      ||y_mag - x_mag||_F / ||y_mag||_F,  log_r = mean |ln x_mag - ln y_mag|,  lin_r = mean |x_mag - y_mag|
+ *   loss      (sum_r w_sc sc_r + w_log_mag log_r + w_lin_mag lin_r) / R
+ * out: 1 + 3 R floats on the device: the loss, then (sc_r, log_r, lin_r) per resolution.  Forward only.
+ *   nws_stft_loss_dft_matrix  the constant operand of a resolution (nws_stft_loss_dft_bytes), built on the device once
+ *   nws_stft_loss             one fused kernel per resolution (no spectrogram reaches memory: one record of four fp64 sums per
+ *                             workgroup into the workspace) + a one-workgroup finalise kernel.  No atomics: equal inputs give
+ *                             equal bits.  Enqueue only.  Workspace: nws_stft_loss_workspace_bytes.
+ * NWS_ERR_BAD_ARG: NULL, B < 1, R outside [1, 8], hop < 1, N <= n_fft / 2 (reflect padding), win_length outside [1, n_fft],
+ * eps <= 0.  NWS_ERR_UNSUPPORTED (0 bytes): n_fft not a power of two in [64, 2048]; the two signal tiles of a workgroup,
+ * 2 x (31 hop + n_fft) samples (+ skew words), over 160 KB of LDS (n_fft 2048: hop <= 589); B > 65535.  All of it is decided
+ * before anything is enqueued.
+ */
+#define NWS_STFT_LOSS_MAX_RES 8
+size_t nws_stft_loss_dft_bytes(int n_fft, int win_length);
+int nws_stft_loss_dft_matrix(int n_fft, int win_length, float* dft_out, void* stream);
+size_t nws_stft_loss_workspace_bytes(int B, int N, int R, const int* n_ffts, const int* hops);
+int nws_stft_loss(const float* x, const float* y, int B, int N, int R, const int* n_ffts, const int* hops, const int* win_lengths,
+                  const float* const* dfts, float w_sc, float w_log_mag, float w_lin_mag, float eps, float* out, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
+/*
  * ---- Runtime-size path (csrc/generic.hip): every gin-configurable size of the reference ------------------------------
  * The fused kernels above are compiled for gin/models/newt.gin.  These entry points take the sizes as arguments and run
  * one plain-fp32 stage kernel each (correct first, stage boundaries materialised); nws_forward_generic chains them into

@@ -20,5 +20,6 @@ from .models.modules.dynamic import FiLM, TimeDistributedLayerNorm, TimeDistribu
 from .models.modules.generators import FIRNoiseSynth, HarmonicOscillator  # noqa: F401
 from .models.modules.shaping import NEWT, FastNEWT, Reverb, Sine, TrainableNonlinearity  # noqa: F401
 from .pipeline import ForwardPipeline  # noqa: F401
+from .losses import MultiResolutionSTFTLoss, STFTLoss  # noqa: F401
 
 __version__ = "0.1.0"

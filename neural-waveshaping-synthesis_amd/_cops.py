@@ -424,6 +424,54 @@ class CtypesOps:
                              nbytes, _stream(audio.device)), "nws_mfcc")
         return out
 
+    # ---- multi-resolution STFT loss (csrc/stft_loss.hip) -------------------------------------------------------------------
+    def stft_loss_dft(self, n_fft, win_length):
+        L = _lib.lib()
+        nbytes = L.nws_stft_loss_dft_bytes(n_fft, win_length) if max(abs(n_fft), abs(win_length)) < 2 ** 31 else 0
+        if nbytes == 0:
+            raise RuntimeError(f"stft_loss: unsupported resolution (n_fft {n_fft}, win_length {win_length}): n_fft a power of two "
+                               "in [64, 2048], 1 <= win_length <= n_fft")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        dft = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+        check(L.nws_stft_loss_dft_matrix(n_fft, win_length, ptr(dft), _stream(dev)), "nws_stft_loss_dft_matrix")
+        return dft
+
+    def stft_loss(self, x, y, dfts, n_ffts, hops, win_lengths, w_sc, w_log_mag, w_lin_mag, eps):
+        for name, t in (("x", x), ("y", y)):
+            if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+                raise RuntimeError(f"stft_loss: {name}: expected a contiguous (B, N) float32 CUDA tensor (there is no CPU fallback), "
+                                   f"got {tuple(t.shape)} {t.dtype} on {t.device}")
+        if x.shape != y.shape or x.device != y.device:
+            raise RuntimeError(f"stft_loss: x {tuple(x.shape)} on {x.device} and y {tuple(y.shape)} on {y.device} must agree")
+        R = len(n_ffts)
+        if not (1 <= R <= 8 and len(hops) == R and len(win_lengths) == R and len(dfts) == R):
+            raise RuntimeError(f"stft_loss: 1 to 8 resolutions, one n_fft, hop, win_length and operand each (got {R}, {len(hops)}, "
+                               f"{len(win_lengths)}, {len(dfts)})")
+        B, N = x.shape
+        L = _lib.lib()
+        ints = [int(v) for v in (*n_ffts, *hops, *win_lengths)]
+        ok = all(abs(v) < 2 ** 31 for v in ints) and 1 <= B and N < 2 ** 31
+        nf, hp, wl = ((C.c_int * R)(*ints[i * R:(i + 1) * R]) for i in range(3)) if ok else (None, None, None)
+        for r in range(R if ok else 0):
+            d = dfts[r]
+            if not d.is_cuda or d.dtype != torch.float32 or d.device != x.device or not d.is_contiguous():
+                raise RuntimeError(f"stft_loss: dfts[{r}]: expected a float32 tensor on x's device, got {d.dtype} on {d.device}")
+            nbytes = L.nws_stft_loss_dft_bytes(nf[r], wl[r])
+            if nbytes == 0 or d.numel() * 4 != nbytes:
+                raise RuntimeError(f"stft_loss: dfts[{r}] does not belong to n_fft = {nf[r]}, win_length = {wl[r]} (n_fft: a power of "
+                                   "two in [64, 2048], 1 <= win_length <= n_fft)")
+        nbytes = L.nws_stft_loss_workspace_bytes(B, N, R, nf, hp) if ok else 0
+        if nbytes == 0:
+            raise RuntimeError(f"stft_loss: unsupported size (B {B}, N {N}, n_ffts {list(n_ffts)}, hops {list(hops)}): N > n_fft / 2 "
+                               "(reflect padding), hop >= 1, the two signal tiles of 31 hop + n_fft samples must fit 160 KB of LDS "
+                               "(n_fft 2048: hop <= 589), B <= 65535")
+        with torch.cuda.device(x.device):
+            ws = _new(x, nbytes, dtype=torch.uint8)
+            out = _new(x, 1 + 3 * R)
+            check(L.nws_stft_loss(ptr(x), ptr(y), B, N, R, nf, hp, wl, _ptrs(dfts), w_sc, w_log_mag, w_lin_mag, eps, ptr(out), ptr(ws),
+                                  nbytes, _stream(x.device)), "nws_stft_loss")
+        return [out[0], out[1:].view(R, 3)]
+
     # ---- runtime-size path (csrc/generic.hip) ----------------------------------------------------------------------------
     def forward_generic(self, gdesc, f0, control, phase_u, rand_phase, noise, plan, reverb_tables, reverb_spectrum,
                         reverb_workspace, workspace, sample_rate):

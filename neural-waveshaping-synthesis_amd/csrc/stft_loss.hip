@@ -1,0 +1,284 @@
+// Multi-resolution STFT loss: the number the reference logs as val/loss and test/loss
+//   (models/neural_waveshaping.py:93, 104-112, 136-165: auraloss.freq.MultiResolutionSTFTLoss()(recon, audio), auraloss 0.2.1).
+//   DESIGN.md 3.12 holds the definition the kernels are tested against; parity with auraloss itself is unpinned.
+//
+// Per resolution (n_fft, hop, win_length): torch.stft (periodic hann of win_length centred in n_fft, centre / reflect padding,
+// 1 + N / hop frames) of x and of y, mag = sqrt(max(re^2 + im^2, eps)), and four sums over the whole (B, bins, frames) array:
+//   sum (y_mag - x_mag)^2, sum y_mag^2, sum |ln x_mag - ln y_mag|, sum |x_mag - y_mag|.
+//
+// Three kernels:
+//   stft_loss_dft_kernel       the constant operand: the row layout of loudness.hip's dft_matrix_kernel (rows 2k / 2k+1 =
+//                              w[n] cos / -w[n] sin, evaluated in double with exact phase reduction), w = the centred window,
+//                              zero outside it.
+//   stft_loss_kernel           the tile of loudness_power_kernel (32 frames x 4 M-tiles per workgroup, skewed LDS staging with
+//                              reflect padding resolved there, v_mfma_f32_32x32x2_f32) with BOTH signals staged and two
+//                              accumulator sets fed by one A operand.  The K loop runs over the columns the window covers only
+//                              (rounded out to 16): 59 / 59 / 47 % of K at the defaults.  Re / Im of a bin are adjacent
+//                              accumulator registers of one lane, so both magnitudes are formed in-lane; the four sums are
+//                              reduced lane -> wave -> workgroup in fp64 in a fixed order and ONE record of four doubles per
+//                              workgroup goes to memory.  No spectrogram is written.
+//   stft_loss_finalise_kernel  one workgroup: the records of each resolution summed in a fixed order in fp64, then sc / log /
+//                              lin, the weighted sum per resolution and the mean over resolutions.
+// No atomics: two calls on the same inputs give the same bits.  Nothing is read back: the call only enqueues.
+//
+// Limits: n_fft a power of two in [64, 2048]; both tiles of 31 hop + n_fft samples (+ skew words) within 160 KB of LDS
+// (n_fft 2048: hop <= 589, n_fft 1024: hop <= 622); B <= 65535; at most 8 resolutions.
+#include "nws_common.h"
+
+namespace {
+
+constexpr int kFrames = 32;  // frames per workgroup (MFMA N)
+constexpr int kMaxRes = NWS_STFT_LOSS_MAX_RES;
+constexpr size_t kLdsCap = 160 * 1024;
+
+__device__ __forceinline__ int reflect_index(long long i, int N) {  // numpy / torch "reflect" (no edge repeat), one fold each side
+  if (i < 0) i = -i;
+  if (i >= N) i = 2LL * (N - 1) - i;
+  return (int)(i < 0 ? 0 : i);
+}
+
+__device__ __forceinline__ int skew(int j) { return j + (j >> 7); }
+
+__global__ void stft_loss_dft_kernel(int n_fft, int win_length, int rows_pad, float* __restrict__ out) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long long)rows_pad * n_fft) return;
+  const int row = (int)(e / n_fft), n = (int)(e - (long long)row * n_fft);
+  const int k = row >> 1;
+  const int m = n - (n_fft - win_length) / 2;  // position inside the centred window (torch.stft pads the window on both sides)
+  float v = 0.0f;
+  if (k <= n_fft / 2 && m >= 0 && m < win_length) {
+    const double w = 0.5 - 0.5 * cospi(2.0 * (double)m / (double)win_length);  // periodic hann
+    const long long kn = ((long long)k * n) % n_fft;                           // exact phase reduction
+    double s, c;
+    sincospi(2.0 * (double)kn / (double)n_fft, &s, &c);
+    v = (float)((row & 1) ? -w * s : w * c);
+  }
+  out[e] = v;
+}
+
+// grid (frame tiles, groups of 4 M-tiles, B).  K runs over [k_lo, k_lo + 2 k_half): lane half kh takes k_lo + k_half kh + s.
+__global__ __launch_bounds__(256) void stft_loss_kernel(const float* __restrict__ x, const float* __restrict__ y, int N, int n_fft,
+                                                        int hop, int frames, const float* __restrict__ dft, int m_tiles, int k_lo,
+                                                        int k_half, float eps, double* __restrict__ partials) {
+  extern __shared__ __align__(16) float lds[];  // skewed windows of the frame tile: x, then y
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int kh = lane >> 5, col = lane & 31;
+  const int t0 = blockIdx.x * kFrames;
+  const int mt = blockIdx.y * 4 + wave;
+  const int b = blockIdx.z;
+  const float* xr = x + (size_t)b * N;
+  const float* yr = y + (size_t)b * N;
+  const int span = (kFrames - 1) * hop + n_fft;
+  float* xs = lds;
+  float* ys = lds + (span + (span >> 7) + 1);
+  const long long first = (long long)hop * t0 - n_fft / 2;  // center=True: frame t covers [hop t - n_fft/2, hop t + n_fft/2)
+  for (int j = tid; j < span; j += 256) {
+    const int i = reflect_index(first + j, N);
+    xs[skew(j)] = xr[i];
+    ys[skew(j)] = yr[i];
+  }
+  __syncthreads();
+
+  double s_sc = 0.0, s_y2 = 0.0, s_log = 0.0, s_lin = 0.0;
+  if (mt < m_tiles) {
+    const float* arow = dft + (size_t)(32 * mt + col) * n_fft + k_lo + k_half * kh;
+    const int boff = hop * col + k_lo + k_half * kh;
+    f32x16 ax = {}, ay = {};
+    for (int s0 = 0; s0 < k_half; s0 += 8) {
+      const float4 a0 = *reinterpret_cast<const float4*>(arow + s0), a1 = *reinterpret_cast<const float4*>(arow + s0 + 4);
+      const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int j = skew(boff + s0 + i);
+        ax = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], xs[j], ax, 0, 0, 0);
+        ay = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], ys[j], ay, 0, 0, 0);
+      }
+    }
+    // rows (r, r+1), r even = (Re, Im) of bin 16 mt + (r&3)/2 + 4 (r>>2) + 2 kh; column = frame t0 + col
+    const int bins = n_fft / 2 + 1;
+    const bool frame_ok = t0 + col < frames;
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+      const int bin = 16 * mt + ((r & 3) >> 1) + 4 * (r >> 2) + 2 * kh;
+      if (bin < bins && frame_ok) {
+        const float xm = sqrtf(fmaxf(fmaf(ax[r], ax[r], ax[r + 1] * ax[r + 1]), eps));  // the clamp is on the power
+        const float ym = sqrtf(fmaxf(fmaf(ay[r], ay[r], ay[r + 1] * ay[r + 1]), eps));
+        const float d = ym - xm;
+        s_sc += (double)d * (double)d;
+        s_y2 += (double)ym * (double)ym;
+        s_log += (double)fabsf(logf(xm) - logf(ym));
+        s_lin += (double)fabsf(d);
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    s_sc += __shfl_xor(s_sc, off, 64);
+    s_y2 += __shfl_xor(s_y2, off, 64);
+    s_log += __shfl_xor(s_log, off, 64);
+    s_lin += __shfl_xor(s_lin, off, 64);
+  }
+  __syncthreads();  // every wave is done with the staged signals: the first 128 bytes become the workgroup's reduction
+  double* red = reinterpret_cast<double*>(lds);
+  if (lane == 0) {
+    red[4 * wave + 0] = s_sc;
+    red[4 * wave + 1] = s_y2;
+    red[4 * wave + 2] = s_log;
+    red[4 * wave + 3] = s_lin;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    const size_t rec = ((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    partials[4 * rec + tid] = ((red[tid] + red[4 + tid]) + red[8 + tid]) + red[12 + tid];
+  }
+}
+
+struct FinaliseArgs {
+  int R;
+  unsigned long long rec_off[kMaxRes], rec_n[kMaxRes];  // records of resolution r: [rec_off, rec_off + rec_n)
+  double count[kMaxRes];                                // B bins frames
+  double w_sc, w_log, w_lin;
+};
+
+// out[0] = loss, out[1 + 3 r + (0, 1, 2)] = (sc_r, log_r, lin_r)
+__global__ __launch_bounds__(256) void stft_loss_finalise_kernel(const double* __restrict__ partials, FinaliseArgs a,
+                                                                 float* __restrict__ out) {
+  __shared__ double red[4][256];
+  const int tid = threadIdx.x;
+  double total = 0.0;
+  for (int r = 0; r < a.R; ++r) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    const double* p = partials + 4 * a.rec_off[r];
+    for (unsigned long long i = tid; i < a.rec_n[r]; i += 256) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) s[q] += p[4 * i + q];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) red[q][tid] = s[q];
+    __syncthreads();
+    for (int off = 128; off >= 1; off >>= 1) {
+      if (tid < off) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) red[q][tid] += red[q][tid + off];
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      const double sc = sqrt(red[0][0]) / sqrt(red[1][0]);  // ||y_mag - x_mag||_F / ||y_mag||_F
+      const double lg = red[2][0] / a.count[r], ln = red[3][0] / a.count[r];
+      out[1 + 3 * r] = (float)sc;
+      out[2 + 3 * r] = (float)lg;
+      out[3 + 3 * r] = (float)ln;
+      total += a.w_sc * sc + a.w_log * lg + a.w_lin * ln;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) out[0] = (float)(total / (double)a.R);
+}
+
+__host__ int rows_padded(int n_fft) { return ((2 * (n_fft / 2 + 1)) + 31) / 32 * 32; }
+__host__ bool n_fft_ok(int n_fft) { return n_fft >= 64 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0; }
+// LDS of one workgroup: the 31 hop + n_fft samples its 32 overlapping frames are cut from (+ skew words), for BOTH signals
+__host__ size_t tile_lds_bytes(int n_fft, int hop) {
+  const size_t span = (size_t)(kFrames - 1) * hop + n_fft;
+  return 2 * (span + (span >> 7) + 1) * sizeof(float);
+}
+__host__ bool tile_ok(int n_fft, int hop) { return hop >= 1 && tile_lds_bytes(n_fft, hop) <= kLdsCap; }
+__host__ int frames_of(int N, int hop) { return 1 + N / hop; }
+
+struct Grid {
+  unsigned gx, gy;
+  unsigned long long records;
+};
+__host__ Grid grid_of(int B, int N, int n_fft, int hop) {
+  Grid g;
+  g.gx = (unsigned)((frames_of(N, hop) + kFrames - 1) / kFrames);
+  g.gy = (unsigned)((rows_padded(n_fft) / 32 + 3) / 4);
+  g.records = (unsigned long long)B * g.gy * g.gx;
+  return g;
+}
+
+// NWS_OK, or why the sizes are refused; nothing here touches the device
+__host__ int check_sizes(int B, int N, int R, const int* n_ffts, const int* hops, const int* win_lengths) {
+  if (!n_ffts || !hops || B < 1 || N < 1 || R < 1 || R > kMaxRes) return NWS_ERR_BAD_ARG;
+  for (int r = 0; r < R; ++r) {
+    if (hops[r] < 1) return NWS_ERR_BAD_ARG;
+    if (win_lengths && (win_lengths[r] < 1 || win_lengths[r] > n_ffts[r])) return NWS_ERR_BAD_ARG;
+    if (!n_fft_ok(n_ffts[r])) return NWS_ERR_UNSUPPORTED;
+    if (N <= n_ffts[r] / 2) return NWS_ERR_BAD_ARG;  // reflect padding needs more than n_fft/2 samples (as in torch.stft)
+    if (!tile_ok(n_ffts[r], hops[r])) return NWS_ERR_UNSUPPORTED;
+  }
+  if (B > 65535) return NWS_ERR_UNSUPPORTED;
+  return NWS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nws_stft_loss_dft_bytes(int n_fft, int win_length) {
+  if (!n_fft_ok(n_fft) || win_length < 1 || win_length > n_fft) return 0;
+  return (size_t)rows_padded(n_fft) * n_fft * sizeof(float);
+}
+
+int nws_stft_loss_dft_matrix(int n_fft, int win_length, float* dft_out, void* stream) {
+  if (!dft_out || win_length < 1 || win_length > n_fft) return NWS_ERR_BAD_ARG;
+  if (!n_fft_ok(n_fft)) return NWS_ERR_UNSUPPORTED;
+  const long long n = (long long)rows_padded(n_fft) * n_fft;
+  stft_loss_dft_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(n_fft, win_length, rows_padded(n_fft), dft_out);
+  NWS_CHECK_LAUNCH();
+  return NWS_OK;
+}
+
+size_t nws_stft_loss_workspace_bytes(int B, int N, int R, const int* n_ffts, const int* hops) {
+  if (check_sizes(B, N, R, n_ffts, hops, nullptr) != NWS_OK) return 0;
+  unsigned long long records = 0;
+  for (int r = 0; r < R; ++r) records += grid_of(B, N, n_ffts[r], hops[r]).records;
+  return (size_t)records * 4 * sizeof(double);
+}
+
+int nws_stft_loss(const float* x, const float* y, int B, int N, int R, const int* n_ffts, const int* hops, const int* win_lengths,
+                  const float* const* dfts, float w_sc, float w_log_mag, float w_lin_mag, float eps, float* out, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+  if (!x || !y || !win_lengths || !dfts || !out || !workspace) return NWS_ERR_BAD_ARG;
+  const int rc = check_sizes(B, N, R, n_ffts, hops, win_lengths);
+  if (rc != NWS_OK) return rc;
+  for (int r = 0; r < R; ++r)
+    if (!dfts[r]) return NWS_ERR_BAD_ARG;
+  if (!(eps > 0.0f)) return NWS_ERR_BAD_ARG;
+  if (workspace_bytes < nws_stft_loss_workspace_bytes(B, N, R, n_ffts, hops)) return NWS_ERR_WORKSPACE;
+
+  hipStream_t st = (hipStream_t)stream;
+  static unsigned long long attr_devices = 0;
+  if (nws_first_use_on_device(attr_devices)) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stft_loss_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap);
+    if (e != hipSuccess) return (int)e;
+  }
+  double* partials = static_cast<double*>(workspace);
+  FinaliseArgs fa;
+  fa.R = R;
+  fa.w_sc = (double)w_sc, fa.w_log = (double)w_log_mag, fa.w_lin = (double)w_lin_mag;
+  unsigned long long off = 0;
+  for (int r = 0; r < kMaxRes; ++r) fa.rec_off[r] = fa.rec_n[r] = 0, fa.count[r] = 1.0;
+  for (int r = 0; r < R; ++r) {
+    const int n_fft = n_ffts[r], hop = hops[r], win = win_lengths[r];
+    const Grid g = grid_of(B, N, n_fft, hop);
+    // the columns the centred window covers, rounded out to a multiple of 16 that starts on a multiple of 4 (float4 loads of A)
+    int k_lo = ((n_fft - win) / 2) & ~3;
+    const int k_len = ((n_fft - win) / 2 + win - k_lo + 15) & ~15;
+    if (k_lo + k_len > n_fft) k_lo = n_fft - k_len;
+    stft_loss_kernel<<<dim3(g.gx, g.gy, (unsigned)B), 256, tile_lds_bytes(n_fft, hop), st>>>(
+        x, y, N, n_fft, hop, frames_of(N, hop), dfts[r], rows_padded(n_fft) / 32, k_lo, k_len / 2, eps, partials + 4 * off);
+    NWS_CHECK_LAUNCH();
+    fa.rec_off[r] = off;
+    fa.rec_n[r] = g.records;
+    fa.count[r] = (double)B * (double)(n_fft / 2 + 1) * (double)frames_of(N, hop);
+    off += g.records;
+  }
+  stft_loss_finalise_kernel<<<1, 256, 0, st>>>(partials, fa, out);
+  NWS_CHECK_LAUNCH();
+  return NWS_OK;
+}
+
+}  // extern "C"

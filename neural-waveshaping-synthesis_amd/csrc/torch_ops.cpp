@@ -14,6 +14,8 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/library.h>
 
+#include <algorithm>
+#include <cstdlib>
 #include <tuple>
 #include <vector>
 
@@ -792,6 +794,59 @@ Tensor mfcc(const Tensor& audio, const Tensor& dft, const Tensor& table, double 
   return out;
 }
 
+// ---- multi-resolution STFT loss (csrc/stft_loss.hip; models/neural_waveshaping.py:93, 104-112 of the reference) ----------
+// the constant operand of one resolution, on the current device
+Tensor stft_loss_dft(int64_t n_fft, int64_t win_length) {
+  const size_t nbytes =
+      std::max(std::abs(n_fft), std::abs(win_length)) <= INT32_MAX ? nws_stft_loss_dft_bytes((int)n_fft, (int)win_length) : 0;
+  TORCH_CHECK(nbytes > 0, "stft_loss: unsupported resolution (n_fft ", n_fft, ", win_length ", win_length,
+              "): n_fft a power of two in [64, 2048], 1 <= win_length <= n_fft");
+  Tensor dft = at::empty({(int64_t)(nbytes / sizeof(float))}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA));
+  Launch L(dft);
+  nws_check(nws_stft_loss_dft_matrix((int)n_fft, (int)win_length, dft.data_ptr<float>(), L.stream), "nws_stft_loss_dft_matrix");
+  return dft;
+}
+
+// x, y (B, N) -> [loss (0-dim), components (R, 3) = (sc_r, log_r, lin_r)]
+std::vector<Tensor> stft_loss(const Tensor& x, const Tensor& y, at::TensorList dfts, at::IntArrayRef n_ffts, at::IntArrayRef hops,
+                              at::IntArrayRef win_lengths, double w_sc, double w_log_mag, double w_lin_mag, double eps) {
+  check_dev(x, "x");
+  check_dev(y, "y");
+  check_same_device(x, "x", y, "y");
+  TORCH_CHECK(x.dim() == 2 && x.sizes() == y.sizes(), "stft_loss: expected x and y of one shape (B, N), got ", x.sizes(), " and ",
+              y.sizes());
+  const size_t R = n_ffts.size();
+  TORCH_CHECK(R >= 1 && R <= NWS_STFT_LOSS_MAX_RES && hops.size() == R && win_lengths.size() == R && dfts.size() == R,
+              "stft_loss: 1 to 8 resolutions, one n_fft, hop, win_length and operand each (got ", R, ", ", hops.size(), ", ",
+              win_lengths.size(), ", ", dfts.size(), ")");
+  const int64_t B = x.size(0), N = x.size(1);
+  int nf[NWS_STFT_LOSS_MAX_RES], hp[NWS_STFT_LOSS_MAX_RES], wl[NWS_STFT_LOSS_MAX_RES];
+  const float* dp[NWS_STFT_LOSS_MAX_RES];
+  bool ok = B >= 1 && N <= INT32_MAX;
+  for (size_t r = 0; r < R; ++r)
+    ok = ok && std::abs(n_ffts[r]) <= INT32_MAX && std::abs(hops[r]) <= INT32_MAX && std::abs(win_lengths[r]) <= INT32_MAX;
+  for (size_t r = 0; ok && r < R; ++r) {
+    nf[r] = (int)n_ffts[r], hp[r] = (int)hops[r], wl[r] = (int)win_lengths[r];
+    check_dev(dfts[r], "dfts");
+    check_same_device(x, "x", dfts[r], "dfts");
+    const size_t nbytes = nws_stft_loss_dft_bytes(nf[r], wl[r]);
+    TORCH_CHECK(nbytes > 0 && (size_t)dfts[r].numel() * sizeof(float) == nbytes, "stft_loss: dfts[", r, "] does not belong to n_fft = ",
+                nf[r], ", win_length = ", wl[r], " (n_fft: a power of two in [64, 2048], 1 <= win_length <= n_fft)");
+    dp[r] = dfts[r].data_ptr<float>();
+  }
+  const size_t nbytes = ok && B <= 65535 ? nws_stft_loss_workspace_bytes((int)B, (int)N, (int)R, nf, hp) : 0;
+  TORCH_CHECK(nbytes > 0, "stft_loss: unsupported size (B ", B, ", N ", N, ", n_ffts ", n_ffts, ", hops ", hops,
+              "): N > n_fft / 2 (reflect padding), hop >= 1, the two signal tiles of 31 hop + n_fft samples must fit 160 KB of LDS "
+              "(n_fft 2048: hop <= 589), B <= 65535");
+  Launch L(x);
+  Tensor ws = at::empty({(int64_t)nbytes}, x.options().dtype(at::kByte));
+  Tensor out = at::empty({(int64_t)(1 + 3 * R)}, x.options());
+  nws_check(nws_stft_loss(x.data_ptr<float>(), y.data_ptr<float>(), (int)B, (int)N, (int)R, nf, hp, wl, dp, (float)w_sc,
+                          (float)w_log_mag, (float)w_lin_mag, (float)eps, out.data_ptr<float>(), ws.data_ptr(), nbytes, L.stream),
+            "nws_stft_loss");
+  return {out[0], out.slice(0, 1).view({(int64_t)R, 3})};
+}
+
 // ---- runtime-size path (csrc/generic.hip): any gin configuration of the reference --------------------------------------
 template <class T>
 const T* struct_of(const Tensor& desc, const char* name) {
@@ -1173,5 +1228,8 @@ TORCH_LIBRARY(newt_hip, m) {
   m.def("resample_bank(int sr_in, int sr_out) -> Tensor", &resample_bank);
   m.def("resample(Tensor audio, Tensor bank, int sr_in, int sr_out) -> Tensor", &resample);
   m.def("mfcc_table(float sample_rate, int n_fft, int n_mfcc, int n_mels) -> Tensor", &mfcc_table);
+  m.def("stft_loss_dft(int n_fft, int win_length) -> Tensor", &stft_loss_dft);
+  m.def("stft_loss(Tensor x, Tensor y, Tensor[] dfts, int[] n_ffts, int[] hops, int[] win_lengths, float w_sc, float w_log_mag, "
+        "float w_lin_mag, float eps) -> Tensor[]", &stft_loss);
   m.def("mfcc(Tensor audio, Tensor dft, Tensor table, float sample_rate, int n_fft, int hop, int n_mfcc, int n_mels) -> Tensor", &mfcc);
 }

@@ -3,8 +3,14 @@
 Mirrors the reference's ``NeuralWaveshaping`` (models/neural_waveshaping.py:29-90): same constructor
 (gin-configurable), sub-module / attribute names, state-dict keys, ``forward(f0, control)``,
 ``render_exciter`` and ``get_embedding``.  ``forward`` is ONE call into the C-ABI (``nws_forward``),
-which enqueues the hand-written HIP kernels on torch's current stream.  Training hooks of the
-reference (:92-165) are out of scope.
+which enqueues the hand-written HIP kernels on torch's current stream.
+
+Of the reference's Lightning hooks (:92-165) the two that need no backward pass are here: ``validation_step``
+and ``test_step`` return ``stft_loss(recon, audio)`` - ``losses.MultiResolutionSTFTLoss``, the HIP restatement
+of the ``auraloss`` loss the reference logs as ``val/loss`` / ``test/loss`` - through the
+reference's ``_run_step``.  ``stft_loss`` is made on first use (in the reference ``configure_optimizers`` makes
+it).  ``training_step`` and ``configure_optimizers`` raise: there is no backward pass in this package
+(SURVEY.md §2 row 1b).  Logging (``self.log``, wandb) is left to the caller.
 
 Hidden inputs, exactly like the reference: every forward draws ``rand_like(osc.rand_phase)`` and then
 ``rand(control_hop*T - 1)`` from the default generator of the module's device, in that order
@@ -177,6 +183,50 @@ class NeuralWaveshaping(nn.Module):
         if self._sub_module_hooks():
             return self._forward_module_by_module(f0, control, phase_u, noise)
         return self._engine.forward(f0, control, phase_u, noise)
+
+    # ---- evaluation hooks (reference :104-112, :136-165): inference + loss, no backward ----------------
+    @property
+    def stft_loss(self):
+        """losses.MultiResolutionSTFTLoss() with the reference's (auraloss's default) resolutions, made on first use"""
+        loss = self.__dict__.get("_stft_loss")
+        if loss is None:
+            from ..losses import MultiResolutionSTFTLoss
+
+            loss = MultiResolutionSTFTLoss()
+            self.__dict__["_stft_loss"] = loss       # not a sub-module: it holds no state and must not enter the state dict
+        return loss
+
+    def _run_step(self, batch):
+        """reference :104-112 -> (loss, recon, audio)"""
+        audio = batch["audio"].float()
+        f0 = batch["f0"].float()
+        control = batch["control"].float()
+
+        recon = self(f0, control)
+
+        if recon.shape[-1] != audio.shape[-1] or recon.shape[0] != audio.shape[0]:
+            raise RuntimeError(f"the model rendered {tuple(recon.shape)} ({int(self.control_hop)} samples per control frame) but the "
+                               f"batch's audio is {tuple(audio.shape)}: the loss compares signals of one length")
+        loss = self.stft_loss(recon, audio.reshape(recon.shape))
+        return loss, recon, audio
+
+    def validation_step(self, batch, batch_idx):
+        """reference :136-150 without the logging: the loss as a 0-dim tensor on the device (nothing is read back)"""
+        with torch.no_grad():
+            return self._run_step(batch)[0]
+
+    def test_step(self, batch, batch_idx):
+        """reference :152-165 without the logging; unlike there, the loss is returned"""
+        with torch.no_grad():
+            return self._run_step(batch)[0]
+
+    def training_step(self, batch, batch_idx):
+        raise NotImplementedError("training_step: there is no backward pass in this package (the HIP kernels are forward-only); "
+                                  "validation_step and test_step give the reference's loss")
+
+    def configure_optimizers(self):
+        raise NotImplementedError("configure_optimizers: there is no backward pass in this package, so there is nothing to optimise; "
+                                  "model.stft_loss is made on first use instead")
 
     def _sub_module_hooks(self) -> bool:
         """Forward hooks on sub-modules (the reference's users tap stages that way, and so does tests/golden/make_golden.py on
