@@ -17,7 +17,10 @@ hipGraph and replayed (`graph=True`, the default): a 256-sample hop is then one 
   * the stream emits audio 64 samples (4 ms) behind the control frames it has seen (linear upsampling looks one frame
     ahead); `push(..., final=True)` releases the remainder exactly like the one-shot forward's right edge;
   * the phase offsets are drawn once per stream and the noise chunk by chunk from the device generator (or both are
-    injected for parity testing), mirroring the reference's two hidden draws.
+    injected for parity testing), mirroring the reference's two hidden draws;
+  * chunk size changes bits at the 1e-6 level: the same frames pushed in other chunk sizes give the same signal to 1e-5 of its
+    RMS, not bit for bit (hops of one or two frames take another frame-MLP kernel than longer chunks, chunks beyond 2048
+    samples sum the reverb in another order).
 
 `VoiceStream` (`model.stream(B, slots=True)`, `nws_stream_step_slots`) is the slot mode: B voices that start and stop on their
 own in one batched stream, with per-slot events as device data; its docstring states the contract.

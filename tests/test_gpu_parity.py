@@ -237,6 +237,51 @@ def test_frame_mlps_of_one_or_two_frames_against_the_tile_kernel(models, B, T):
     assert not torch.equal(film, film_t) or B * T == 0          # it IS another kernel (same bits would mean the switch did nothing)
 
 
+@pytest.fixture(scope="module")
+def g1_stage_taps(oracle):
+    g = load_npz("g1_realistic.npz")
+    st = {}
+    oracle[0](g["f0"], g["control"], g["phase_u"], g["noise"], stages=st)
+    Ht = st["H"].transpose(1, 2)
+    h = torch.fft.irfft(torch.complex(Ht, torch.zeros_like(Ht))).roll(128, -1) * torch.hann_window(256).view(1, 1, -1)
+    # frames as rows: the frame MLPs are time-distributed, any consecutive rows of a long run are a reference for a short one
+    return (st["gru_out"].reshape(-1, 128).contiguous(), st["film"].transpose(1, 2).reshape(-1, 256).numpy(),
+            h[..., 128:].reshape(-1, 128).numpy(), float(st["H"].abs().max()))
+
+
+@pytest.mark.parametrize("B,T", [(1, 1), (1, 2), (3, 2), (5, 1), (17, 2)])
+def test_few_frame_mlp_kernel_against_the_stage_taps(models, g1_stage_taps, B, T):
+    """The matrix-vector kernel of csrc/mlp_few.h (every call of one or two frames without the embedding / H taps: each hop of a
+    256-sample stream) against the ORACLE's FiLM rows and FIR half-taps, with the bars the tile kernels are held to - not only
+    against the tile kernel.  B x T consecutive frames of the oracle's run on g1_realistic, from another offset per case.
+    Measured max-abs error (FiLM bar 5e-5; half-taps bar 2e-6, max|H| = 0.076):
+      (B, T)   (1,1)    (1,2)    (3,2)    (5,1)    (17,2)
+      FiLM     8.9e-7   7.9e-7   9.5e-7   7.2e-7   1.0e-6
+      FIR      7.0e-9   9.3e-9   1.0e-8   1.1e-8   1.2e-8"""
+    from nws_amd import _lib
+    m, _ = models
+    m._engine.weights()
+    L = _lib.lib()
+    gru_all, film_ref, fir_ref, H_max = g1_stage_taps
+    at = 7 * B + 100 * T
+    assert at + B * T <= gru_all.shape[0]
+    gru = gru_all[at:at + B * T].reshape(B, T, 128).cuda()
+    try:
+        _, film, _, fir = m._engine.frame_mlps(gru)
+        assert L.nws_debug_frame_mlps_kernel(1) == 0
+        _, film_t, _, fir_t = m._engine.frame_mlps(gru)
+    finally:
+        L.nws_debug_frame_mlps_kernel(0)
+    assert film.shape == (B, T, 256) and fir.shape == (B, T, 128)
+    assert not torch.equal(film, film_t)          # the few-frame kernel ran: the tile kernel gives other bits
+    e_film = maxabs(film.cpu().numpy().reshape(-1, 256), film_ref[at:at + B * T])
+    e_fir = maxabs(fir.cpu().numpy().reshape(-1, 128), fir_ref[at:at + B * T])
+    record(f"frame_mlps_few_vs_oracle_B{B}_T{T}", film=e_film, fir=e_fir, H_max=H_max)
+    print("few vs oracle", B, T, e_film, e_fir, H_max)
+    assert e_film <= 5e-5, e_film
+    assert e_fir <= 2e-6 * max(1.0, H_max), (e_fir, H_max)
+
+
 def test_forward_pipeline_matches_plain_forward(models, oracle):
     """ForwardPipeline (control half on side streams, batched GRU, ring of workspaces) must return what model() returns for
     the same inputs and draws, batch after batch, including a shape change in mid-stream; one batch is also held against
