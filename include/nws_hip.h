@@ -553,6 +553,20 @@ int nws_stft_loss(const float* x, const float* y, int B, int N, int R, const int
                   size_t workspace_bytes, void* stream);
 
 /*
+ * Gradient of that loss with respect to the reconstruction x (csrc/stft_grad.hip; DESIGN.md 3.13 is the definition).  Same
+ * arguments, operands (dfts) and refusals as the forward call above; grad_out: (B, N) fp32 on the device, overwritten.  There is no gradient
+ * with respect to the target y.  Per resolution: the forward tile twice (the two Frobenius sums as per-workgroup fp64 records
+ * reduced in a fixed order, then G formed in-lane), z = D^T G on the matrix pipe, and the overlap-add with the reflect fold as a
+ * gather.  No floating-point atomics: equal inputs give equal bits.  Enqueue only.  The workspace (nws_stft_grad_workspace_bytes,
+ * 0 for a refused size) holds G and z of the largest resolution - spectrogram-sized - and is reused across resolutions;
+ * NWS_ERR_WORKSPACE if it is too small.
+ */
+size_t nws_stft_grad_workspace_bytes(int B, int N, int R, const int* n_ffts, const int* hops, const int* win_lengths);
+int nws_stft_grad(const float* x, const float* y, int B, int N, int R, const int* n_ffts, const int* hops, const int* win_lengths,
+                  const float* const* dfts, float w_sc, float w_log_mag, float w_lin_mag, float eps, float* grad_out, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
+/*
  * ---- Runtime-size path (csrc/generic.hip): every gin-configurable size of the reference ------------------------------
  * The fused kernels above are compiled for gin/models/newt.gin.  These entry points take the sizes as arguments and run
  * one plain-fp32 stage kernel each (correct first, stage boundaries materialised); nws_forward_generic chains them into

@@ -436,16 +436,19 @@ class CtypesOps:
         check(L.nws_stft_loss_dft_matrix(n_fft, win_length, ptr(dft), _stream(dev)), "nws_stft_loss_dft_matrix")
         return dft
 
-    def stft_loss(self, x, y, dfts, n_ffts, hops, win_lengths, w_sc, w_log_mag, w_lin_mag, eps):
+    @staticmethod
+    def _stft_sizes(op, x, y, dfts, n_ffts, hops, win_lengths):
+        """the argument checks stft_loss and stft_loss_grad share -> B, N, R and the three int arrays (None where a size does not
+        fit an int: the caller's workspace query then reports the size as unsupported)"""
         for name, t in (("x", x), ("y", y)):
             if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
-                raise RuntimeError(f"stft_loss: {name}: expected a contiguous (B, N) float32 CUDA tensor (there is no CPU fallback), "
+                raise RuntimeError(f"{op}: {name}: expected a contiguous (B, N) float32 CUDA tensor (there is no CPU fallback), "
                                    f"got {tuple(t.shape)} {t.dtype} on {t.device}")
         if x.shape != y.shape or x.device != y.device:
-            raise RuntimeError(f"stft_loss: x {tuple(x.shape)} on {x.device} and y {tuple(y.shape)} on {y.device} must agree")
+            raise RuntimeError(f"{op}: x {tuple(x.shape)} on {x.device} and y {tuple(y.shape)} on {y.device} must agree")
         R = len(n_ffts)
         if not (1 <= R <= 8 and len(hops) == R and len(win_lengths) == R and len(dfts) == R):
-            raise RuntimeError(f"stft_loss: 1 to 8 resolutions, one n_fft, hop, win_length and operand each (got {R}, {len(hops)}, "
+            raise RuntimeError(f"{op}: 1 to 8 resolutions, one n_fft, hop, win_length and operand each (got {R}, {len(hops)}, "
                                f"{len(win_lengths)}, {len(dfts)})")
         B, N = x.shape
         L = _lib.lib()
@@ -455,22 +458,45 @@ class CtypesOps:
         for r in range(R if ok else 0):
             d = dfts[r]
             if not d.is_cuda or d.dtype != torch.float32 or d.device != x.device or not d.is_contiguous():
-                raise RuntimeError(f"stft_loss: dfts[{r}]: expected a float32 tensor on x's device, got {d.dtype} on {d.device}")
+                raise RuntimeError(f"{op}: dfts[{r}]: expected a float32 tensor on x's device, got {d.dtype} on {d.device}")
             nbytes = L.nws_stft_loss_dft_bytes(nf[r], wl[r])
             if nbytes == 0 or d.numel() * 4 != nbytes:
-                raise RuntimeError(f"stft_loss: dfts[{r}] does not belong to n_fft = {nf[r]}, win_length = {wl[r]} (n_fft: a power of "
+                raise RuntimeError(f"{op}: dfts[{r}] does not belong to n_fft = {nf[r]}, win_length = {wl[r]} (n_fft: a power of "
                                    "two in [64, 2048], 1 <= win_length <= n_fft)")
-        nbytes = L.nws_stft_loss_workspace_bytes(B, N, R, nf, hp) if ok else 0
+        return B, N, R, nf, hp, wl
+
+    @staticmethod
+    def _stft_unsupported(op, B, N, n_ffts, hops):
+        return RuntimeError(f"{op}: unsupported size (B {B}, N {N}, n_ffts {list(n_ffts)}, hops {list(hops)}): N > n_fft / 2 "
+                            "(reflect padding), hop >= 1, the two signal tiles of 31 hop + n_fft samples must fit 160 KB of LDS "
+                            "(n_fft 2048: hop <= 589), B <= 65535")
+
+    def stft_loss(self, x, y, dfts, n_ffts, hops, win_lengths, w_sc, w_log_mag, w_lin_mag, eps):
+        B, N, R, nf, hp, wl = self._stft_sizes("stft_loss", x, y, dfts, n_ffts, hops, win_lengths)
+        L = _lib.lib()
+        nbytes = L.nws_stft_loss_workspace_bytes(B, N, R, nf, hp) if nf is not None else 0
         if nbytes == 0:
-            raise RuntimeError(f"stft_loss: unsupported size (B {B}, N {N}, n_ffts {list(n_ffts)}, hops {list(hops)}): N > n_fft / 2 "
-                               "(reflect padding), hop >= 1, the two signal tiles of 31 hop + n_fft samples must fit 160 KB of LDS "
-                               "(n_fft 2048: hop <= 589), B <= 65535")
+            raise self._stft_unsupported("stft_loss", B, N, n_ffts, hops)
         with torch.cuda.device(x.device):
             ws = _new(x, nbytes, dtype=torch.uint8)
             out = _new(x, 1 + 3 * R)
             check(L.nws_stft_loss(ptr(x), ptr(y), B, N, R, nf, hp, wl, _ptrs(dfts), w_sc, w_log_mag, w_lin_mag, eps, ptr(out), ptr(ws),
                                   nbytes, _stream(x.device)), "nws_stft_loss")
         return [out[0], out[1:].view(R, 3)]
+
+    def stft_loss_grad(self, x, y, dfts, n_ffts, hops, win_lengths, w_sc, w_log_mag, w_lin_mag, eps):
+        """dL/dx of stft_loss (csrc/stft_grad.hip): (B, N)"""
+        B, N, R, nf, hp, wl = self._stft_sizes("stft_loss_grad", x, y, dfts, n_ffts, hops, win_lengths)
+        L = _lib.lib()
+        nbytes = L.nws_stft_grad_workspace_bytes(B, N, R, nf, hp, wl) if nf is not None else 0
+        if nbytes == 0:
+            raise self._stft_unsupported("stft_loss_grad", B, N, n_ffts, hops)
+        with torch.cuda.device(x.device):
+            ws = _new(x, nbytes, dtype=torch.uint8)
+            grad = _new(x, B, N)
+            check(L.nws_stft_grad(ptr(x), ptr(y), B, N, R, nf, hp, wl, _ptrs(dfts), w_sc, w_log_mag, w_lin_mag, eps, ptr(grad), ptr(ws),
+                                  nbytes, _stream(x.device)), "nws_stft_grad")
+        return grad
 
     # ---- runtime-size path (csrc/generic.hip) ----------------------------------------------------------------------------
     def forward_generic(self, gdesc, f0, control, phase_u, rand_phase, noise, plan, reverb_tables, reverb_spectrum,

@@ -10,7 +10,8 @@
 //   stft_loss_dft_kernel       the constant operand: the row layout of loudness.hip's dft_matrix_kernel (rows 2k / 2k+1 =
 //                              w[n] cos / -w[n] sin, evaluated in double with exact phase reduction), w = the centred window,
 //                              zero outside it.
-//   stft_loss_kernel           the tile of loudness_power_kernel (32 frames x 4 M-tiles per workgroup, skewed LDS staging with
+//   stft_loss_kernel           (the tile itself lives in stft_tile.h, which stft_grad.hip shares)
+//                              the tile of loudness_power_kernel (32 frames x 4 M-tiles per workgroup, skewed LDS staging with
 //                              reflect padding resolved there, v_mfma_f32_32x32x2_f32) with BOTH signals staged and two
 //                              accumulator sets fed by one A operand.  The K loop runs over the columns the window covers only
 //                              (rounded out to 16): 59 / 59 / 47 % of K at the defaults.  Re / Im of a bin are adjacent
@@ -23,21 +24,9 @@
 //
 // Limits: n_fft a power of two in [64, 2048]; both tiles of 31 hop + n_fft samples (+ skew words) within 160 KB of LDS
 // (n_fft 2048: hop <= 589, n_fft 1024: hop <= 622); B <= 65535; at most 8 resolutions.
-#include "nws_common.h"
+#include "stft_tile.h"  // the tile, its limits and the refusals: shared with stft_grad.hip
 
 namespace {
-
-constexpr int kFrames = 32;  // frames per workgroup (MFMA N)
-constexpr int kMaxRes = NWS_STFT_LOSS_MAX_RES;
-constexpr size_t kLdsCap = 160 * 1024;
-
-__device__ __forceinline__ int reflect_index(long long i, int N) {  // numpy / torch "reflect" (no edge repeat), one fold each side
-  if (i < 0) i = -i;
-  if (i >= N) i = 2LL * (N - 1) - i;
-  return (int)(i < 0 ? 0 : i);
-}
-
-__device__ __forceinline__ int skew(int j) { return j + (j >> 7); }
 
 __global__ void stft_loss_dft_kernel(int n_fft, int win_length, int rows_pad, float* __restrict__ out) {
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -66,41 +55,20 @@ __global__ __launch_bounds__(256) void stft_loss_kernel(const float* __restrict_
   const int t0 = blockIdx.x * kFrames;
   const int mt = blockIdx.y * 4 + wave;
   const int b = blockIdx.z;
-  const float* xr = x + (size_t)b * N;
-  const float* yr = y + (size_t)b * N;
-  const int span = (kFrames - 1) * hop + n_fft;
   float* xs = lds;
-  float* ys = lds + (span + (span >> 7) + 1);
-  const long long first = (long long)hop * t0 - n_fft / 2;  // center=True: frame t covers [hop t - n_fft/2, hop t + n_fft/2)
-  for (int j = tid; j < span; j += 256) {
-    const int i = reflect_index(first + j, N);
-    xs[skew(j)] = xr[i];
-    ys[skew(j)] = yr[i];
-  }
-  __syncthreads();
+  float* ys = lds + tile_words(n_fft, hop);
+  tile_stage(x + (size_t)b * N, y + (size_t)b * N, N, n_fft, hop, t0, xs, ys);
 
   double s_sc = 0.0, s_y2 = 0.0, s_log = 0.0, s_lin = 0.0;
   if (mt < m_tiles) {
-    const float* arow = dft + (size_t)(32 * mt + col) * n_fft + k_lo + k_half * kh;
-    const int boff = hop * col + k_lo + k_half * kh;
     f32x16 ax = {}, ay = {};
-    for (int s0 = 0; s0 < k_half; s0 += 8) {
-      const float4 a0 = *reinterpret_cast<const float4*>(arow + s0), a1 = *reinterpret_cast<const float4*>(arow + s0 + 4);
-      const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int j = skew(boff + s0 + i);
-        ax = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], xs[j], ax, 0, 0, 0);
-        ay = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], ys[j], ay, 0, 0, 0);
-      }
-    }
+    tile_transform(dft, xs, ys, n_fft, hop, mt, k_lo, k_half, ax, ay);
     // rows (r, r+1), r even = (Re, Im) of bin 16 mt + (r&3)/2 + 4 (r>>2) + 2 kh; column = frame t0 + col
     const int bins = n_fft / 2 + 1;
     const bool frame_ok = t0 + col < frames;
 #pragma unroll
     for (int r = 0; r < 16; r += 2) {
-      const int bin = 16 * mt + ((r & 3) >> 1) + 4 * (r >> 2) + 2 * kh;
-      if (bin < bins && frame_ok) {
+      if (tile_bin(mt, r, kh) < bins && frame_ok) {
         const float xm = sqrtf(fmaxf(fmaf(ax[r], ax[r], ax[r + 1] * ax[r + 1]), eps));  // the clamp is on the power
         const float ym = sqrtf(fmaxf(fmaf(ay[r], ay[r], ay[r + 1] * ay[r + 1]), eps));
         const float d = ym - xm;
@@ -176,42 +144,6 @@ __global__ __launch_bounds__(256) void stft_loss_finalise_kernel(const double* _
   if (tid == 0) out[0] = (float)(total / (double)a.R);
 }
 
-__host__ int rows_padded(int n_fft) { return ((2 * (n_fft / 2 + 1)) + 31) / 32 * 32; }
-__host__ bool n_fft_ok(int n_fft) { return n_fft >= 64 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0; }
-// LDS of one workgroup: the 31 hop + n_fft samples its 32 overlapping frames are cut from (+ skew words), for BOTH signals
-__host__ size_t tile_lds_bytes(int n_fft, int hop) {
-  const size_t span = (size_t)(kFrames - 1) * hop + n_fft;
-  return 2 * (span + (span >> 7) + 1) * sizeof(float);
-}
-__host__ bool tile_ok(int n_fft, int hop) { return hop >= 1 && tile_lds_bytes(n_fft, hop) <= kLdsCap; }
-__host__ int frames_of(int N, int hop) { return 1 + N / hop; }
-
-struct Grid {
-  unsigned gx, gy;
-  unsigned long long records;
-};
-__host__ Grid grid_of(int B, int N, int n_fft, int hop) {
-  Grid g;
-  g.gx = (unsigned)((frames_of(N, hop) + kFrames - 1) / kFrames);
-  g.gy = (unsigned)((rows_padded(n_fft) / 32 + 3) / 4);
-  g.records = (unsigned long long)B * g.gy * g.gx;
-  return g;
-}
-
-// NWS_OK, or why the sizes are refused; nothing here touches the device
-__host__ int check_sizes(int B, int N, int R, const int* n_ffts, const int* hops, const int* win_lengths) {
-  if (!n_ffts || !hops || B < 1 || N < 1 || R < 1 || R > kMaxRes) return NWS_ERR_BAD_ARG;
-  for (int r = 0; r < R; ++r) {
-    if (hops[r] < 1) return NWS_ERR_BAD_ARG;
-    if (win_lengths && (win_lengths[r] < 1 || win_lengths[r] > n_ffts[r])) return NWS_ERR_BAD_ARG;
-    if (!n_fft_ok(n_ffts[r])) return NWS_ERR_UNSUPPORTED;
-    if (N <= n_ffts[r] / 2) return NWS_ERR_BAD_ARG;  // reflect padding needs more than n_fft/2 samples (as in torch.stft)
-    if (!tile_ok(n_ffts[r], hops[r])) return NWS_ERR_UNSUPPORTED;
-  }
-  if (B > 65535) return NWS_ERR_UNSUPPORTED;
-  return NWS_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -264,12 +196,9 @@ int nws_stft_loss(const float* x, const float* y, int B, int N, int R, const int
   for (int r = 0; r < R; ++r) {
     const int n_fft = n_ffts[r], hop = hops[r], win = win_lengths[r];
     const Grid g = grid_of(B, N, n_fft, hop);
-    // the columns the centred window covers, rounded out to a multiple of 16 that starts on a multiple of 4 (float4 loads of A)
-    int k_lo = ((n_fft - win) / 2) & ~3;
-    const int k_len = ((n_fft - win) / 2 + win - k_lo + 15) & ~15;
-    if (k_lo + k_len > n_fft) k_lo = n_fft - k_len;
+    const KRange k = k_range_of(n_fft, win);
     stft_loss_kernel<<<dim3(g.gx, g.gy, (unsigned)B), 256, tile_lds_bytes(n_fft, hop), st>>>(
-        x, y, N, n_fft, hop, frames_of(N, hop), dfts[r], rows_padded(n_fft) / 32, k_lo, k_len / 2, eps, partials + 4 * off);
+        x, y, N, n_fft, hop, frames_of(N, hop), dfts[r], rows_padded(n_fft) / 32, k.k_lo, k.k_len / 2, eps, partials + 4 * off);
     NWS_CHECK_LAUNCH();
     fa.rec_off[r] = off;
     fa.rec_n[r] = g.records;

@@ -807,44 +807,76 @@ Tensor stft_loss_dft(int64_t n_fft, int64_t win_length) {
   return dft;
 }
 
-// x, y (B, N) -> [loss (0-dim), components (R, 3) = (sc_r, log_r, lin_r)]
-std::vector<Tensor> stft_loss(const Tensor& x, const Tensor& y, at::TensorList dfts, at::IntArrayRef n_ffts, at::IntArrayRef hops,
-                              at::IntArrayRef win_lengths, double w_sc, double w_log_mag, double w_lin_mag, double eps) {
+// the argument checks stft_loss and stft_loss_grad share; ok == false: a size does not fit an int (reported as unsupported)
+struct StftSizes {
+  int64_t B, N;
+  size_t R;
+  bool ok;
+  int nf[NWS_STFT_LOSS_MAX_RES], hp[NWS_STFT_LOSS_MAX_RES], wl[NWS_STFT_LOSS_MAX_RES];
+  const float* dp[NWS_STFT_LOSS_MAX_RES];
+};
+StftSizes stft_sizes(const char* op, const Tensor& x, const Tensor& y, at::TensorList dfts, at::IntArrayRef n_ffts, at::IntArrayRef hops,
+                     at::IntArrayRef win_lengths) {
   check_dev(x, "x");
   check_dev(y, "y");
   check_same_device(x, "x", y, "y");
-  TORCH_CHECK(x.dim() == 2 && x.sizes() == y.sizes(), "stft_loss: expected x and y of one shape (B, N), got ", x.sizes(), " and ",
-              y.sizes());
-  const size_t R = n_ffts.size();
-  TORCH_CHECK(R >= 1 && R <= NWS_STFT_LOSS_MAX_RES && hops.size() == R && win_lengths.size() == R && dfts.size() == R,
-              "stft_loss: 1 to 8 resolutions, one n_fft, hop, win_length and operand each (got ", R, ", ", hops.size(), ", ",
-              win_lengths.size(), ", ", dfts.size(), ")");
-  const int64_t B = x.size(0), N = x.size(1);
-  int nf[NWS_STFT_LOSS_MAX_RES], hp[NWS_STFT_LOSS_MAX_RES], wl[NWS_STFT_LOSS_MAX_RES];
-  const float* dp[NWS_STFT_LOSS_MAX_RES];
-  bool ok = B >= 1 && N <= INT32_MAX;
+  TORCH_CHECK(x.dim() == 2 && x.sizes() == y.sizes(), op, ": expected x and y of one shape (B, N), got ", x.sizes(), " and ", y.sizes());
+  StftSizes s;
+  s.R = n_ffts.size();
+  const size_t R = s.R;
+  TORCH_CHECK(R >= 1 && R <= NWS_STFT_LOSS_MAX_RES && hops.size() == R && win_lengths.size() == R && dfts.size() == R, op,
+              ": 1 to 8 resolutions, one n_fft, hop, win_length and operand each (got ", R, ", ", hops.size(), ", ", win_lengths.size(),
+              ", ", dfts.size(), ")");
+  s.B = x.size(0), s.N = x.size(1);
+  s.ok = s.B >= 1 && s.B <= 65535 && s.N <= INT32_MAX;
   for (size_t r = 0; r < R; ++r)
-    ok = ok && std::abs(n_ffts[r]) <= INT32_MAX && std::abs(hops[r]) <= INT32_MAX && std::abs(win_lengths[r]) <= INT32_MAX;
-  for (size_t r = 0; ok && r < R; ++r) {
-    nf[r] = (int)n_ffts[r], hp[r] = (int)hops[r], wl[r] = (int)win_lengths[r];
+    s.ok = s.ok && std::abs(n_ffts[r]) <= INT32_MAX && std::abs(hops[r]) <= INT32_MAX && std::abs(win_lengths[r]) <= INT32_MAX;
+  for (size_t r = 0; s.ok && r < R; ++r) {
+    s.nf[r] = (int)n_ffts[r], s.hp[r] = (int)hops[r], s.wl[r] = (int)win_lengths[r];
     check_dev(dfts[r], "dfts");
     check_same_device(x, "x", dfts[r], "dfts");
-    const size_t nbytes = nws_stft_loss_dft_bytes(nf[r], wl[r]);
-    TORCH_CHECK(nbytes > 0 && (size_t)dfts[r].numel() * sizeof(float) == nbytes, "stft_loss: dfts[", r, "] does not belong to n_fft = ",
-                nf[r], ", win_length = ", wl[r], " (n_fft: a power of two in [64, 2048], 1 <= win_length <= n_fft)");
-    dp[r] = dfts[r].data_ptr<float>();
+    const size_t nbytes = nws_stft_loss_dft_bytes(s.nf[r], s.wl[r]);
+    TORCH_CHECK(nbytes > 0 && (size_t)dfts[r].numel() * sizeof(float) == nbytes, op, ": dfts[", r, "] does not belong to n_fft = ",
+                s.nf[r], ", win_length = ", s.wl[r], " (n_fft: a power of two in [64, 2048], 1 <= win_length <= n_fft)");
+    s.dp[r] = dfts[r].data_ptr<float>();
   }
-  const size_t nbytes = ok && B <= 65535 ? nws_stft_loss_workspace_bytes((int)B, (int)N, (int)R, nf, hp) : 0;
-  TORCH_CHECK(nbytes > 0, "stft_loss: unsupported size (B ", B, ", N ", N, ", n_ffts ", n_ffts, ", hops ", hops,
-              "): N > n_fft / 2 (reflect padding), hop >= 1, the two signal tiles of 31 hop + n_fft samples must fit 160 KB of LDS "
-              "(n_fft 2048: hop <= 589), B <= 65535");
+  return s;
+}
+#define STFT_CHECK_SUPPORTED(op, nbytes, s, n_ffts, hops)                                                                              \
+  TORCH_CHECK(nbytes > 0, op, ": unsupported size (B ", s.B, ", N ", s.N, ", n_ffts ", n_ffts, ", hops ", hops,                        \
+              "): N > n_fft / 2 (reflect padding), hop >= 1, the two signal tiles of 31 hop + n_fft samples must fit 160 KB of LDS " \
+              "(n_fft 2048: hop <= 589), B <= 65535")
+
+// x, y (B, N) -> [loss (0-dim), components (R, 3) = (sc_r, log_r, lin_r)]
+std::vector<Tensor> stft_loss(const Tensor& x, const Tensor& y, at::TensorList dfts, at::IntArrayRef n_ffts, at::IntArrayRef hops,
+                              at::IntArrayRef win_lengths, double w_sc, double w_log_mag, double w_lin_mag, double eps) {
+  const StftSizes s = stft_sizes("stft_loss", x, y, dfts, n_ffts, hops, win_lengths);
+  const int B = (int)s.B, N = (int)s.N, R = (int)s.R;
+  const size_t nbytes = s.ok ? nws_stft_loss_workspace_bytes(B, N, R, s.nf, s.hp) : 0;
+  STFT_CHECK_SUPPORTED("stft_loss", nbytes, s, n_ffts, hops);
   Launch L(x);
   Tensor ws = at::empty({(int64_t)nbytes}, x.options().dtype(at::kByte));
   Tensor out = at::empty({(int64_t)(1 + 3 * R)}, x.options());
-  nws_check(nws_stft_loss(x.data_ptr<float>(), y.data_ptr<float>(), (int)B, (int)N, (int)R, nf, hp, wl, dp, (float)w_sc,
-                          (float)w_log_mag, (float)w_lin_mag, (float)eps, out.data_ptr<float>(), ws.data_ptr(), nbytes, L.stream),
+  nws_check(nws_stft_loss(x.data_ptr<float>(), y.data_ptr<float>(), B, N, R, s.nf, s.hp, s.wl, s.dp, (float)w_sc, (float)w_log_mag,
+                          (float)w_lin_mag, (float)eps, out.data_ptr<float>(), ws.data_ptr(), nbytes, L.stream),
             "nws_stft_loss");
   return {out[0], out.slice(0, 1).view({(int64_t)R, 3})};
+}
+
+// dL/dx of stft_loss(x, y, ...) (csrc/stft_grad.hip): x, y (B, N) -> (B, N).  No gradient for the target y.
+Tensor stft_loss_grad(const Tensor& x, const Tensor& y, at::TensorList dfts, at::IntArrayRef n_ffts, at::IntArrayRef hops,
+                      at::IntArrayRef win_lengths, double w_sc, double w_log_mag, double w_lin_mag, double eps) {
+  const StftSizes s = stft_sizes("stft_loss_grad", x, y, dfts, n_ffts, hops, win_lengths);
+  const int B = (int)s.B, N = (int)s.N, R = (int)s.R;
+  const size_t nbytes = s.ok ? nws_stft_grad_workspace_bytes(B, N, R, s.nf, s.hp, s.wl) : 0;
+  STFT_CHECK_SUPPORTED("stft_loss_grad", nbytes, s, n_ffts, hops);
+  Launch L(x);
+  Tensor ws = at::empty({(int64_t)nbytes}, x.options().dtype(at::kByte));
+  Tensor grad = at::empty({s.B, s.N}, x.options());
+  nws_check(nws_stft_grad(x.data_ptr<float>(), y.data_ptr<float>(), B, N, R, s.nf, s.hp, s.wl, s.dp, (float)w_sc, (float)w_log_mag,
+                          (float)w_lin_mag, (float)eps, grad.data_ptr<float>(), ws.data_ptr(), nbytes, L.stream),
+            "nws_stft_grad");
+  return grad;
 }
 
 // ---- runtime-size path (csrc/generic.hip): any gin configuration of the reference --------------------------------------
@@ -1231,5 +1263,7 @@ TORCH_LIBRARY(newt_hip, m) {
   m.def("stft_loss_dft(int n_fft, int win_length) -> Tensor", &stft_loss_dft);
   m.def("stft_loss(Tensor x, Tensor y, Tensor[] dfts, int[] n_ffts, int[] hops, int[] win_lengths, float w_sc, float w_log_mag, "
         "float w_lin_mag, float eps) -> Tensor[]", &stft_loss);
+  m.def("stft_loss_grad(Tensor x, Tensor y, Tensor[] dfts, int[] n_ffts, int[] hops, int[] win_lengths, float w_sc, float w_log_mag, "
+        "float w_lin_mag, float eps) -> Tensor", &stft_loss_grad);
   m.def("mfcc(Tensor audio, Tensor dft, Tensor table, float sample_rate, int n_fft, int hop, int n_mfcc, int n_mels) -> Tensor", &mfcc);
 }
