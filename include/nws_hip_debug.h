@@ -18,6 +18,21 @@ int nws_debug_frame_mlps_kernel(int mode);
  * busy for `spin_us` microseconds of the wall clock - what a collective's ring kernels take from the oscillator kernel. */
 int nws_debug_queue_busy(int groups, int spin_us, float* sink /* device float[256] */, void* stream);
 
+/* Tests: which oscillator-to-NEWT kernel nws_forward_generic launches for `model` (sizes and shaper.lut == NULL only: no pointer
+ * is followed) at batch B and T frames, and with what.  Reports, launches nothing, changes nothing.
+ *   out[0] family: 0 none (more than 64 shapers / 4 output channels, or LDS: the stage kernels run), 1 g_exciter_newt_mfma_kernel
+ *                  <MT, OCT>, 2 g_exciter_newt_kernel<SB, EXC_ONLY> (thread per sample: the mixer fragments do not fit LDS)
+ *   out[1] MT (family 1) or SB (family 2)     out[2] OCT: 1 / 2 / 4, 0 = the kernel stops at the exciter (sin-MLP shapers)
+ *   out[3] tpw, tiles of 32 samples per wave (family 1)     out[4] nf, FiLM frames staged per workgroup
+ *   out[5] dynamic LDS bytes     out[6] 1: nws_g_film_shaper and nws_g_conv1x1 follow the kernel
+ *   out[7] tpw by the ">= 1024 workgroups" rule alone, before the LDS rules lowered it (family 1) */
+int nws_debug_generic_exciter_plan(const NwsGenericModel* model, int B, int T, int out[8]);
+
+/* Tests: which recurrence nws_g_gru launches.  out[0]: 0 the default-shape kernel of csrc/control_gru.hip (hidden 128, C_in 2),
+ * 1 g_gru_q_kernel<kq> (W_hh in registers), 2 g_gru_kernel (W_hh streamed from L2); out[1] kq (8 / 16 / 32, else 0); out[2]
+ * workgroup size; out[3] dynamic LDS bytes.  NWS_ERR_UNSUPPORTED where nws_g_gru refuses. */
+int nws_debug_generic_gru_plan(int hidden, int C_in, int out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -205,6 +205,8 @@ _PROTOTYPES = {
     "nws_g_fir_noise": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp]),
     "nws_g_reverb_direct": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "nws_forward_generic_workspace_bytes": (C.c_size_t, [C.POINTER(NwsGenericModel), C.c_int, C.c_int]),
+    "nws_debug_generic_exciter_plan": (C.c_int, [C.POINTER(NwsGenericModel), C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "nws_debug_generic_gru_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "nws_forward_generic": (C.c_int, [C.POINTER(NwsGenericModel), _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp,
                                       C.POINTER(NwsReverbPlan), _fp, _fp, _fp, C.c_size_t, _fp, _fp, C.c_size_t, _fp]),
     "nws_stream_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.POINTER(NwsReverbPlan)]),

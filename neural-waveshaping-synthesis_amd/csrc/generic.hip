@@ -1211,6 +1211,85 @@ int ensure_lds(const void* fn, unsigned long long& mask) {
 
 size_t al(size_t b) { return (b + 255) & ~size_t(255); }
 
+// ---- which recurrence nws_g_gru launches (the host-side choice in one place; nws_debug_generic_gru_plan reports it) --------
+enum { kGGruDefault = 0, kGGruQuad = 1, kGGruStream = 2 };
+struct GGruPlan {
+  int kernel;      // kGGruDefault: control_gru.hip's kernel (GRU(2 -> 128)); kGGruQuad: g_gru_q_kernel<kq>; kGGruStream: g_gru_kernel
+  int kq;          // 8 / 16 / 32 (kGGruQuad), else 0
+  int threads;     // workgroup size
+  size_t lds;      // dynamic LDS bytes of the launch (0 for the default kernel: static)
+};
+size_t g_gru_stream_lds(int hidden, int C_in) { return ((size_t)2 * hidden + C_in) * sizeof(float); }
+GGruPlan g_gru_plan(int hidden, int C_in) {
+  if (hidden == 128 && C_in == 2) return GGruPlan{kGGruDefault, 0, 0, 0};
+  if (hidden <= 128) {
+    // W_hh in registers: four lanes per hidden unit (whole waves: units rounded up to 16)
+    const int threads = 4 * ((hidden + 15) & ~15);
+    const int kq = hidden <= 32 ? 8 : hidden <= 64 ? 16 : 32;
+    const size_t qlds = ((size_t)2 * 4 * kq + 2 * C_in + (size_t)3 * hidden * C_in) * sizeof(float);
+    // (g_gru_q_kernel stages a frame's C_in inputs with one thread each: more channels than threads - 64 threads at hidden <= 16 -
+    // would leave the rest of the frame unread, so those sizes take g_gru_kernel, whose loads stride)
+    if (qlds <= 64 * 1024 && C_in <= threads) return GGruPlan{kGGruQuad, kq, threads, qlds};
+  }
+  return GGruPlan{kGGruStream, 0, 256, g_gru_stream_lds(hidden, C_in)};
+}
+
+// ---- which kernel g_exciter_newt_fused launches, and with what (nws_debug_generic_exciter_plan reports it) ---------------
+enum { kGExcStages = 0, kGExcMfma = 1, kGExcThread = 2 };
+struct GExciterPlan {
+  int family;      // kGExcStages: nothing fits, the caller runs the stage kernels; kGExcMfma: g_exciter_newt_mfma_kernel<MT, OCT>;
+                   // kGExcThread: g_exciter_newt_kernel<SB, EXC_ONLY> (thread per sample)
+  int size;        // MT (kGExcMfma) or SB (kGExcThread)
+  int oct;         // output-channel bucket 1 / 2 / 4; 0: the kernel stops at the exciter (sin-MLP shapers)
+  int tpw;         // tiles of 32 samples per wave (kGExcMfma), else 0
+  int nf;          // FiLM frames staged per workgroup
+  size_t lds;      // dynamic LDS bytes
+  int follow;      // 1: nws_g_film_shaper + nws_g_conv1x1 follow the kernel (oct == 0)
+  int tpw_grid;    // tpw by the >= 1024 workgroups rule alone, before the LDS rules lowered it (kGExcMfma)
+};
+GExciterPlan g_exciter_plan(int S, int K, int OC, int hop, bool exc_only, int B, int N) {
+  GExciterPlan p{};
+  if (S > 64 || OC > 4 || B > 65535) return p;
+  p.oct = exc_only ? 0 : OC == 1 ? 1 : OC == 2 ? 2 : 4;
+  p.follow = exc_only ? 1 : 0;
+  {
+    // matrix-pipe mixer (the thread-per-sample kernel below when its LDS does not fit): tiles of 32 samples, `tpw` per wave as long as the launch keeps >= 1024 workgroups
+    const int MT = S <= 32 ? 1 : 2, SBM = 32 * MT, K16 = (K + 15) / 16;
+    int tpw = 4;
+    while (tpw > 1 && (long long)((N + 128 * tpw - 1) / (128 * tpw)) * B < 1024) tpw >>= 1;
+    p.tpw_grid = tpw;
+    // ... and as long as the FiLM rows of the workgroup's frames fit LDS next to the fragments (short hops: many frames per tile)
+    auto lds_of = [&](int t) {
+      const size_t frames = (size_t)(128 * t / hop + 3);
+      return ((size_t)K16 * MT * 512 + 16 * K16 + 5 * (size_t)SBM + (exc_only ? 0 : (size_t)8 * SBM * frames)) * sizeof(float);
+    };
+    // FOUR workgroups per CU when fewer tiles per wave allow it (120 registers permit 4 waves per SIMD; the fragments alone
+    // are 28 KB at the default sizes: 44.7 KB = 3 workgroups with four tiles per wave, 40.6 KB = 4 with two), else two
+    constexpr size_t lds_goal = 40960;
+    {
+      int t4 = tpw;
+      while (t4 > 1 && lds_of(t4) > lds_goal) t4 >>= 1;
+      if (lds_of(t4) <= lds_goal) tpw = t4;
+    }
+    while (tpw > 1 && lds_of(tpw) > 80 * 1024) tpw >>= 1;     // two workgroups per CU
+    if (lds_of(tpw) <= 160 * 1024) {
+      p.family = kGExcMfma;
+      p.size = MT;
+      p.tpw = tpw;
+      p.nf = 128 * tpw / hop + 3;
+      p.lds = lds_of(tpw);
+      return p;
+    }
+  }
+  p.tpw_grid = 0;
+  p.nf = 256 / hop + 3;                  // frames 256 consecutive samples can touch (+ the clamped right neighbour)
+  p.lds = exc_only ? (size_t)K * sizeof(float) : ((size_t)K + (size_t)4 * S * p.nf) * sizeof(float);
+  if (p.lds > 160 * 1024) return GExciterPlan{};
+  p.family = kGExcThread;
+  p.size = S <= 8 ? 8 : S <= 16 ? 16 : S <= 32 ? 32 : 64;
+  return p;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1223,10 +1302,11 @@ int nws_g_gru(const float* w_ih, const float* w_hh, const float* b_ih, const flo
   if (!w_ih || !w_hh || !b_ih || !b_hh || !control || !out || !workspace) return NWS_ERR_BAD_ARG;
   if (B <= 0 || T <= 0 || hidden <= 0 || C_in <= 0 || C_total < C_in) return NWS_ERR_BAD_ARG;
   if (workspace_bytes < nws_g_gru_workspace_bytes(hidden)) return NWS_ERR_WORKSPACE;
-  const size_t lds = ((size_t)2 * hidden + C_in) * sizeof(float);
+  const size_t lds = g_gru_stream_lds(hidden, C_in);
   if (lds > 160 * 1024) return NWS_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  if (hidden == 128 && C_in == 2) {
+  const GGruPlan plan = g_gru_plan(hidden, C_in);
+  if (plan.kernel == kGGruDefault) {
     // the reference's default recurrence (GRU(2 -> 128)) inside an otherwise non-default configuration: the fused path's
     // kernel (control_gru.hip: 0.44 us per step against 0.8 for the runtime-size recurrence below), same layouts
     NwsWeights w{};
@@ -1236,20 +1316,17 @@ int nws_g_gru(const float* w_ih, const float* w_hh, const float* b_ih, const flo
     w.gru_b_hh = b_hh;
     return nws_control_gru_state(&w, control, B, C_total, T, h0, out, hT, stream);
   }
-  if (hidden <= 128) {
+  if (plan.kernel == kGGruQuad) {
     // W_hh in registers: four lanes per hidden unit (whole waves: units rounded up to 16)
-    const int threads = 4 * ((hidden + 15) & ~15);
-    const int kq = hidden <= 32 ? 8 : hidden <= 64 ? 16 : 32;
-    const size_t qlds = ((size_t)2 * 4 * kq + 2 * C_in + (size_t)3 * hidden * C_in) * sizeof(float);
-    if (qlds <= 64 * 1024) {
-      switch (kq) {
-        case 8: g_gru_q_kernel<8><<<B, threads, qlds, st>>>(w_ih, w_hh, b_ih, b_hh, control, C_total, C_in, hidden, T, h0, out, hT); break;
-        case 16: g_gru_q_kernel<16><<<B, threads, qlds, st>>>(w_ih, w_hh, b_ih, b_hh, control, C_total, C_in, hidden, T, h0, out, hT); break;
-        default: g_gru_q_kernel<32><<<B, threads, qlds, st>>>(w_ih, w_hh, b_ih, b_hh, control, C_total, C_in, hidden, T, h0, out, hT); break;
-      }
-      NWS_CHECK_LAUNCH();
-      return NWS_OK;
+    const int threads = plan.threads;
+    const size_t qlds = plan.lds;
+    switch (plan.kq) {
+      case 8: g_gru_q_kernel<8><<<B, threads, qlds, st>>>(w_ih, w_hh, b_ih, b_hh, control, C_total, C_in, hidden, T, h0, out, hT); break;
+      case 16: g_gru_q_kernel<16><<<B, threads, qlds, st>>>(w_ih, w_hh, b_ih, b_hh, control, C_total, C_in, hidden, T, h0, out, hT); break;
+      default: g_gru_q_kernel<32><<<B, threads, qlds, st>>>(w_ih, w_hh, b_ih, b_hh, control, C_total, C_in, hidden, T, h0, out, hT); break;
     }
+    NWS_CHECK_LAUNCH();
+    return NWS_OK;
   }
   float* wt = static_cast<float*>(workspace);
   const int cells = 3 * hidden * hidden;
@@ -1544,34 +1621,18 @@ static int g_exciter_newt_fused(const NwsGenericModel* m, const float* f0_up, co
                                 const float* rand_phase, const float* film, int B, int T, int N, float sample_rate, float* scratch,
                                 float* newt_out, float* exciter_out, float* shaped, void* stream) {
   const int S = m->n_shapers, K = m->n_harmonics, OC = m->out_channels;
-  if (S > 64 || OC > 4 || B > 65535) return NWS_ERR_UNSUPPORTED;
   const bool exc_only = m->shaper.lut == nullptr;     // sin-MLP shapers: see EXC_ONLY
+  const GExciterPlan plan = g_exciter_plan(S, K, OC, m->hop, exc_only, B, N);
+  if (plan.family == kGExcStages) return NWS_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const float scale = (float)T / (float)N;
   const NwsShaperDesc* d = &m->shaper;
   const GShaper P = to_dev(d);
   {
-    // matrix-pipe mixer (the thread-per-sample kernel below when its LDS does not fit): tiles of 32 samples, `tpw` per wave as long as the launch keeps >= 1024 workgroups
-    const int MT = S <= 32 ? 1 : 2, SBM = 32 * MT, K16 = (K + 15) / 16;
-    int tpw = 4;
-    while (tpw > 1 && (long long)((N + 128 * tpw - 1) / (128 * tpw)) * B < 1024) tpw >>= 1;
-    // ... and as long as the FiLM rows of the workgroup's frames fit LDS next to the fragments (short hops: many frames per tile)
-    auto lds_of = [&](int t) {
-      const size_t frames = (size_t)(128 * t / m->hop + 3);
-      return ((size_t)K16 * MT * 512 + 16 * K16 + 5 * (size_t)SBM + (exc_only ? 0 : (size_t)8 * SBM * frames)) * sizeof(float);
-    };
-    // FOUR workgroups per CU when fewer tiles per wave allow it (120 registers permit 4 waves per SIMD; the fragments alone
-    // are 28 KB at the default sizes: 44.7 KB = 3 workgroups with four tiles per wave, 40.6 KB = 4 with two), else two
-    constexpr size_t lds_goal = 40960;
-    {
-      int t4 = tpw;
-      while (t4 > 1 && lds_of(t4) > lds_goal) t4 >>= 1;
-      if (lds_of(t4) <= lds_goal) tpw = t4;
-    }
-    while (tpw > 1 && lds_of(tpw) > 80 * 1024) tpw >>= 1;     // two workgroups per CU
-    const int nf = 128 * tpw / m->hop + 3;
-    const size_t lds = lds_of(tpw);
-    if (lds <= 160 * 1024) {
+    if (plan.family == kGExcMfma) {
+      const int MT = plan.size, SBM = 32 * MT, K16 = (K + 15) / 16;
+      const int tpw = plan.tpw, nf = plan.nf;
+      const size_t lds = plan.lds;
       // scratch: [fragments K16 x MT x 512 floats | scale, 1 / scale, pad | table pairs]
       gf16x8* frag = reinterpret_cast<gf16x8*>(scratch);
       float* scl = scratch + (size_t)K16 * MT * 512;
@@ -1591,7 +1652,7 @@ static int g_exciter_newt_fused(const NwsGenericModel* m, const float* f0_up, co
                                                                   m->newt_out_w, m->newt_out_b, pairs, K, T, N, scale,             \
                                                                   sample_rate, OC, nf, tpw, rdiv, OCTV == 0 ? exciter_out : newt_out); \
   }
-      const int oct = exc_only ? 0 : OC == 1 ? 1 : OC == 2 ? 2 : 4;
+      const int oct = plan.oct;
       const float rdiv = exc_only ? 0.0f : (float)(1.0 / (double)(P.lut_max - P.lut_min));
       if (MT == 1) {
         if (oct == 0) NWS_G_EM(1, 0) else if (oct == 1) NWS_G_EM(1, 1) else if (oct == 2) NWS_G_EM(1, 2) else NWS_G_EM(1, 4)
@@ -1608,10 +1669,8 @@ static int g_exciter_newt_fused(const NwsGenericModel* m, const float* f0_up, co
       return NWS_OK;
     }
   }
-  const int SB = S <= 8 ? 8 : S <= 16 ? 16 : S <= 32 ? 32 : 64;
-  const int nf = 256 / m->hop + 3;                  // frames 256 consecutive samples can touch (+ the clamped right neighbour)
-  const size_t lds = exc_only ? (size_t)K * sizeof(float) : ((size_t)K + (size_t)4 * S * nf) * sizeof(float);
-  if (lds > 160 * 1024) return NWS_ERR_UNSUPPORTED;
+  const int SB = plan.size, nf = plan.nf;
+  const size_t lds = plan.lds;
   g_mixer_t_kernel<<<(K * SB + 255) / 256, 256, 0, st>>>(m->mixer_w, S, K, SB, scratch);
   NWS_CHECK_LAUNCH();
   const dim3 grid((N + 255) / 256, 1, B);
@@ -1655,6 +1714,35 @@ size_t nws_forward_generic_workspace_bytes(const NwsGenericModel* m, int B, int 
   t += fb((size_t)B * m->out_channels * N) + fb((size_t)B * N) + fb(g_tab_floats(m));
   t += fb((size_t)(m->fir_len / 2 + 1) * m->fir_len) + al(g_phase_partials(B, (long long)N) * sizeof(double));
   return t;
+}
+
+// Diagnostics (include/nws_hip_debug.h): what the two choosers above decide for given sizes.  Host arithmetic only: nothing is
+// launched, no pointer of the model is followed (shaper.lut is only compared with NULL).
+int nws_debug_generic_exciter_plan(const NwsGenericModel* m, int B, int T, int out[8]) {
+  if (!m || !out || B <= 0 || T <= 0 || m->n_shapers < 1 || m->n_harmonics < 1 || m->out_channels < 1 || m->hop < 1) return NWS_ERR_BAD_ARG;
+  const long long N = (long long)T * m->hop;
+  if (N > (1ll << 30)) return NWS_ERR_UNSUPPORTED;
+  const GExciterPlan p = g_exciter_plan(m->n_shapers, m->n_harmonics, m->out_channels, m->hop, m->shaper.lut == nullptr, B, (int)N);
+  out[0] = p.family;
+  out[1] = p.size;
+  out[2] = p.oct;
+  out[3] = p.tpw;
+  out[4] = p.nf;
+  out[5] = (int)p.lds;
+  out[6] = p.follow;
+  out[7] = p.tpw_grid;
+  return NWS_OK;
+}
+
+int nws_debug_generic_gru_plan(int hidden, int C_in, int out[4]) {
+  if (!out || hidden <= 0 || C_in <= 0) return NWS_ERR_BAD_ARG;
+  if (g_gru_stream_lds(hidden, C_in) > 160 * 1024) return NWS_ERR_UNSUPPORTED;
+  const GGruPlan p = g_gru_plan(hidden, C_in);
+  out[0] = p.kernel;
+  out[1] = p.kq;
+  out[2] = p.threads;
+  out[3] = (int)p.lds;
+  return NWS_OK;
 }
 
 int nws_forward_generic(const NwsGenericModel* m, const float* f0, const float* control, int B, int C, int T, float sample_rate,
