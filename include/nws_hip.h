@@ -257,6 +257,21 @@ int nws_reverb_ir_spectrum(const NwsReverbPlan* plan, const void* tables, const 
 int nws_reverb(const NwsReverbPlan* plan, const void* tables, const void* spectrum, const float* x /* (B,N) */,
                int B, int N, float* y /* (B,N) */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The transpose of nws_reverb for g = dL/dy (B,N), same plan, tables and spectrum:
+ *   dx[b,i]  = g[b,i] + sum_m h[m] g_[b,(i+m) mod Lc]           i < N          (circular correlation with h = [0, ir, 0...])
+ *   dir[j-1] = sum_b sum_{n<N} g[b,n] x_[b,(n-j) mod Lc]        j = 1..ir_len  (summed over the batch)
+ * grad_x is the forward's three launches with the conjugated spectrum; grad_ir transforms the x pairs and the g pairs, sums
+ * conj(Zx) Zg per bin over pairs and blocks in a fixed order (no atomics: equal inputs give equal bits) and runs ONE inverse
+ * transform.  Both launch on `stream`, read nothing back, and refuse like nws_reverb (NWS_ERR_BAD_ARG, NWS_ERR_WORKSPACE,
+ * NWS_ERR_UNSUPPORTED beyond 65 535 utterance pairs) before the first launch.  Workspace: nws_reverb_grad_workspace_bytes
+ * (host only; 0 for a bad plan or B < 1; want_ir = 0: what grad_x needs = nws_reverb_workspace_bytes). */
+size_t nws_reverb_grad_workspace_bytes(const NwsReverbPlan* plan, int B, int want_ir);
+int nws_reverb_grad_x(const NwsReverbPlan* plan, const void* tables, const void* spectrum, const float* g /* (B,N) */,
+                      int B, int N, float* dx /* (B,N) */, void* workspace, size_t workspace_bytes, void* stream);
+int nws_reverb_grad_ir(const NwsReverbPlan* plan, const void* tables, const float* x /* (B,N) */, const float* g /* (B,N) */,
+                       int B, int N, int ir_len, float* dir /* (ir_len) */, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* streaming (LINEAR, non-wrapping) variant, one chunk of M samples: y = x + wet[0:M] + tail_in[0:M]; tail_out = shifted
  * tail_in + rest of wet.  plan->L >= M + tail_len (tail_len = len(ir)+1 = 32000); workspace (2*ceil(B/2)*L + B*L) floats. */
 int nws_reverb_linear_chunk(const NwsReverbPlan* plan, const void* tables, const void* spectrum, const float* x, int B, int M,

@@ -232,6 +232,30 @@ class CtypesOps:
                                         _stream(x.device)), "nws_reverb")
         return y
 
+    def reverb_grad_x(self, plan, tables, spectrum, grad_out):
+        B, N = grad_out.shape
+        p = _plan(plan)
+        with torch.cuda.device(grad_out.device):
+            nbytes = _lib.lib().nws_reverb_grad_workspace_bytes(C.byref(p), B, 0)
+            ws = _new(grad_out, nbytes, dtype=torch.uint8)
+            dx = torch.empty_like(grad_out)
+            check(_lib.lib().nws_reverb_grad_x(C.byref(p), ptr(tables), ptr(spectrum), ptr(grad_out), B, N, ptr(dx), ptr(ws), nbytes,
+                                               _stream(grad_out.device)), "nws_reverb_grad_x")
+        return dx
+
+    def reverb_grad_ir(self, plan, tables, x, grad_out, ir_len):
+        B, N = x.shape
+        if tuple(grad_out.shape) != (B, N):
+            raise RuntimeError(f"reverb_grad_ir: x {tuple(x.shape)} and grad_out {tuple(grad_out.shape)} differ in shape")
+        p = _plan(plan)
+        with torch.cuda.device(x.device):
+            nbytes = _lib.lib().nws_reverb_grad_workspace_bytes(C.byref(p), B, 1)
+            ws = _new(x, nbytes, dtype=torch.uint8)
+            dir_ = _new(x, ir_len)
+            check(_lib.lib().nws_reverb_grad_ir(C.byref(p), ptr(tables), ptr(x), ptr(grad_out), B, N, ir_len, ptr(dir_), ptr(ws),
+                                                nbytes, _stream(x.device)), "nws_reverb_grad_ir")
+        return dir_
+
     def reverb_linear_chunk(self, plan, tables, spectrum, x, tail_in):
         B, M = x.shape
         p = _plan(plan)

@@ -19,6 +19,11 @@
 // L = 125 * 2^k point transform that starts hist = len(ir) samples before output j * (L - hist); its last L - hist points are
 // final samples of the length-Lc circular convolution.  The wrap-around lives in the column pass's loads; the row pass sees
 // pairs * nblk independent transforms.  So every even Lc has a plan (Reverb.forward takes any N, shaping.py:161-173).
+//
+// The TRANSPOSE runs on the same kernels: dL/dx = g + circular correlation of g with [0, ir] is the forward with the
+// cached spectrum conjugated (and, in overlap-save, blocks that look ahead instead of back); dL/d(ir) transforms the x pairs and
+// the g pairs, sums conj(Zx) Zg per bin over pairs and blocks in a fixed order and inverts that ONE sum - with the forward's packing
+// Re of it is corr(x_a, g_a) + corr(x_b, g_b), the cross terms land in Im.
 #include <stdlib.h>
 
 #include "nws_common.h"
@@ -181,7 +186,12 @@ __device__ __forceinline__ void fft125_tile(float2* bufA, float2* bufB, const fl
   }
 }
 
-template <bool OLS>
+// overlap-save block geometry of the column loads: the forward's block starts `hist` samples BEFORE its
+// first output; the transpose (dL/dx) starts AT its first output and looks ahead; dL/d(ir) correlates the forward's own
+// block with one that holds only the block's own outputs (positions < hist and samples >= N are zero)
+constexpr int kGeomHistory = 0, kGeomAhead = 1, kGeomOwn = 2;
+
+template <bool OLS, int GEOM = kGeomHistory>
 __global__ __launch_bounds__(kColThreads) void col125_fwd_kernel(PlanDev d, const float2* __restrict__ tw125_g,
                                                          const float* __restrict__ x, int B, int N, long long x_stride,
                                                          float* __restrict__ Ure, float* __restrict__ Uim) {
@@ -205,8 +215,11 @@ __global__ __launch_bounds__(kColThreads) void col125_fwd_kernel(PlanDev d, cons
       const int e = tid + kColThreads * i;
       int n = d.N2 * (e >> 5) + c0 + (e & 31);
       if (OLS) {   // position n of block blk = sample (blk P - hist + n) of the Lc-periodic signal (N .. Lc-1: zeros)
-        n += blk * d.P - d.hist;
+        const int pos = n;
+        n += GEOM == kGeomAhead ? blk * d.P : blk * d.P - d.hist;
+        const bool own = GEOM != kGeomOwn || (pos >= d.hist && n < N);   // before the wrap: a sample past Lc is not an output
         n = n < 0 ? n + d.Lc : (int)((unsigned)n % (unsigned)d.Lc);
+        if (!own) n = N;
       }
       const bool in = n < N;
       v[i] = make_float2((in && x0) ? x0[n] : 0.0f, (in && x1) ? x1[n] : 0.0f);
@@ -226,7 +239,7 @@ __global__ __launch_bounds__(kColThreads) void col125_fwd_kernel(PlanDev d, cons
   }
 }
 
-template <bool OLS>
+template <bool OLS, bool AHEAD = false>
 __global__ __launch_bounds__(kColThreads) void col125_inv_kernel(PlanDev d, const float2* __restrict__ tw125_g,
                                                          const float* __restrict__ Ure, const float* __restrict__ Uim,
                                                          const float* __restrict__ x, int B, int N,
@@ -262,8 +275,9 @@ __global__ __launch_bounds__(kColThreads) void col125_inv_kernel(PlanDev d, cons
   for (int i = 0; i < kColPer; ++i) {
     const int e = tid + kColThreads * i;
     const int pos = d.N2 * (e >> 5) + c0 + (e & 31);
-    const long long n = OLS ? (long long)blk * d.P + pos - d.hist : (long long)pos;
-    const bool keep = OLS ? (pos >= d.hist && n < N) : (e < rows_out * 32 && n < N);
+    // (AHEAD, the transpose: position i of block blk is output blk P + i, the LAST hist positions are wrapped look-ahead)
+    const long long n = OLS ? (AHEAD ? (long long)blk * d.P + pos : (long long)blk * d.P + pos - d.hist) : (long long)pos;
+    const bool keep = OLS ? ((AHEAD ? pos < d.P : pos >= d.hist) && n < N) : (e < rows_out * 32 && n < N);
     nout[i] = keep ? n : -1;
     const bool in = x != nullptr && keep;
     const size_t o0 = (size_t)(2 * p) * N + (keep ? n : 0);
@@ -420,7 +434,16 @@ __device__ __forceinline__ float2* stockham(float2* x, float2* y, const float2* 
   return x;
 }
 
-template <bool SPECTRUM_ONLY, int kMaxPer>
+// what a row kernel does between its load and its store:
+//   kRowFused        forward, x spectrum H[k1][.], inverse                          (Reverb.forward)
+//   kRowSpectrum     forward only, written to S[k1][.]: ONE transform                (the IR spectrum)
+//   kRowFusedConj    kRowFused with conj(H): circular CORRELATION with the kernel    (dL/dx)
+//   kRowSpectrumSlots forward only, in place on U: any number of transforms          (dL/d(ir): spectra of the x and g pairs)
+//   kRowInverse      inverse only, in place on U (which holds a spectrum)            (dL/d(ir): the summed cross spectrum)
+constexpr int kRowFused = 0, kRowSpectrum = 1, kRowFusedConj = 2, kRowSpectrumSlots = 3, kRowInverse = 4;
+constexpr bool row_fused(int mode) { return mode == kRowFused || mode == kRowFusedConj; }
+
+template <int MODE, int kMaxPer>
 __global__ __launch_bounds__(256) void row_kernel(PlanDev d, float* __restrict__ Ure, float* __restrict__ Uim,
                                                   const float2* __restrict__ tw, const float2* __restrict__ rowtw_g,
                                                   const float* __restrict__ Hre, const float* __restrict__ Him,
@@ -443,26 +466,36 @@ __global__ __launch_bounds__(256) void row_kernel(PlanDev d, float* __restrict__
     const bool in = i < d.N2;
     z[e] = in ? make_float2(Ure[base + i], Uim[base + i]) : make_float2(0.0f, 0.0f);
     t4[e] = in ? tw[hbase + i] : make_float2(0.0f, 0.0f);
-    h4[e] = (!SPECTRUM_ONLY && in) ? make_float2(Hre[hbase + i], Him[hbase + i]) : make_float2(0.0f, 0.0f);
+    h4[e] = (row_fused(MODE) && in) ? make_float2(Hre[hbase + i], MODE == kRowFusedConj ? -Him[hbase + i] : Him[hbase + i])
+                                    : make_float2(0.0f, 0.0f);
   }
   for (int i = tid; i < d.N2 / 2; i += 256) rowtw[i] = rowtw_g[i];
 #pragma unroll
   for (int e = 0; e < kMaxPer; ++e)
-    if (tid + 256 * e < d.N2) buf0[tid + 256 * e] = cmul(z[e], t4[e]);
+    if (tid + 256 * e < d.N2) buf0[tid + 256 * e] = MODE == kRowInverse ? z[e] : cmul(z[e], t4[e]);
   __syncthreads();
-  float2* cur = stockham<false>(buf0, buf1, rowtw, d.N2, tid, 256);
-  if (SPECTRUM_ONLY) {
+  float2* cur = MODE == kRowInverse ? buf0 : stockham<false>(buf0, buf1, rowtw, d.N2, tid, 256);
+  if (MODE == kRowSpectrum) {
     for (int i = tid; i < d.N2; i += 256) {
       Sre[hbase + i] = cur[i].x;
       Sim[hbase + i] = cur[i].y;
     }
     return;
   }
+  if (MODE == kRowSpectrumSlots) {
+    for (int i = tid; i < d.N2; i += 256) {
+      Ure[base + i] = cur[i].x;
+      Uim[base + i] = cur[i].y;
+    }
+    return;
+  }
   float2* other = cur == buf0 ? buf1 : buf0;
+  if (MODE != kRowInverse) {
 #pragma unroll
-  for (int e = 0; e < kMaxPer; ++e)
-    if (tid + 256 * e < d.N2) cur[tid + 256 * e] = cmul(cur[tid + 256 * e], h4[e]);
-  __syncthreads();
+    for (int e = 0; e < kMaxPer; ++e)
+      if (tid + 256 * e < d.N2) cur[tid + 256 * e] = cmul(cur[tid + 256 * e], h4[e]);
+    __syncthreads();
+  }
   cur = stockham<true>(cur, other, rowtw, d.N2, tid, 256);
   const float inv_l = 1.0f / (float)d.L;
 #pragma unroll
@@ -540,7 +573,7 @@ constexpr int kR8Floats = 2 * 8 * kR8Stride;       // re | im planes of one wave
 // both for the writers (k1, b) of one k2a and for the readers (k1, k2a) of one b
 __device__ __forceinline__ int r8_addr2(int k1, int b, int k2a) { return 64 * k1 + 8 * ((k1 + b) & 7) + ((b + k2a) & 7); }
 
-template <bool SPECTRUM_ONLY>
+template <int MODE>
 __global__ __launch_bounds__(256) void row512_kernel(PlanDev d, int rows, float* __restrict__ Ure, float* __restrict__ Uim,
                                                      const float2* __restrict__ tw, const float2* __restrict__ r8,
                                                      const float* __restrict__ Hre, const float* __restrict__ Him,
@@ -565,11 +598,11 @@ __global__ __launch_bounds__(256) void row512_kernel(PlanDev d, int rows, float*
     t4.re[j] = t.x;
     t4.im[j] = t.y;
   }
-  if (!SPECTRUM_ONLY) {
+  if (row_fused(MODE)) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       h.re[j] = Hre[hbase + lane + 64 * j];
-      h.im[j] = Him[hbase + lane + 64 * j];
+      h.im[j] = MODE == kRowFusedConj ? -Him[hbase + lane + 64 * j] : Him[hbase + lane + 64 * j];
     }
   }
   // twiddles of the two inner steps, k = 1..7: W512^(lane k) and W64^(lo3 k), lane-major tables (coalesced loads)
@@ -581,11 +614,13 @@ __global__ __launch_bounds__(256) void row512_kernel(PlanDev d, int rows, float*
     w2r[k] = c.x; w2i[k] = c.y;
   }
   // four-step twiddle of the column pass (tw[k1][n2])
+  if (MODE != kRowInverse) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float r = fmaf(z.re[j], t4.re[j], -(z.im[j] * t4.im[j])), i = fmaf(z.re[j], t4.im[j], z.im[j] * t4.re[j]);
-    z.re[j] = r;
-    z.im[j] = i;
+    for (int j = 0; j < 8; ++j) {
+      const float r = fmaf(z.re[j], t4.re[j], -(z.im[j] * t4.im[j])), i = fmaf(z.re[j], t4.im[j], z.im[j] * t4.re[j]);
+      z.re[j] = r;
+      z.im[j] = i;
+    }
   }
 
   auto twiddle = [](C8& v, const float (&wr)[8], const float (&wi)[8], bool conj) {
@@ -598,34 +633,36 @@ __global__ __launch_bounds__(256) void row512_kernel(PlanDev d, int rows, float*
     }
   };
   // ---- forward ----
-  dft8<false>(z);
-  twiddle(z, w1r, w1i, false);
+  if (MODE != kRowInverse) {
+    dft8<false>(z);
+    twiddle(z, w1r, w1i, false);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {          // writer lane l, register k1 = k
-    Lre[k * kR8Stride + lane] = z.re[k];
-    Lim[k * kR8Stride + lane] = z.im[k];
-  }
+    for (int k = 0; k < 8; ++k) {          // writer lane l, register k1 = k
+      Lre[k * kR8Stride + lane] = z.re[k];
+      Lim[k * kR8Stride + lane] = z.im[k];
+    }
 #pragma unroll
-  for (int a = 0; a < 8; ++a) {          // reader lane (k1 = hi3, b = lo3), register a
-    z.re[a] = Lre[hi3 * kR8Stride + 8 * a + lo3];
-    z.im[a] = Lim[hi3 * kR8Stride + 8 * a + lo3];
-  }
-  dft8<false>(z);
-  twiddle(z, w2r, w2i, false);
+    for (int a = 0; a < 8; ++a) {          // reader lane (k1 = hi3, b = lo3), register a
+      z.re[a] = Lre[hi3 * kR8Stride + 8 * a + lo3];
+      z.im[a] = Lim[hi3 * kR8Stride + 8 * a + lo3];
+    }
+    dft8<false>(z);
+    twiddle(z, w2r, w2i, false);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {          // writer lane (k1, b), register k2a = k
-    const int ad = r8_addr2(hi3, lo3, k);
-    Lre[ad] = z.re[k];
-    Lim[ad] = z.im[k];
-  }
+    for (int k = 0; k < 8; ++k) {          // writer lane (k1, b), register k2a = k
+      const int ad = r8_addr2(hi3, lo3, k);
+      Lre[ad] = z.re[k];
+      Lim[ad] = z.im[k];
+    }
 #pragma unroll
-  for (int b = 0; b < 8; ++b) {          // reader lane (k1, k2a = lo3), register b
-    const int ad = r8_addr2(hi3, b, lo3);
-    z.re[b] = Lre[ad];
-    z.im[b] = Lim[ad];
+    for (int b = 0; b < 8; ++b) {          // reader lane (k1, k2a = lo3), register b
+      const int ad = r8_addr2(hi3, b, lo3);
+      z.re[b] = Lre[ad];
+      z.im[b] = Lim[ad];
+    }
+    dft8<false>(z);
   }
-  dft8<false>(z);
-  if (SPECTRUM_ONLY) {
+  if (MODE == kRowSpectrum) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       Sre[hbase + lane + 64 * j] = z.re[j];
@@ -633,12 +670,22 @@ __global__ __launch_bounds__(256) void row512_kernel(PlanDev d, int rows, float*
     }
     return;
   }
-  // ---- x IR spectrum (same (lane, register) order) ----
+  if (MODE == kRowSpectrumSlots) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float r = fmaf(z.re[j], h.re[j], -(z.im[j] * h.im[j])), i = fmaf(z.re[j], h.im[j], z.im[j] * h.re[j]);
-    z.re[j] = r;
-    z.im[j] = i;
+    for (int j = 0; j < 8; ++j) {
+      Ure[base + lane + 64 * j] = z.re[j];
+      Uim[base + lane + 64 * j] = z.im[j];
+    }
+    return;
+  }
+  // ---- x IR spectrum (same (lane, register) order) ----
+  if (row_fused(MODE)) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float r = fmaf(z.re[j], h.re[j], -(z.im[j] * h.im[j])), i = fmaf(z.re[j], h.im[j], z.im[j] * h.re[j]);
+      z.re[j] = r;
+      z.im[j] = i;
+    }
   }
   // ---- inverse: the same three passes backwards ----
   dft8<true>(z);                          // over k2b -> b
@@ -704,7 +751,9 @@ __global__ void reverb_tail_kernel(const float* __restrict__ x, const float* __r
 // short streaming buffers of scripts/time_buffer_sizes.py (N <= 1024 << L = 32000) that is N^2 MACs from LDS in ONE launch
 // instead of three latency-bound FFT passes over 32000 points.  Four partial sums per thread; a direct fp32 sum of <= 1024
 // products is at least as close to the reference's result as a fp32 FFT.
+// ADJOINT (dL/dx of the same buffers): dx[n] = g[n] + sum_{k<N} g[k] irz[(k - n) mod L], the lag table read backwards.
 constexpr int kDirectMaxN = 1024;
+template <bool ADJOINT = false>
 __global__ __launch_bounds__(256) void reverb_direct_kernel(const float* __restrict__ x, const float* __restrict__ irz, int N,
                                                             int L, float* __restrict__ y) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -714,8 +763,8 @@ __global__ __launch_bounds__(256) void reverb_direct_kernel(const float* __restr
   const int n = blockIdx.x * 256 + tid;
   for (int i = tid; i < N; i += 256) xs[i] = x[(size_t)b * N + i];
   for (int i = tid; i < 2 * N; i += 256) {
-    const int d = i - N;
-    hs[i] = irz[d >= 0 ? d : d + L];
+    const int d = ADJOINT ? N - i : i - N;        // ADJOINT: d = N only at i = 0, which no thread reads (n + N - k >= 1)
+    hs[i] = irz[d >= 0 ? (ADJOINT && d >= L ? d - L : d) : d + L];
   }
   __syncthreads();
   if (n >= N) return;
@@ -738,15 +787,41 @@ __global__ void build_irz_kernel(const float* __restrict__ ir, int ir_len, int L
   if (i < L) out[i] = (i >= 1 && i <= ir_len) ? ir[i - 1] : 0.0f;
 }
 
+// dL/d(ir), per bin of the transform: sum over the slots (utterance pairs x overlap-save blocks) of conj(Zx) Zg, in slot order
+// by one thread - no atomics, so equal inputs give equal bits.  Re of the inverse transform of the packed product is
+// corr(x_a, g_a) + corr(x_b, g_b); the cross terms of the packing land in Im.
+__global__ __launch_bounds__(256) void cross_spectrum_kernel(const float* __restrict__ Xre, const float* __restrict__ Xim,
+                                                             const float* __restrict__ Gre, const float* __restrict__ Gim,
+                                                             int slots, int L, float* __restrict__ Are, float* __restrict__ Aim) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= L) return;
+  float ar = 0.0f, ai = 0.0f;
+#pragma unroll 4
+  for (int s = 0; s < slots; ++s) {
+    const size_t o = (size_t)s * L + e;
+    const float xr = Xre[o], xi = Xim[o], gr = Gre[o], gi = Gim[o];
+    ar = fmaf(xr, gr, fmaf(xi, gi, ar));
+    ai = fmaf(xr, gi, fmaf(-xi, gr, ai));
+  }
+  Are[e] = ar;
+  Aim[e] = ai;
+}
+
+// dir[j - 1] = c[j], j = 1 .. ir_len (lag 0 belongs to initial_zero, a buffer)
+__global__ void lags_to_ir_kernel(const float* __restrict__ c, int ir_len, float* __restrict__ dir) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < ir_len) dir[i] = c[i + 1];
+}
+
 // row pass of `pairs` packed transforms: wave-per-row radix-8 kernel for N2 = 512, the Stockham workgroup-per-row form otherwise
-template <bool SPECTRUM_ONLY>
+template <int MODE>
 void launch_rows(const PlanDev& d, int pairs, float* Ure, float* Uim, const float* t, const float* Sre_in, const float* Sim_in,
                         float* Sre_out, float* Sim_out, hipStream_t st) {
   const float2* tw = reinterpret_cast<const float2*>(t + off_tw(d));
   const float2* rowtw = reinterpret_cast<const float2*>(t + off_rowtw(d));
   if (d.N2 == 512) {
     const int rows = pairs * d.N1;
-    row512_kernel<SPECTRUM_ONLY><<<(rows + 3) / 4, 256, 0, st>>>(d, rows, Ure, Uim, tw, reinterpret_cast<const float2*>(t + off_r8(d)), Sre_in, Sim_in,
+    row512_kernel<MODE><<<(rows + 3) / 4, 256, 0, st>>>(d, rows, Ure, Uim, tw, reinterpret_cast<const float2*>(t + off_r8(d)), Sre_in, Sim_in,
                                                                 Sre_out, Sim_out);
   } else {
     // `pairs` counts transforms (utterance pairs x overlap-save blocks): grid.y in slices of 65535
@@ -756,9 +831,9 @@ void launch_rows(const PlanDev& d, int pairs, float* Ure, float* Uim, const floa
       float* uim = Uim + (size_t)q0 * d.L;
       const size_t lds = (size_t)(2 * d.N2 + d.N2 / 2) * sizeof(float2);
       if (d.N2 <= 1024)
-        row_kernel<SPECTRUM_ONLY, 4><<<dim3(d.N1, nq), 256, lds, st>>>(d, ure, uim, tw, rowtw, Sre_in, Sim_in, Sre_out, Sim_out);
+        row_kernel<MODE, 4><<<dim3(d.N1, nq), 256, lds, st>>>(d, ure, uim, tw, rowtw, Sre_in, Sim_in, Sre_out, Sim_out);
       else
-        row_kernel<SPECTRUM_ONLY, 8><<<dim3(d.N1, nq), 256, lds, st>>>(d, ure, uim, tw, rowtw, Sre_in, Sim_in, Sre_out, Sim_out);
+        row_kernel<MODE, 8><<<dim3(d.N1, nq), 256, lds, st>>>(d, ure, uim, tw, rowtw, Sre_in, Sim_in, Sre_out, Sim_out);
     }
   }
 }
@@ -871,11 +946,24 @@ size_t nws_reverb_workspace_bytes(const NwsReverbPlan* plan, int B) {
   return (f > g ? f : g) * sizeof(float);
 }
 
+// dL/dx runs in the forward's workspace.  dL/d(ir): planar spectra of the x slots and of the g slots (4 * pairs * nblk * L),
+// the summed cross spectrum (2 L) and its inverse transform's lags (L)
+size_t nws_reverb_grad_workspace_bytes(const NwsReverbPlan* plan, int B, int want_ir) {
+  const size_t f = nws_reverb_workspace_bytes(plan, B);
+  if (f == 0 || !want_ir) return f;
+  const size_t pairs = (size_t)(B + 1) / 2;
+  const size_t g = (4 * pairs * (size_t)plan->nblk + 3) * (size_t)plan->L * sizeof(float);
+  return g > f ? g : f;
+}
+
 static int ensure_col125_attrs() {
   static unsigned long long attr_devices = 0;
   if (nws_first_use_on_device(attr_devices)) {
-    const void* fns[4] = {reinterpret_cast<const void*>(col125_fwd_kernel<false>), reinterpret_cast<const void*>(col125_fwd_kernel<true>),
-                          reinterpret_cast<const void*>(col125_inv_kernel<false>), reinterpret_cast<const void*>(col125_inv_kernel<true>)};
+    const void* fns[7] = {reinterpret_cast<const void*>(col125_fwd_kernel<false>), reinterpret_cast<const void*>(col125_fwd_kernel<true>),
+                          reinterpret_cast<const void*>(col125_inv_kernel<false>), reinterpret_cast<const void*>(col125_inv_kernel<true>),
+                          reinterpret_cast<const void*>(col125_fwd_kernel<true, kGeomAhead>),
+                          reinterpret_cast<const void*>(col125_fwd_kernel<true, kGeomOwn>),
+                          reinterpret_cast<const void*>(col125_inv_kernel<true, true>)};
     for (const void* fn : fns) {
       const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCol125Lds);
       if (e != hipSuccess) return (int)e;
@@ -934,7 +1022,7 @@ int nws_reverb_ir_spectrum(const NwsReverbPlan* plan, const void* tables, const 
     col_fwd_kernel<<<g1, 256, 0, st>>>(t + off_afwd(d), d, irp, 1, ir_len + 1, 0, Ure, Uim);
   }
   NWS_CHECK_LAUNCH();
-  launch_rows<true>(d, 1, Ure, Uim, t, nullptr, nullptr, Sre, Sim, st);
+  launch_rows<kRowSpectrum>(d, 1, Ure, Uim, t, nullptr, nullptr, Sre, Sim, st);
   NWS_CHECK_LAUNCH();
   return NWS_OK;
 }
@@ -961,14 +1049,14 @@ int nws_reverb(const NwsReverbPlan* plan, const void* tables, const void* spectr
     Uim = Ure + (size_t)pairs * e.nblk * d.L;
     col125_fwd_kernel<true><<<dim3(d.N2 / 32, pairs, e.nblk), kColThreads, kCol125Lds, st>>>(e, tw125, x, B, N, (long long)N, Ure, Uim);
     NWS_CHECK_LAUNCH();
-    launch_rows<false>(e, pairs * e.nblk, Ure, Uim, t, Sre, Sim, nullptr, nullptr, st);
+    launch_rows<kRowFused>(e, pairs * e.nblk, Ure, Uim, t, Sre, Sim, nullptr, nullptr, st);
     NWS_CHECK_LAUNCH();
     col125_inv_kernel<true><<<dim3(d.N2 / 32, pairs, e.nblk), kColThreads, kCol125Lds, st>>>(e, tw125, Ure, Uim, x, B, N, y);
     NWS_CHECK_LAUNCH();
     return NWS_OK;
   }
   if (N <= kDirectMaxN && B <= 65535) {
-    reverb_direct_kernel<<<dim3((N + 255) / 256, B), 256, (size_t)3 * N * sizeof(float), st>>>(x, Sim + d.L, N, d.L, y);
+    reverb_direct_kernel<false><<<dim3((N + 255) / 256, B), 256, (size_t)3 * N * sizeof(float), st>>>(x, Sim + d.L, N, d.L, y);
     NWS_CHECK_LAUNCH();
     return NWS_OK;
   }
@@ -980,7 +1068,7 @@ int nws_reverb(const NwsReverbPlan* plan, const void* tables, const void* spectr
     col_fwd_kernel<<<g1, 256, 0, st>>>(t + off_afwd(d), d, x, B, N, (long long)N, Ure, Uim);
   }
   NWS_CHECK_LAUNCH();
-  launch_rows<false>(d, pairs, Ure, Uim, t, Sre, Sim, nullptr, nullptr, st);
+  launch_rows<kRowFused>(d, pairs, Ure, Uim, t, Sre, Sim, nullptr, nullptr, st);
   NWS_CHECK_LAUNCH();
   if (d.N1 == 125) {
     col125_inv_kernel<false><<<dim3(d.N2 / 32, pairs), kColThreads, kCol125Lds, st>>>(d, tw125, Ure, Uim, x, B, N, y);
@@ -990,6 +1078,128 @@ int nws_reverb(const NwsReverbPlan* plan, const void* tables, const void* spectr
     const dim3 g3(d.N2 / 32, (2 * nt + 3) / 4, pairs);
     col_inv_kernel<<<g3, 256, 0, st>>>(t + off_ainv(d), d, Ure, Uim, x, B, N, y);
   }
+  NWS_CHECK_LAUNCH();
+  return NWS_OK;
+}
+
+// dL/dx of nws_reverb: dx = g + circular CORRELATION of g with [0, ir] - the forward's three launches with the conjugated
+// spectrum; overlap-save blocks start at their first output and look ahead where the forward's look back
+int nws_reverb_grad_x(const NwsReverbPlan* plan, const void* tables, const void* spectrum, const float* g, int B, int N,
+                      float* dx, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!plan_ok(plan) || !tables || !spectrum || !g || !dx || !workspace || B <= 0 || N <= 0) return NWS_ERR_BAD_ARG;
+  if (!nws_reverb_plan_serves(plan, N, 0)) return NWS_ERR_BAD_ARG;
+  if (workspace_bytes < nws_reverb_grad_workspace_bytes(plan, B, 0)) return NWS_ERR_WORKSPACE;
+  const PlanDev d = plan_dev(plan);
+  const int pairs = (B + 1) / 2;
+  if (pairs > 65535) return NWS_ERR_UNSUPPORTED;
+  const float* t = static_cast<const float*>(tables);
+  hipStream_t st = (hipStream_t)stream;
+  float* Ure = static_cast<float*>(workspace);
+  float* Uim = Ure + (size_t)pairs * d.nblk * d.L;
+  const float* Sre = static_cast<const float*>(spectrum);
+  const float* Sim = Sre + d.L;
+  const float2* tw125 = reinterpret_cast<const float2*>(t + off_tw125(d));
+  if (plan->Lc > 0) {
+    PlanDev e = d;
+    e.nblk = (int)(((long long)N + d.P - 1) / d.P);
+    Uim = Ure + (size_t)pairs * e.nblk * d.L;
+    col125_fwd_kernel<true, kGeomAhead><<<dim3(d.N2 / 32, pairs, e.nblk), kColThreads, kCol125Lds, st>>>(e, tw125, g, B, N, (long long)N, Ure, Uim);
+    NWS_CHECK_LAUNCH();
+    launch_rows<kRowFusedConj>(e, pairs * e.nblk, Ure, Uim, t, Sre, Sim, nullptr, nullptr, st);
+    NWS_CHECK_LAUNCH();
+    col125_inv_kernel<true, true><<<dim3(d.N2 / 32, pairs, e.nblk), kColThreads, kCol125Lds, st>>>(e, tw125, Ure, Uim, g, B, N, dx);
+    NWS_CHECK_LAUNCH();
+    return NWS_OK;
+  }
+  if (N <= kDirectMaxN && B <= 65535) {
+    reverb_direct_kernel<true><<<dim3((N + 255) / 256, B), 256, (size_t)3 * N * sizeof(float), st>>>(g, Sim + d.L, N, d.L, dx);
+    NWS_CHECK_LAUNCH();
+    return NWS_OK;
+  }
+  if (d.N1 == 125) {
+    col125_fwd_kernel<false><<<dim3(d.N2 / 32, pairs), kColThreads, kCol125Lds, st>>>(d, tw125, g, B, N, (long long)N, Ure, Uim);
+  } else {
+    const dim3 g1(d.N2 / 32, (d.M2 / 32 + 3) / 4, pairs);
+    col_fwd_kernel<<<g1, 256, 0, st>>>(t + off_afwd(d), d, g, B, N, (long long)N, Ure, Uim);
+  }
+  NWS_CHECK_LAUNCH();
+  launch_rows<kRowFusedConj>(d, pairs, Ure, Uim, t, Sre, Sim, nullptr, nullptr, st);
+  NWS_CHECK_LAUNCH();
+  if (d.N1 == 125) {
+    col125_inv_kernel<false><<<dim3(d.N2 / 32, pairs), kColThreads, kCol125Lds, st>>>(d, tw125, Ure, Uim, g, B, N, dx);
+  } else {
+    const int rows_out = (N + d.N2 - 1) / d.N2;
+    const int nt = (rows_out + 31) / 32;
+    const dim3 g3(d.N2 / 32, (2 * nt + 3) / 4, pairs);
+    col_inv_kernel<<<g3, 256, 0, st>>>(t + off_ainv(d), d, Ure, Uim, g, B, N, dx);
+  }
+  NWS_CHECK_LAUNCH();
+  return NWS_OK;
+}
+
+// dL/d(ir) of nws_reverb, summed over the batch: dir[j - 1] = sum_b sum_n g[b, n] x_[b, (n - j) mod Lc], j = 1 .. ir_len.
+// Column and row passes of the x pairs and of the g pairs (spectra only, one row launch for both), the per-bin sum of
+// conj(Zx) Zg over pairs and blocks, ONE inverse transform of that sum.
+int nws_reverb_grad_ir(const NwsReverbPlan* plan, const void* tables, const float* x, const float* g, int B, int N, int ir_len,
+                       float* dir, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!plan_ok(plan) || !tables || !x || !g || !dir || !workspace || B <= 0 || N <= 0 || ir_len <= 0) return NWS_ERR_BAD_ARG;
+  if (!nws_reverb_plan_serves(plan, N, 0)) return NWS_ERR_BAD_ARG;
+  if (plan->Lc > 0 ? ir_len != plan->hist : ir_len + 1 > plan->L) return NWS_ERR_BAD_ARG;
+  if (workspace_bytes < nws_reverb_grad_workspace_bytes(plan, B, 1)) return NWS_ERR_WORKSPACE;
+  const PlanDev d = plan_dev(plan);
+  const int pairs = (B + 1) / 2;
+  if (pairs > 65535) return NWS_ERR_UNSUPPORTED;
+  PlanDev e = d;
+  if (plan->Lc > 0) e.nblk = (int)(((long long)N + d.P - 1) / d.P);
+  if (2LL * pairs * e.nblk * d.N1 > 0x7fffffffLL) return NWS_ERR_UNSUPPORTED;   // rows of one row-pass launch
+  const int slots = pairs * e.nblk;
+  const float* t = static_cast<const float*>(tables);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t half = (size_t)slots * d.L;
+  float* Ure = static_cast<float*>(workspace);   // x slots | g slots
+  float* Uim = Ure + 2 * half;
+  float* Are = Uim + 2 * half;
+  float* Aim = Are + d.L;
+  float* lags = Aim + d.L;
+  const float2* tw125 = reinterpret_cast<const float2*>(t + off_tw125(d));
+  if (plan->Lc > 0) {
+    const dim3 grid(d.N2 / 32, pairs, e.nblk);
+    col125_fwd_kernel<true><<<grid, kColThreads, kCol125Lds, st>>>(e, tw125, x, B, N, (long long)N, Ure, Uim);
+    NWS_CHECK_LAUNCH();
+    col125_fwd_kernel<true, kGeomOwn><<<grid, kColThreads, kCol125Lds, st>>>(e, tw125, g, B, N, (long long)N, Ure + half, Uim + half);
+  } else if (d.N1 == 125) {
+    col125_fwd_kernel<false><<<dim3(d.N2 / 32, pairs), kColThreads, kCol125Lds, st>>>(d, tw125, x, B, N, (long long)N, Ure, Uim);
+    NWS_CHECK_LAUNCH();
+    col125_fwd_kernel<false><<<dim3(d.N2 / 32, pairs), kColThreads, kCol125Lds, st>>>(d, tw125, g, B, N, (long long)N, Ure + half, Uim + half);
+  } else {
+    const dim3 g1(d.N2 / 32, (d.M2 / 32 + 3) / 4, pairs);
+    col_fwd_kernel<<<g1, 256, 0, st>>>(t + off_afwd(d), d, x, B, N, (long long)N, Ure, Uim);
+    NWS_CHECK_LAUNCH();
+    col_fwd_kernel<<<g1, 256, 0, st>>>(t + off_afwd(d), d, g, B, N, (long long)N, Ure + half, Uim + half);
+  }
+  NWS_CHECK_LAUNCH();
+  launch_rows<kRowSpectrumSlots>(e, 2 * slots, Ure, Uim, t, nullptr, nullptr, nullptr, nullptr, st);
+  NWS_CHECK_LAUNCH();
+  cross_spectrum_kernel<<<(d.L + 255) / 256, 256, 0, st>>>(Ure, Uim, Ure + half, Uim + half, slots, d.L, Are, Aim);
+  NWS_CHECK_LAUNCH();
+  // one plain transform of length L back: lags 0 .. ir_len of a block product cannot wrap (ir_len = hist < L)
+  PlanDev one = d;
+  one.Lc = d.L;
+  one.hist = 0;
+  one.nblk = 1;
+  one.P = d.L;
+  launch_rows<kRowInverse>(one, 1, Are, Aim, t, nullptr, nullptr, nullptr, nullptr, st);
+  NWS_CHECK_LAUNCH();
+  if (d.N1 == 125) {
+    col125_inv_kernel<false><<<dim3(d.N2 / 32, 1), kColThreads, kCol125Lds, st>>>(one, tw125, Are, Aim, nullptr, 1, ir_len + 1, lags);
+  } else {
+    const int rows_out = (ir_len + 1 + d.N2 - 1) / d.N2;
+    const int nt = (rows_out + 31) / 32;
+    const dim3 g3(d.N2 / 32, (2 * nt + 3) / 4, 1);
+    col_inv_kernel<<<g3, 256, 0, st>>>(t + off_ainv(d), one, Are, Aim, nullptr, 1, ir_len + 1, lags);
+  }
+  NWS_CHECK_LAUNCH();
+  lags_to_ir_kernel<<<(ir_len + 255) / 256, 256, 0, st>>>(lags, ir_len, dir);
   NWS_CHECK_LAUNCH();
   return NWS_OK;
 }
@@ -1020,7 +1230,7 @@ int nws_reverb_linear_chunk(const NwsReverbPlan* plan, const void* tables, const
     col_fwd_kernel<<<g1, 256, 0, st>>>(t + off_afwd(d), d, x, B, M, (long long)M, Ure, Uim);
   }
   NWS_CHECK_LAUNCH();
-  launch_rows<false>(d, pairs, Ure, Uim, t, Sre, Sim, nullptr, nullptr, st);
+  launch_rows<kRowFused>(d, pairs, Ure, Uim, t, Sre, Sim, nullptr, nullptr, st);
   NWS_CHECK_LAUNCH();
   if (d.N1 == 125) {
     col125_inv_kernel<false><<<dim3(d.N2 / 32, pairs), kColThreads, kCol125Lds, st>>>(d, tw125, Ure, Uim, nullptr, B, d.L, wet);

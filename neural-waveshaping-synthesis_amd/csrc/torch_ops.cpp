@@ -434,6 +434,53 @@ Tensor reverb(const Tensor& plan_t, const Tensor& tables, const Tensor& spectrum
   return y;
 }
 
+// dL/dx of Reverb.forward for grad_out = dL/dy (B, N): the forward's launches with the conjugated IR spectrum
+Tensor reverb_grad_x(const Tensor& plan_t, const Tensor& tables, const Tensor& spectrum, const Tensor& grad_out) {
+  NwsReverbPlan plan = plan_of(plan_t);
+  check_dev(grad_out, "grad_out");
+  check_dev(tables, "reverb_tables");
+  check_dev(spectrum, "reverb_spectrum");
+  check_same_device(grad_out, "grad_out", tables, "reverb tables");
+  check_same_device(grad_out, "grad_out", spectrum, "reverb.ir spectrum");
+  TORCH_CHECK(grad_out.dim() == 2, "reverb_grad_x: expected (B, N), got ", grad_out.sizes());
+  check_reverb_buffers(plan, tables, spectrum);
+  const int64_t B = grad_out.size(0), N = grad_out.size(1);
+  TORCH_CHECK(nws_reverb_plan_serves(&plan, (int)N, 0), "reverb_grad_x: the plan [L ", plan.L, ", Lc ", plan.Lc, ", hist ", plan.hist,
+              ", nblk ", plan.nblk, "] was not made for ", N, " samples");
+  Launch L(grad_out);
+  const size_t nbytes = nws_reverb_grad_workspace_bytes(&plan, (int)B, 0);
+  Tensor ws = at::empty({(int64_t)nbytes}, grad_out.options().dtype(at::kByte));
+  Tensor dx = at::empty_like(grad_out);
+  nws_check(nws_reverb_grad_x(&plan, tables.data_ptr(), spectrum.data_ptr(), grad_out.data_ptr<float>(), (int)B, (int)N,
+                              dx.data_ptr<float>(), ws.data_ptr(), nbytes, L.stream), "nws_reverb_grad_x");
+  return dx;
+}
+
+// dL/d(ir) of Reverb.forward, summed over the batch: (ir_len)
+Tensor reverb_grad_ir(const Tensor& plan_t, const Tensor& tables, const Tensor& x, const Tensor& grad_out, int64_t ir_len) {
+  NwsReverbPlan plan = plan_of(plan_t);
+  check_dev(x, "x");
+  check_dev(grad_out, "grad_out");
+  check_dev(tables, "reverb_tables");
+  check_same_device(x, "x", tables, "reverb tables");
+  check_same_device(x, "x", grad_out, "grad_out");
+  TORCH_CHECK(x.dim() == 2 && grad_out.sizes() == x.sizes(), "reverb_grad_ir: x ", x.sizes(), " and grad_out ", grad_out.sizes(),
+              " differ in shape");
+  TORCH_CHECK((size_t)tables.numel() * tables.element_size() == nws_reverb_table_bytes(&plan), "reverb_tables: ",
+              (size_t)tables.numel() * tables.element_size(), " bytes, the plan (L = ", plan.L, ") needs ", nws_reverb_table_bytes(&plan));
+  const int64_t B = x.size(0), N = x.size(1);
+  TORCH_CHECK(ir_len > 0 && ir_len < (1 << 30) && nws_reverb_plan_serves(&plan, (int)N, (int)ir_len + 1), "reverb_grad_ir: the plan [L ",
+              plan.L, ", Lc ", plan.Lc, ", hist ", plan.hist, ", nblk ", plan.nblk, "] was not made for ", N, " samples and an impulse response of ",
+              ir_len);
+  Launch L(x);
+  const size_t nbytes = nws_reverb_grad_workspace_bytes(&plan, (int)B, 1);
+  Tensor ws = at::empty({(int64_t)nbytes}, x.options().dtype(at::kByte));
+  Tensor dir = at::empty({ir_len}, x.options());
+  nws_check(nws_reverb_grad_ir(&plan, tables.data_ptr(), x.data_ptr<float>(), grad_out.data_ptr<float>(), (int)B, (int)N, (int)ir_len,
+                               dir.data_ptr<float>(), ws.data_ptr(), nbytes, L.stream), "nws_reverb_grad_ir");
+  return dir;
+}
+
 // streaming (linear) reverb chunk: -> (y (B, M), tail_out (B, tail_len))
 std::tuple<Tensor, Tensor> reverb_linear_chunk(const Tensor& plan_t, const Tensor& tables, const Tensor& spectrum, const Tensor& x,
                                                const Tensor& tail_in) {
@@ -1219,6 +1266,8 @@ TORCH_LIBRARY(newt_hip, m) {
   m.def("fir_noise(Tensor fir, Tensor noise, Tensor? add_in, int origin) -> Tensor", &fir_noise);
   m.def("fir_from_h(Tensor H, Tensor fir_design) -> Tensor", &fir_from_h);
   m.def("reverb(Tensor plan, Tensor tables, Tensor spectrum, Tensor x) -> Tensor", &reverb);
+  m.def("reverb_grad_x(Tensor plan, Tensor tables, Tensor spectrum, Tensor grad_out) -> Tensor", &reverb_grad_x);
+  m.def("reverb_grad_ir(Tensor plan, Tensor tables, Tensor x, Tensor grad_out, int ir_len) -> Tensor", &reverb_grad_ir);
   m.def("reverb_linear_chunk(Tensor plan, Tensor tables, Tensor spectrum, Tensor x, Tensor tail_in) -> (Tensor, Tensor)",
         &reverb_linear_chunk);
   m.def("shaper_apply(Tensor wdesc, Tensor x) -> Tensor", &shaper_apply);

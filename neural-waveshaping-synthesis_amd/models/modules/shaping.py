@@ -230,14 +230,41 @@ class FastNEWT(NEWT):
         return sa.call("shaper_apply", self._lut_desc.get(*self._lut_fields()), x)
 
 
+class _ReverbFunction(torch.autograd.Function):
+    """Reverb.forward with its transpose attached (csrc/reverb_fft.hip): backward runs reverb_grad_x and
+    reverb_grad_ir, each only when its gradient is needed"""
+
+    @staticmethod
+    def forward(ctx, x, ir, module):
+        xd = x.detach()
+        y = module._forward_detached(xd)
+        ctx.module = module
+        ctx.save_for_backward(xd, ir)          # ir itself: an in-place change before backward is autograd's to refuse
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        xd, ir = ctx.saved_tensors
+        dx, dir_ = ctx.module.vjp(xd, grad_out, need_x=ctx.needs_input_grad[0], need_ir=ctx.needs_input_grad[1])
+        return dx, dir_, None
+
+
 @gin.configurable
 class Reverb(nn.Module):
-    """x + circular_conv(x, [0, ir]) of length max(N, len(ir)+1) (reference shaping.py:154-173)."""
+    """x + circular_conv(x, [0, ir]) of length max(N, len(ir)+1) (reference shaping.py:154-173).
+
+    ``differentiable`` (a plain attribute, default False): forward only, the result carries no graph.  Set to True, a forward
+    under grad mode whose x or ir requires grad returns the same bits with a ``torch.autograd.Function`` attached that gives
+    dL/dx and dL/d(ir) (``initial_zero`` is a buffer).  ``vjp`` is the same pair of gradients without autograd."""
+
+    differentiable = False      # also the value of a module unpickled from before the flag existed
 
     def __init__(self, length_in_seconds, sr):
         super().__init__()
         self.ir = nn.Parameter(torch.randn(1, sr * length_in_seconds - 1) * 1e-6)
         self.register_buffer("initial_zero", torch.zeros(1, 1))
+        self.differentiable = False
         self._tables = {}
 
     def __getstate__(self):
@@ -245,23 +272,20 @@ class Reverb(nn.Module):
         d["_tables"] = {}
         return d
 
-    def forward(self, x):
-        """Stand-alone reverb on a (B, N) CUDA tensor: four-step FFT kernels of csrc/reverb_fft.hip."""
+    def _plan_and_spectrum(self, x, ir, need_plan=False):
+        """(plan tensor, tables, IR spectrum) of a (B, N) call, or None when the circular length is odd and has no plan; the
+        spectrum is cached until ir changes (in place: ir._version)"""
+        from ..._lib import NwsReverbPlan
         from ...engine import reverb_plan_and_tables
 
-        x = sa.contiguous(x, "x")
-        if x.dim() != 2:
-            raise RuntimeError(f"expected (B, N), got {tuple(x.shape)}")
-        ir = sa._req(self.ir.detach(), "reverb.ir")
-        if ir.device != x.device:
-            raise RuntimeError(f"x is on {x.device} but reverb.ir is on {ir.device}")
         N = x.shape[1]
-        from ..._lib import NwsReverbPlan
-
         probe = NwsReverbPlan()
         if sa._lib.lib().nws_reverb_plan(int(N), int(ir.numel()) + 1, C.byref(probe)) != 0:
-            # odd circular length (every even one has a plan): the reference's own rfft / irfft expression (csrc/generic.hip)
-            return sa.call("g_reverb_direct", x, ir.reshape(-1))
+            if need_plan:
+                raise RuntimeError(f"Reverb: no gradient for an odd circular length (max(N, len(ir) + 1) = {max(N, ir.numel() + 1)}): "
+                                   "the reference's rfft / irfft pair is not a circular convolution there, and the transform "
+                                   "kernels that carry the backward have a plan for even lengths only")
+            return None
         plan, tables, plan_t = reverb_plan_and_tables(x.device, N, ir.numel() + 1)
         L = sa._lib.lib()
         key = (plan.L, ir.data_ptr(), ir._version)
@@ -276,4 +300,46 @@ class Reverb(nn.Module):
                                                     spec.data_ptr(), ws1.data_ptr(), nb, sa.stream_ptr(x.device)),
                            "nws_reverb_ir_spectrum")
             self._tables[key] = spec
+        return plan_t, tables, spec
+
+    def _checked_input(self, x, name="x"):
+        x = sa.contiguous(x, name)
+        if x.dim() != 2:
+            raise RuntimeError(f"{name}: expected (B, N), got {tuple(x.shape)}")
+        ir = sa._req(self.ir.detach(), "reverb.ir")
+        if ir.device != x.device:
+            raise RuntimeError(f"{name} is on {x.device} but reverb.ir is on {ir.device}")
+        return x, ir
+
+    def _forward_detached(self, x):
+        x, ir = self._checked_input(x)
+        aux = self._plan_and_spectrum(x, ir)
+        if aux is None:
+            # odd circular length (every even one has a plan): the reference's own rfft / irfft expression (csrc/generic.hip)
+            return sa.call("g_reverb_direct", x, ir.reshape(-1))
+        plan_t, tables, spec = aux
         return sa.call("reverb", plan_t, tables, spec, x)
+
+    def forward(self, x):
+        """Stand-alone reverb on a (B, N) CUDA tensor: four-step FFT kernels of csrc/reverb_fft.hip."""
+        if self.differentiable and torch.is_grad_enabled() and isinstance(x, torch.Tensor) and (x.requires_grad or self.ir.requires_grad):
+            xc, ir = self._checked_input(x.detach())
+            self._plan_and_spectrum(xc, ir, need_plan=True)       # refusals before autograd is involved
+            return _ReverbFunction.apply(x, self.ir, self)
+        return self._forward_detached(x)
+
+    def vjp(self, x, grad_out, need_x=True, need_ir=True):
+        """(dL/dx | None, dL/d(ir) | None) of ``forward`` at x for grad_out = dL/dy: dx in the shape of x, dir in the shape of
+        ir, (1, ir_len), summed over the batch.  Whatever ``differentiable`` and the grad mode say; autograd is not involved
+        and the results carry no graph."""
+        with torch.no_grad():
+            x, ir = self._checked_input(x.detach())
+            g, _ = self._checked_input(grad_out.detach(), "grad_out")
+            if g.shape != x.shape:
+                raise RuntimeError(f"grad_out {tuple(g.shape)} is not in the shape of x {tuple(x.shape)}")
+            if not (need_x or need_ir):
+                return None, None
+            plan_t, tables, spec = self._plan_and_spectrum(x, ir, need_plan=True)
+            dx = sa.call("reverb_grad_x", plan_t, tables, spec, g) if need_x else None
+            dir_ = sa.call("reverb_grad_ir", plan_t, tables, x, g, int(ir.numel())).reshape(self.ir.shape) if need_ir else None
+            return dx, dir_

@@ -9,8 +9,9 @@ Of the reference's Lightning hooks (:92-165) the two that need no backward pass 
 and ``test_step`` return ``stft_loss(recon, audio)`` - ``losses.MultiResolutionSTFTLoss``, the HIP restatement
 of the ``auraloss`` loss the reference logs as ``val/loss`` / ``test/loss`` - through the
 reference's ``_run_step``.  ``stft_loss`` is made on first use (in the reference ``configure_optimizers`` makes
-it).  ``training_step`` and ``configure_optimizers`` raise: there is no backward pass in this package
-(SURVEY.md §2 row 1b).  Logging (``self.log``, wandb) is left to the caller.
+it).  ``training_step`` and ``configure_optimizers`` raise: the loss and the reverb have a backward pass
+(DESIGN.md 3.13, 3.14), nothing upstream of the reverb has one.  ``pre_reverb`` renders the
+reverb's input, which is what fitting ``reverb.ir`` alone needs.  Logging (``self.log``, wandb) is left to the caller.
 
 Hidden inputs, exactly like the reference: every forward draws ``rand_like(osc.rand_phase)`` and then
 ``rand(control_hop*T - 1)`` from the default generator of the module's device, in that order
@@ -159,7 +160,7 @@ class NeuralWaveshaping(nn.Module):
         emb, _, _, _ = self._engine.frame_mlps(gru, want_emb=True)
         return emb
 
-    def forward(self, f0, control, *, phase_u=None, noise=None):
+    def _checked_inputs(self, f0, control, phase_u, noise):
         # strided views (control[:, :2], expand()) are accepted like in the reference: compacted by torch
         f0 = _req(f0 if f0.is_contiguous() else f0.contiguous(), "f0")
         control = _req(control if control.is_contiguous() else control.contiguous(), "control")
@@ -180,9 +181,21 @@ class NeuralWaveshaping(nn.Module):
         if noise is None:
             noise = torch.rand(self.control_hop * T - 1, device=dev)  # RNG draw #2 (generators.py:30)
         noise = _req(noise, "noise", self.control_hop * T - 1)
+        return f0, control, phase_u, noise
+
+    def forward(self, f0, control, *, phase_u=None, noise=None):
+        f0, control, phase_u, noise = self._checked_inputs(f0, control, phase_u, noise)
         if self._sub_module_hooks():
             return self._forward_module_by_module(f0, control, phase_u, noise)
         return self._engine.forward(f0, control, phase_u, noise)
+
+    def pre_reverb(self, f0, control, phase_u=None, noise=None):
+        """(B, N) input of ``self.reverb`` for the same draws as ``forward`` (reference :74-86: everything before :88), so that
+        ``self.reverb(self.pre_reverb(...))`` is the forward within the parity bar.  Runs the stage kernels one module after
+        the other under ``no_grad``: nothing upstream of the reverb has a backward, and the result carries no graph - it is
+        what ``Reverb.vjp`` and a differentiable ``Reverb`` take as x (scripts/fit_reverb.py)."""
+        f0, control, phase_u, noise = self._checked_inputs(f0, control, phase_u, noise)
+        return self._pre_reverb_module_by_module(f0, control, phase_u, noise)
 
     # ---- evaluation hooks (reference :104-112, :136-165): inference + loss, no backward ----------------
     @property
@@ -221,11 +234,14 @@ class NeuralWaveshaping(nn.Module):
             return self._run_step(batch)[0]
 
     def training_step(self, batch, batch_idx):
-        raise NotImplementedError("training_step: there is no backward pass in this package (the HIP kernels are forward-only); "
-                                  "validation_step and test_step give the reference's loss")
+        raise NotImplementedError("training_step: there is no backward pass in this package upstream of the reverb - the loss "
+                                  "(losses.MultiResolutionSTFTLoss(differentiable=True)) and the reverb (Reverb.differentiable, "
+                                  "Reverb.vjp) have one, the rest of the model does not; validation_step and test_step give the "
+                                  "reference's loss, and scripts/fit_reverb.py fits reverb.ir alone")
 
     def configure_optimizers(self):
-        raise NotImplementedError("configure_optimizers: there is no backward pass in this package, so there is nothing to optimise; "
+        raise NotImplementedError("configure_optimizers: there is no backward pass in this package upstream of the reverb (the loss "
+                                  "and the reverb have one), so the only parameter to optimise is reverb.ir (scripts/fit_reverb.py); "
                                   "model.stft_loss is made on first use instead")
 
     def _sub_module_hooks(self) -> bool:
@@ -244,6 +260,11 @@ class NeuralWaveshaping(nn.Module):
         return False
 
     def _forward_module_by_module(self, f0, control, phase_u, noise):
+        x = self._pre_reverb_module_by_module(f0, control, phase_u, noise)
+        with torch.no_grad():
+            return self.reverb(x)                                                 # :88
+
+    def _pre_reverb_module_by_module(self, f0, control, phase_u, noise):
         with torch.no_grad():
             f0_up = upsample_linear(f0, int(self.control_hop))                    # :75
             sig = self.osc(f0_up[:, 0], phase_u=phase_u)                          # :65   (draw #1 injected / made above)
@@ -252,8 +273,7 @@ class NeuralWaveshaping(nn.Module):
             x = self.newt(x, emb)                                                 # :80
             H = self.h_generator(emb)                                             # :82
             nz = self.noise_synth(H, noise=noise)                                 # :83   (draw #2)
-            x = sa.sum_channels(torch.cat((x, nz), dim=1))                        # :85-86 (cat: plumbing; the sum: a HIP kernel)
-            return self.reverb(x)                                                 # :88
+            return sa.sum_channels(torch.cat((x, nz), dim=1))                     # :85-86 (cat: plumbing; the sum: a HIP kernel)
 
     # ---- checkpoints (Lightning .ckpt as shipped by the reference, or flat .npz fixtures) -------------
     @classmethod

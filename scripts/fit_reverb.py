@@ -1,0 +1,107 @@
+#!/usr/bin/env python
+"""Fit a checkpoint's room to a set of recordings: optimise `reverb.ir` alone, everything else frozen (same instrument,
+different hall).  The reverb is the model's last stage and the only one with a backward pass (csrc/reverb_fft.hip, DESIGN.md
+3.14); the loss is the one the model was trained on, with its gradient (csrc/stft_grad.hip).  Per step and per
+batch of the split that has target audio: `model.pre_reverb` renders the reverb's input (no graph), `Reverb(differentiable=True)`
+and `MultiResolutionSTFTLoss(differentiable=True)` carry the gradient to `reverb.ir`, the batches' gradients are summed and
+`torch.optim.Adam` takes one step.  Render, loss and both backward passes run as HIP kernels; one number per batch is read back.
+
+    python scripts/fit_reverb.py --model-checkpoint ckpt --dataset-root data/ --split train --steps 200 --lr 1e-4 \\
+        --output ckpt_out [--use-fastnewt] [--seed 0]
+
+The hidden draws of the render (phase offsets, noise excitation) come from the device generator, which is re-seeded with --seed
+at the start of every step: every step sees the same draws, so the printed losses are values of one fixed objective and a run
+repeats to the bit.  The output is written in the input's format (a flat .npz, or a torch checkpoint with `state_dict` and
+`hyper_parameters`) and differs from the input checkpoint in `reverb.ir` only; `NeuralWaveshaping.load_from_checkpoint` reads it.
+"""
+import importlib
+import os
+import sys
+
+import click
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def write_checkpoint(path, source, ir):
+    """the checkpoint `source` with `reverb.ir` replaced, as .npz (every array of the source is kept) or as a torch checkpoint"""
+    ckpt = importlib.import_module("neural-waveshaping-synthesis_amd.checkpoint")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    ir = ir.detach().cpu()
+    if str(path).endswith(".npz"):
+        if str(source).endswith(".npz"):
+            z = np.load(source)
+            arrays = {k: z[k] for k in z.files}
+        else:
+            arrays = {k: np.asarray(v) for k, v in ckpt.read_checkpoint(source)[0].items()}
+        arrays["reverb.ir"] = ir.numpy().astype(arrays["reverb.ir"].dtype)
+        np.savez(path, **arrays)
+        return
+    state, hparams = ckpt.read_checkpoint(source)
+    state = {k: torch.as_tensor(v) for k, v in state.items()}
+    state["reverb.ir"] = ir.to(state["reverb.ir"].dtype)
+    torch.save({"state_dict": state, "hyper_parameters": hparams}, path)
+
+
+@click.command()
+@click.option("--model-gin", default=None)
+@click.option("--model-checkpoint", required=True)
+@click.option("--dataset-root", required=True)
+@click.option("--split", default="train")
+@click.option("--batch-size", default=64)
+@click.option("--steps", default=100, help="optimiser steps; each one passes over every batch of the split once")
+@click.option("--lr", default=1e-4, help="Adam's learning rate for reverb.ir")
+@click.option("--output", required=True, help="checkpoint to write (.npz: flat arrays; anything else: a torch checkpoint)")
+@click.option("--use-fastnewt", is_flag=True)
+@click.option("--seed", default=0, help="seeds the device generator the hidden draws of the render come from, at every step")
+def main(model_gin, model_checkpoint, dataset_root, split, batch_size, steps, lr, output, use_fastnewt, seed):
+    nws = importlib.import_module("neural-waveshaping-synthesis_amd")
+    ds_mod = importlib.import_module("neural-waveshaping-synthesis_amd.dataset")
+    dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+    torch.cuda.set_device(dev)
+    if model_gin:
+        nws.gin.parse_config_file(model_gin)
+    else:
+        nws.ensure_default_config()
+    data = ds_mod.ControlDataset(dataset_root, split)
+    model = nws.NeuralWaveshaping.load_from_checkpoint(model_checkpoint).eval()
+    if use_fastnewt:
+        model.newt = nws.FastNEWT(model.newt)
+    model = model.to(dev)
+    for p in model.parameters():
+        p.requires_grad_(False)
+    reverb = model.reverb
+    reverb.ir.requires_grad_(True)
+    reverb.differentiable = True
+    loss_fn = nws.MultiResolutionSTFTLoss(differentiable=True)
+    opt = torch.optim.Adam([reverb.ir], lr=float(lr))
+    with_audio = [n for n in data.names if os.path.exists(os.path.join(data.audio_dir, f"audio_{n}.npy"))]
+    if len(with_audio) < len(data):
+        print(f"{len(data) - len(with_audio)} of {len(data)} items of {split!r} have no target audio and are left out")
+    if not with_audio:
+        raise click.ClickException(f"no item of {split!r} under {dataset_root} has target audio: nothing to fit to")
+    for step in range(int(steps)):
+        torch.cuda.manual_seed(int(seed))
+        opt.zero_grad(set_to_none=True)
+        losses, sizes = [], []
+        for batch in data.batches(with_audio, batch_size):
+            audio = torch.from_numpy(np.stack(batch["audio"])).to(dev)
+            f0, control = torch.from_numpy(batch["f0"]).to(dev), torch.from_numpy(batch["control"]).to(dev)
+            pre = model.pre_reverb(f0, control)
+            if pre.shape != audio.shape:
+                raise click.ClickException(f"the model renders {tuple(pre.shape)} but the batch's audio is {tuple(audio.shape)}")
+            loss = loss_fn(reverb(pre), audio)
+            loss.backward()                                   # the batches' gradients add up in reverb.ir.grad
+            losses.append(float(loss))
+            sizes.append(len(batch["names"]))
+        opt.step()
+        print(f"step {step}: loss {float(np.average(losses, weights=sizes)):.6f}  ({sum(sizes)} items in {len(sizes)} batches)")
+    write_checkpoint(output, model_checkpoint, reverb.ir)
+    print(f"wrote {output}: reverb.ir fitted in {int(steps)} steps, every other tensor as in {model_checkpoint}")
+
+
+if __name__ == "__main__":
+    main()
