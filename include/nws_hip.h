@@ -223,6 +223,27 @@ int nws_fir_noise(const float* fir /* (B,T,128): upper half-taps, see nws_frame_
 int nws_fir_noise_window(const float* fir, const float* noise, int noise_len, int origin, const float* add_in, int B, int T,
                          float* out, void* stream);
 
+/* The transpose of nws_fir_noise and of nws_fir_from_h for g = dL/d(out) (B,N), N = 128 T.  For a fixed
+ * excitation the noise branch is linear in H, so nothing is saved but the noise vector.  Whole-clip form only (origin 128,
+ * noise_len N-1); the windowed streaming form has no backward, and neither the excitation nor the design matrix gets a gradient.
+ *   g^[j]          = g[b,j] / c[j] (c = 1 for j < 128, else 2; 0 for N <= j < N + 128: the cropped half of frame T-1)
+ *   dh[b,t,m]      = sum_{n<256} g^[128 t + n] x_t[(n - m) mod 256],  x_t[n] = noise[refl(128 (t-1) + n)]
+ *   grad_fir[b,t,d] = dh[b,t,128+d] + dh[b,t,128-d] (d = 1..127), dh[b,t,128] (d = 0): the gradient of the stored half row
+ *   grad_H[b,k,t]  = sum_{d<128} fir_design[128+d][k] grad_fir[b,t,d]
+ * nws_fir_noise_grad: one launch, per frame pair one forward and one inverse 256-point transform, the noise spectra once per
+ * workgroup; every row of grad_fir is written by one wave, no atomics: equal inputs give equal bits.  nws_fir_from_h_grad: one
+ * launch, plain fp32, summed over d in order.  Both launch on `stream`, read nothing back and decide every refusal before the
+ * launch: NWS_ERR_BAD_ARG for a NULL pointer, B < 1 or T < 2; NWS_ERR_UNSUPPORTED for T > 2^23, more than 2^30 workgroups
+ * (nws_fir_noise_grad: ceil(T/8) ceil(B/8)) or B > 65 535 (nws_fir_from_h_grad). */
+int nws_fir_noise_grad(const float* noise /* (N-1) */, const float* grad_out /* (B,N) */, int B, int T,
+                       float* grad_fir /* (B,T,128) */, void* stream);
+int nws_fir_from_h_grad(const float* grad_fir /* (B,T,128) */, const float* fir_design /* (256,132) */, int B, int T,
+                        float* grad_H /* (B,129,T) */, void* stream);
+/* out[c] = sum over b and t of x[b,c,t], accumulated in float64 in a fixed order (per channel: 256 partial sums, each over
+ * t = i, i + 256, ... of utterance 0, 1, ... in turn, then a fixed tree), rounded once to fp32: equal inputs give equal bits.  Carries a gradient of shape (B,C,T) onto a
+ * per-channel offset.  NWS_ERR_BAD_ARG for a NULL pointer or a size < 1. */
+int nws_sum_batch_time(const float* x /* (B,C,T) */, int B, int C, int T, float* out /* (C) */, void* stream);
+
 /* ---- learned reverb (models/modules/shaping.py:161-173): y = x + circconv_Lc(x, [0, ir])[:N], Lc = max(N, ir_len+1) ----
  * A plan exists for EVERY even circular length (the reference takes any N; for an odd Lc its rfft / irfft pair is not a
  * circular convolution at all - runtime-size path, nws_g_reverb_direct).  Two forms:

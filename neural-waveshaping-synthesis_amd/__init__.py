@@ -17,7 +17,7 @@ from . import ginlite as gin  # noqa: F401,E402
 from ._lib import LIB_PATH, NwsError  # noqa: F401
 from .models.neural_waveshaping import ControlModule, NeuralWaveshaping, ensure_default_config, _DEFAULT_GIN as DEFAULT_GIN  # noqa: F401,E501
 from .models.modules.dynamic import FiLM, TimeDistributedLayerNorm, TimeDistributedMLP  # noqa: F401
-from .models.modules.generators import FIRNoiseSynth, HarmonicOscillator  # noqa: F401
+from .models.modules.generators import FIRNoiseSynth, HarmonicOscillator, add_channel_offset  # noqa: F401
 from .models.modules.shaping import NEWT, FastNEWT, Reverb, Sine, TrainableNonlinearity  # noqa: F401
 from .pipeline import ForwardPipeline  # noqa: F401
 from .losses import MultiResolutionSTFTLoss, STFTLoss  # noqa: F401

@@ -221,6 +221,33 @@ class CtypesOps:
             check(_lib.lib().nws_fir_from_h(ptr(H), ptr(fir_design), B, T, ptr(fir), _stream(H.device)), "nws_fir_from_h")
         return fir
 
+    def fir_noise_grad(self, noise, grad_out):
+        B, N = grad_out.shape
+        T = N // HOP
+        if N != T * HOP or T < 2 or noise.numel() != N - 1:
+            raise RuntimeError(f"fir_noise_grad: grad_out {tuple(grad_out.shape)} must be (B, 128 T) with T >= 2 and noise "
+                               f"{tuple(noise.shape)} its {N - 1} samples")
+        with torch.cuda.device(grad_out.device):
+            grad_fir = _new(grad_out, B, T, _lib.FIR_HALF)
+            check(_lib.lib().nws_fir_noise_grad(ptr(noise), ptr(grad_out), B, T, ptr(grad_fir), _stream(grad_out.device)),
+                  "nws_fir_noise_grad")
+        return grad_fir
+
+    def fir_from_h_grad(self, grad_fir, fir_design):
+        B, T, _ = grad_fir.shape
+        with torch.cuda.device(grad_fir.device):
+            grad_H = _new(grad_fir, B, _lib.N_BANDS, T)
+            check(_lib.lib().nws_fir_from_h_grad(ptr(grad_fir), ptr(fir_design), B, T, ptr(grad_H), _stream(grad_fir.device)),
+                  "nws_fir_from_h_grad")
+        return grad_H
+
+    def sum_batch_time(self, x):
+        B, Cc, T = x.shape
+        with torch.cuda.device(x.device):
+            out = _new(x, Cc)
+            check(_lib.lib().nws_sum_batch_time(ptr(x), B, Cc, T, ptr(out), _stream(x.device)), "nws_sum_batch_time")
+        return out
+
     def reverb(self, plan, tables, spectrum, x):
         B, N = x.shape
         p = _plan(plan)

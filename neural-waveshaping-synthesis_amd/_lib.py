@@ -117,6 +117,9 @@ _PROTOTYPES = {
     "nws_fir_design_matrix": (C.c_int, [_fp, _fp, _fp]),
     "nws_fir_noise": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "nws_fir_noise_window": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp]),
+    "nws_fir_noise_grad": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, _fp]),
+    "nws_fir_from_h_grad": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, _fp]),
+    "nws_sum_batch_time": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "nws_reverb_linear_chunk": (C.c_int, [C.POINTER(NwsReverbPlan), _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, _fp,
                                           C.c_size_t, _fp]),
     "nws_reverb_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(NwsReverbPlan)]),

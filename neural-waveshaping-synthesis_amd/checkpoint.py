@@ -5,7 +5,8 @@ Reads either
     zip-pickle with ``state_dict`` and ``hyper_parameters``; the pickle references one
     pytorch_lightning class, resolved here with a throw-away stand-in so Lightning is not needed), or
   * a flat ``.npz`` of state-dict arrays (tests/golden/weights_vn.npz).
-and the ``data_mean.npy`` / ``data_std.npy`` normalisation statistics next to it.
+and the ``data_mean.npy`` / ``data_std.npy`` normalisation statistics next to it; ``write_checkpoint`` writes a checkpoint
+back with named tensors replaced (scripts/fit_reverb.py, scripts/fit_noise.py).
 """
 import contextlib
 import os
@@ -51,6 +52,29 @@ def read_checkpoint(path):
         ck = torch.load(path, map_location="cpu", weights_only=False)
     hp = {k: v for k, v in dict(ck.get("hyper_parameters", {})).items() if k in _HPARAM_KEYS}
     return dict(ck["state_dict"]), hp
+
+
+def write_checkpoint(path, source, replace):
+    """Write the checkpoint `source` to `path` with the tensors named in `replace` ({state-dict key: tensor}) replaced, each
+    cast to the dtype it has in the source: as .npz (every array of the source is kept, the `__`-prefixed ones too) or, for any
+    other suffix, as a torch checkpoint with `state_dict` and `hyper_parameters`."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    replace = {k: v.detach().cpu() for k, v in replace.items()}
+    if str(path).endswith(".npz"):
+        if str(source).endswith(".npz"):
+            z = np.load(source)
+            arrays = {k: z[k] for k in z.files}
+        else:
+            arrays = {k: np.asarray(v) for k, v in read_checkpoint(source)[0].items()}
+        for k, v in replace.items():
+            arrays[k] = v.numpy().astype(arrays[k].dtype)
+        np.savez(path, **arrays)
+        return
+    state, hparams = read_checkpoint(source)
+    state = {k: torch.as_tensor(v) for k, v in state.items()}
+    for k, v in replace.items():
+        state[k] = v.to(state[k].dtype)
+    torch.save({"state_dict": state, "hyper_parameters": hparams}, path)
 
 
 def load_normalisation(checkpoint_dir):

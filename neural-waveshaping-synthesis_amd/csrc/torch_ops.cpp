@@ -412,6 +412,47 @@ Tensor fir_from_h(const Tensor& H, const Tensor& fir_design) {
   return fir;
 }
 
+// dL/d(fir) of fir_noise for grad_out = dL/d(out) (B, 128 T) and the excitation the forward used: (B, T, 128)
+Tensor fir_noise_grad(const Tensor& noise, const Tensor& grad_out) {
+  check_dev(noise, "noise");
+  check_dev(grad_out, "grad_out");
+  check_same_device(grad_out, "grad_out", noise, "noise");
+  TORCH_CHECK(grad_out.dim() == 2 && grad_out.size(1) % NWS_HOP == 0 && grad_out.size(1) >= 2 * NWS_HOP,
+              "fir_noise_grad: expected grad_out (B, 128 T) with T >= 2, got ", grad_out.sizes());
+  const int64_t B = grad_out.size(0), T = grad_out.size(1) / NWS_HOP;
+  TORCH_CHECK(noise.numel() == T * NWS_HOP - 1, "noise: expected ", T * NWS_HOP - 1, " samples, got ", noise.sizes());
+  Launch L(grad_out);
+  Tensor grad_fir = at::empty({B, T, NWS_FIR_HALF}, grad_out.options());
+  nws_check(nws_fir_noise_grad(noise.data_ptr<float>(), grad_out.data_ptr<float>(), (int)B, (int)T, grad_fir.data_ptr<float>(),
+                               L.stream), "nws_fir_noise_grad");
+  return grad_fir;
+}
+
+// dL/dH of fir_from_h for grad_fir (B, T, 128): (B, 129, T)
+Tensor fir_from_h_grad(const Tensor& grad_fir, const Tensor& fir_design) {
+  check_dev(grad_fir, "grad_fir");
+  check_dev(fir_design, "fir_design");
+  check_same_device(grad_fir, "grad_fir", fir_design, "fir_design");
+  TORCH_CHECK(grad_fir.dim() == 3 && grad_fir.size(2) == NWS_FIR_HALF, "fir_from_h_grad: expected grad_fir (B, T, 128), got ", grad_fir.sizes());
+  TORCH_CHECK(fir_design.numel() == NWS_FIR_LEN * 132, "fir_design: expected (256, 132)");
+  Launch L(grad_fir);
+  Tensor grad_H = at::empty({grad_fir.size(0), NWS_N_BANDS, grad_fir.size(1)}, grad_fir.options());
+  nws_check(nws_fir_from_h_grad(grad_fir.data_ptr<float>(), fir_design.data_ptr<float>(), (int)grad_fir.size(0), (int)grad_fir.size(1),
+                                grad_H.data_ptr<float>(), L.stream), "nws_fir_from_h_grad");
+  return grad_H;
+}
+
+// (B, C, T) -> (C): the sum over batch and time in float64, in a fixed order (the backward of adding a per-channel offset)
+Tensor sum_batch_time(const Tensor& x) {
+  check_dev(x, "x");
+  TORCH_CHECK(x.dim() == 3, "sum_batch_time: expected (B, C, T), got ", x.sizes());
+  Launch L(x);
+  Tensor out = at::empty({x.size(1)}, x.options());
+  nws_check(nws_sum_batch_time(x.data_ptr<float>(), (int)x.size(0), (int)x.size(1), (int)x.size(2), out.data_ptr<float>(), L.stream),
+            "nws_sum_batch_time");
+  return out;
+}
+
 // Reverb.forward (shaping.py:161-173): x (B, N) -> x + circconv_L(x, [0, ir])[:N]
 Tensor reverb(const Tensor& plan_t, const Tensor& tables, const Tensor& spectrum, const Tensor& x) {
   NwsReverbPlan plan = plan_of(plan_t);
@@ -1265,6 +1306,9 @@ TORCH_LIBRARY(newt_hip, m) {
         &frame_mlps);
   m.def("fir_noise(Tensor fir, Tensor noise, Tensor? add_in, int origin) -> Tensor", &fir_noise);
   m.def("fir_from_h(Tensor H, Tensor fir_design) -> Tensor", &fir_from_h);
+  m.def("fir_noise_grad(Tensor noise, Tensor grad_out) -> Tensor", &fir_noise_grad);
+  m.def("fir_from_h_grad(Tensor grad_fir, Tensor fir_design) -> Tensor", &fir_from_h_grad);
+  m.def("sum_batch_time(Tensor x) -> Tensor", &sum_batch_time);
   m.def("reverb(Tensor plan, Tensor tables, Tensor spectrum, Tensor x) -> Tensor", &reverb);
   m.def("reverb_grad_x(Tensor plan, Tensor tables, Tensor spectrum, Tensor grad_out) -> Tensor", &reverb_grad_x);
   m.def("reverb_grad_ir(Tensor plan, Tensor tables, Tensor x, Tensor grad_out, int ir_len) -> Tensor", &reverb_grad_ir);

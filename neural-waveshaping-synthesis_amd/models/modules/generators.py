@@ -16,13 +16,67 @@ from ... import ginlite as gin
 from . import _standalone as sa
 
 
+class _FIRNoiseFunction(torch.autograd.Function):
+    """FIRNoiseSynth.forward with its transpose attached (csrc/fir_noise_grad.hip): backward runs
+    fir_noise_grad and fir_from_h_grad on the excitation the forward used"""
+
+    @staticmethod
+    def forward(ctx, H_re, noise, module):
+        y = module._forward_detached(H_re.detach(), noise)
+        ctx.module = module
+        ctx.save_for_backward(noise)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (noise,) = ctx.saved_tensors
+        return ctx.module.vjp(grad_out[:, 0], noise), None, None
+
+
+class _ChannelOffsetFunction(torch.autograd.Function):
+    """x + offset[None, :, None]: the add is plumbing, its backward onto the offset is the fixed-order float64 reduction over
+    batch and time (sum_batch_time, csrc/fir_noise_grad.hip)"""
+
+    @staticmethod
+    def forward(ctx, x, offset):
+        return x.detach() + offset.detach()[None, :, None]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        gx = grad_out if ctx.needs_input_grad[0] else None
+        go = sa.binding().sum_batch_time(sa.contiguous(grad_out, "grad_out")) if ctx.needs_input_grad[1] else None
+        return gx, go
+
+
+def add_channel_offset(x, offset):
+    """(B, C, T) + (C,) per-channel offset -> (B, C, T), differentiable in both: what moves a gradient with respect to the noise
+    filter magnitudes H onto the last bias of the MLP that made them (scripts/fit_noise.py)"""
+    x = sa.contiguous(x, "x")
+    offset = sa._req(offset, "offset", x.shape[1] if x.dim() == 3 else None)
+    if x.dim() != 3 or offset.dim() != 1:
+        raise RuntimeError(f"add_channel_offset: expected (B, C, T) and (C,), got {tuple(x.shape)} and {tuple(offset.shape)}")
+    return _ChannelOffsetFunction.apply(x, offset)
+
+
 @gin.configurable
 class FIRNoiseSynth(nn.Module):
+    """Time-varying FIR filtered noise (reference generators.py:11-35).
+
+    ``differentiable`` (a plain attribute, default False): forward only, the result carries no graph and an ``H_re`` that
+    requires grad is refused.  Set to True, a forward under grad mode whose ``H_re`` requires grad returns the same bits with a
+    ``torch.autograd.Function`` attached that gives dL/dH for the excitation that call used, injected or drawn (the excitation,
+    the window and the design matrix get no gradient).  ``vjp`` is the same gradient without autograd."""
+
+    differentiable = False      # also the value of a module unpickled from before the flag existed
+
     def __init__(self, ir_length: int, hop_length: int, window_fn: Callable = torch.hann_window):
         super().__init__()
         self.ir_length = ir_length
         self.hop_length = hop_length
         self.register_buffer("window", window_fn(ir_length))
+        self.differentiable = False
         self._design = {}
 
     def __getstate__(self):
@@ -44,23 +98,68 @@ class FIRNoiseSynth(nn.Module):
             self._design[key] = hit
         return hit
 
+    def _specialised(self):
+        return self.ir_length == sa._lib.FIR_LEN and self.hop_length == sa._lib.HOP and self._window_symmetric()
+
+    def _checked_noise(self, noise, T, dev):
+        if noise is None:
+            noise = torch.rand(self.hop_length * T - 1, device=dev)               # the reference's draw (generators.py:30)
+        elif noise.requires_grad:
+            raise RuntimeError("FIRNoiseSynth: the excitation gets no gradient (noise requires grad)")
+        return sa._req(noise.detach(), "noise", self.hop_length * T - 1)
+
     def forward(self, H_re, *, noise=None):
         """H_re (B, ir_length/2 + 1, T) real filter magnitudes -> (B, 1, hop * T) filtered noise (generators.py:21-35).
         `noise` injects the excitation draw (hop * T - 1 samples) for parity tests."""
-        if self.ir_length != sa._lib.FIR_LEN or self.hop_length != sa._lib.HOP or not self._window_symmetric():
+        wants_grad = (self.differentiable and torch.is_grad_enabled() and isinstance(H_re, torch.Tensor) and H_re.requires_grad)
+        if not self._specialised():
+            if wants_grad:
+                raise RuntimeError("FIRNoiseSynth: the runtime-size path (any other ir_length, hop_length or window than 256, 128 "
+                                   "and a window symmetric about tap 128) has no gradient; only the specialised kernels have a transpose")
             return self._forward_generic(H_re, noise)
+        if wants_grad:
+            H = self._checked_H(H_re.detach())                                    # refusals before autograd is involved
+            noise = self._checked_noise(noise, H.shape[2], H.device)
+            return _FIRNoiseFunction.apply(H_re, noise, self)
+        return self._forward_detached(H_re, noise)
+
+    def _checked_H(self, H_re):
         H = sa.contiguous(H_re, "H_re")
         if H.dim() != 3 or H.shape[1] != sa._lib.N_BANDS:
             raise RuntimeError(f"FIRNoiseSynth: expected (B, {sa._lib.N_BANDS}, T), got {tuple(H.shape)}")
-        B, _, T = H.shape
-        if T < 2:
+        if H.shape[2] < 2:
             raise RuntimeError("need at least 2 frames (reflect padding of the noise STFT, generators.py:31)")
+        return H
+
+    def _forward_detached(self, H_re, noise):
+        H = self._checked_H(H_re)
         D = self._design_matrix(H.device)
-        if noise is None:
-            noise = torch.rand(self.hop_length * T - 1, device=H.device)          # the reference's draw (generators.py:30)
-        noise = sa._req(noise, "noise", self.hop_length * T - 1)
+        sa.no_autograd(inputs=(H,))
+        noise = self._checked_noise(noise, H.shape[2], H.device)
         b = sa.binding()
         return b.fir_noise(b.fir_from_h(H, D), noise, None, -1).unsqueeze(1)
+
+    def vjp(self, grad_out, noise):
+        """dL/dH (B, ir_length/2 + 1, T) of ``forward`` for grad_out = dL/d(out) (B, hop * T) (or (B, 1, hop * T)) and the
+        excitation that forward used.  Whatever ``differentiable`` and the grad mode say; autograd is not involved and the result
+        carries no graph."""
+        if not self._specialised():
+            raise RuntimeError("FIRNoiseSynth.vjp: the runtime-size path (any other ir_length, hop_length or window than 256, 128 "
+                               "and a window symmetric about tap 128) has no gradient")
+        with torch.no_grad():
+            g = grad_out.detach()
+            if g.dim() == 3 and g.shape[1] == 1:
+                g = g[:, 0]
+            g = sa.contiguous(g, "grad_out")
+            hop = int(self.hop_length)
+            if g.dim() != 2 or g.shape[1] % hop or g.shape[1] < 2 * hop:
+                raise RuntimeError(f"grad_out: expected (B, {hop} T) with T >= 2, got {tuple(g.shape)}")
+            noise = self._checked_noise(noise, g.shape[1] // hop, g.device)
+            if noise.device != g.device:
+                raise RuntimeError(f"grad_out is on {g.device} but noise is on {noise.device}")
+            D = self._design_matrix(g.device)
+            b = sa.binding()
+            return b.fir_from_h_grad(b.fir_noise_grad(noise, g), D)
 
     def _window_symmetric(self):
         """the specialised kernels pass half rows of taps (include/nws_hip.h, nws_frame_mlps): needs a window that is symmetric

@@ -9,9 +9,11 @@ Of the reference's Lightning hooks (:92-165) the two that need no backward pass 
 and ``test_step`` return ``stft_loss(recon, audio)`` - ``losses.MultiResolutionSTFTLoss``, the HIP restatement
 of the ``auraloss`` loss the reference logs as ``val/loss`` / ``test/loss`` - through the
 reference's ``_run_step``.  ``stft_loss`` is made on first use (in the reference ``configure_optimizers`` makes
-it).  ``training_step`` and ``configure_optimizers`` raise: the loss and the reverb have a backward pass
-(DESIGN.md 3.13, 3.14), nothing upstream of the reverb has one.  ``pre_reverb`` renders the
-reverb's input, which is what fitting ``reverb.ir`` alone needs.  Logging (``self.log``, wandb) is left to the caller.
+it).  ``training_step`` and ``configure_optimizers`` raise: the loss, the reverb and the noise branch's filter have a
+backward pass, the frame MLPs, the recurrence and the oscillator branch have none
+(SURVEY.md §2 row 1b).  ``pre_reverb`` renders the reverb's input, which is what fitting ``reverb.ir`` alone needs;
+``pre_reverb_parts`` renders it in two parts with the noise filter's input, which is what fitting the noise colour
+needs.  Logging (``self.log``, wandb) is left to the caller.
 
 Hidden inputs, exactly like the reference: every forward draws ``rand_like(osc.rand_phase)`` and then
 ``rand(control_hop*T - 1)`` from the default generator of the module's device, in that order
@@ -197,6 +199,22 @@ class NeuralWaveshaping(nn.Module):
         f0, control, phase_u, noise = self._checked_inputs(f0, control, phase_u, noise)
         return self._pre_reverb_module_by_module(f0, control, phase_u, noise)
 
+    def pre_reverb_parts(self, f0, control, phase_u=None, noise=None):
+        """``pre_reverb`` taken apart where the noise branch's backward starts: (newt_sum (B, N), H (B, 129, T), noise (N - 1)) -
+        the summed oscillator branch, the noise filter magnitudes ``h_generator(emb)`` and the excitation draw, so that
+        ``newt_sum + self.noise_synth(H, noise=noise)[:, 0]`` is ``pre_reverb`` for the same draws (the sum of the channels in
+        another order: within the parity bar, not to the bit).  Same module-by-module kernels, under ``no_grad``; nothing
+        carries a graph.  With ``noise_synth.differentiable`` a gradient reaches H (scripts/fit_noise.py)."""
+        f0, control, phase_u, noise = self._checked_inputs(f0, control, phase_u, noise)
+        with torch.no_grad():
+            f0_up = upsample_linear(f0, int(self.control_hop))                    # :75
+            sig = self.osc(f0_up[:, 0], phase_u=phase_u)                          # :65   (draw #1 injected / made above)
+            x = self.harmonic_mixer(sig)                                          # :66
+            emb = self.embedding(control[:, 0:2].contiguous())                    # :69-72
+            x = self.newt(x, emb)                                                 # :80
+            H = self.h_generator(emb)                                             # :82
+            return sa.sum_channels(x), H, noise                                   # :86 without the noise channel
+
     # ---- evaluation hooks (reference :104-112, :136-165): inference + loss, no backward ----------------
     @property
     def stft_loss(self):
@@ -234,15 +252,18 @@ class NeuralWaveshaping(nn.Module):
             return self._run_step(batch)[0]
 
     def training_step(self, batch, batch_idx):
-        raise NotImplementedError("training_step: there is no backward pass in this package upstream of the reverb - the loss "
-                                  "(losses.MultiResolutionSTFTLoss(differentiable=True)) and the reverb (Reverb.differentiable, "
-                                  "Reverb.vjp) have one, the rest of the model does not; validation_step and test_step give the "
-                                  "reference's loss, and scripts/fit_reverb.py fits reverb.ir alone")
+        raise NotImplementedError("training_step: there is no backward pass in this package for the whole model - the loss "
+                                  "(losses.MultiResolutionSTFTLoss(differentiable=True)), the reverb (Reverb.differentiable, "
+                                  "Reverb.vjp) and the noise branch's filter (FIRNoiseSynth.differentiable, FIRNoiseSynth.vjp: "
+                                  "dL/dH) have one, the frame MLPs, the recurrence and the oscillator branch do not; "
+                                  "validation_step and test_step give the reference's loss, scripts/fit_reverb.py fits reverb.ir "
+                                  "and scripts/fit_noise.py the noise colour (h_generator's last bias)")
 
     def configure_optimizers(self):
-        raise NotImplementedError("configure_optimizers: there is no backward pass in this package upstream of the reverb (the loss "
-                                  "and the reverb have one), so the only parameter to optimise is reverb.ir (scripts/fit_reverb.py); "
-                                  "model.stft_loss is made on first use instead")
+        raise NotImplementedError("configure_optimizers: there is no backward pass in this package for the whole model (the loss, "
+                                  "the reverb and the noise branch's filter have one), so the parameters to optimise are reverb.ir "
+                                  "(scripts/fit_reverb.py) and h_generator's last bias (scripts/fit_noise.py); model.stft_loss is "
+                                  "made on first use instead")
 
     def _sub_module_hooks(self) -> bool:
         """Forward hooks on sub-modules (the reference's users tap stages that way, and so does tests/golden/make_golden.py on
