@@ -374,6 +374,21 @@ int nws_newt_apply(const NwsWeights* w, const float* exciter, const float* film,
 int nws_td_mlp(const float* x, int B, int in_size, int hidden, int out_size, int depth, int T, const float* const* w,
                const float* const* b, const float* const* ln_g, const float* const* ln_b, float ln_eps, float leaky_slope,
                float* y, void* stream);
+/* The backward of nws_td_mlp for grad_y = dL/dy (B, out, T): grad_x (B, in, T) and, when grad_w and grad_b are
+ * given, the gradient of every parameter: grad_w[i] like w[i], grad_b[i] like b[i] (depth entries each), grad_ln_g[i] and
+ * grad_ln_b[i] (depth-1 entries each).  grad_w == grad_b == NULL: the data gradient alone, no workspace.  Nothing is saved by the
+ * forward: the frame tile's forward is recomputed from x.  Exact fp32 products, sums over batch and time in a fixed order in
+ * float64, no atomics: equal inputs give equal bits, grad_y = 0 gives zeros.  LeakyReLU' at v = 0 is `leaky_slope` (torch's).
+ * Launches on `stream` (the recomputing kernel, then with parameters the dW contraction and two reductions), reads nothing back
+ * and decides every refusal before the first launch: NWS_ERR_BAD_ARG for a NULL required pointer, a size < 1 or a workspace
+ * smaller than nws_td_mlp_grad_workspace_bytes; NWS_ERR_UNSUPPORTED for depth outside 1 .. 8, B > 65 535, a layer width above
+ * 256 or more than 160 KB of LDS ((max(in, hidden) + (depth-1) hidden) 132 bytes + 2 KB + (depth-1) 128).
+ * nws_td_mlp_grad_workspace_bytes: 0 without want_params or for sizes that are refused. */
+size_t nws_td_mlp_grad_workspace_bytes(int B, int in_size, int hidden, int out_size, int depth, int T, int want_params);
+int nws_td_mlp_grad(const float* x, const float* grad_y, int B, int in_size, int hidden, int out_size, int depth, int T,
+                    const float* const* w, const float* const* b, const float* const* ln_g, const float* const* ln_b,
+                    float ln_eps, float leaky_slope, float* grad_x /* (B,in,T) */, float* const* grad_w, float* const* grad_b,
+                    float* const* grad_ln_g, float* const* grad_ln_b, void* workspace, size_t workspace_bytes, void* stream);
 /* TimeDistributedLayerNorm.forward (dynamic.py:11-17): LayerNorm over the channel axis of (B, C, T) */
 int nws_td_layer_norm(const float* x, const float* gain, const float* bias, int B, int C, int T, float eps, float* y,
                       void* stream);

@@ -330,6 +330,30 @@ class CtypesOps:
                                         _ptrs(ln_w), _ptrs(ln_b), eps, slope, ptr(y), _stream(x.device)), "nws_td_mlp")
         return y
 
+    def td_mlp_grad(self, x, grad_y, weights, biases, ln_w, ln_b, eps, slope, want_params):
+        B, in_size, T = x.shape
+        depth = len(weights)
+        hidden, out_size = weights[0].shape[0], weights[-1].shape[0]
+        if tuple(grad_y.shape) != (B, out_size, T):
+            raise RuntimeError(f"td_mlp_grad: grad_y {tuple(grad_y.shape)} is not ({B}, {out_size}, {T})")
+        if len(biases) != depth or len(ln_w) != depth - 1 or len(ln_b) != depth - 1:
+            raise RuntimeError("td_mlp_grad: inconsistent layer lists")
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            grad_x = torch.empty_like(x)
+            gw, gb, gg, gl, ws, nbytes = [], [], [], [], None, 0
+            if want_params:
+                gw, gb = [torch.empty_like(t) for t in weights], [torch.empty_like(t) for t in biases]
+                gg, gl = [torch.empty_like(t) for t in ln_w], [torch.empty_like(t) for t in ln_b]
+                nbytes = L.nws_td_mlp_grad_workspace_bytes(B, in_size, hidden, out_size, depth, T, 1)
+                ws = _new(x, max(nbytes, 1), dtype=torch.uint8)
+            none = None
+            check(L.nws_td_mlp_grad(ptr(x), ptr(grad_y), B, in_size, hidden, out_size, depth, T, _ptrs(weights), _ptrs(biases),
+                                    _ptrs(ln_w), _ptrs(ln_b), eps, slope, ptr(grad_x), _ptrs(gw) if want_params else none,
+                                    _ptrs(gb) if want_params else none, _ptrs(gg) if want_params else none,
+                                    _ptrs(gl) if want_params else none, ptr(ws), nbytes, _stream(x.device)), "nws_td_mlp_grad")
+        return [grad_x] + gw + gb + gg + gl
+
     def td_layer_norm(self, x, weight, bias, eps):
         with torch.cuda.device(x.device):
             y = torch.empty_like(x)

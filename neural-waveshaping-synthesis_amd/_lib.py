@@ -193,6 +193,10 @@ _PROTOTYPES = {
     "nws_newt_apply": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "nws_td_mlp": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),
                              C.POINTER(_fp), C.POINTER(_fp), C.c_float, C.c_float, _fp, _fp]),
+    "nws_td_mlp_grad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nws_td_mlp_grad": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),
+                                  C.POINTER(_fp), C.POINTER(_fp), C.c_float, C.c_float, _fp, C.POINTER(_fp), C.POINTER(_fp),
+                                  C.POINTER(_fp), C.POINTER(_fp), _fp, C.c_size_t, _fp]),
     "nws_td_layer_norm": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp]),
     "nws_film": (C.c_int, [_fp, _fp, _fp, C.c_int64, _fp, _fp]),
     "nws_fir_from_h": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, _fp]),

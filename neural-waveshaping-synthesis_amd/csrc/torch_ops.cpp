@@ -630,6 +630,73 @@ Tensor td_mlp(const Tensor& x, at::TensorList weights, at::TensorList biases, at
   return y;
 }
 
+// The backward of td_mlp for grad_y = dL/dy: [grad_x] + grad_weights + grad_biases + grad_ln_w + grad_ln_b, or
+// grad_x alone without want_params.  Nothing was saved by the forward; the workspace comes from torch's allocator.
+std::vector<Tensor> td_mlp_grad(const Tensor& x, const Tensor& grad_y, at::TensorList weights, at::TensorList biases, at::TensorList ln_w,
+                                at::TensorList ln_b, double eps, double slope, bool want_params) {
+  check_dev(x, "x");
+  check_dev(grad_y, "grad_y");
+  check_same_device(x, "x", grad_y, "grad_y");
+  TORCH_CHECK(x.dim() == 3, "td_mlp_grad: expected x (B, C, T), got ", x.sizes());
+  const int depth = (int)weights.size();
+  TORCH_CHECK(depth >= 1 && depth <= 8 && (int)biases.size() == depth && (int)ln_w.size() == depth - 1 &&
+                  (int)ln_b.size() == depth - 1, "td_mlp_grad: inconsistent layer lists");
+  const int64_t B = x.size(0), in_size = x.size(1), T = x.size(2);
+  const int64_t hidden = weights[0].size(0), out_size = weights[depth - 1].size(0);
+  TORCH_CHECK(grad_y.dim() == 3 && grad_y.size(0) == B && grad_y.size(1) == out_size && grad_y.size(2) == T,
+              "td_mlp_grad: grad_y ", grad_y.sizes(), " is not (", B, ", ", out_size, ", ", T, ")");
+  const float* wp[8];
+  const float* bp[8];
+  const float* gp[8] = {nullptr};
+  const float* lp[8] = {nullptr};
+  float* gwp[8] = {nullptr};
+  float* gbp[8] = {nullptr};
+  float* ggp[8] = {nullptr};
+  float* glp[8] = {nullptr};
+  std::vector<Tensor> gw, gb, gg, gl;
+  for (int i = 0; i < depth; ++i) {
+    check_dev(weights[i], "net weight");
+    check_dev(biases[i], "net bias");
+    check_same_device(x, "x", weights[i], "the MLP's parameters");
+    const int64_t rows = i == depth - 1 ? out_size : hidden, cols = i == 0 ? in_size : hidden;
+    TORCH_CHECK(weights[i].numel() == rows * cols && weights[i].size(0) == rows, "td_mlp_grad layer ", i, ": weight ",
+                weights[i].sizes(), " does not match (", rows, ", ", cols, ") - input has ", in_size, " channels");
+    TORCH_CHECK(biases[i].numel() == rows, "td_mlp_grad layer ", i, ": bias ", biases[i].sizes());
+    wp[i] = weights[i].data_ptr<float>();
+    bp[i] = biases[i].data_ptr<float>();
+    if (want_params) {
+      gw.push_back(at::empty(weights[i].sizes(), x.options()));
+      gb.push_back(at::empty(biases[i].sizes(), x.options()));
+      gwp[i] = gw.back().data_ptr<float>();
+      gbp[i] = gb.back().data_ptr<float>();
+    }
+    if (i < depth - 1) {
+      check_dev(ln_w[i], "layer_norm weight");
+      check_dev(ln_b[i], "layer_norm bias");
+      TORCH_CHECK(ln_w[i].numel() == hidden && ln_b[i].numel() == hidden, "LayerNorm ", i, ": expected ", hidden, " elements");
+      gp[i] = ln_w[i].data_ptr<float>();
+      lp[i] = ln_b[i].data_ptr<float>();
+      if (want_params) {
+        gg.push_back(at::empty(ln_w[i].sizes(), x.options()));
+        gl.push_back(at::empty(ln_b[i].sizes(), x.options()));
+        ggp[i] = gg.back().data_ptr<float>();
+        glp[i] = gl.back().data_ptr<float>();
+      }
+    }
+  }
+  Launch L(x);
+  Tensor grad_x = at::empty_like(x);
+  const size_t nbytes = want_params ? nws_td_mlp_grad_workspace_bytes((int)B, (int)in_size, (int)hidden, (int)out_size, depth, (int)T, 1) : 0;
+  Tensor ws = at::empty({(int64_t)(nbytes > 0 ? nbytes : 1)}, x.options().dtype(at::kByte));
+  nws_check(nws_td_mlp_grad(x.data_ptr<float>(), grad_y.data_ptr<float>(), (int)B, (int)in_size, (int)hidden, (int)out_size, depth,
+                            (int)T, wp, bp, gp, lp, (float)eps, (float)slope, grad_x.data_ptr<float>(), want_params ? gwp : nullptr,
+                            want_params ? gbp : nullptr, want_params ? ggp : nullptr, want_params ? glp : nullptr,
+                            ws.data_ptr(), nbytes, L.stream), "nws_td_mlp_grad");
+  std::vector<Tensor> out{grad_x};
+  for (auto* lst : {&gw, &gb, &gg, &gl}) out.insert(out.end(), lst->begin(), lst->end());
+  return out;
+}
+
 Tensor td_layer_norm(const Tensor& x, const Tensor& weight, const Tensor& bias, double eps) {
   check_dev(x, "x");
   check_dev(weight, "layer_norm.weight");
@@ -1318,6 +1385,8 @@ TORCH_LIBRARY(newt_hip, m) {
   m.def("shaper_table(Tensor wdesc, Tensor like, int size, float tmin, float tmax) -> Tensor", &shaper_table);
   m.def("newt_apply(Tensor wdesc, Tensor exciter, Tensor film) -> Tensor", &newt_apply);
   m.def("td_mlp(Tensor x, Tensor[] weights, Tensor[] biases, Tensor[] ln_w, Tensor[] ln_b, float eps, float slope) -> Tensor", &td_mlp);
+  m.def("td_mlp_grad(Tensor x, Tensor grad_y, Tensor[] weights, Tensor[] biases, Tensor[] ln_w, Tensor[] ln_b, float eps, float slope, "
+        "bool want_params) -> Tensor[]", &td_mlp_grad);
   m.def("td_layer_norm(Tensor x, Tensor weight, Tensor bias, float eps) -> Tensor", &td_layer_norm);
   m.def("film(Tensor x, Tensor gamma, Tensor beta) -> Tensor", &film);
   m.def("sine(Tensor x) -> Tensor", &sine);

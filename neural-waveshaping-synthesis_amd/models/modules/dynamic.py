@@ -63,8 +63,38 @@ class TimeDistributedLayerNorm(nn.Module):
         return sa.call("td_layer_norm", x, g, b, float(ln.eps))
 
 
+class _TDMLPFunction(torch.autograd.Function):
+    """TimeDistributedMLP.forward with its backward attached (csrc/td_mlp_grad.hip): saves x alone; backward
+    recomputes the forward per frame tile and hands gradients to x and to every parameter that requires grad"""
+
+    @staticmethod
+    def forward(ctx, x, module, *params):
+        with torch.no_grad():
+            y = td_mlp_forward(x.detach(), module.net)
+        ctx.module = module
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        (x,) = ctx.saved_tensors
+        named = list(ctx.module.net.named_parameters())
+        want = any(ctx.needs_input_grad[2:])
+        gx, grads = td_mlp_vjp(x, ctx.module.net, grad_y, want_params=want)
+        out = [grads[k].view_as(p) if need else None for (k, p), need in zip(named, ctx.needs_input_grad[2:])] if want else [None] * len(named)
+        return (gx if ctx.needs_input_grad[0] else None, None, *out)
+
+
 @gin.configurable
 class TimeDistributedMLP(nn.Module):
+    """``differentiable`` (a plain attribute, default False): forward only, as the stage kernels are.  Set to True, a forward
+    under grad mode returns the same bits with a ``torch.autograd.Function`` attached that saves ``x``; its backward runs
+    ``td_mlp_grad`` and hands gradients to ``x`` and to every parameter that requires grad.  ``vjp`` is the same gradient
+    without autograd."""
+
+    differentiable = False      # also the value of a module unpickled from before the flag existed
+
     def __init__(self, in_size: int, hidden_size: int, out_size: int, depth: int = 3):
         super().__init__()
         assert depth >= 3, "Depth must be at least 3"
@@ -76,18 +106,38 @@ class TimeDistributedMLP(nn.Module):
                 stack += [TimeDistributedLayerNorm(hidden_size), nn.LeakyReLU()]
         self.net = nn.Sequential(*stack)
         self.in_size, self.hidden_size, self.out_size, self.depth = in_size, hidden_size, out_size, depth
+        self.differentiable = False
 
     def forward(self, x):
         """(B, in_size, T) -> (B, out_size, T) on a CUDA tensor: one launch of td_mlp_kernel (csrc/stages.hip)."""
+        if self.differentiable and torch.is_grad_enabled():
+            xc = sa.contiguous(x.detach(), "x")
+            if xc.dim() != 3 or xc.shape[1] != self.in_size:
+                raise RuntimeError(f"TimeDistributedMLP: expected (B, {self.in_size}, T), got {tuple(x.shape)}")
+            params = list(self.net.parameters())
+            if x.requires_grad or any(p.requires_grad for p in params):
+                return _TDMLPFunction.apply(x if x.is_contiguous() else x.contiguous(), self, *params)
+            return td_mlp_forward(xc, self.net)
         x = sa.contiguous(x, "x")
         if x.dim() != 3 or x.shape[1] != self.in_size:
             raise RuntimeError(f"TimeDistributedMLP: expected (B, {self.in_size}, T), got {tuple(x.shape)}")
         return td_mlp_forward(x, self.net)
 
+    def vjp(self, grad_y, x, want_params=True):
+        """(dL/dx, {state-dict key: gradient}) of ``forward`` at ``x`` for grad_y = dL/dy (B, out_size, T); keys like
+        ``net.3.weight`` and ``net.1.layer_norm.bias``, an empty dict without ``want_params``.  Whatever ``differentiable`` and
+        the grad mode say; autograd is not involved and the results carry no graph."""
+        if x.dim() != 3 or x.shape[1] != self.in_size:
+            raise RuntimeError(f"TimeDistributedMLP: expected (B, {self.in_size}, T), got {tuple(x.shape)}")
+        gx, grads = td_mlp_vjp(x, self.net, grad_y, want_params)
+        return gx, {"net." + k: v for k, v in grads.items()}
 
-def td_mlp_forward(x, net):
-    """Run a Conv1d(k=1) [-> TimeDistributedLayerNorm -> LeakyReLU] ... stack (or a bare Conv1d) on (B, C, T)."""
-    mods = list(net) if isinstance(net, (nn.Sequential, list, tuple)) else [net]
+
+def _td_mlp_stack(net):
+    """the checked pieces of a Conv1d(k=1) [-> TimeDistributedLayerNorm -> LeakyReLU] ... stack (or a bare Conv1d):
+    (convs, weights, biases, ln weights, ln biases, eps, slope, state-dict key prefixes of the convs, of the norms)"""
+    seq = isinstance(net, (nn.Sequential, list, tuple))
+    mods = list(net) if seq else [net]
     convs = [m for m in mods if isinstance(m, nn.Conv1d)]
     norms = [m for m in mods if isinstance(m, TimeDistributedLayerNorm)]
     acts = [m for m in mods if isinstance(m, nn.LeakyReLU)]
@@ -105,5 +155,36 @@ def td_mlp_forward(x, net):
                            "stack; these layers differ")
     if len(acts) != len(norms) or any(not n.layer_norm.elementwise_affine for n in norms):
         raise RuntimeError("TimeDistributedMLP: expected Conv1d -> LayerNorm(affine) -> LeakyReLU blocks")
+    cpre = [f"{mods.index(c)}." if seq else "" for c in convs]
+    npre = [f"{mods.index(n)}.layer_norm." for n in norms]
+    return convs, ws, bs, gs, ls, eps, slope, cpre, npre
+
+
+def td_mlp_forward(x, net):
+    """Run a Conv1d(k=1) [-> TimeDistributedLayerNorm -> LeakyReLU] ... stack (or a bare Conv1d) on (B, C, T)."""
+    convs, ws, bs, gs, ls, eps, slope, _, _ = _td_mlp_stack(net)
     sa.no_autograd(params=[p for c in convs for p in (c.weight, c.bias)])
     return sa.call("td_mlp", x, ws, bs, gs, ls, eps, slope)
+
+
+def td_mlp_vjp(x, net, grad_y, want_params=True):
+    """The backward of ``td_mlp_forward(x, net)`` for grad_y = dL/dy (B, out, T): ``(grad_x, {state-dict key relative to net:
+    gradient})`` (an empty dict without ``want_params``), from one call of the ``td_mlp_grad`` op (csrc/td_mlp_grad.hip).  The
+    forward saved nothing: the op recomputes it from ``x``.  Autograd is not involved and the results carry no graph."""
+    with torch.no_grad():
+        convs, ws, bs, gs, ls, eps, slope, cpre, npre = _td_mlp_stack(net)
+        x = sa.contiguous(x.detach(), "x")
+        g = sa.contiguous(grad_y.detach(), "grad_y")
+        if x.dim() != 3 or x.shape[1] != ws[0].shape[1]:
+            raise RuntimeError(f"td_mlp_vjp: expected x (B, {ws[0].shape[1]}, T), got {tuple(x.shape)}")
+        if tuple(g.shape) != (x.shape[0], ws[-1].shape[0], x.shape[2]):
+            raise RuntimeError(f"td_mlp_vjp: expected grad_y {(x.shape[0], ws[-1].shape[0], x.shape[2])}, got {tuple(g.shape)}")
+        if g.device != x.device:
+            raise RuntimeError(f"x is on {x.device} but grad_y is on {g.device}")
+        out = sa.binding().td_mlp_grad(x, g, ws, bs, gs, ls, eps, slope, bool(want_params))
+        if not want_params:
+            return out[0], {}
+        d, nl = len(ws), len(gs)
+        keys = ([p + "weight" for p in cpre] + [p + "bias" for p in cpre] + [p + "weight" for p in npre] + [p + "bias" for p in npre])
+        assert len(out) == 1 + 2 * d + 2 * nl
+        return out[0], dict(zip(keys, out[1:]))

@@ -199,12 +199,14 @@ class NeuralWaveshaping(nn.Module):
         f0, control, phase_u, noise = self._checked_inputs(f0, control, phase_u, noise)
         return self._pre_reverb_module_by_module(f0, control, phase_u, noise)
 
-    def pre_reverb_parts(self, f0, control, phase_u=None, noise=None):
+    def pre_reverb_parts(self, f0, control, phase_u=None, noise=None, want_emb=False):
         """``pre_reverb`` taken apart where the noise branch's backward starts: (newt_sum (B, N), H (B, 129, T), noise (N - 1)) -
         the summed oscillator branch, the noise filter magnitudes ``h_generator(emb)`` and the excitation draw, so that
         ``newt_sum + self.noise_synth(H, noise=noise)[:, 0]`` is ``pre_reverb`` for the same draws (the sum of the channels in
         another order: within the parity bar, not to the bit).  Same module-by-module kernels, under ``no_grad``; nothing
-        carries a graph.  With ``noise_synth.differentiable`` a gradient reaches H (scripts/fit_noise.py)."""
+        carries a graph.  With ``noise_synth.differentiable`` a gradient reaches H (scripts/fit_noise.py).  ``want_emb``: also
+        the control embedding (B, 128, T) that ``h_generator`` turned into H, as a fourth value - with
+        ``h_generator.differentiable`` the gradient goes on from H to the MLP's parameters."""
         f0, control, phase_u, noise = self._checked_inputs(f0, control, phase_u, noise)
         with torch.no_grad():
             f0_up = upsample_linear(f0, int(self.control_hop))                    # :75
@@ -213,7 +215,8 @@ class NeuralWaveshaping(nn.Module):
             emb = self.embedding(control[:, 0:2].contiguous())                    # :69-72
             x = self.newt(x, emb)                                                 # :80
             H = self.h_generator(emb)                                             # :82
-            return sa.sum_channels(x), H, noise                                   # :86 without the noise channel
+            parts = (sa.sum_channels(x), H, noise)                                # :86 without the noise channel
+            return parts + (emb,) if want_emb else parts
 
     # ---- evaluation hooks (reference :104-112, :136-165): inference + loss, no backward ----------------
     @property
@@ -255,15 +258,17 @@ class NeuralWaveshaping(nn.Module):
         raise NotImplementedError("training_step: there is no backward pass in this package for the whole model - the loss "
                                   "(losses.MultiResolutionSTFTLoss(differentiable=True)), the reverb (Reverb.differentiable, "
                                   "Reverb.vjp) and the noise branch's filter (FIRNoiseSynth.differentiable, FIRNoiseSynth.vjp: "
-                                  "dL/dH) have one, the frame MLPs, the recurrence and the oscillator branch do not; "
-                                  "validation_step and test_step give the reference's loss, scripts/fit_reverb.py fits reverb.ir "
-                                  "and scripts/fit_noise.py the noise colour (h_generator's last bias)")
+                                  "dL/dH) and a frame MLP called on its own (TimeDistributedMLP.differentiable, .vjp, td_mlp_vjp) "
+                                  "have one, the recurrence and the oscillator branch do not; validation_step and test_step "
+                                  "give the reference's loss, scripts/fit_reverb.py fits reverb.ir and scripts/fit_noise.py the "
+                                  "noise colour (h_generator's last bias) or, with --h-generator all, the whole h_generator")
 
     def configure_optimizers(self):
         raise NotImplementedError("configure_optimizers: there is no backward pass in this package for the whole model (the loss, "
-                                  "the reverb and the noise branch's filter have one), so the parameters to optimise are reverb.ir "
-                                  "(scripts/fit_reverb.py) and h_generator's last bias (scripts/fit_noise.py); model.stft_loss is "
-                                  "made on first use instead")
+                                  "the reverb, the noise branch's filter and a frame MLP called on its own have one), so the "
+                                  "parameters to optimise are reverb.ir (scripts/fit_reverb.py) and h_generator's last bias or, "
+                                  "with --h-generator all, every h_generator tensor (scripts/fit_noise.py); model.stft_loss is made "
+                                  "on first use instead")
 
     def _sub_module_hooks(self) -> bool:
         """Forward hooks on sub-modules (the reference's users tap stages that way, and so does tests/golden/make_golden.py on
