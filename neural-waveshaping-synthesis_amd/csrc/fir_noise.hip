@@ -12,16 +12,7 @@
 // 8-tap register window of the taps and of a copy delayed by one sample (so that tap PAIRS are
 // even-aligned for both output parities): two ds_read_b128 of taps + one broadcast ds_read_b128 of
 // noise feed 8 v_pk_fma_f32 = 16 MACs.  The NEWT branch is added here (cat + sum(1), models/neural_waveshaping.py:85-86).
-#include "nws_common.h"
-#include "fir_spectral_fft.h"
-
-// the two-float value type of fir_spectral_fft.h's templates
-template <>
-struct SpOps<f32x2> {
-  static __device__ __forceinline__ f32x2 fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-  static __device__ __forceinline__ f32x2 of(float v) { return f32x2{v, v}; }
-  static __device__ __forceinline__ f32x2 at(const float* p) { return *reinterpret_cast<const f32x2*>(p); }
-};
+#include "fir_spectral_wave.h"  // padded_noise and the wave-level transform pieces: shared with fir_noise_grad.hip
 
 namespace {
 
@@ -35,16 +26,6 @@ struct NoiseLds {
   float taps1[kHopsPerBlock + 1][kL];         // the same taps delayed by one: taps1[k] = taps[(k-1) & 255]
   float sig[(kHopsPerBlock + 1) * kHop + kHop];  // padded noise [128(t0-1), 128(t0+3)+256)
 };
-
-// reflect-padded noise (torch.stft center=True, pad_mode="reflect", pad 128 each side).  One-shot forward: origin = 128,
-// len = N-1.  Streaming windows pass the absolute noise stream with origin 0 and a len that only bites at the stream's end.
-__device__ __forceinline__ float padded_noise(const float* __restrict__ noise, int len, int origin, int i) {
-  int s = i - origin;
-  if (s < 0) s = -s;
-  if (s > len - 1) s = 2 * (len - 1) - s;
-  s = s < 0 ? 0 : s;
-  return noise[s];
-}
 
 // slot mode of a streaming window (ROWS): row b's noise reflects about its own bounds rows[b].x (first) and rows[b].y (last
 // sample) instead of 0 and len - 1, and its frames start at window frame rows[b].z: earlier frames are silent and the first
@@ -184,37 +165,6 @@ struct SpectralLds {
                                                // same plane (47 KB per workgroup: three of them on a CU)
 };
 
-// a wave's LDS traffic is ordered by itself; this keeps the compiler from moving accesses across an exchange
-__device__ __forceinline__ void sp_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the 16 x 16 transpose: (register k, lane l) -> (lane k, register l).  Rows of 17 entries: 8-byte entries of 16 lanes x 4
-// transforms fall on distinct bank pairs both ways (fir_spectral_fft.h)
-template <class T>
-__device__ __forceinline__ void sp_transpose(T (&v)[16], T* x, int l) {
-#pragma unroll
-  for (int k = 0; k < 16; ++k) x[k * kSpRow + l] = v[k];
-  sp_wave_sync();
-#pragma unroll
-  for (int j = 0; j < 16; ++j) v[j] = x[l * kSpRow + j];
-  sp_wave_sync();
-}
-// 256-point transform of (lane l, register j) = x[16 j + l] into (lane k1, register k2) = X[k1 + 16 k2]; INV: the same with
-// conjugate twiddles, (lane k1, register k2) -> (lane l, register j), no scaling.  x: this transform's LDS plane.
-template <bool INV, class T>
-__device__ __forceinline__ void sp_fft256(C16T<T>& z, const float* tw, T* x, int l) {
-  sp_pass1<INV>(z, tw);
-  sp_transpose(z.re, x, l);
-  sp_transpose(z.im, x, l);
-  sp_dft16<INV>(z);
-}
-
-__device__ __forceinline__ f32x2 sp_shfl(f32x2 v, int src) { return f32x2{__shfl(v.x, src, 64), __shfl(v.y, src, 64)}; }
-__device__ __forceinline__ f32x2 sp_select(bool c, f32x2 a, f32x2 b) { return f32x2{c ? a.x : b.x, c ? a.y : b.y}; }
-
 // Spectrum of the filters of a frame pair from their stored half rows: on return (lane k1, register k2) holds
 // (G_a, G_b)[k1 + 16 k2] as (re, im).  ua / ub: u[16 j + l] of the two rows, already zero for a silent frame.
 __device__ __forceinline__ void sp_filter_spectrum(C16T<f32x2>& z, const f32x2 (&ua)[8], const f32x2 (&ub)[8], const float* tw,
@@ -271,13 +221,7 @@ __global__ __launch_bounds__(64 * kSpWaves, 3) void fir_noise_spectral_kernel(co
     ua[j] = f32x2{rowa0[16 * j], rowa1[16 * j]};
     ub[j] = f32x2{rowb0[16 * j], rowb1[16 * j]};
   }
-  // W256^(l k): the twiddle between the two passes, the same table in both directions, (cos, sin) at [k][l] (a wave's four
-  // transforms read the same 256 B per k: broadcast; each value twice, see SpOps); in LDS because 30 registers of them per lane cost a wave per SIMD
-  {
-    float c, s;
-    sp_twiddle((tid & 15) * (tid >> 4), c, s);
-    L.tw[tid] = make_float4(c, c, s, s);
-  }
+  sp_fill_twiddles(L.tw, tid);
   const float* tw = reinterpret_cast<const float*>(&L.tw[l]);
   __syncthreads();
 
@@ -299,16 +243,8 @@ __global__ __launch_bounds__(64 * kSpWaves, 3) void fir_noise_spectral_kernel(co
     // Z = X_a + i X_b in (lane k1, register k2).  X_a = (Z[k] + conj Z[-k]) / 2, i X_b = (Z[k] - conj Z[-k]) / 2: the
     // mirror through this transform's own LDS plane, in natural order
     float mr[16], mi[16];
-    auto mirror = [&](const float (&v)[16], float (&m)[16]) {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) xs[l + 16 * j] = v[j];
-      sp_wave_sync();
-#pragma unroll
-      for (int j = 0; j < 16; ++j) m[j] = xs[(256 - (l + 16 * j)) & 255];
-      sp_wave_sync();
-    };
-    mirror(z.re, mr);
-    mirror(z.im, mi);
+    sp_mirror(z.re, mr, xs, l);
+    sp_mirror(z.im, mi, xs, l);
     const float c = (l & 1) ? -(1.0f / 512.0f) : (1.0f / 512.0f);   // (-1)^k / 2 / 256, exact
 #pragma unroll
     for (int j = 0; j < 9; ++j)      // bins 0 .. 143; S[-k] = conj S[k] and D[-k] = -conj D[k] give the rest

@@ -24,16 +24,7 @@
 //    equal bits whatever the launch order.  g = 0 gives exactly 0 (Z = 0, products and sums of zeros).
 // fir_from_h_grad_kernel: the transposed design-matrix product in plain fp32, sequential over d (a fixed order).
 // sum_batch_time_kernel: (B, C, T) -> (C) in fp64 in a fixed order: carries a gradient onto a per-channel offset.
-#include "nws_common.h"
-#include "fir_spectral_fft.h"
-
-// the two-float value type of fir_spectral_fft.h's templates (as in fir_noise.hip)
-template <>
-struct SpOps<f32x2> {
-  static __device__ __forceinline__ f32x2 fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-  static __device__ __forceinline__ f32x2 of(float v) { return f32x2{v, v}; }
-  static __device__ __forceinline__ f32x2 at(const float* p) { return *reinterpret_cast<const f32x2*>(p); }
-};
+#include "fir_spectral_wave.h"  // padded_noise and the wave-level transform pieces: shared with fir_noise.hip
 
 namespace {
 
@@ -49,55 +40,6 @@ struct GradLds {
   float4 tw[256];                              // (cos, cos, sin, sin)(2 pi l k / 256) at [k][l]
   f32x2 x[kGWaves][kGPairs * kSpPlane];        // per transform: the 16 x 16 transpose plane, also the 256-entry mirror plane
 };
-
-// reflect-padded noise of the whole-clip form (torch.stft center=True, pad 128 each side): padded index i -> noise[refl(i - 128)]
-__device__ __forceinline__ float padded_noise(const float* __restrict__ noise, int len, int i) {
-  int s = i - kHop;
-  if (s < 0) s = -s;
-  if (s > len - 1) s = 2 * (len - 1) - s;
-  s = s < 0 ? 0 : s;
-  return noise[s];
-}
-
-// a wave's LDS traffic is ordered by itself; this keeps the compiler from moving accesses across an exchange
-__device__ __forceinline__ void sp_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the 16 x 16 transpose: (register k, lane l) -> (lane k, register l), rows of 17 entries (fir_spectral_fft.h)
-template <class T>
-__device__ __forceinline__ void sp_transpose(T (&v)[16], T* x, int l) {
-#pragma unroll
-  for (int k = 0; k < 16; ++k) x[k * kSpRow + l] = v[k];
-  sp_wave_sync();
-#pragma unroll
-  for (int j = 0; j < 16; ++j) v[j] = x[l * kSpRow + j];
-  sp_wave_sync();
-}
-// 256-point transform of (lane l, register j) = x[16 j + l] into (lane k1, register k2) = X[k1 + 16 k2]; INV: conjugate
-// twiddles, (lane k1, register k2) -> (lane l, register j), no scaling.  x: this transform's LDS plane.
-template <bool INV, class T>
-__device__ __forceinline__ void sp_fft256(C16T<T>& z, const float* tw, T* x, int l) {
-  sp_pass1<INV>(z, tw);
-  sp_transpose(z.re, x, l);
-  sp_transpose(z.im, x, l);
-  sp_dft16<INV>(z);
-}
-// (lane k1, register k2) = V[k1 + 16 k2]  ->  m = V[(256 - k) & 255] through the transform's plane, in natural order
-template <class T>
-__device__ __forceinline__ void sp_mirror(const T (&v)[16], T (&m)[16], T* x, int l) {
-#pragma unroll
-  for (int j = 0; j < 16; ++j) x[l + 16 * j] = v[j];
-  sp_wave_sync();
-#pragma unroll
-  for (int j = 0; j < 16; ++j) m[j] = x[(256 - (l + 16 * j)) & 255];
-  sp_wave_sync();
-}
-
-__device__ __forceinline__ f32x2 sp_shfl(f32x2 v, int src) { return f32x2{__shfl(v.x, src, 64), __shfl(v.y, src, 64)}; }
-__device__ __forceinline__ f32x2 sp_select(bool c, f32x2 a, f32x2 b) { return f32x2{c ? a.x : b.x, c ? a.y : b.y}; }
 
 __global__ __launch_bounds__(64 * kGWaves) void fir_noise_grad_kernel(const float* __restrict__ noise,
                                                                       const float* __restrict__ grad_out, int B, int T,
@@ -130,12 +72,7 @@ __global__ __launch_bounds__(64 * kGWaves) void fir_noise_grad_kernel(const floa
       z.im[j] = sp_select(inb, f32x2{ga0[jbc], ga1[jbc]} * sb, zero);
     }
   }
-  // W256^(l k): the twiddle between the two passes, the same table in both directions, each value twice (SpOps::at)
-  {
-    float c, s;
-    sp_twiddle((tid & 15) * (tid >> 4), c, s);
-    L.tw[tid] = make_float4(c, c, s, s);
-  }
+  sp_fill_twiddles(L.tw, tid);
   const float* tw = reinterpret_cast<const float*>(&L.tw[l]);
   __syncthreads();
 
@@ -146,8 +83,8 @@ __global__ __launch_bounds__(64 * kGWaves) void fir_noise_grad_kernel(const floa
     float* xs = reinterpret_cast<float*>(x);
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
-      n.re[j] = padded_noise(noise, N - 1, kHop * tac + 16 * j + l);
-      n.im[j] = padded_noise(noise, N - 1, kHop * tbc + 16 * j + l);
+      n.re[j] = padded_noise(noise, N - 1, kHop, kHop * tac + 16 * j + l);   // the whole-clip form: origin = 128
+      n.im[j] = padded_noise(noise, N - 1, kHop, kHop * tbc + 16 * j + l);
     }
     sp_fft256<false>(n, tw, xs, l);
     // Zn = X_a + i X_b:  X_a = (Zn[k] + conj Zn[-k]) / 2,  X_b = (Zn[k] - conj Zn[-k]) / (2 i)

@@ -1,4 +1,5 @@
-// 256-point complex FFT pieces of the batched FIR-noise kernel (fir_noise.hip, fir_noise_spectral_kernel): a 16-point DFT in
+// 256-point complex FFT pieces of the batched FIR-noise kernel (fir_noise.hip, fir_noise_spectral_kernel) and of its backward
+// (fir_noise_grad.hip); the wave-level, device-only half is fir_spectral_wave.h.  Here: a 16-point DFT in
 // registers and the W256 twiddles.  256 = 16 x 16: sixteen lanes hold sixteen points each, one transpose through LDS between
 // the two register passes.  re and im sit in separate registers: the "times -i" of a packed complex type is exactly the
 // operand swizzle the build refuses.  Everything is a template on the value type T: float, or a two-float
@@ -124,7 +125,7 @@ constexpr int kSpRow = 17;
 constexpr int kSpPlane = 16 * kSpRow;
 constexpr int kSpTwStride = 64;
 
-// First pass of the 256-point transform, up to the exchange (sp_fft256 of fir_noise.hip: this, the transpose, sp_dft16):
+// First pass of the 256-point transform, up to the exchange (sp_fft256 of fir_spectral_wave.h: this, the transpose, sp_dft16):
 //   tw: (cos, cos, sin, sin)(2 pi l k / 256) of this lane at tw[64 k .. 64 k + 3] (kSpTwStride: 16 lanes x 4 floats);
 //   forward: lane l holds x[16 j + l] in register j;  after sp_dft16 + twiddle W256^(l k1), register k1 is Y[l][k1];
 //   transpose: lane k1 holds Y[l][k1] in register l;  after sp_dft16, register k2 is X[k1 + 16 k2].

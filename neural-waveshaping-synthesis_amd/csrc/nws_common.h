@@ -247,6 +247,13 @@ __device__ __forceinline__ float nws_swap_halves(float v) { return __shfl_xor(v,
 
 __device__ __forceinline__ float nws_leaky_relu(float x) { return x > 0.0f ? x : 0.01f * x; }
 
+// numpy / torch "reflect" padding (no edge repeat) of a signal of N samples, one fold each side: padded position i -> sample
+__device__ __forceinline__ int reflect_index(long long i, int N) {
+  if (i < 0) i = -i;
+  if (i >= N) i = 2LL * (N - 1) - i;
+  return (int)(i < 0 ? 0 : i);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Stateful streaming (stream.hip): the time-domain reverb of a hop as partial sums over 256 taps.  Shared with
 // control_gru.hip: in a hop of <= 256 emitted samples every part but the first reads reverb input of EARLIER hops only, so

@@ -89,12 +89,6 @@ __host__ bool pyin_dims(double sr, double fmin, double fmax, int fl, int hop, Py
   return true;
 }
 
-__device__ __forceinline__ int reflect_index(long long i, int N) {  // numpy "reflect" (no edge repeat), one fold each side
-  if (i < 0) i = -i;
-  if (i >= N) i = 2LL * (N - 1) - i;
-  return (int)(i < 0 ? 0 : (i >= N ? N - 1 : i));
-}
-
 // sum_{j < n} (xa[j] - xb[j])^2: two packed accumulators (4 interleaved chains), then the tail
 __device__ __forceinline__ float sqdiff_sum(const float* xa, const float* xb, int n) {
   f32x2 acc0 = {0.0f, 0.0f}, acc1 = {0.0f, 0.0f};

@@ -33,71 +33,33 @@ __global__ __launch_bounds__(256) void stft_grad_norm_kernel(const float* __rest
                                                              int hop, int frames, const float* __restrict__ dft, int m_tiles, int k_lo,
                                                              int k_half, float eps, double* __restrict__ records) {
   extern __shared__ __align__(16) float lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int kh = lane >> 5, col = lane & 31;
-  const int t0 = blockIdx.x * kFrames;
-  const int mt = blockIdx.y * 4 + wave;
-  const int b = blockIdx.z;
-  float* xs = lds;
-  float* ys = lds + tile_words(n_fft, hop);
-  tile_stage(x + (size_t)b * N, y + (size_t)b * N, N, n_fft, hop, t0, xs, ys);
-
+  const TileCoord c;
+  TileAcc a;
   double s_sc = 0.0, s_y2 = 0.0;
-  if (mt < m_tiles) {
-    f32x16 ax = {}, ay = {};
-    tile_transform(dft, xs, ys, n_fft, hop, mt, k_lo, k_half, ax, ay);
+  if (tile_prologue<2>(c, {x, y}, N, n_fft, hop, dft, m_tiles, k_lo, k_half, lds, a)) {
     const int bins = n_fft / 2 + 1;
-    const bool frame_ok = t0 + col < frames;
+    const bool frame_ok = c.t0 + c.col < frames;
 #pragma unroll
     for (int r = 0; r < 16; r += 2) {
-      if (tile_bin(mt, r, kh) < bins && frame_ok) {
-        const float xm = sqrtf(fmaxf(fmaf(ax[r], ax[r], ax[r + 1] * ax[r + 1]), eps));
-        const float ym = sqrtf(fmaxf(fmaf(ay[r], ay[r], ay[r + 1] * ay[r + 1]), eps));
+      if (tile_bin(c.mt, r, c.kh) < bins && frame_ok) {
+        const float xm = sqrtf(fmaxf(fmaf(a.x[r], a.x[r], a.x[r + 1] * a.x[r + 1]), eps));
+        const float ym = sqrtf(fmaxf(fmaf(a.y[r], a.y[r], a.y[r + 1] * a.y[r + 1]), eps));
         const float d = ym - xm;
         s_sc += (double)d * (double)d;
         s_y2 += (double)ym * (double)ym;
       }
     }
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    s_sc += __shfl_xor(s_sc, off, 64);
-    s_y2 += __shfl_xor(s_y2, off, 64);
-  }
-  __syncthreads();  // every wave is done with the staged signals: the first 64 bytes become the workgroup's reduction
-  double* red = reinterpret_cast<double*>(lds);
-  if (lane == 0) {
-    red[2 * wave + 0] = s_sc;
-    red[2 * wave + 1] = s_y2;
-  }
-  __syncthreads();
-  if (tid < 2) {
-    const size_t rec = ((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    records[2 * rec + tid] = ((red[tid] + red[2 + tid]) + red[4 + tid]) + red[6 + tid];
-  }
+  double s[2] = {s_sc, s_y2};
+  tile_reduce(c, s, lds, records);
 }
 
 // coef[0] = w_sc_over_r / (||y_mag - x_mag||_F ||y_mag||_F), 0 where the first norm is 0 (the subgradient torch takes there)
 __global__ __launch_bounds__(256) void stft_grad_coef_kernel(const double* __restrict__ records, unsigned long long n, double w_sc_over_r,
                                                              double* __restrict__ coef) {
   __shared__ double red[2][256];
-  const int tid = threadIdx.x;
-  double s0 = 0.0, s1 = 0.0;
-  for (unsigned long long i = tid; i < n; i += 256) {
-    s0 += records[2 * i];
-    s1 += records[2 * i + 1];
-  }
-  red[0][tid] = s0;
-  red[1][tid] = s1;
-  __syncthreads();
-  for (int off = 128; off >= 1; off >>= 1) {
-    if (tid < off) {
-      red[0][tid] += red[0][tid + off];
-      red[1][tid] += red[1][tid + off];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) coef[0] = red[0][0] > 0.0 ? w_sc_over_r / (sqrt(red[0][0]) * sqrt(red[1][0])) : 0.0;
+  records_sum(records, n, red);
+  if (threadIdx.x == 0) coef[0] = red[0][0] > 0.0 ? w_sc_over_r / (sqrt(red[0][0]) * sqrt(red[1][0])) : 0.0;
 }
 
 __device__ __forceinline__ float sign_of(float v) { return (float)(v > 0.0f) - (float)(v < 0.0f); }
@@ -108,22 +70,15 @@ __global__ __launch_bounds__(256) void stft_grad_spectrum_kernel(const float* __
                                                                  int k_half, float eps, const double* __restrict__ coef, float c_log,
                                                                  float c_lin, float* __restrict__ G) {
   extern __shared__ __align__(16) float lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int kh = lane >> 5, col = lane & 31;
-  const int t0 = blockIdx.x * kFrames;
-  const int mt = blockIdx.y * 4 + wave;
-  const int b = blockIdx.z;
-  float* xs = lds;
-  float* ys = lds + tile_words(n_fft, hop);
-  tile_stage(x + (size_t)b * N, y + (size_t)b * N, N, n_fft, hop, t0, xs, ys);
-  if (mt >= m_tiles) return;
-
-  f32x16 ax = {}, ay = {};
-  tile_transform(dft, xs, ys, n_fft, hop, mt, k_lo, k_half, ax, ay);
+  const TileCoord c;
+  TileAcc a;
+  if (!tile_prologue<2>(c, {x, y}, N, n_fft, hop, dft, m_tiles, k_lo, k_half, lds, a)) return;
+  const f32x16 &ax = a.x, &ay = a.y;
+  const int mt = c.mt, kh = c.kh, col = c.col;
   const float c_sc = (float)coef[0];
   const int bins = n_fft / 2 + 1;
-  const bool frame_ok = t0 + col < frames;
-  float* out = G + (((size_t)b * gridDim.x + blockIdx.x) * (32 * (size_t)m_tiles) + 32 * (size_t)mt) * 32 + col;
+  const bool frame_ok = c.t0 + col < frames;
+  float* out = G + (((size_t)c.b * gridDim.x + blockIdx.x) * (32 * (size_t)m_tiles) + 32 * (size_t)mt) * 32 + col;
 #pragma unroll
   for (int r = 0; r < 16; r += 2) {
     float g_re = 0.0f, g_im = 0.0f;
@@ -298,12 +253,12 @@ int nws_stft_grad(const float* x, const float* y, int B, int N, int R, const int
     const NRange n = n_range_of(n_fft, win_lengths[r]);
     const double count = (double)B * (double)(n_fft / 2 + 1) * (double)frames;
     const dim3 tile_grid(g.gx, g.gy, (unsigned)B);
-    stft_grad_norm_kernel<<<tile_grid, 256, tile_lds_bytes(n_fft, hop), st>>>(x, y, N, n_fft, hop, frames, dfts[r], rows_pad / 32, k.k_lo,
+    stft_grad_norm_kernel<<<tile_grid, 256, tile_lds_bytes(n_fft, hop, 2), st>>>(x, y, N, n_fft, hop, frames, dfts[r], rows_pad / 32, k.k_lo,
                                                                                k.k_len / 2, eps, records);
     NWS_CHECK_LAUNCH();
     stft_grad_coef_kernel<<<1, 256, 0, st>>>(records, g.records, (double)w_sc / (double)R, coef);
     NWS_CHECK_LAUNCH();
-    stft_grad_spectrum_kernel<<<tile_grid, 256, tile_lds_bytes(n_fft, hop), st>>>(
+    stft_grad_spectrum_kernel<<<tile_grid, 256, tile_lds_bytes(n_fft, hop, 2), st>>>(
         x, y, N, n_fft, hop, frames, dfts[r], rows_pad / 32, k.k_lo, k.k_len / 2, eps, coef, (float)((double)w_log_mag / ((double)R * count)),
         (float)((double)w_lin_mag / ((double)R * count)), G);
     NWS_CHECK_LAUNCH();

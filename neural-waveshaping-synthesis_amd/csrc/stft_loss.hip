@@ -7,12 +7,13 @@
 //   sum (y_mag - x_mag)^2, sum y_mag^2, sum |ln x_mag - ln y_mag|, sum |x_mag - y_mag|.
 //
 // Three kernels:
-//   stft_loss_dft_kernel       the constant operand: the row layout of loudness.hip's dft_matrix_kernel (rows 2k / 2k+1 =
-//                              w[n] cos / -w[n] sin, evaluated in double with exact phase reduction), w = the centred window,
-//                              zero outside it.
-//   stft_loss_kernel           (the tile itself lives in stft_tile.h, which stft_grad.hip shares)
-//                              the tile of loudness_power_kernel (32 frames x 4 M-tiles per workgroup, skewed LDS staging with
-//                              reflect padding resolved there, v_mfma_f32_32x32x2_f32) with BOTH signals staged and two
+//   stft_loss_dft_kernel       the constant operand, the only builder of it (nws_loudness_dft_matrix asks for win_length = n_fft):
+//                              rows 2k / 2k+1 = w[n] cos / -w[n] sin of bin k in plain row-major order, evaluated in double with
+//                              exact phase reduction, w = the periodic hann window of win_length centred in n_fft, zero outside
+//                              it; rows beyond 2 (n_fft/2 + 1) are zero.
+//   stft_loss_kernel           (the tile itself lives in stft_tile.h, which loudness.hip and stft_grad.hip share)
+//                              32 frames x 4 M-tiles per workgroup, skewed LDS staging with reflect padding resolved there,
+//                              v_mfma_f32_32x32x2_f32, with BOTH signals staged and two
 //                              accumulator sets fed by one A operand.  The K loop runs over the columns the window covers only
 //                              (rounded out to 16): 59 / 59 / 47 % of K at the defaults.  Re / Im of a bin are adjacent
 //                              accumulator registers of one lane, so both magnitudes are formed in-lane; the four sums are
@@ -50,27 +51,18 @@ __global__ __launch_bounds__(256) void stft_loss_kernel(const float* __restrict_
                                                         int hop, int frames, const float* __restrict__ dft, int m_tiles, int k_lo,
                                                         int k_half, float eps, double* __restrict__ partials) {
   extern __shared__ __align__(16) float lds[];  // skewed windows of the frame tile: x, then y
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int kh = lane >> 5, col = lane & 31;
-  const int t0 = blockIdx.x * kFrames;
-  const int mt = blockIdx.y * 4 + wave;
-  const int b = blockIdx.z;
-  float* xs = lds;
-  float* ys = lds + tile_words(n_fft, hop);
-  tile_stage(x + (size_t)b * N, y + (size_t)b * N, N, n_fft, hop, t0, xs, ys);
-
+  const TileCoord c;
+  TileAcc a;
   double s_sc = 0.0, s_y2 = 0.0, s_log = 0.0, s_lin = 0.0;
-  if (mt < m_tiles) {
-    f32x16 ax = {}, ay = {};
-    tile_transform(dft, xs, ys, n_fft, hop, mt, k_lo, k_half, ax, ay);
-    // rows (r, r+1), r even = (Re, Im) of bin 16 mt + (r&3)/2 + 4 (r>>2) + 2 kh; column = frame t0 + col
+  if (tile_prologue<2>(c, {x, y}, N, n_fft, hop, dft, m_tiles, k_lo, k_half, lds, a)) {
+    // rows (r, r+1), r even = (Re, Im) of bin tile_bin(c.mt, r, c.kh); column = frame t0 + col
     const int bins = n_fft / 2 + 1;
-    const bool frame_ok = t0 + col < frames;
+    const bool frame_ok = c.t0 + c.col < frames;
 #pragma unroll
     for (int r = 0; r < 16; r += 2) {
-      if (tile_bin(mt, r, kh) < bins && frame_ok) {
-        const float xm = sqrtf(fmaxf(fmaf(ax[r], ax[r], ax[r + 1] * ax[r + 1]), eps));  // the clamp is on the power
-        const float ym = sqrtf(fmaxf(fmaf(ay[r], ay[r], ay[r + 1] * ay[r + 1]), eps));
+      if (tile_bin(c.mt, r, c.kh) < bins && frame_ok) {
+        const float xm = sqrtf(fmaxf(fmaf(a.x[r], a.x[r], a.x[r + 1] * a.x[r + 1]), eps));  // the clamp is on the power
+        const float ym = sqrtf(fmaxf(fmaf(a.y[r], a.y[r], a.y[r + 1] * a.y[r + 1]), eps));
         const float d = ym - xm;
         s_sc += (double)d * (double)d;
         s_y2 += (double)ym * (double)ym;
@@ -79,26 +71,8 @@ __global__ __launch_bounds__(256) void stft_loss_kernel(const float* __restrict_
       }
     }
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    s_sc += __shfl_xor(s_sc, off, 64);
-    s_y2 += __shfl_xor(s_y2, off, 64);
-    s_log += __shfl_xor(s_log, off, 64);
-    s_lin += __shfl_xor(s_lin, off, 64);
-  }
-  __syncthreads();  // every wave is done with the staged signals: the first 128 bytes become the workgroup's reduction
-  double* red = reinterpret_cast<double*>(lds);
-  if (lane == 0) {
-    red[4 * wave + 0] = s_sc;
-    red[4 * wave + 1] = s_y2;
-    red[4 * wave + 2] = s_log;
-    red[4 * wave + 3] = s_lin;
-  }
-  __syncthreads();
-  if (tid < 4) {
-    const size_t rec = ((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partials[4 * rec + tid] = ((red[tid] + red[4 + tid]) + red[8 + tid]) + red[12 + tid];
-  }
+  double s[4] = {s_sc, s_y2, s_log, s_lin};
+  tile_reduce(c, s, lds, partials);
 }
 
 struct FinaliseArgs {
@@ -115,22 +89,7 @@ __global__ __launch_bounds__(256) void stft_loss_finalise_kernel(const double* _
   const int tid = threadIdx.x;
   double total = 0.0;
   for (int r = 0; r < a.R; ++r) {
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    const double* p = partials + 4 * a.rec_off[r];
-    for (unsigned long long i = tid; i < a.rec_n[r]; i += 256) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) s[q] += p[4 * i + q];
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) red[q][tid] = s[q];
-    __syncthreads();
-    for (int off = 128; off >= 1; off >>= 1) {
-      if (tid < off) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) red[q][tid] += red[q][tid + off];
-      }
-      __syncthreads();
-    }
+    records_sum(partials + 4 * a.rec_off[r], a.rec_n[r], red);
     if (tid == 0) {
       const double sc = sqrt(red[0][0]) / sqrt(red[1][0]);  // ||y_mag - x_mag||_F / ||y_mag||_F
       const double lg = red[2][0] / a.count[r], ln = red[3][0] / a.count[r];
@@ -150,7 +109,7 @@ extern "C" {
 
 size_t nws_stft_loss_dft_bytes(int n_fft, int win_length) {
   if (!n_fft_ok(n_fft) || win_length < 1 || win_length > n_fft) return 0;
-  return (size_t)rows_padded(n_fft) * n_fft * sizeof(float);
+  return dft_operand_bytes(n_fft);
 }
 
 int nws_stft_loss_dft_matrix(int n_fft, int win_length, float* dft_out, void* stream) {
@@ -197,7 +156,7 @@ int nws_stft_loss(const float* x, const float* y, int B, int N, int R, const int
     const int n_fft = n_ffts[r], hop = hops[r], win = win_lengths[r];
     const Grid g = grid_of(B, N, n_fft, hop);
     const KRange k = k_range_of(n_fft, win);
-    stft_loss_kernel<<<dim3(g.gx, g.gy, (unsigned)B), 256, tile_lds_bytes(n_fft, hop), st>>>(
+    stft_loss_kernel<<<dim3(g.gx, g.gy, (unsigned)B), 256, tile_lds_bytes(n_fft, hop, 2), st>>>(
         x, y, N, n_fft, hop, frames_of(N, hop), dfts[r], rows_padded(n_fft) / 32, k.k_lo, k.k_len / 2, eps, partials + 4 * off);
     NWS_CHECK_LAUNCH();
     fa.rec_off[r] = off;

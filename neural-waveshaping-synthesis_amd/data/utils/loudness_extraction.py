@@ -15,26 +15,14 @@ import torch
 
 from ... import _lib
 from ... import ginlite as gin
-from ..._lib import check, ptr
-from ...engine import binding, stream_ptr
+from ... import losses
+from ...engine import binding
 from .upsampling import linear_interpolation
-
-_DFT_CACHE: dict = {}
 
 
 def _dft_operand(n_fft: int, device) -> torch.Tensor:
-    key = (n_fft, str(device))
-    t = _DFT_CACHE.get(key)
-    if t is None:
-        nbytes = _lib.lib().nws_loudness_dft_bytes(n_fft)
-        if nbytes == 0:
-            raise RuntimeError(f"n_fft must be a power of two in [64, 2048], got {n_fft}")
-        with torch.cuda.device(device):
-            t = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
-            check(_lib.lib().nws_loudness_dft_matrix(n_fft, ptr(t), stream_ptr(device)), "nws_loudness_dft_matrix")
-            torch.cuda.current_stream(device).synchronize()     # shared by every later caller, whatever its stream
-        _DFT_CACHE[key] = t
-    return t
+    """the STFT loss's operand with the hann window as long as the transform; losses.py builds and caches it"""
+    return losses._dft_operand(n_fft, n_fft, device)
 
 
 def loudness_frames(audio: torch.Tensor, n_fft: int, hop_length: int, epsilon: float = 1e-5, top_db: float = 80.0,

@@ -40,6 +40,39 @@ def test_loudness_matches_oracle(name):
     assert err <= 2e-5, (name, err)
 
 
+def test_loudness_smallest_transform_partial_tiles():
+    """n_fft 64: only 66 of the M-tile group's 128 rows are bins (the third M-tile is mostly padding, the fourth wave has none);
+    82 frames: the third frame tile is partial; hop 37 is odd"""
+    import nws_amd
+    from nws_amd.data.utils.loudness_extraction import loudness_frames
+    from oracle import loudness_oracle as lo
+    x = (0.3 * np.random.default_rng(11).standard_normal((2, 3001))).astype(np.float32)
+    x[1] *= 0.05                                   # per-utterance reference maximum
+    out = loudness_frames(torch.from_numpy(x).cuda(), 64, 37).cpu().numpy()
+    assert out.shape == (2, 82)
+    for i in range(2):
+        ref = lo.extract_perceptual_loudness(x[i].astype(np.float64), n_fft=64, hop_length=37)
+        err = float(np.abs(out[i] - ref).max())
+        print(f"row {i}: max_abs_err_normalised {err:.3e}")
+        assert err <= 2e-5, (i, err)
+
+
+@pytest.mark.parametrize("n_fft", [64, 256, 2048])
+def test_loudness_operand_is_the_stft_loss_operand_with_a_full_window(n_fft):
+    """nws_loudness_dft_matrix(n_fft) and stft_loss_dft(n_fft, n_fft) give the same bytes: the loudness / MFCC path takes its operand
+    from the STFT loss's cache on the strength of this"""
+    import nws_amd
+    from nws_amd import _lib
+    from nws_amd.engine import binding, stream_ptr
+    L = _lib.lib()
+    nbytes = L.nws_loudness_dft_bytes(n_fft)
+    assert nbytes == L.nws_stft_loss_dft_bytes(n_fft, n_fft) > 0
+    dev = torch.device("cuda", torch.cuda.current_device())
+    t = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    _lib.check(L.nws_loudness_dft_matrix(n_fft, _lib.ptr(t), stream_ptr(dev)), "nws_loudness_dft_matrix")
+    assert torch.equal(t, binding().stft_loss_dft(n_fft, n_fft))
+
+
 def test_loudness_batched_tensor_api_interpolation_and_errors():
     import nws_amd
     from nws_amd.data.utils.loudness_extraction import extract_perceptual_loudness, loudness_frames
