@@ -184,6 +184,24 @@ int nws_control_gru_carry(const NwsWeights* w, const float* control, const float
  * form to run beside throughput kernels of other streams (nws_forward_control, batched_gru = 1).  Any B >= 1. */
 int nws_control_gru_batched(const NwsWeights* w, const float* control, int B, int C, int T, const float* h0, float* gru_out,
                             float* hT, void* stream);
+/* The backward of nws_control_gru_state for grad_out = dL/d(gru_out) (B, T, 128) and grad_hT = dL/d(hT) (B, 128)
+ * [NULL = zeros].  control, h0 and gru_out are the forward's own input, initial state [NULL = zeros] and output: the recurrence is
+ * not run again.  grad_control (B, 2, T) [NULL = not wanted] is the gradient of channels 0 and 1 of control (the only ones read;
+ * C >= 2 is control's channel count), grad_h0 (B, 128) [NULL = dropped], and grad_w_ih (384, 2), grad_w_hh (384, 128), grad_b_ih
+ * (384), grad_b_hh (384) - all four or none - the gradients of w->gru_*.  Exact fp32 products, sums over batch and time in a fixed
+ * order in float64, no atomics: equal inputs give equal bits, grad_out = 0 without grad_hT gives zeros.
+ * Launches on `stream` (gate coefficients, the sequential kernel, then - when asked for - the input gradient with the column sums,
+ * the dW_hh contraction and two reductions), reads nothing back and decides every refusal before the first launch:
+ * NWS_ERR_BAD_ARG for a NULL required pointer, some but not all of the four parameter gradients, a size < 1, C < 2, or a workspace
+ * that is NULL, not 16-byte aligned or smaller than nws_control_gru_grad_workspace_bytes; NWS_ERR_UNSUPPORTED for B > 65 535 (or
+ * more than 2^30 32-frame chunks in all).  The workspace (six (B, T, 128) planes, with want_params the partial sums too) is needed
+ * in every form; nws_control_gru_grad_workspace_bytes is 0 for sizes that are refused. */
+size_t nws_control_gru_grad_workspace_bytes(int B, int T, int want_params);
+int nws_control_gru_grad(const NwsWeights* w, const float* control, int B, int C, int T, const float* h0 /* NULL = zeros */,
+                         const float* gru_out, const float* grad_out /* (B,T,128) */, const float* grad_hT /* NULL = zeros */,
+                         float* grad_control /* (B,2,T), NULL = not wanted */, float* grad_h0 /* (B,128), NULL = dropped */,
+                         float* grad_w_ih, float* grad_w_hh, float* grad_b_ih, float* grad_b_hh /* all four or none */,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Frame-rate MLPs on the GRU output (one kernel):

@@ -192,6 +192,30 @@ class CtypesOps:
                      _stream(control.device)), "nws_control_gru")
         return out, hT
 
+    def control_gru_grad(self, wdesc, control, h0, gru_out, grad_out, grad_hT, want_params):
+        B, Cc, T = control.shape
+        H = _lib.HIDDEN
+        if B < 1 or T < 1:
+            raise RuntimeError("control: need at least one utterance and one frame")
+        for t in (gru_out, grad_out):
+            if tuple(t.shape) != (B, T, H):
+                raise RuntimeError(f"control_gru_grad: gru_out / grad_out {tuple(t.shape)} is not ({B}, {T}, {H})")
+        for t in (h0, grad_hT):
+            if t is not None and t.numel() != B * H:
+                raise RuntimeError(f"h0 / grad_hT: expected ({B}, {H}), got {tuple(t.shape)}")
+        L = _lib.lib()
+        with torch.cuda.device(control.device):
+            out = [_new(control, B, 2, T), _new(control, B, H)]
+            if want_params:
+                out += [_new(control, 3 * H, 2), _new(control, 3 * H, H), _new(control, 3 * H), _new(control, 3 * H)]
+            gp = out[2:] if want_params else [None] * 4
+            nbytes = L.nws_control_gru_grad_workspace_bytes(B, T, 1 if want_params else 0)
+            ws = _new(control, max(nbytes, 1), dtype=torch.uint8)
+            check(L.nws_control_gru_grad(C.byref(_struct(wdesc, NwsWeights)), ptr(control), B, Cc, T, ptr(h0), ptr(gru_out),
+                                         ptr(grad_out), ptr(grad_hT), ptr(out[0]), ptr(out[1]), ptr(gp[0]), ptr(gp[1]), ptr(gp[2]),
+                                         ptr(gp[3]), ptr(ws), nbytes, _stream(control.device)), "nws_control_gru_grad")
+        return out
+
     def frame_mlps(self, wdesc, gru_out, fir_design, want_emb, want_H):
         B, T, _ = gru_out.shape
         with torch.cuda.device(gru_out.device):

@@ -351,6 +351,49 @@ std::tuple<Tensor, Tensor> control_gru(const Tensor& wdesc, const Tensor& contro
   return {out, hT};
 }
 
+// The backward of control_gru for grad_out = dL/d(gru_out) (B, T, 128) and grad_hT = dL/d(hT): [grad_control
+// (B, 2, T), grad_h0 (B, 128)], with want_params followed by [grad_w_ih, grad_w_hh, grad_b_ih, grad_b_hh].  gru_out is the forward's
+// own output; the workspace comes from torch's allocator.
+std::vector<Tensor> control_gru_grad(const Tensor& wdesc, const Tensor& control, const OptTensor& h0, const Tensor& gru_out,
+                                     const Tensor& grad_out, const OptTensor& grad_hT, bool want_params) {
+  const NwsWeights* w = weights_of(wdesc);
+  check_dev(control, "control");
+  check_dev(gru_out, "gru_out");
+  check_dev(grad_out, "grad_out");
+  check_same_device(control, "control", gru_out, "gru_out");
+  check_same_device(control, "control", grad_out, "grad_out");
+  TORCH_CHECK(control.dim() == 3 && control.size(1) >= 2, "control: expected (B, C>=2, T), got ", control.sizes());
+  const int64_t B = control.size(0), C = control.size(1), T = control.size(2);
+  TORCH_CHECK(B >= 1 && T >= 1, "control: need at least one utterance and one frame");
+  for (const Tensor* t : {&gru_out, &grad_out})
+    TORCH_CHECK(t->dim() == 3 && t->size(0) == B && t->size(1) == T && t->size(2) == NWS_HIDDEN,
+                "control_gru_grad: gru_out / grad_out ", t->sizes(), " is not (", B, ", ", T, ", 128)");
+  for (const OptTensor* o : {&h0, &grad_hT})
+    if (o->has_value()) {
+      check_dev(**o, "h0 / grad_hT");
+      check_same_device(control, "control", **o, "h0 / grad_hT");
+      TORCH_CHECK((*o)->numel() == B * NWS_HIDDEN, "h0 / grad_hT: expected (", B, ", 128), got ", (*o)->sizes());
+    }
+  Launch L(control);
+  Tensor grad_control = at::empty({B, 2, T}, control.options());
+  Tensor grad_h0 = at::empty({B, NWS_HIDDEN}, control.options());
+  std::vector<Tensor> out{grad_control, grad_h0};
+  float* gp[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (want_params) {
+    out.push_back(at::empty({3 * NWS_HIDDEN, 2}, control.options()));
+    out.push_back(at::empty({3 * NWS_HIDDEN, NWS_HIDDEN}, control.options()));
+    out.push_back(at::empty({3 * NWS_HIDDEN}, control.options()));
+    out.push_back(at::empty({3 * NWS_HIDDEN}, control.options()));
+    for (int i = 0; i < 4; ++i) gp[i] = out[2 + i].data_ptr<float>();
+  }
+  const size_t nbytes = nws_control_gru_grad_workspace_bytes((int)B, (int)T, want_params ? 1 : 0);
+  Tensor ws = at::empty({(int64_t)(nbytes > 0 ? nbytes : 1)}, control.options().dtype(at::kByte));
+  nws_check(nws_control_gru_grad(w, control.data_ptr<float>(), (int)B, (int)C, (int)T, fptr(h0), gru_out.data_ptr<float>(),
+                                 grad_out.data_ptr<float>(), fptr(grad_hT), grad_control.data_ptr<float>(), grad_h0.data_ptr<float>(),
+                                 gp[0], gp[1], gp[2], gp[3], ws.data_ptr(), nbytes, L.stream), "nws_control_gru_grad");
+  return out;
+}
+
 // proj + newt.mlp + h_generator + FIR design in one kernel: -> (emb (B,128,T), film (B,T,256), H (B,T,129), fir (B,T,128) upper half-taps)
 std::tuple<Tensor, Tensor, Tensor, Tensor> frame_mlps(const Tensor& wdesc, const Tensor& gru_out, const Tensor& fir_design,
                                                        bool want_emb, bool want_H) {
@@ -1369,6 +1412,8 @@ TORCH_LIBRARY(newt_hip, m) {
         "float sample_rate, bool want_exciter, bool want_newt) -> (Tensor, Tensor)", &exciter_newt);
   m.def("oscillator(Tensor f0_up, Tensor phase_u, Tensor rand_phase, float sample_rate) -> Tensor", &oscillator);
   m.def("control_gru(Tensor wdesc, Tensor control, Tensor? h0, bool batched) -> (Tensor, Tensor)", &control_gru);
+  m.def("control_gru_grad(Tensor wdesc, Tensor control, Tensor? h0, Tensor gru_out, Tensor grad_out, Tensor? grad_hT, "
+        "bool want_params) -> Tensor[]", &control_gru_grad);
   m.def("frame_mlps(Tensor wdesc, Tensor gru_out, Tensor fir_design, bool want_emb, bool want_H) -> (Tensor, Tensor, Tensor, Tensor)",
         &frame_mlps);
   m.def("fir_noise(Tensor fir, Tensor noise, Tensor? add_in, int origin) -> Tensor", &fir_noise);

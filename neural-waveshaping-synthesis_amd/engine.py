@@ -510,6 +510,13 @@ class Engine:
         out, hT = binding().control_gru(r.wdesc, control, h0, bool(batched))
         return (out, hT) if return_state else out
 
+    def control_gru_grad(self, control, gru_out, grad_out, h0=None, grad_hT=None, want_params=True):
+        """the backward of `control_gru` (csrc/control_gru_grad.hip): [grad_control (B, 2, T), grad_h0 (B, 128)],
+        with `want_params` followed by the gradients of gru.weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0"""
+        r = self._wd()
+        same_device(r.device, control=control, gru_out=gru_out, grad_out=grad_out, h0=h0, grad_hT=grad_hT)
+        return list(binding().control_gru_grad(r.wdesc, control, h0, gru_out, grad_out, grad_hT, bool(want_params)))
+
     def frame_mlps(self, gru_out, want_emb=False, want_H=False):
         r = self._wd()
         same_device(r.device, gru_out=gru_out)

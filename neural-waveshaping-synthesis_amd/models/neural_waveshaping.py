@@ -10,8 +10,8 @@ and ``test_step`` return ``stft_loss(recon, audio)`` - ``losses.MultiResolutionS
 of the ``auraloss`` loss the reference logs as ``val/loss`` / ``test/loss`` - through the
 reference's ``_run_step``.  ``stft_loss`` is made on first use (in the reference ``configure_optimizers`` makes
 it).  ``training_step`` and ``configure_optimizers`` raise: the loss, the reverb and the noise branch's filter have a
-backward pass, the frame MLPs, the recurrence and the oscillator branch have none
-(SURVEY.md §2 row 1b).  ``pre_reverb`` renders the reverb's input, which is what fitting ``reverb.ir`` alone needs;
+backward pass, and so have a frame MLP and the control encoder called on their own (3.16, 3.17:
+``ControlModule.differentiable``, ``.vjp``); the oscillator branch has none (SURVEY.md §2 row 1b).  ``pre_reverb`` renders the reverb's input, which is what fitting ``reverb.ir`` alone needs;
 ``pre_reverb_parts`` renders it in two parts with the noise filter's input, which is what fitting the noise colour
 needs.  Logging (``self.log``, wandb) is left to the caller.
 
@@ -29,7 +29,7 @@ from .. import _lib
 from .. import ginlite as gin
 from ..engine import Engine, _req
 from .modules import _standalone as sa
-from .modules.dynamic import Conv1x1, TimeDistributedMLP, td_mlp_forward, upsample_linear
+from .modules.dynamic import Conv1x1, TimeDistributedMLP, td_mlp_forward, td_mlp_vjp, upsample_linear
 from .modules.generators import FIRNoiseSynth, HarmonicOscillator
 from .modules.shaping import NEWT, Reverb
 
@@ -39,14 +39,52 @@ gin.external_configurable(nn.Conv1d, module="torch.nn")
 _DEFAULT_GIN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gin", "models", "newt.gin")
 
 
+_GRU_KEYS = ("gru.weight_ih_l0", "gru.weight_hh_l0", "gru.bias_ih_l0", "gru.bias_hh_l0")
+
+
+class _ControlFunction(torch.autograd.Function):
+    """ControlModule.forward with its backward attached (csrc/control_gru_grad.hip): saves x and gru_out; backward
+    runs proj's part through td_mlp_vjp and the recurrence's through control_gru_grad and hands gradients to x and to every
+    parameter that requires grad"""
+
+    @staticmethod
+    def forward(ctx, x, module, *params):
+        with torch.no_grad():
+            xd = x.detach()
+            h = module._gru_out(xd)
+            y = td_mlp_forward(h.transpose(1, 2).contiguous(), module.proj)
+        ctx.module = module
+        ctx.save_for_backward(xd, h)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_emb):
+        x, h = ctx.saved_tensors
+        want = any(ctx.needs_input_grad[2:])
+        gx, grads = ctx.module._vjp(grad_emb, x, h, want)
+        keys = _GRU_KEYS + ("proj.weight", "proj.bias")
+        named = dict(ctx.module.named_parameters())
+        out = [grads[k].view_as(named[k]) if need else None for k, need in zip(keys, ctx.needs_input_grad[2:])] if want else [None] * 6
+        return (gx if ctx.needs_input_grad[0] else None, None, *out)
+
+
 @gin.configurable
 class ControlModule(nn.Module):
-    """GRU(control_size -> hidden) + Conv1d(hidden -> embedding, 1) (reference :17-26)."""
+    """GRU(control_size -> hidden) + Conv1d(hidden -> embedding, 1) (reference :17-26).
+
+    ``differentiable`` (a plain attribute, default False): forward only, as the stage kernels are.  Set to True (GRU(2 -> 128)
+    only: the runtime-size recurrence has no backward), a forward under grad mode whose ``x`` or parameters require grad returns
+    the same bits with a ``torch.autograd.Function`` attached that saves ``x`` and ``gru_out``; its backward hands gradients to
+    ``x`` and to each of the six parameters that requires grad.  ``vjp`` is the same gradient without autograd."""
+
+    differentiable = False      # also the value of a module unpickled from before the flag existed
 
     def __init__(self, control_size: int, hidden_size: int, embedding_size: int):
         super().__init__()
         self.gru = nn.GRU(control_size, hidden_size, batch_first=True)
         self.proj = nn.Conv1d(hidden_size, embedding_size, 1)
+        self.differentiable = False
 
         self._desc = sa.Desc()
 
@@ -55,25 +93,73 @@ class ControlModule(nn.Module):
         d["_desc"] = sa.Desc()
         return d
 
-    def forward(self, x):
-        """(B, control_size, T) -> (B, embedding_size, T): persistent GRU kernel (csrc/control_gru.hip) + Conv1d(k=1).
-        Stand-alone form of what NeuralWaveshaping.forward runs fused (GRU, then proj inside frame_mlps16_kernel)."""
-        x = sa.contiguous(x, "x")
+    def _checked(self, x):
         g = self.gru
         if g.num_layers != 1 or g.bidirectional or not g.batch_first:
             raise RuntimeError("the HIP path implements nn.GRU(control_size, hidden_size, batch_first=True), one layer")
         if x.dim() != 3 or x.shape[1] != g.input_size:
             raise RuntimeError(f"ControlModule: expected (B, {g.input_size}, T), got {tuple(x.shape)}")
-        if g.input_size != 2 or g.hidden_size != sa._lib.HIDDEN:
+        return g.input_size == 2 and g.hidden_size == sa._lib.HIDDEN
+
+    def _wdesc(self):
+        g = self.gru
+        return self._desc.get({"gru_w_ih": g.weight_ih_l0, "gru_w_hh": g.weight_hh_l0, "gru_b_ih": g.bias_ih_l0,
+                               "gru_b_hh": g.bias_hh_l0})
+
+    def _gru_out(self, x):
+        """(B, 2, T) -> gru_out (B, T, 128): the persistent GRU kernel on a checked, contiguous x"""
+        return sa.binding().control_gru(self._wdesc(), x, None, False)[0]
+
+    def _need_backward_sizes(self, x):
+        if not self._checked(x):
+            raise RuntimeError("ControlModule: the recurrence's backward (csrc/control_gru_grad.hip) exists for GRU(2 -> 128) only; "
+                               f"this is GRU({self.gru.input_size} -> {self.gru.hidden_size}), which runs on the runtime-size path "
+                               "and has no backward")
+
+    def forward(self, x):
+        """(B, control_size, T) -> (B, embedding_size, T): persistent GRU kernel (csrc/control_gru.hip) + Conv1d(k=1).
+        Stand-alone form of what NeuralWaveshaping.forward runs fused (GRU, then proj inside frame_mlps16_kernel)."""
+        if self.differentiable:
+            xc = sa.contiguous(x.detach(), "x")
+            self._need_backward_sizes(xc)
+            if torch.is_grad_enabled():
+                params = [dict(self.named_parameters())[k] for k in _GRU_KEYS + ("proj.weight", "proj.bias")]
+                if x.requires_grad or any(p.requires_grad for p in params):
+                    return _ControlFunction.apply(x if x.is_contiguous() else x.contiguous(), self, *params)
+            return td_mlp_forward(self._gru_out(xc).transpose(1, 2).contiguous(), self.proj)
+        x = sa.contiguous(x, "x")
+        g = self.gru
+        sa.no_autograd(inputs=(x,))
+        if not self._checked(x):
             # any control_size / hidden_size: runtime-size recurrence (csrc/generic.hip: g_gru_kernel)
             ps = [sa._req(p.detach(), "gru parameter") for p in (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)]
             sa.no_autograd(params=[g.weight_ih_l0])
             h = sa.call("g_gru", ps[0], ps[1], ps[2], ps[3], x, None)[0]
         else:
-            wdesc = self._desc.get({"gru_w_ih": g.weight_ih_l0, "gru_w_hh": g.weight_hh_l0, "gru_b_ih": g.bias_ih_l0,
-                                    "gru_b_hh": g.bias_hh_l0})
-            h = sa.binding().control_gru(wdesc, x, None, False)[0]      # (B, T, 128)
+            h = self._gru_out(x)                                        # (B, T, 128)
         return td_mlp_forward(h.transpose(1, 2).contiguous(), self.proj)
+
+    def _vjp(self, grad_emb, x, gru_out, want_params):
+        with torch.no_grad():
+            g_h, pg = td_mlp_vjp(gru_out.transpose(1, 2).contiguous(), self.proj, grad_emb, want_params)      # dL/d(gru_out) (B, 128, T)
+            out = sa.binding().control_gru_grad(self._wdesc(), x, None, gru_out, g_h.transpose(1, 2).contiguous(), None,
+                                                bool(want_params))
+            if not want_params:
+                return out[0], {}
+            grads = dict(zip(_GRU_KEYS, out[2:]))
+            grads["proj.weight"], grads["proj.bias"] = pg["weight"], pg["bias"]
+            return out[0], grads
+
+    def vjp(self, grad_emb, x, want_params=True):
+        """(dL/dx (B, 2, T), {state-dict key: gradient}) of ``forward`` at ``x`` for grad_emb = dL/d(emb) (B, embedding_size, T);
+        keys ``gru.weight_ih_l0``, ``gru.weight_hh_l0``, ``gru.bias_ih_l0``, ``gru.bias_hh_l0``, ``proj.weight``, ``proj.bias``, an
+        empty dict without ``want_params``.  Reruns the forward GRU kernel for gru_out, takes proj's part from ``td_mlp_vjp`` and the
+        recurrence's from ``control_gru_grad``.  Whatever ``differentiable`` and the grad mode say; autograd is not
+        involved and the results carry no graph."""
+        with torch.no_grad():
+            x = sa.contiguous(x.detach(), "x")
+            self._need_backward_sizes(x)
+            return self._vjp(grad_emb, x, self._gru_out(x), want_params)
 
 
 @gin.configurable
@@ -258,14 +344,16 @@ class NeuralWaveshaping(nn.Module):
         raise NotImplementedError("training_step: there is no backward pass in this package for the whole model - the loss "
                                   "(losses.MultiResolutionSTFTLoss(differentiable=True)), the reverb (Reverb.differentiable, "
                                   "Reverb.vjp) and the noise branch's filter (FIRNoiseSynth.differentiable, FIRNoiseSynth.vjp: "
-                                  "dL/dH) and a frame MLP called on its own (TimeDistributedMLP.differentiable, .vjp, td_mlp_vjp) "
-                                  "have one, the recurrence and the oscillator branch do not; validation_step and test_step "
+                                  "dL/dH), a frame MLP called on its own (TimeDistributedMLP.differentiable, .vjp, td_mlp_vjp) and "
+                                  "the control encoder (ControlModule.differentiable, .vjp: the recurrence and proj) have one, "
+                                  "the oscillator branch does not; validation_step and test_step "
                                   "give the reference's loss, scripts/fit_reverb.py fits reverb.ir and scripts/fit_noise.py the "
                                   "noise colour (h_generator's last bias) or, with --h-generator all, the whole h_generator")
 
     def configure_optimizers(self):
         raise NotImplementedError("configure_optimizers: there is no backward pass in this package for the whole model (the loss, "
-                                  "the reverb, the noise branch's filter and a frame MLP called on its own have one), so the "
+                                  "the reverb, the noise branch's filter, a frame MLP and the control encoder called on their own have one; the "
+                                  "oscillator branch has none, so no gradient of the whole loss reaches the recurrence yet), so the "
                                   "parameters to optimise are reverb.ir (scripts/fit_reverb.py) and h_generator's last bias or, "
                                   "with --h-generator all, every h_generator tensor (scripts/fit_noise.py); model.stft_loss is made "
                                   "on first use instead")
