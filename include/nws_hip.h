@@ -104,6 +104,11 @@ typedef struct NwsWeights {
   /* options of the fused oscillator + waveshaper kernel's FastNEWT path (0 = default: FiLM interpolation on the matrix
    * pipe, sines as two fp16 terms = 22-bit products) */
   int32_t exciter_opts;
+  /* nonzero: mlp_frags is NWS_MLP_FRAGS_BYTES + NWS_MLP_SPEC_BYTES long and nws_mlp_spec_frags() has filled the second part (proj
+   * folded into the first hidden layers, h_generator's output layer emitting filter spectra): the forward may hand spectra
+   * instead of taps from the frame MLPs to the noise kernel (nws_frame_mlps_spec).  Sits in what was padding: a caller that
+   * zero-fills the struct and never sets it keeps the tap hand-over. */
+  int32_t mlp_spec;
   /* optional (64) from nws_exciter_bound(): X[s] >= |harmonic_mixer output of shaper s| for ANY phases (sum_k |W[s][k]| + |b[s]|,
    * rounded up).  With it the fused kernel proves per workgroup, from the FiLM rows it stages, which groups of eight shapers keep
    * their table index inside the table whatever the oscillator does, and runs those lookups without floor / clamp (bit-identical
@@ -229,6 +234,36 @@ int nws_mlp_frags(const NwsWeights* w, const float* fir_design /* (256,132) */, 
 int nws_fir_design_matrix(const float* window /* (256) */, float* D_out, void* stream);
 
 /*
+ * Spectrum hand-over.  Everything between the GRU output and the first LayerNorm of either frame MLP, and
+ * everything between h_generator's last LayerNorm and the noise kernel's product of spectra, is linear in model constants:
+ *   W1' = W1 Wp, b1' = W1 bp + b1          proj folded into the first Conv1d of newt.mlp and of h_generator
+ *   W_G = S W_out, b_G = S b_out           h_generator's last layer emits G = S H, the REAL spectrum of the frame's zero-phase filter
+ * S (129 x 129) is bands -> spectrum in exactly the form the noise kernel multiplies with: u[d] = D[128 + d] H are the stored
+ * half-taps, e[n] = u[min(n, 256 - n)] (u[128] := 0) the even extension, G[k] = sum_n e[n] cos(2 pi k n / 256), k = 0 .. 128
+ * (forward transform, no scaling, bin k at index k; G[256 - k] = G[k]).  It depends on noise_synth.window only.
+ * nws_fir_spectrum_map and nws_mlp_spec_fold are HOST functions on host pointers (float64 sums rounded once to fp32; no GPU):
+ *   folded_out: [W1' newt.mlp (128,128) | W1' h_generator (128,128) | W_G (129,128) | b1' newt.mlp (128) | b1' h_generator (128) |
+ *                b_G (129) + 3 zeros]
+ * nws_mlp_spec_frags splits a device copy of `folded` into the fragment order of the wave-resident kernel and writes the
+ * NWS_MLP_SPEC_BYTES behind the first NWS_MLP_FRAGS_BYTES of `frags` (which nws_mlp_frags fills).  The caller checks the folded
+ * weights against the fp16 range (engine.py) before it sets NwsWeights.mlp_spec.
+ */
+#define NWS_SPEC_ROW 132             /* floats per (utterance, frame) row of filter spectra: G[0 .. 128], 16-byte aligned rows */
+#define NWS_MLP_SPEC_BYTES 200704
+#define NWS_MLP_SPEC_FOLD_FLOATS 49668
+int nws_fir_spectrum_map(const float* fir_design /* host (256,132) */, double* S_out /* host (129,129) */);
+int nws_mlp_spec_fold(const float* proj_w, const float* proj_b, const float* newt_w0, const float* newt_b0, const float* hgen_w0,
+                      const float* hgen_b0, const float* hgen_w3 /* (129,128) */, const float* hgen_b3 /* (129) */,
+                      const double* S /* (129,129) */, float* folded_out /* NWS_MLP_SPEC_FOLD_FLOATS */);
+int nws_mlp_spec_frags(const float* folded /* device */, void* frags /* device, NWS_MLP_FRAGS_BYTES + NWS_MLP_SPEC_BYTES */, void* stream);
+/* 1 when nws_frame_mlps_spec / nws_fir_noise_spec serve this size: w->mlp_frags and w->mlp_spec are set, nws_frame_mlps would take
+ * its wave-resident kernel (B x T frames fill the chip) and nws_fir_noise its batched kernel (B >= 16); else 0 */
+int nws_frame_mlps_spec_serves(const NwsWeights* w, int B, int T);
+/* nws_frame_mlps with the folded weights: film_out (B,T,256) as before, spec_out (B,T,NWS_SPEC_ROW) rows G[0 .. 128] (the three
+ * floats behind them are not written).  NWS_ERR_UNSUPPORTED where nws_frame_mlps_spec_serves is 0. */
+int nws_frame_mlps_spec(const NwsWeights* w, const float* gru_out, int B, int T, float* film_out, float* spec_out, void* stream);
+
+/*
  * Time-varying FIR noise (models/modules/generators.py:30-35): rectangular-window STFT of the
  * shared noise vector (N-1 samples, reflect-padded by 128), per-frame 256-point CIRCULAR
  * convolution with fir[b][t], overlap-add / overlap count.   out = add_in + noise_branch
@@ -240,6 +275,11 @@ int nws_fir_noise(const float* fir /* (B,T,128): upper half-taps, see nws_frame_
  * torch.stft's reflect padding (nws_fir_noise == origin 128, noise_len N-1); streaming windows use origin 0 */
 int nws_fir_noise_window(const float* fir, const float* noise, int noise_len, int origin, const float* add_in, int B, int T,
                          float* out, void* stream);
+/* nws_fir_noise on rows of filter spectra (nws_frame_mlps_spec: spec[b][t][k] = G[k], k = 0 .. 128, row stride NWS_SPEC_ROW)
+ * instead of half-taps: the batched kernel without its tap loads, mirror exchange and filter transform; everything behind the
+ * product of spectra is the same code.  B >= 16 only (NWS_ERR_UNSUPPORTED below; the per-utterance kernel convolves taps). */
+int nws_fir_noise_spec(const float* spec /* (B,T,NWS_SPEC_ROW) */, const float* noise /* (N-1) */, const float* add_in /* (B,N) */,
+                       int B, int T, float* out /* (B,N) */, void* stream);
 
 /* The transpose of nws_fir_noise and of nws_fir_from_h for g = dL/d(out) (B,N), N = 128 T.  For a fixed
  * excitation the noise branch is linear in H, so nothing is saved but the noise vector.  Whole-clip form only (origin 128,

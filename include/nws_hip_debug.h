@@ -14,6 +14,10 @@ extern "C" {
  * tile kernels below), 1 the tile kernels, 2 wave-resident frames at any size.  Any other mode: NWS_ERR_BAD_ARG. */
 int nws_debug_frame_mlps_kernel(int mode);
 
+/* Tests / A-B measurements: on = 0 keeps the forward on the tap hand-over (nws_frame_mlps + nws_fir_noise) where it would hand
+ * filter spectra over (nws_frame_mlps_spec_serves then answers 0); any other value restores the default. */
+int nws_debug_forward_spec(int on);
+
 /* Diagnostics only (tools/cu_pressure.py): a resident load of `groups` 256-thread workgroups that keep their CUs' vector pipes
  * busy for `spin_us` microseconds of the wall clock - what a collective's ring kernels take from the oscillator kernel. */
 int nws_debug_queue_busy(int groups, int spin_us, float* sink /* device float[256] */, void* stream);

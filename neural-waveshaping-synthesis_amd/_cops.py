@@ -238,6 +238,26 @@ class CtypesOps:
                                                       _stream(fir.device)), "nws_fir_noise_window")
         return out
 
+    def frame_mlps_spec(self, wdesc, gru_out):
+        B, T, _ = gru_out.shape
+        with torch.cuda.device(gru_out.device):
+            film = _new(gru_out, B, T, _lib.FILM_CH)
+            spec = torch.zeros((B, T, _lib.SPEC_ROW), dtype=torch.float32, device=gru_out.device)   # (3 floats per row never written)
+            check(_lib.lib().nws_frame_mlps_spec(C.byref(_struct(wdesc, NwsWeights)), ptr(gru_out), B, T, ptr(film), ptr(spec),
+                                                 _stream(gru_out.device)), "nws_frame_mlps_spec")
+        return film, spec
+
+    def fir_noise_spec(self, spec, noise, add_in):
+        B, T, row = spec.shape
+        if row != _lib.SPEC_ROW or noise.numel() != T * HOP - 1:
+            raise RuntimeError(f"fir_noise_spec: spec {tuple(spec.shape)} must be (B, T, {_lib.SPEC_ROW}) and noise {tuple(noise.shape)} "
+                               f"its {T * HOP - 1} samples")
+        with torch.cuda.device(spec.device):
+            out = _new(spec, B, T * HOP)
+            check(_lib.lib().nws_fir_noise_spec(ptr(spec), ptr(noise), ptr(add_in), B, T, ptr(out), _stream(spec.device)),
+                  "nws_fir_noise_spec")
+        return out
+
     def fir_from_h(self, H, fir_design):
         B, _, T = H.shape
         with torch.cuda.device(H.device):

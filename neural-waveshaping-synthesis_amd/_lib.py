@@ -26,6 +26,9 @@ HOP = 128
 FIR_LEN = 256
 FIR_HALF = 128           # taps per row handed from the frame MLPs to the noise kernels: h[128 .. 255] (include/nws_hip.h)
 MLP_FRAGS_BYTES = 1474560
+MLP_SPEC_BYTES = 200704  # the folded tables behind them (NwsWeights.mlp_spec, nws_mlp_spec_frags)
+MLP_SPEC_FOLD_FLOATS = 49668
+SPEC_ROW = 132           # floats per row of filter spectra handed from the frame MLPs to the noise kernel (nws_frame_mlps_spec)
 N_BANDS = 129
 FILM_CH = 256
 SHAPER_WIDTH = 8
@@ -50,6 +53,7 @@ class NwsWeights(C.Structure):
         ("newt_out_w", _fp), ("newt_out_b", _fp),
         ("noise_window", _fp),
         ("exciter_opts", C.c_int32),
+        ("mlp_spec", C.c_int32),      # (in what was padding: the struct's size and every other offset are unchanged)
         ("exciter_bound", _fp),
     ]
 
@@ -117,6 +121,13 @@ _PROTOTYPES = {
     "nws_frame_mlps": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
     "nws_mlp_frags": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, _fp]),
     "nws_debug_frame_mlps_kernel": (C.c_int, [C.c_int]),
+    "nws_debug_forward_spec": (C.c_int, [C.c_int]),
+    "nws_fir_spectrum_map": (C.c_int, [_fp, _fp]),
+    "nws_mlp_spec_fold": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "nws_mlp_spec_frags": (C.c_int, [_fp, _fp, _fp]),
+    "nws_frame_mlps_spec_serves": (C.c_int, [C.POINTER(NwsWeights), C.c_int, C.c_int]),
+    "nws_frame_mlps_spec": (C.c_int, [C.POINTER(NwsWeights), _fp, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "nws_fir_noise_spec": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "nws_fir_design_matrix": (C.c_int, [_fp, _fp, _fp]),
     "nws_fir_noise": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "nws_fir_noise_window": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp]),

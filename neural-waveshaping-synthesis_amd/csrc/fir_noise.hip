@@ -187,6 +187,12 @@ __device__ __forceinline__ void sp_filter_spectrum(C16T<f32x2>& z, const f32x2 (
   sp_fft256<false>(z, tw, x, l);
 }
 
+// SPEC: `fir` holds rows of NWS_SPEC_ROW floats, the filter spectrum G[0 .. 128] itself (nws_frame_mlps_spec), and the two utterances'
+// G_a, G_b are loaded straight into (lane k1, register k2) = G[k1 + 16 k2], where sp_filter_spectrum would have left them; a bin
+// above 128 is read at its mirror image 256 - k (G is real and even).  Register j < 8 of a transform's 16 lanes reads the 64
+// contiguous bytes G[16 j .. 16 j + 15], register j >= 8 the 64 bytes G[241 - 16 j .. 256 - 16 j]: whole segments either way.  No
+// mirror exchange and no filter transform (32 more loads per lane instead); silence, clamping and containment as in the tap form.
+template <bool SPEC>
 __global__ __launch_bounds__(64 * kSpWaves, 3) void fir_noise_spectral_kernel(const float* __restrict__ fir,
                                                                              const float* __restrict__ noise,
                                                                              const float* __restrict__ add_in, int B, int T, int len,
@@ -211,15 +217,25 @@ __global__ __launch_bounds__(64 * kSpWaves, 3) void fir_noise_spectral_kernel(co
   // tap rows first: they fly under the twiddle set-up and, in wave 0, under the noise transform.  Always-in-bounds addresses
   // and a select afterwards (never a multiplication: 0 * Inf = NaN would leak a clamped row into a silent frame).
   const int bc0 = b0 < B ? b0 : B - 1, bc1 = b1 < B ? b1 : B - 1;
-  const float* rowa0 = &fir[((size_t)bc0 * T + tac) * kHalf + l];
-  const float* rowb0 = &fir[((size_t)bc0 * T + tbc) * kHalf + l];
-  const float* rowa1 = &fir[((size_t)bc1 * T + tac) * kHalf + l];
-  const float* rowb1 = &fir[((size_t)bc1 * T + tbc) * kHalf + l];
-  f32x2 ua[8], ub[8];
+  constexpr int kRow = SPEC ? NWS_SPEC_ROW : kHalf;
+  const float* rowa0 = &fir[((size_t)bc0 * T + tac) * kRow + l];
+  const float* rowb0 = &fir[((size_t)bc0 * T + tbc) * kRow + l];
+  const float* rowa1 = &fir[((size_t)bc1 * T + tac) * kRow + l];
+  const float* rowb1 = &fir[((size_t)bc1 * T + tbc) * kRow + l];
+  f32x2 ua[SPEC ? 16 : 8], ub[SPEC ? 16 : 8];   // SPEC: (G_a, G_b)[l + 16 j] of the two utterances
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     ua[j] = f32x2{rowa0[16 * j], rowa1[16 * j]};
     ub[j] = f32x2{rowb0[16 * j], rowb1[16 * j]};
+  }
+  if constexpr (SPEC) {
+    // bin l + 16 j >= 128 at 256 - 16 j - l (row + l - 2 l); j = 8: 128 - l, which is bin 128 itself for l = 0
+#pragma unroll
+    for (int j = 8; j < 16; ++j) {
+      const int m = 256 - 16 * j - 2 * l;
+      ua[j] = f32x2{rowa0[m], rowa1[m]};
+      ub[j] = f32x2{rowb0[m], rowb1[m]};
+    }
   }
   sp_fill_twiddles(L.tw, tid);
   const float* tw = reinterpret_cast<const float*>(&L.tw[l]);
@@ -252,12 +268,20 @@ __global__ __launch_bounds__(64 * kSpWaves, 3) void fir_noise_spectral_kernel(co
   }
   const f32x2 zero = {0.0f, 0.0f};
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
+  for (int j = 0; j < (SPEC ? 16 : 8); ++j) {
     ua[j] = sp_select(oka, ua[j], zero);
     ub[j] = sp_select(okb, ub[j], zero);
   }
   C16T<f32x2> z;
-  sp_filter_spectrum(z, ua, ub, tw, x, lane, l);
+  if constexpr (SPEC) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      z.re[j] = ua[j];
+      z.im[j] = ub[j];
+    }
+  } else {
+    sp_filter_spectrum(z, ua, ub, tw, x, lane, l);
+  }
   __syncthreads();                                               // the noise spectra are in place
 
   // the other branch's samples of the hops this lane stores (cat + sum(1)): requested before the inverse transform
@@ -340,8 +364,8 @@ extern "C" int nws_fir_noise_window(const float* fir, const float* noise, int no
     const long long nruns = (T + kSpHops - 1) / kSpHops, total = nruns * ((B + kSpUtt - 1) / kSpUtt);
     if (total > (1ll << 30)) return NWS_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)(8 * ((total + 7) / 8)));           // see the XCD note in the kernel
-    fir_noise_spectral_kernel<<<grid, 64 * kSpWaves, 0, (hipStream_t)stream>>>(fir, noise, add_in, B, T, noise_len, origin, out,
-                                                                             (int)nruns, (int)total);
+    fir_noise_spectral_kernel<false><<<grid, 64 * kSpWaves, 0, (hipStream_t)stream>>>(fir, noise, add_in, B, T, noise_len, origin, out,
+                                                                                    (int)nruns, (int)total);
     NWS_CHECK_LAUNCH();
     return NWS_OK;
   }
@@ -366,4 +390,17 @@ extern "C" int nws_fir_noise_window_rows(const float* fir, const float* noise, i
 extern "C" int nws_fir_noise(const float* fir, const float* noise, const float* add_in, int B, int T, float* out,
                              void* stream) {
   return nws_fir_noise_window(fir, noise, T * kHop - 1, kL / 2, add_in, B, T, out, stream);
+}
+
+// the batched kernel on rows of filter spectra (whole-clip framing: origin 128, N - 1 noise samples)
+extern "C" int nws_fir_noise_spec(const float* spec, const float* noise, const float* add_in, int B, int T, float* out, void* stream) {
+  if (!spec || !noise || !out || B <= 0 || T <= 0) return NWS_ERR_BAD_ARG;
+  if (B < 16 || B > 65535) return NWS_ERR_UNSUPPORTED;
+  const long long nruns = (T + kSpHops - 1) / kSpHops, total = nruns * ((B + kSpUtt - 1) / kSpUtt);
+  if (total > (1ll << 30)) return NWS_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)(8 * ((total + 7) / 8)));           // see the XCD note in the kernel
+  fir_noise_spectral_kernel<true><<<grid, 64 * kSpWaves, 0, (hipStream_t)stream>>>(spec, noise, add_in, B, T, T * kHop - 1, kL / 2, out,
+                                                                                 (int)nruns, (int)total);
+  NWS_CHECK_LAUNCH();
+  return NWS_OK;
 }

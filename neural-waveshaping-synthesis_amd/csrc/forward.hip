@@ -27,6 +27,9 @@ struct Carve {
 
 size_t aligned(size_t b) { return (b + 255) & ~size_t(255); }
 
+// floats per (utterance, frame) of the region the frame MLPs hand to the noise kernel: the wider of its two forms
+constexpr size_t kFirRow = NWS_SPEC_ROW > NWS_FIR_HALF ? NWS_SPEC_ROW : NWS_FIR_HALF;
+
 // ---- optional live profiling: hipEvents recorded on the launch stream around each stage ----
 constexpr int kStages = 6;  // carry, gru, mlps, exciter_newt, fir_noise, reverb
 struct Profile {
@@ -52,7 +55,7 @@ size_t nws_forward_workspace_bytes(const NwsReverbPlan* plan, int B, int T) {
   total += aligned((size_t)B * (N / 32) * sizeof(double));          // carries
   total += aligned((size_t)B * T * NWS_HIDDEN * sizeof(float));     // gru_out
   total += aligned((size_t)B * T * NWS_FILM_CH * sizeof(float));    // film
-  total += aligned((size_t)B * T * NWS_FIR_HALF * sizeof(float));   // fir (upper half-taps)
+  total += aligned((size_t)B * T * kFirRow * sizeof(float));        // fir (upper half-taps, or rows of filter spectra)
   total += aligned((size_t)B * N * sizeof(float));                  // noise branch (B, N)
   total += aligned((size_t)B * N * sizeof(float));                  // pre-reverb
   total += aligned(nws_reverb_workspace_bytes(plan, B));
@@ -81,7 +84,7 @@ Arena carve_arena(const NwsReverbPlan* plan, void* workspace, size_t bytes, int 
   a.gru_out = static_cast<float*>(cv.take((size_t)B * T * NWS_HIDDEN * sizeof(float)));
   if (!head_only) {
     a.film = static_cast<float*>(cv.take((size_t)B * T * NWS_FILM_CH * sizeof(float)));
-    a.fir = static_cast<float*>(cv.take((size_t)B * T * NWS_FIR_HALF * sizeof(float)));
+    a.fir = static_cast<float*>(cv.take((size_t)B * T * kFirRow * sizeof(float)));
     a.noise_out = static_cast<float*>(cv.take((size_t)B * N * sizeof(float)));
     a.pre = static_cast<float*>(cv.take((size_t)B * N * sizeof(float)));
     a.rv_bytes = nws_reverb_workspace_bytes(plan, B);
@@ -122,11 +125,20 @@ int audio_half(const NwsWeights* w, const NwsForwardAux* aux, const float* f0, i
   hipStream_t st = (hipStream_t)stream;
   int rc = NWS_OK;
   const size_t N = (size_t)T * NWS_HOP;
-  NWS_STAGE(2, nws_frame_mlps(w, a.gru_out, aux->fir_design, B, T, nullptr, a.film, nullptr, a.fir, stream));
+  // Where the wave-resident frame-MLP kernel and the batched noise kernel would run and the weights carry the folded tables, the
+  // two hand over filter spectra instead of taps: the same two stages, one decision for every caller
+  const bool spec = nws_frame_mlps_spec_serves(w, B, T) != 0;
+  if (spec)
+    NWS_STAGE(2, nws_frame_mlps_spec(w, a.gru_out, B, T, a.film, a.fir, stream));
+  else
+    NWS_STAGE(2, nws_frame_mlps(w, a.gru_out, aux->fir_design, B, T, nullptr, a.film, nullptr, a.fir, stream));
   // the noise branch first (its output starts the NEWT sum), then the oscillator kernel adds its own sum on top and leaves
   // pre = newt + noise (models/neural_waveshaping.py:77-81; a + b in either order is the same fp32 sum): the FIR-noise kernel
   // neither reads the other branch nor waits for the chain of exciter events
-  NWS_STAGE(4, nws_fir_noise(a.fir, noise, nullptr, B, T, a.noise_out, stream));
+  if (spec)
+    NWS_STAGE(4, nws_fir_noise_spec(a.fir, noise, nullptr, B, T, a.noise_out, stream));
+  else
+    NWS_STAGE(4, nws_fir_noise(a.fir, noise, nullptr, B, T, a.noise_out, stream));
   if (wait_before_exciter != nullptr) {
     const hipError_t e = hipStreamWaitEvent(st, (hipEvent_t)wait_before_exciter, 0);
     if (e != hipSuccess) return (int)e;

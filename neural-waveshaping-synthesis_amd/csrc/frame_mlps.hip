@@ -819,6 +819,17 @@ constexpr int kT2Base = kFragTotal * 16;
 constexpr int kT2Kb[2][6] = {{0, 64, 128, 192, 256, 320}, {0, 384, 448, 512, 576, 640}};
 constexpr int kT2Bytes = 712 * 1024;
 static_assert(kT2Base + kT2Bytes == NWS_MLP_FRAGS_BYTES, "fragment table size");
+// third table, behind the second (NwsWeights.mlp_spec, nws_mlp_spec_frags): what the folded form (SPEC) of the kernel adds.
+//   KB 0 | 64: the first hidden layer of newt.mlp | h_generator with proj folded in (W1 Wp; contraction order kperm_in)
+//   KB 128   : rows 0..127 of W_G = S W_out, h_generator's output layer emitting filter spectra (kperm_d)
+//   KB 192   : floats b1' newt.mlp (128) | b1' h_generator (128) | b_G[0..127] | row 128 of W_G (128) | b_G[128]
+constexpr int kT3Base = NWS_MLP_FRAGS_BYTES;
+constexpr int kT3ParKb = 192;
+static_assert((kT3ParKb + 4) * 1024 == NWS_MLP_SPEC_BYTES, "third fragment table size");
+// nws_mlp_spec_fold's output (floats)
+constexpr int kFoldW1n = 0, kFoldW1h = 128 * 128, kFoldWg = 2 * 128 * 128, kFoldB1n = kFoldWg + NWS_N_BANDS * 128,
+              kFoldB1h = kFoldB1n + 128, kFoldBg = kFoldB1h + 128;
+static_assert(kFoldBg + 132 == NWS_MLP_SPEC_FOLD_FLOATS, "folded weights");
 
 // contraction order of a layer whose input is (a) the GRU output read from memory: lane half h holds channels 64 h .. 64 h + 63
 // of its frame; (b) a previous layer's accumulators: K-step (mt, g) holds registers 8 g .. 8 g + 7 of M-tile mt
@@ -849,6 +860,16 @@ __device__ __forceinline__ void wr_pack8(const float (&y)[8], f16x8& hi, f16x8& 
   wr_split2(y[6], y[7], h3, l3);
   hi = f16x8{h0.x, h0.y, h1.x, h1.y, h2.x, h2.y, h3.x, h3.y};
   lo = f16x8{l0.x, l0.y, l1.x, l1.y, l2.x, l2.y, l3.x, l3.y};
+}
+
+// folded form: weight chunk k of a path, 64 KB each: 0 the folded first hidden layer | 1, 2 the other two hidden layers |
+// 3 (and 4, newt.mlp) the output layer
+__device__ __forceinline__ const char* wr_spec_chunk(const char* frags, int path, int k) {
+  if (k == 0) return frags + kT3Base + (size_t)path * 65536;
+  if (k == 1) return frags + kT2Base + (size_t)(path ? kT2Kb[1][2] : kT2Kb[0][2]) * 1024;
+  if (k == 2) return frags + kT2Base + (size_t)(path ? kT2Kb[1][3] : kT2Kb[0][3]) * 1024;
+  if (k == 3) return path ? frags + kT3Base + 131072 : frags + kT2Base + (size_t)kT2Kb[0][4] * 1024;
+  return frags + kT2Base + (size_t)kT2Kb[0][5] * 1024;
 }
 
 // this wave's share (1/8) of a chunk: global -> LDS by the DMA path, 1 KB per instruction
@@ -985,11 +1006,16 @@ __device__ __forceinline__ void wr_store_rows(__amdgpu_buffer_rsrc_t out, const 
                                           lane_off + ((r & 3) * LD + 32 * tile) * 4, 8 * (r >> 2) * LD * 4, 0);
 }
 
-template <bool TAPS>
+// SPEC (the forward's form when NwsWeights.mlp_spec is set): proj is folded into the first hidden layer of either
+// path (layer 0, its weight chunk and its barrier are gone: newt.mlp runs five chunks and barriers, h_generator four)
+// and h_generator's output layer is W_G = S W_out, so `fir_out` receives rows of NWS_SPEC_ROW floats, the real filter spectrum
+// G[0 .. 128] of the frame as the noise kernel multiplies it, instead of half-taps: the FIR-design contraction is gone as well.
+template <bool TAPS, bool SPEC = false>
 __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, const float* __restrict__ gru_out, int F, int T,
                                                                  float* __restrict__ emb_out, float* __restrict__ film_out,
                                                                  float* __restrict__ H_out, float* __restrict__ fir_out,
                                                                  const int xcd_blocks = 0) {
+  static_assert(!(TAPS && SPEC), "the folded form has neither an embedding nor H to store");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   WrLds& L = *reinterpret_cast<WrLds*>(smem_raw);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1004,7 +1030,9 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
   const int half = lane >> 5, col = lane & 31;
   const int f0 = fb * kWrFrames + 32 * wave;         // first frame of this wave
   const int frame = f0 + col;                        // this lane's frame (standard orientation)
-  const char* T2 = static_cast<const char*>(w.mlp_frags) + kT2Base;
+  const char* const frags = static_cast<const char*>(w.mlp_frags);
+  const char* T2 = frags + kT2Base;
+  const float* const spar = reinterpret_cast<const float*>(frags + kT3Base + kT3ParKb * 1024);   // SPEC only
   char* const S0 = L.slot[0];
   char* const S1 = L.slot[1];
 
@@ -1013,14 +1041,14 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
   // request in front of the first use of a loaded register while an LDS-bound load is in flight, so chunk 1 is requested only
   // after that point, LAST: the first barrier waits for everything but the eight most recent requests (memory reads return in
   // order) and the first layer runs while chunk 1 is still arriving ----
-  wr_dma(T2 + (size_t)kT2Kb[0][0] * 1024, S0, 64, wave, lane);
+  wr_dma(SPEC ? wr_spec_chunk(frags, path, 0) : T2 + (size_t)kT2Kb[0][0] * 1024, S0, 64, wave, lane);
   const int grp = wave >> 1, pc = tid & 127;
   float pv[4];
   {
     // vector n of the parameter block goes to par[128 n ..]; quarter `grp` of the workgroup fetches vectors grp, grp + 4, ...
     // (compile-time struct indices selected by scalar compares: a run-time index into the by-value struct would be a private copy)
     auto sel4 = [&](const float* a, const float* b, const float* c, const float* d) { return grp == 0 ? a : grp == 1 ? b : grp == 2 ? c : d; };
-    const float* const hb0 = path ? w.hgen_b[0] : w.newt_mlp_b[0];
+    const float* const hb0 = SPEC ? spar + 128 * path : path ? w.hgen_b[0] : w.newt_mlp_b[0];
     const float* const hg0 = path ? w.hgen_ln_g[0] : w.newt_ln_g[0];
     const float* const ht0 = path ? w.hgen_ln_b[0] : w.newt_ln_b[0];
     const float* const hb1 = path ? w.hgen_b[1] : w.newt_mlp_b[1];
@@ -1029,14 +1057,14 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
     const float* const hb2 = path ? w.hgen_b[2] : w.newt_mlp_b[2];
     const float* const hg2 = path ? w.hgen_ln_g[2] : w.newt_ln_g[2];
     const float* const ht2 = path ? w.hgen_ln_b[2] : w.newt_ln_b[2];
-    const float* const ob = path ? w.hgen_b[3] : w.newt_mlp_b[3];
-    const float* const ox = path ? w.hgen_w[3] + (size_t)128 * NWS_HIDDEN : w.newt_mlp_b[3] + 128;
+    const float* const ob = path ? (SPEC ? spar + 256 : w.hgen_b[3]) : w.newt_mlp_b[3];
+    const float* const ox = path ? (SPEC ? spar + 384 : w.hgen_w[3] + (size_t)128 * NWS_HIDDEN) : w.newt_mlp_b[3] + 128;
     pv[0] = sel4(w.proj_b, hb0, hg0, ht0)[pc];
     pv[1] = sel4(hb1, hg1, ht1, hb2)[pc];
     pv[2] = sel4(hg2, ht2, ob, ox)[pc];
     pv[3] = w.proj_b[pc];   // (vector 12 does not exist: quarter 0 rewrites vector 0 with the same values)
   }
-  const float b128 = path ? w.hgen_b[3][128] : 0.0f;
+  const float b128 = path ? (SPEC ? spar[512] : w.hgen_b[3][128]) : 0.0f;
   float4 in[16];
   {
     // (frames >= F read the last row: their results are never stored)
@@ -1058,7 +1086,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
     wr_pack8(y, X.hi[ks], X.lo[ks]);
   }
   __builtin_amdgcn_sched_barrier(0);
-  wr_dma(T2 + (size_t)(path ? kT2Kb[1][1] : kT2Kb[0][1]) * 1024, S1, 64, wave, lane);   // the wave's 8 most recent requests
+  wr_dma(SPEC ? wr_spec_chunk(frags, path, 1) : T2 + (size_t)(path ? kT2Kb[1][1] : kT2Kb[0][1]) * 1024, S1, 64, wave, lane);   // the wave's 8 most recent requests
   __builtin_amdgcn_sched_barrier(0);
   // barrier k closes interval k: every wave has finished reading slot (k - 1) & 1, and its share of chunk k (requested one
   // interval earlier) has landed; then chunk k + 1 goes into the slot just released
@@ -1068,30 +1096,36 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
     // (not __syncthreads(): hipcc puts a vmcnt(0) in front of it while LDS-bound loads are in flight, which would wait for
     // chunk 1 as well; the LDS writes of the parameters are drained by the lgkmcnt(0))
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (k >= 1 && k <= 4) wr_dma(T2 + (size_t)(path ? kT2Kb[1][k + 1] : kT2Kb[0][k + 1]) * 1024, ((k + 1) & 1) ? S1 : S0, (path == 1 && k == 4) ? 72 : 64, wave, lane);
+    if (SPEC) {
+      if (k >= 1 && k + 1 <= (path ? 3 : 4)) wr_dma(wr_spec_chunk(frags, path, k + 1), ((k + 1) & 1) ? S1 : S0, 64, wave, lane);
+    } else if (k >= 1 && k <= 4) {
+      wr_dma(T2 + (size_t)(path ? kT2Kb[1][k + 1] : kT2Kb[0][k + 1]) * 1024, ((k + 1) & 1) ? S1 : S0, (path == 1 && k == 4) ? 72 : 64, wave, lane);
+    }
   };
   sync(0);
 
   f32x16 v[4];
-  // ---- layer 0: emb = proj(gru_out) ----
-  wr_lane_vec(L.par, half, v);
-  wr_layer_mma<8, 4, false, false>(S0, 0, X, v, lane);
-  if (TAPS && path == 0 && emb_out != nullptr && frame < F) {
-    const int b = frame / T, t = frame - b * T;
+  if constexpr (!SPEC) {
+    // ---- layer 0: emb = proj(gru_out) ----
+    wr_lane_vec(L.par, half, v);
+    wr_layer_mma<8, 4, false, false>(S0, 0, X, v, lane);
+    if (TAPS && path == 0 && emb_out != nullptr && frame < F) {
+      const int b = frame / T, t = frame - b * T;
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
+      for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) emb_out[((size_t)b * NWS_HIDDEN + 32 * mt + frag_row(r, half)) * T + t] = v[mt][r];
+        for (int r = 0; r < 16; ++r) emb_out[((size_t)b * NWS_HIDDEN + 32 * mt + frag_row(r, half)) * T + t] = v[mt][r];
+    }
+    wr_pack(v, X);
+    sync(1);
   }
-  wr_pack(v, X);
-  sync(1);
 
   // ---- three hidden layers: X = LeakyReLU(LayerNorm(W X + b)) ----
   float h128 = 0.0f;
 #pragma unroll
   for (int l = 0; l < 3; ++l) {
     const float* par = L.par + 128 + 384 * l;
-    const char* slot = (l & 1) ? S0 : S1;          // chunks 1, 2, 3 -> slots 1, 0, 1
+    const char* slot = ((l & 1) != 0) != SPEC ? S0 : S1;   // chunks 1, 2, 3 -> slots 1, 0, 1; SPEC: chunks 0, 1, 2 -> slots 0, 1, 0
     wr_lane_vec(par, half, v);
     wr_layer_mma<8, 4, false, false>(slot, 0, X, v, lane);
     wr_layer_norm(v, par + 128, par + 256, half);
@@ -1112,16 +1146,17 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
       h128 = d + L.par[1536];
     }
     wr_pack(v, X);
-    sync(l + 2);
+    sync(SPEC ? l + 1 : l + 2);
   }
 
   if (path == 0) {
     // ---- film = last layer of newt.mlp, transposed: lane = channel, register = frame; chunk 4 (slot 0): tiles 0..3, chunk 5: 4..7
+    // (SPEC: chunks 3 and 4, slots 1 and 0)
     const __amdgpu_buffer_rsrc_t film_rs = __builtin_amdgcn_make_buffer_rsrc(film_out, 0, F * NWS_FILM_CH * 4, 0x00020000);
     const int lane_off = ((f0 + 4 * half) * NWS_FILM_CH + col) * 4;
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      const char* slot = c ? S1 : S0;
+      const char* slot = (c != 0) != SPEC ? S1 : S0;
 #pragma unroll
       for (int pr = 0; pr < 2; ++pr) {           // two tiles at a time: two accumulator chains
         f32x16 acc[2];
@@ -1130,8 +1165,21 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
         for (int j = 0; j < 2; ++j)
           wr_store_rows<NWS_FILM_CH, true>(film_rs, acc[j], lane_off, 4 * c + 2 * pr + j, L.par[1280 + 32 * (4 * c + 2 * pr + j) + col]);
       }
-      if (c == 0) sync(5);
+      if (c == 0) sync(SPEC ? 4 : 5);
     }
+  } else if constexpr (SPEC) {
+    // ---- G = W_G X + b_G, transposed (chunk 3, slot 1): bins 0..127 on the matrix pipe, straight into frame-major rows; bin 128
+    // from the dot product above ----
+    const __amdgpu_buffer_rsrc_t g_rs = __builtin_amdgcn_make_buffer_rsrc(fir_out, 0, F * NWS_SPEC_ROW * 4, 0x00020000);
+    const int lane_off = ((f0 + 4 * half) * NWS_SPEC_ROW + col) * 4;
+#pragma unroll
+    for (int pr = 0; pr < 2; ++pr) {
+      f32x16 acc[2];
+      wr_layer_mma<8, 2, true, true>(S1, 2 * pr, X, acc, lane);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) wr_store_rows<NWS_SPEC_ROW, true>(g_rs, acc[j], lane_off, 2 * pr + j, L.par[1280 + 32 * (2 * pr + j) + col]);
+    }
+    if (half == 0 && frame < F) fir_out[(size_t)frame * NWS_SPEC_ROW + 128] = h128;
   } else {
     // ---- H = last layer of h_generator (bands 0..127 on the matrix pipe, band 128 from above) -> operand of the FIR design ----
     wr_lane_vec(L.par + 1280, half, v);
@@ -1225,6 +1273,37 @@ __global__ void mlp_frags_kernel(NwsWeights w, const float* __restrict__ fir_des
   dst[64] = lo;
 }
 
+// third fragment table from the folded weights (nws_mlp_spec_fold's layout): chunks 0, 1 in the contraction order of a layer that
+// reads the GRU row, chunk 2 in the order of one that reads accumulators; then the parameter block
+__global__ void mlp_spec_frags_kernel(const float* __restrict__ folded, char* __restrict__ out) {
+  const int e0 = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e0 < 3 * 2048) {
+    const int id = e0 >> 11, e = e0 & 2047;
+    const int li = e & 63, ks = (e >> 6) & 7, mt = e >> 9;
+    const int row = 32 * mt + (li & 31), h = li >> 5;
+    const float* W = folded + (id == 0 ? kFoldW1n : id == 1 ? kFoldW1h : kFoldWg);
+    f16x8 hi, lo;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int k = id < 2 ? kperm_in(ks, h, i) : kperm_d(ks, h, i);
+      const float v = W[row * NWS_HIDDEN + k];
+      hi[i] = (_Float16)v;
+      lo[i] = (_Float16)(v - (float)hi[i]);
+    }
+    f16x8* dst = reinterpret_cast<f16x8*>(out) + (size_t)id * 4096 + ((size_t)(mt * 8 + ks) * 2) * 64 + li;
+    dst[0] = hi;
+    dst[64] = lo;
+  }
+  if (e0 <= 512) {
+    float* par = reinterpret_cast<float*>(out + kT3ParKb * 1024);
+    par[e0] = e0 < 128   ? folded[kFoldB1n + e0]
+              : e0 < 256 ? folded[kFoldB1h + e0 - 128]
+              : e0 < 384 ? folded[kFoldBg + e0 - 256]
+              : e0 < 512 ? folded[kFoldWg + 128 * NWS_HIDDEN + e0 - 384]
+                         : folded[kFoldBg + 128];
+  }
+}
+
 // D[n][k] (256 x 132): fir[n] = window[n] * h0[(n - 128) mod 256],
 //   h0[m] = irfft(H)[m] = (1/256) (H_0 + (-1)^m H_128 + 2 sum_{k=1}^{127} H_k cos(2 pi k m / 256))
 __global__ void fir_design_kernel(const float* __restrict__ window, float* __restrict__ D) {
@@ -1280,11 +1359,120 @@ int nws_mlp_frags(const NwsWeights* w, const float* fir_design, void* frags_out,
   return NWS_OK;
 }
 
+// Host: S[k][band], bands -> the real filter spectrum the noise kernel multiplies (fir_noise.hip, sp_filter_spectrum: the stored
+// half row u[d] = D[128 + d][band] extended to e[n] = u[min(n, 256 - n)] with u[128] := 0, then the forward transform without
+// scaling, bin k at index k).  e is real and even, so G[k] = u[0] + 2 sum_{d=1}^{127} u[d] cos(2 pi k d / 256).  The columns of the
+// fp32 design matrix as the kernels read them, summed in float64.
+int nws_fir_spectrum_map(const float* fir_design, double* S_out) {
+  if (!fir_design || !S_out) return NWS_ERR_BAD_ARG;
+  double c[NWS_FIR_LEN];
+  for (int m = 0; m < NWS_FIR_LEN; ++m) c[m] = cos(2.0 * 3.14159265358979323846 * (double)m / (double)NWS_FIR_LEN);
+  c[64] = c[192] = 0.0;
+  for (int k = 0; k < NWS_N_BANDS; ++k)
+    for (int band = 0; band < NWS_N_BANDS; ++band) {
+      double acc = 0.0;
+      for (int d = NWS_FIR_HALF - 1; d >= 1; --d) acc += (double)fir_design[(size_t)(NWS_FIR_HALF + d) * kDK + band] * c[(k * d) & (NWS_FIR_LEN - 1)];
+      S_out[k * NWS_N_BANDS + band] = (double)fir_design[(size_t)NWS_FIR_HALF * kDK + band] + 2.0 * acc;
+    }
+  return NWS_OK;
+}
+
+// Host: the folded weights (include/nws_hip.h), float64 sums rounded once to fp32
+int nws_mlp_spec_fold(const float* proj_w, const float* proj_b, const float* newt_w0, const float* newt_b0, const float* hgen_w0,
+                      const float* hgen_b0, const float* hgen_w3, const float* hgen_b3, const double* S, float* folded_out) {
+  if (!proj_w || !proj_b || !newt_w0 || !newt_b0 || !hgen_w0 || !hgen_b0 || !hgen_w3 || !hgen_b3 || !S || !folded_out) return NWS_ERR_BAD_ARG;
+  constexpr int H = NWS_HIDDEN;
+  for (int p = 0; p < 2; ++p) {
+    const float* W1 = p ? hgen_w0 : newt_w0;
+    const float* b1 = p ? hgen_b0 : newt_b0;
+    float* Wf = folded_out + (p ? kFoldW1h : kFoldW1n);
+    float* bf = folded_out + (p ? kFoldB1h : kFoldB1n);
+    for (int r = 0; r < H; ++r) {
+      double row[H];
+      for (int c = 0; c < H; ++c) row[c] = 0.0;
+      double bias = (double)b1[r];
+      for (int k = 0; k < H; ++k) {
+        const double a = (double)W1[r * H + k];
+        for (int c = 0; c < H; ++c) row[c] += a * (double)proj_w[k * H + c];
+        bias += a * (double)proj_b[k];
+      }
+      for (int c = 0; c < H; ++c) Wf[r * H + c] = (float)row[c];
+      bf[r] = (float)bias;
+    }
+  }
+  for (int j = 0; j < NWS_N_BANDS; ++j) {
+    double row[H];
+    for (int c = 0; c < H; ++c) row[c] = 0.0;
+    double bias = 0.0;
+    for (int k = 0; k < NWS_N_BANDS; ++k) {
+      const double a = S[j * NWS_N_BANDS + k];
+      for (int c = 0; c < H; ++c) row[c] += a * (double)hgen_w3[k * H + c];
+      bias += a * (double)hgen_b3[k];
+    }
+    for (int c = 0; c < H; ++c) folded_out[kFoldWg + j * H + c] = (float)row[c];
+    folded_out[kFoldBg + j] = (float)bias;
+  }
+  for (int j = NWS_N_BANDS; j < 132; ++j) folded_out[kFoldBg + j] = 0.0f;
+  return NWS_OK;
+}
+
+int nws_mlp_spec_frags(const float* folded, void* frags, void* stream) {
+  if (!folded || !frags) return NWS_ERR_BAD_ARG;
+  mlp_spec_frags_kernel<<<(3 * 2048 + 255) / 256, 256, 0, (hipStream_t)stream>>>(folded, static_cast<char*>(frags) + kT3Base);
+  NWS_CHECK_LAUNCH();
+  return NWS_OK;
+}
+
 // tests: 0 automatic (by frame count), 1 tile kernels (frame_mlps16 / 64), 2 wave-resident frames
 static int g_mlp_kernel_mode = 0;
 int nws_debug_frame_mlps_kernel(int mode) {
   if (mode < 0 || mode > 2) return NWS_ERR_BAD_ARG;
   g_mlp_kernel_mode = mode;
+  return NWS_OK;
+}
+
+// tests and A/B timing: 0 keeps the forward on the tap hand-over whatever NwsWeights.mlp_spec says (nws_frame_mlps_spec_serves
+// answers 0; nws_frame_mlps_spec itself is not affected)
+static int g_forward_spec = 1;
+int nws_debug_forward_spec(int on) {
+  g_forward_spec = on != 0;
+  return NWS_OK;
+}
+
+// the frame counts at which nws_frame_mlps takes the wave-resident kernel (see there)
+static bool wr_kernel_serves(const NwsWeights* w, int B, int T) {
+  const long long F = (long long)B * T;
+  const bool many = (long long)B * ((T + kFT2 - 1) / kFT2) > 256;
+  return w->mlp_frags != nullptr && g_mlp_kernel_mode != 1 && (many || g_mlp_kernel_mode == 2) &&
+         F * NWS_FILM_CH * (long long)sizeof(float) < (1ll << 31);
+}
+
+static bool spec_serves(const NwsWeights* w, int B, int T) {
+  return w && B >= 16 && B <= 65535 && T > 0 && w->mlp_spec != 0 && wr_kernel_serves(w, B, T);
+}
+
+int nws_frame_mlps_spec_serves(const NwsWeights* w, int B, int T) { return g_forward_spec && spec_serves(w, B, T) ? 1 : 0; }
+
+int nws_frame_mlps_spec(const NwsWeights* w, const float* gru_out, int B, int T, float* film_out, float* spec_out, void* stream) {
+  if (!w || !gru_out || !film_out || !spec_out || B <= 0 || T <= 0) return NWS_ERR_BAD_ARG;
+  for (int i = 0; i < 4; ++i)
+    if (!w->newt_mlp_w[i] || !w->newt_mlp_b[i] || !w->hgen_w[i] || !w->hgen_b[i]) return NWS_ERR_BAD_ARG;
+  for (int i = 0; i < 3; ++i)
+    if (!w->newt_ln_g[i] || !w->newt_ln_b[i] || !w->hgen_ln_g[i] || !w->hgen_ln_b[i]) return NWS_ERR_BAD_ARG;
+  if (!w->proj_b) return NWS_ERR_BAD_ARG;
+  if (!spec_serves(w, B, T)) return NWS_ERR_UNSUPPORTED;
+  static unsigned long long attr_devices = 0;
+  if (nws_first_use_on_device(attr_devices)) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(frame_mlps_wr_kernel<false, true>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WrLds));
+    if (e != hipSuccess) return (int)e;
+  }
+  const long long F = (long long)B * T;
+  const unsigned nblk = (unsigned)((F + kWrFrames - 1) / kWrFrames);
+  const dim3 gridw(16 * ((nblk + 7) / 8), 1);      // both paths of a frame block on one XCD (see the kernel)
+  frame_mlps_wr_kernel<false, true><<<gridw, 512, sizeof(WrLds), (hipStream_t)stream>>>(*w, gru_out, (int)F, T, nullptr, film_out, nullptr,
+                                                                                         spec_out, (int)nblk);
+  NWS_CHECK_LAUNCH();
   return NWS_OK;
 }
 
@@ -1321,12 +1509,11 @@ int nws_frame_mlps(const NwsWeights* w, const float* gru_out, const float* fir_d
   // enough frames to give most CUs a 256-frame workgroup: wave-resident frames
   const int mode = g_mlp_kernel_mode;
   const long long F = (long long)B * T;
-  // (from the point where the 64-frame tile kernel needs a second round of workgroups: 256 tiles)
-  const bool many = (long long)B * ((T + kFT2 - 1) / kFT2) > 256;
+  // (wr_kernel_serves: from the point where the 64-frame tile kernel needs a second round of workgroups, 256 tiles)
   // (the wave-resident kernel addresses its outputs through buffer resources with 32-bit BYTE offsets - num_records and the
   // per-lane offsets of the film rows, the widest output: F * 256 * 4 bytes must stay below 2^31, i.e. F < 2^21 frames = 64 x 8.7 min;
   // beyond that the tile kernels below, which index with size_t, take over)
-  if (w->mlp_frags != nullptr && mode != 1 && (many || mode == 2) && F * NWS_FILM_CH * (long long)sizeof(float) < (1ll << 31)) {
+  if (wr_kernel_serves(w, B, T)) {
     static unsigned long long attr_wr = 0;
     if (nws_first_use_on_device(attr_wr)) {
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(frame_mlps_wr_kernel<false>),

@@ -441,6 +441,40 @@ Tensor fir_noise(const Tensor& fir, const Tensor& noise, const OptTensor& add_in
   return out;
 }
 
+// the frame MLPs with the folded weights (NwsWeights.mlp_spec): -> (film (B,T,256), spec (B,T,132) rows of filter spectra G[0 .. 128])
+std::tuple<Tensor, Tensor> frame_mlps_spec(const Tensor& wdesc, const Tensor& gru_out) {
+  const NwsWeights* w = weights_of(wdesc);
+  check_dev(gru_out, "gru_out");
+  TORCH_CHECK(gru_out.dim() == 3 && gru_out.size(2) == NWS_HIDDEN, "gru_out: expected (B, T, 128), got ", gru_out.sizes());
+  const int64_t B = gru_out.size(0), T = gru_out.size(1);
+  Launch L(gru_out);
+  Tensor film = at::empty({B, T, NWS_FILM_CH}, gru_out.options());
+  Tensor spec = at::zeros({B, T, NWS_SPEC_ROW}, gru_out.options());      // (the three floats behind bin 128 are never written)
+  nws_check(nws_frame_mlps_spec(w, gru_out.data_ptr<float>(), (int)B, (int)T, film.data_ptr<float>(), spec.data_ptr<float>(), L.stream),
+            "nws_frame_mlps_spec");
+  return {film, spec};
+}
+
+// fir_noise on rows of filter spectra (B, T, 132) instead of half-taps; the reference's own framing, B >= 16
+Tensor fir_noise_spec(const Tensor& spec, const Tensor& noise, const OptTensor& add_in) {
+  check_dev(spec, "spec");
+  check_dev(noise, "noise");
+  check_same_device(spec, "spec", noise, "noise");
+  TORCH_CHECK(spec.dim() == 3 && spec.size(2) == NWS_SPEC_ROW, "spec: expected (B, T, 132) filter spectra (nws_frame_mlps_spec), got ", spec.sizes());
+  const int64_t B = spec.size(0), T = spec.size(1);
+  TORCH_CHECK(noise.numel() == T * NWS_HOP - 1, "noise: expected ", T * NWS_HOP - 1, " samples, got ", noise.sizes());
+  if (add_in.has_value()) {
+    check_dev(*add_in, "add_in");
+    check_same_device(spec, "spec", *add_in, "add_in");
+    TORCH_CHECK(add_in->numel() == B * T * NWS_HOP, "add_in: expected (", B, ", ", T * NWS_HOP, "), got ", add_in->sizes());
+  }
+  Launch L(spec);
+  Tensor out = at::empty({B, T * NWS_HOP}, spec.options());
+  nws_check(nws_fir_noise_spec(spec.data_ptr<float>(), noise.data_ptr<float>(), fptr(add_in), (int)B, (int)T, out.data_ptr<float>(), L.stream),
+            "nws_fir_noise_spec");
+  return out;
+}
+
 // FIRNoiseSynth's zero-phase FIR design from H (B, 129, T) (generators.py:22-28) -> upper half-taps (B, T, 128)
 Tensor fir_from_h(const Tensor& H, const Tensor& fir_design) {
   check_dev(H, "H");
@@ -1417,6 +1451,8 @@ TORCH_LIBRARY(newt_hip, m) {
   m.def("frame_mlps(Tensor wdesc, Tensor gru_out, Tensor fir_design, bool want_emb, bool want_H) -> (Tensor, Tensor, Tensor, Tensor)",
         &frame_mlps);
   m.def("fir_noise(Tensor fir, Tensor noise, Tensor? add_in, int origin) -> Tensor", &fir_noise);
+  m.def("frame_mlps_spec(Tensor wdesc, Tensor gru_out) -> (Tensor, Tensor)", &frame_mlps_spec);
+  m.def("fir_noise_spec(Tensor spec, Tensor noise, Tensor? add_in) -> Tensor", &fir_noise_spec);
   m.def("fir_from_h(Tensor H, Tensor fir_design) -> Tensor", &fir_from_h);
   m.def("fir_noise_grad(Tensor noise, Tensor grad_out) -> Tensor", &fir_noise_grad);
   m.def("fir_from_h_grad(Tensor grad_fir, Tensor fir_design) -> Tensor", &fir_from_h_grad);

@@ -371,11 +371,20 @@ class Engine:
             check(L.nws_fir_design_matrix(w.noise_window, ptr(fd), st), "nws_fir_design_matrix")
             keep.append(fd)
             w.mlp_frags = None
+            w.mlp_spec = 0
             if self.fp16_mlp_safe():
-                frags = torch.empty(_lib.MLP_FRAGS_BYTES, dtype=torch.uint8, device=dev)
+                frags = torch.empty(_lib.MLP_FRAGS_BYTES + _lib.MLP_SPEC_BYTES, dtype=torch.uint8, device=dev)
                 check(L.nws_mlp_frags(C.byref(w), ptr(fd), ptr(frags), st), "nws_mlp_frags")
                 keep.append(frags)
                 w.mlp_frags = frags.data_ptr()
+                # proj folded into the first hidden layers and h_generator's output layer emitting filter spectra (host, float64,
+                # once per weights version); where the folded weights fail the range check the forward keeps the tap hand-over
+                folded = self.spec_fold(fd)
+                if self.fp16_spec_safe(folded):
+                    fdev = folded.to(dev)
+                    check(L.nws_mlp_spec_frags(ptr(fdev), ptr(frags), st), "nws_mlp_spec_frags")
+                    keep.append(fdev)
+                    w.mlp_spec = 1
             rand_phase = _req(m.osc.rand_phase.detach(), "osc.rand_phase", 101)
             ir = _req(m.reverb.ir.detach(), "reverb.ir")
             keep += [rand_phase, ir]
@@ -451,6 +460,43 @@ class Engine:
             bounds.append(l1(m.h_generator.net[9].weight, m.h_generator.net[9].bias, ln(m.h_generator.net[7])))
             wmax = max(float(p.detach().abs().max()) for mlp in (m.newt.mlp, m.h_generator) for p in mlp.parameters())
         return max(bounds + [wmax]) < limit and all(b == b for b in bounds)
+
+    def spec_fold(self, fir_design: torch.Tensor) -> torch.Tensor:
+        """The folded weights of the spectrum hand-over (include/nws_hip.h, nws_mlp_spec_fold) as a CPU tensor of
+        MLP_SPEC_FOLD_FLOATS: host code of the library on host copies of eight parameter tensors and of the design matrix,
+        float64 sums rounded once to fp32."""
+        m = self._model_ref
+        L = _lib.lib()
+
+        def host(t):
+            return t.detach().to("cpu", torch.float32).contiguous()
+
+        D = host(fir_design)
+        S = torch.empty(_lib.N_BANDS * _lib.N_BANDS, dtype=torch.float64)
+        check(L.nws_fir_spectrum_map(ptr(D), ptr(S)), "nws_fir_spectrum_map")
+        src = [host(t) for t in (m.embedding.proj.weight, m.embedding.proj.bias, m.newt.mlp.net[0].weight, m.newt.mlp.net[0].bias,
+                                 m.h_generator.net[0].weight, m.h_generator.net[0].bias, m.h_generator.net[9].weight,
+                                 m.h_generator.net[9].bias)]
+        folded = torch.empty(_lib.MLP_SPEC_FOLD_FLOATS, dtype=torch.float32)
+        check(L.nws_mlp_spec_fold(*[ptr(t) for t in src], ptr(S), ptr(folded)), "nws_mlp_spec_fold")
+        return folded
+
+    def fp16_spec_safe(self, folded: torch.Tensor, limit: float = 3.0e4) -> bool:
+        """fp16_mlp_safe's worst-case check on the folded weights: the input of a folded first layer is the GRU output (|x| < 1),
+        so its rows are bounded by ||W1'||_1 + |b1'|; the spectrum layer reads the last LayerNorm like the layer it replaces:
+        ||W_G||_1 * ln_bound + |b_G|.  The fp16 terms of the weights themselves must be in range as well."""
+        H, NB = _lib.HIDDEN, _lib.N_BANDS
+        f = folded.double()
+        w1n, w1h = f[:H * H].view(H, H), f[H * H:2 * H * H].view(H, H)
+        wg = f[2 * H * H:2 * H * H + NB * H].view(NB, H)
+        o = 2 * H * H + NB * H
+        b1n, b1h, bg = f[o:o + H], f[o + H:o + 2 * H], f[o + 2 * H:o + 2 * H + NB]
+        ln3 = self._model_ref.h_generator.net[7].layer_norm
+        with torch.no_grad():
+            ln_bound = float(math.sqrt(H - 1) * ln3.weight.detach().abs().max() + ln3.bias.detach().abs().max())
+        bounds = [float((w1n.abs().sum(1) + b1n.abs()).max()), float((w1h.abs().sum(1) + b1h.abs()).max()),
+                  float((wg.abs().sum(1) * ln_bound + bg.abs()).max()), float(f.abs().max())]
+        return all(b == b and b < limit for b in bounds)
 
     @property
     def device(self):
@@ -529,6 +575,18 @@ class Engine:
         same_device(fir.device, noise=noise, add_in=add_in)
         nz = noise if noise_len is None or noise_len == noise.numel() else noise[:noise_len]
         return binding().fir_noise(fir, nz, add_in, -1 if origin is None else int(origin))
+
+    def frame_mlps_spec(self, gru_out):
+        """the frame MLPs in the folded form the forward runs at batch sizes that fill the chip: (film (B, T, 256), rows of filter
+        spectra (B, T, 132)); raises where the weights carry no folded tables or the size takes another kernel"""
+        r = self._wd()
+        same_device(r.device, gru_out=gru_out)
+        return binding().frame_mlps_spec(r.wdesc, gru_out)
+
+    def fir_noise_spec(self, spec, noise, add_in=None):
+        """`fir_noise` on rows of filter spectra (frame_mlps_spec) instead of half-taps; B >= 16"""
+        same_device(spec.device, noise=noise, add_in=add_in)
+        return binding().fir_noise_spec(spec, noise, add_in)
 
     def reverb(self, x):
         same_device(self._wd().device, x=x)
