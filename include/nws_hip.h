@@ -425,6 +425,22 @@ int nws_oscillator(const float* f0_up, const double* carry, const float* phase_u
  * film (B, 256, T) = newt.mlp(control_embedding) channel-major as the reference's Conv1d stack returns it; out (B, N).
  * w: shaper_* or lut fields, newt_out_w / newt_out_b. */
 int nws_newt_apply(const NwsWeights* w, const float* exciter, const float* film, int B, int T, float* out, void* stream);
+/* The backward of nws_newt_apply with the exact shapers for grad_out = dL/d(out) (B, N): grad_film (B, 256, T),
+ * grad_exciter (B, 64, N) unless NULL, and, when all eleven are given, the parameter gradients in the layout of their parameters:
+ * shaping_fn.input_scale (64), net.0.weight / bias (512 each), net.2.weight (512, 8) / bias (512), net.4.weight / bias likewise,
+ * net.6.weight (64, 8) / bias (64), mixer.0.weight (64) / bias (1).  Nothing is saved by the forward: it is recomputed per
+ * sample from exciter and film with nws_newt_apply's arithmetic.  No atomics, sums over batch and time in a fixed order in
+ * float64: equal inputs give equal bits, grad_out = 0 gives zeros.  Launches on `stream` (the recomputing kernel, the fold of the
+ * upsampling's transpose, with parameters one reduction), reads nothing back and decides every refusal before the first launch:
+ * NWS_ERR_BAD_ARG for a NULL required pointer (w's shaper_* and newt_out_* fields included), some but not all of the eleven
+ * parameter gradients, a size < 1, or a workspace that is NULL or smaller than nws_newt_grad_workspace_bytes;
+ * NWS_ERR_UNSUPPORTED for T > 65 535, B T > 2^28, or a w that carries a lookup table (FastNEWT has no backward).
+ * nws_newt_grad_workspace_bytes: 0 for sizes that are refused. */
+size_t nws_newt_grad_workspace_bytes(int B, int T, int want_params);
+int nws_newt_grad(const NwsWeights* w, const float* exciter, const float* film, const float* grad_out, int B, int T,
+                  float* grad_exciter /* may be NULL */, float* grad_film, float* grad_in_scale, float* grad_w0, float* grad_b0,
+                  float* grad_w2, float* grad_b2, float* grad_w4, float* grad_b4, float* grad_w6, float* grad_b6,
+                  float* grad_mix_w, float* grad_mix_b, void* workspace, size_t workspace_bytes, void* stream);
 /* TimeDistributedMLP.forward (models/modules/dynamic.py:20-40), any sizes: x (B, in, T) -> y (B, out, T);
  * depth Conv1d(k=1) layers (HOST arrays of depth device pointers: w[i] (rows_i, cols_i), b[i]), LayerNorm over channels
  * (ln_g[i], ln_b[i], i < depth-1, biased variance, eps) + LeakyReLU(slope) after every layer but the last.

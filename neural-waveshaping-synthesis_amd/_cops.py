@@ -364,6 +364,38 @@ class CtypesOps:
                                             _stream(exciter.device)), "nws_newt_apply")
         return out
 
+    def newt_grad(self, wdesc, exciter, film, grad_out, want_exciter, want_params):
+        B, S, N = exciter.shape
+        T = film.shape[2]
+        if S != _lib.N_SHAPERS or tuple(film.shape) != (B, _lib.FILM_CH, T) or N != T * HOP:
+            raise RuntimeError(f"NEWT: exciter {tuple(exciter.shape)} and FiLM parameters {tuple(film.shape)} disagree")
+        if B < 1 or T < 1:
+            raise RuntimeError("newt_grad: need at least one utterance and one frame")
+        if grad_out.numel() != B * N or grad_out.shape[0] != B:
+            raise RuntimeError(f"newt_grad: grad_out {tuple(grad_out.shape)} is not ({B}, 1, {N})")
+        w = _struct(wdesc, NwsWeights)
+        if w.lut:
+            raise RuntimeError("newt_grad: the lookup table has no backward")
+        L = _lib.lib()
+        nbytes = L.nws_newt_grad_workspace_bytes(B, T, 1 if want_params else 0) if max(B, T) < 2 ** 30 else 0
+        if nbytes == 0:
+            raise RuntimeError(f"newt_grad: unsupported size (B {B}, T {T}): T <= 65535, B T <= 2^28")
+        with torch.cuda.device(exciter.device):
+            out = [_new(exciter, B, _lib.FILM_CH, T)]
+            ge = torch.empty_like(exciter) if want_exciter else None
+            if want_exciter:
+                out.append(ge)
+            gp = [None] * 11
+            if want_params:
+                SW = S * _lib.SHAPER_WIDTH
+                shapes = [(1, S, 1), (SW, 1, 1), (SW,), (SW, 8, 1), (SW,), (SW, 8, 1), (SW,), (S, 8, 1), (S,), (1, S, 1), (1,)]
+                gp = [_new(exciter, *sh) for sh in shapes]
+                out += gp
+            ws = _new(exciter, nbytes, dtype=torch.uint8)
+            check(L.nws_newt_grad(C.byref(w), ptr(exciter), ptr(film), ptr(grad_out), B, T, ptr(ge), ptr(out[0]),
+                                  *[ptr(t) for t in gp], ptr(ws), nbytes, _stream(exciter.device)), "nws_newt_grad")
+        return out
+
     # ---- stand-alone stage kernels (csrc/stages.hip) ---------------------------------------------------------------------
     def td_mlp(self, x, weights, biases, ln_w, ln_b, eps, slope):
         B, in_size, T = x.shape

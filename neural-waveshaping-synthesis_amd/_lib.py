@@ -205,6 +205,9 @@ _PROTOTYPES = {
                                 C.POINTER(_fp), C.c_float, C.c_float, C.c_float, C.c_float, _fp, _fp, C.c_size_t, _fp]),
     "nws_oscillator": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_float, _fp, _fp]),
     "nws_newt_apply": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
+    "nws_newt_grad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nws_newt_grad": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
     "nws_td_mlp": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),
                              C.POINTER(_fp), C.POINTER(_fp), C.c_float, C.c_float, _fp, _fp]),
     "nws_td_mlp_grad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -153,6 +153,39 @@ __device__ __forceinline__ float nws_sinf_nocall(float x) {
   return (q & 2) ? -v : v;
 }
 
+// sin and cos of one argument without a device function call on any path (newt_grad.hip: the backward of a sine layer needs
+// the cosine of every pre-activation).  Up to 6e6 it is nws_sinf's own reduction and its two polynomials, which nws_sinf
+// evaluates anyway: the sine has nws_sinf's bits there, the cosine is the same pair read one quadrant on.  Beyond, the fp64
+// reduction to turns of nws_sin_wide feeds v_sin_f32 and v_cos_f32.
+__device__ __forceinline__ void nws_sincosf_nocall(float x, float& sn, float& cs) {
+  if (__builtin_expect(fabsf(x) > 6.0e6f, 0)) {
+    const double c1 = 0x1.45f306dc9c883p-3, c2 = -0x1.6b01ec5417056p-57;
+    const double xd = (double)x;
+    const double p = xd * c1;
+    const double e = __builtin_fma(xd, c1, -p);
+    const float t = (float)(__builtin_amdgcn_fract(p) + __builtin_fma(xd, c2, e));
+    sn = __builtin_amdgcn_sinf(t);
+    cs = __builtin_amdgcn_cosf(t);
+    return;
+  }
+  const float fq = rintf(x * 0.6366197723675814f);
+  float r = fmaf(fq, -1.5707963705062866f, x);
+  r = fmaf(fq, 4.371138828673793e-08f, r);
+  int q = (int)fq;
+  if (fabsf(x) > 32768.0f) {
+    const float fq2 = rintf(r * 0.6366197723675814f);
+    r = fmaf(fq2, -1.5707963705062866f, r);
+    r = fmaf(fq2, 4.371138828673793e-08f, r);
+    q += (int)fq2;
+  }
+  const float sv = nws_sin_poly(r);
+  const float cv = nws_cos_poly(r);
+  const float a = (q & 1) ? cv : sv;          // sin(r + q pi/2)
+  const float b = (q & 1) ? sv : cv;          // cos(r + q pi/2) = sin(r + (q + 1) pi/2)
+  sn = (q & 2) ? -a : a;
+  cs = ((q + 1) & 2) ? -b : b;
+}
+
 __device__ __forceinline__ float nws_sin_turns_checked(float x) {
   return __builtin_expect(fabsf(x) > 6.0e6f, 0) ? nws_sin_wide(x) : nws_sin_turns(x);
 }

@@ -667,6 +667,54 @@ Tensor newt_apply(const Tensor& wdesc, const Tensor& exciter, const Tensor& film
   return out;
 }
 
+// The backward of newt_apply with the exact shapers for grad_out = dL/d(out) (B, 1, N): [grad_film (B, 256, T)],
+// then grad_exciter (B, 64, N) when wanted, then with want_params the eleven parameter gradients in the shapes of their
+// parameters: input_scale, net.0.weight, net.0.bias, net.2.*, net.4.*, net.6.*, mixer.0.weight, mixer.0.bias.  Nothing was saved
+// by the forward; the workspace comes from torch's allocator.
+std::vector<Tensor> newt_grad(const Tensor& wdesc, const Tensor& exciter, const Tensor& film, const Tensor& grad_out, bool want_exciter,
+                              bool want_params) {
+  const NwsWeights* w = weights_of(wdesc);
+  check_dev(exciter, "exciter");
+  check_dev(film, "film_params");
+  check_dev(grad_out, "grad_out");
+  check_same_device(exciter, "exciter", film, "control embedding");
+  check_same_device(exciter, "exciter", grad_out, "grad_out");
+  TORCH_CHECK(exciter.dim() == 3 && exciter.size(1) == NWS_N_SHAPERS, "NEWT: expected an exciter of shape (B, 64, N), got ", exciter.sizes());
+  TORCH_CHECK(film.dim() == 3 && film.size(1) == NWS_FILM_CH && film.size(0) == exciter.size(0),
+              "NEWT: expected FiLM parameters of shape (B, 256, T), got ", film.sizes());
+  const int64_t B = exciter.size(0), T = film.size(2), N = T * NWS_HOP;
+  TORCH_CHECK(B >= 1 && T >= 1, "newt_grad: need at least one utterance and one frame");
+  TORCH_CHECK(exciter.size(2) == N, "NEWT: exciter has ", exciter.size(2), " samples, the control embedding ", T, " frames (x128 = ",
+              N, ")");
+  TORCH_CHECK(grad_out.numel() == B * N && grad_out.size(0) == B, "newt_grad: grad_out ", grad_out.sizes(), " is not (", B, ", 1, ", N, ")");
+  TORCH_CHECK(w->lut == nullptr, "newt_grad: the lookup table has no backward");
+  const size_t nbytes = B < (1 << 30) && T < (1 << 30) ? nws_newt_grad_workspace_bytes((int)B, (int)T, want_params ? 1 : 0) : 0;
+  TORCH_CHECK(nbytes > 0, "newt_grad: unsupported size (B ", B, ", T ", T, "): T <= 65535, B T <= 2^28");
+  Launch L(exciter);
+  auto opt = exciter.options();
+  std::vector<Tensor> out{at::empty({B, NWS_FILM_CH, T}, opt)};
+  float* ge = nullptr;
+  if (want_exciter) {
+    out.push_back(at::empty_like(exciter));
+    ge = out.back().data_ptr<float>();
+  }
+  float* gp[11] = {nullptr};
+  if (want_params) {
+    const int64_t S = NWS_N_SHAPERS, SW = NWS_N_SHAPERS * 8;
+    const std::vector<std::vector<int64_t>> shapes = {{1, S, 1}, {SW, 1, 1}, {SW}, {SW, 8, 1}, {SW}, {SW, 8, 1}, {SW}, {S, 8, 1}, {S},
+                                                      {1, S, 1}, {1}};
+    for (int i = 0; i < 11; ++i) {
+      out.push_back(at::empty(shapes[i], opt));
+      gp[i] = out.back().data_ptr<float>();
+    }
+  }
+  Tensor ws = at::empty({(int64_t)nbytes}, opt.dtype(at::kByte));
+  nws_check(nws_newt_grad(w, exciter.data_ptr<float>(), film.data_ptr<float>(), grad_out.data_ptr<float>(), (int)B, (int)T, ge,
+                          out[0].data_ptr<float>(), gp[0], gp[1], gp[2], gp[3], gp[4], gp[5], gp[6], gp[7], gp[8], gp[9], gp[10],
+                          ws.data_ptr(), nbytes, L.stream), "nws_newt_grad");
+  return out;
+}
+
 // TimeDistributedMLP.forward (dynamic.py:20-40): x (B, in, T); weights[i] (rows_i, cols_i[, 1]), biases[i]; ln_w / ln_b for
 // every layer but the last
 Tensor td_mlp(const Tensor& x, at::TensorList weights, at::TensorList biases, at::TensorList ln_w, at::TensorList ln_b, double eps,
@@ -1465,6 +1513,8 @@ TORCH_LIBRARY(newt_hip, m) {
   m.def("shaper_apply(Tensor wdesc, Tensor x) -> Tensor", &shaper_apply);
   m.def("shaper_table(Tensor wdesc, Tensor like, int size, float tmin, float tmax) -> Tensor", &shaper_table);
   m.def("newt_apply(Tensor wdesc, Tensor exciter, Tensor film) -> Tensor", &newt_apply);
+  m.def("newt_grad(Tensor wdesc, Tensor exciter, Tensor film, Tensor grad_out, bool want_exciter, bool want_params) -> Tensor[]",
+        &newt_grad);
   m.def("td_mlp(Tensor x, Tensor[] weights, Tensor[] biases, Tensor[] ln_w, Tensor[] ln_b, float eps, float slope) -> Tensor", &td_mlp);
   m.def("td_mlp_grad(Tensor x, Tensor grad_y, Tensor[] weights, Tensor[] biases, Tensor[] ln_w, Tensor[] ln_b, float eps, float slope, "
         "bool want_params) -> Tensor[]", &td_mlp_grad);

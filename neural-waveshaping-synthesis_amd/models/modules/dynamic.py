@@ -21,17 +21,69 @@ class FiLM(nn.Module):
         return sa.call("film", x, gamma, beta)
 
 
+class _Conv1x1Function(torch.autograd.Function):
+    """Conv1x1.forward with its backward attached (td_mlp_grad on a one-layer stack): saves x"""
+
+    @staticmethod
+    def forward(ctx, x, module, *params):
+        with torch.no_grad():
+            y = module._forward_detached(x.detach())
+        ctx.module = module
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        (x,) = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = any(need[2:])
+        gx, grads = ctx.module.vjp(grad_y, x, want_params=want)
+        out = [grads[k].view_as(p) if n else None for (k, p), n in zip(ctx.module.named_parameters(), need[2:])] if want else [None, None]
+        return (gx if need[0] else None, None, *out)
+
+
 class Conv1x1(nn.Conv1d):
     """nn.Conv1d(in, out, 1) with the reference's parameters / state-dict keys whose forward is a HIP kernel (g_conv1x1_kernel,
     csrc/generic.hip): harmonic_mixer (models/neural_waveshaping.py:54) and newt.mixer (shaping.py:63-65) called on their own -
-    what the forward runs instead of the fused kernels when somebody has registered forward hooks on sub-modules."""
+    what the forward runs instead of the fused kernels when somebody has registered forward hooks on sub-modules.
+
+    ``differentiable`` (a plain attribute, default False): forward only.  Set to True, a forward under grad mode whose ``x``,
+    weight or bias requires grad returns the same bits with a ``torch.autograd.Function`` attached that saves ``x``; its backward
+    is ``vjp``: the existing ``td_mlp_grad`` op on a one-layer stack (no kernel of its own; the op always computes dL/dx too)."""
+
+    differentiable = False      # also the value of a module unpickled from before the flag existed
 
     def __init__(self, in_channels, out_channels, kernel_size=1, **kw):
         if kernel_size not in (1, (1,)) or kw.get("groups", 1) != 1:
             raise RuntimeError("Conv1x1: kernel_size 1, groups 1")
         super().__init__(in_channels, out_channels, 1, **kw)
 
+    def _forward_detached(self, x):
+        wt = sa._req(self.weight.detach(), "weight")
+        bt = sa._req(self.bias.detach(), "bias") if self.bias is not None else None
+        return sa.call("g_conv1x1", x, wt, bt)
+
+    def vjp(self, grad_y, x, want_params=True):
+        """(dL/dx (B, in, N), {"weight": dW, "bias": db}) of ``forward`` at ``x`` for grad_y = dL/dy (B, out, N), an empty dict
+        without ``want_params``: ``td_mlp_vjp`` on this one layer.  Whatever ``differentiable`` and the grad mode say; autograd
+        is not involved and the results carry no graph."""
+        if self.bias is None:
+            raise RuntimeError("Conv1x1.vjp: the backward (td_mlp_grad) takes a layer with a bias")
+        if x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise RuntimeError(f"Conv1d({self.in_channels}, {self.out_channels}, 1): expected (B, {self.in_channels}, N), got {tuple(x.shape)}")
+        return td_mlp_vjp(x, self, grad_y, want_params)
+
     def forward(self, x):
+        if self.differentiable and torch.is_grad_enabled() and isinstance(x, torch.Tensor):
+            params = [self.weight] + ([self.bias] if self.bias is not None else [])
+            if x.requires_grad or any(p.requires_grad for p in params):
+                if self.bias is None:
+                    raise RuntimeError("Conv1x1.differentiable: the backward (td_mlp_grad) takes a layer with a bias")
+                xc = sa.contiguous(x.detach(), "x")
+                if xc.dim() != 3 or xc.shape[1] != self.in_channels:
+                    raise RuntimeError(f"Conv1d({self.in_channels}, {self.out_channels}, 1): expected (B, {self.in_channels}, N), got {tuple(x.shape)}")
+                return _Conv1x1Function.apply(x if x.is_contiguous() else x.contiguous(), self, *params)
         x = sa.contiguous(x, "x")
         if x.dim() != 3 or x.shape[1] != self.in_channels:
             raise RuntimeError(f"Conv1d({self.in_channels}, {self.out_channels}, 1): expected (B, {self.in_channels}, N), got {tuple(x.shape)}")

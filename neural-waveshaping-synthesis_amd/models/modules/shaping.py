@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from ... import ginlite as gin
 from . import _standalone as sa
-from .dynamic import Conv1x1, FiLM, TimeDistributedMLP, upsample_linear
+from .dynamic import Conv1x1, FiLM, TimeDistributedMLP, td_mlp_vjp, upsample_linear
 
 
 class Sine(nn.Module):
@@ -82,8 +82,45 @@ class TrainableNonlinearity(nn.Module):
         return sa.call("shaper_apply", self._desc.get(sa.shaper_fields(self)), x)
 
 
+_NEWT_GRAD_KEYS = ("shaping_fn.input_scale", "shaping_fn.net.0.weight", "shaping_fn.net.0.bias", "shaping_fn.net.2.weight",
+                   "shaping_fn.net.2.bias", "shaping_fn.net.4.weight", "shaping_fn.net.4.bias", "shaping_fn.net.6.weight",
+                   "shaping_fn.net.6.bias", "mixer.0.weight", "mixer.0.bias")       # the op's eleven, in its order
+
+
+class _NEWTFunction(torch.autograd.Function):
+    """NEWT.forward with its backward attached (csrc/newt_grad.hip): saves the two inputs; backward is
+    ``NEWT.vjp`` and hands gradients to the exciter, the control embedding and every parameter that requires grad"""
+
+    @staticmethod
+    def forward(ctx, exciter, control_embedding, module, *params):
+        with torch.no_grad():
+            y = module._forward_detached(exciter.detach(), control_embedding.detach())
+        ctx.module = module
+        ctx.save_for_backward(exciter, control_embedding)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        exciter, emb = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = any(need[3:])
+        ge, gemb, grads = ctx.module.vjp(grad_out, exciter, emb, want_params=want, want_exciter=need[0])
+        named = list(ctx.module.named_parameters())
+        out = [grads[k].view_as(p) if n else None for (k, p), n in zip(named, need[3:])] if want else [None] * len(named)
+        return (ge, gemb if need[1] else None, None, *out)
+
+
 @gin.configurable
 class NEWT(nn.Module):
+    """``differentiable`` (a plain attribute, default False): forward only, as the stage kernels are.  Set to True (packaged
+    sizes only: 64 shapers of width 8 and depth 4, hop 128, one output channel), a forward under grad mode whose exciter,
+    control embedding or parameters require grad returns the same bits with a ``torch.autograd.Function`` attached that saves
+    the two inputs; its backward hands gradients to both and to each of the 25 parameters that requires grad.  ``vjp`` is the
+    same gradient without autograd."""
+
+    differentiable = False      # also the value of a module unpickled from before the flag existed
+
     def __init__(self, n_waveshapers: int, control_embedding_size: int, shaping_fn_size: int = 16,
                  out_channels: int = 1):
         super().__init__()
@@ -120,9 +157,80 @@ class NEWT(nn.Module):
         mb = sa._req(self.mixer[0].bias.detach(), "newt.mixer.0.bias")
         return sa.call("g_newt_apply", self._g_shaper(), exciter, film, mw, mb)
 
+    def _need_backward(self, hop=None):
+        """the backward kernel serves the packaged sizes, and a forward that carries it never calls the inner modules"""
+        sh = self._modules["shaping_fn"]
+        if not NEWT._specialised(self, sa._lib.HOP if hop is None else hop):
+            raise RuntimeError("NEWT: the backward (csrc/newt_grad.hip) exists for 64 shapers of width 8 and depth 4, hop 128 and one "
+                               f"output channel only; this is {self.n_waveshapers} shapers of width {sh.width} and depth {sh.depth}, "
+                               f"hop {sa._lib.HOP if hop is None else hop}, {self.mixer[0].out_channels} output channel(s), which "
+                               "runs on the runtime-size path and has no backward")
+        if not all(isinstance(m, Sine) for m in list(sh.net)[1::2]):
+            raise RuntimeError("NEWT: the backward implements the sine activations NEWT configures (nonlinearity=Sine)")
+
+    def _checked_pair(self, exciter, control_embedding):
+        exciter = sa.contiguous(exciter, "exciter")
+        emb = sa.contiguous(control_embedding, "control_embedding")
+        if exciter.dim() != 3 or exciter.shape[1] != self.n_waveshapers:
+            raise RuntimeError(f"NEWT: expected an exciter of shape (B, {self.n_waveshapers}, N), got {tuple(exciter.shape)}")
+        if emb.dim() != 3 or emb.shape[0] != exciter.shape[0] or emb.shape[2] < 1 or exciter.shape[2] % emb.shape[2]:
+            raise RuntimeError(f"NEWT: exciter {tuple(exciter.shape)} does not match a control embedding {tuple(emb.shape)}")
+        if emb.device != exciter.device:
+            raise RuntimeError(f"exciter is on {exciter.device} but the control embedding is on {emb.device}")
+        return exciter, emb
+
+    def _wdesc(self):
+        tensors, scalars = NEWT._apply_fields(self)
+        tensors = dict(tensors, newt_out_w=self.mixer[0].weight, newt_out_b=self.mixer[0].bias)
+        return self._newt_desc.get(tensors, scalars)
+
+    def _forward_detached(self, exciter, control_embedding):
+        """the forward of the packaged sizes on checked, detached inputs (callers hold no_grad): the two launches of ``forward``"""
+        film = self.mlp(control_embedding)
+        return sa.call("newt_apply", self._wdesc(), exciter, film)
+
+    def vjp(self, grad_out, exciter, control_embedding, want_params=True, want_exciter=True):
+        """(dL/d(exciter) (B, 64, N) | None, dL/d(control_embedding) (B, 128, T), {state-dict key relative to this module:
+        gradient}) of ``forward`` at (exciter, control_embedding) for grad_out = dL/d(out) (B, 1, N); the 25 keys ``mlp.net.*``,
+        ``shaping_fn.*`` and ``mixer.0.*``, an empty dict without ``want_params``.  Reruns ``self.mlp`` for the FiLM parameters,
+        takes their gradient and the sample-rate part from the ``newt_grad`` op (csrc/newt_grad.hip) and the
+        MLP's part from ``td_mlp_vjp``.  Whatever ``differentiable`` and the grad mode say; autograd is not involved and the
+        results carry no graph."""
+        with torch.no_grad():
+            self._need_backward()
+            exciter, emb = self._checked_pair(exciter.detach(), control_embedding.detach())
+            g = sa.contiguous(grad_out.detach(), "grad_out")
+            self._need_backward(exciter.shape[2] // emb.shape[2])
+            if g.numel() != exciter.shape[0] * exciter.shape[2] or g.shape[0] != exciter.shape[0]:
+                raise RuntimeError(f"NEWT: grad_out {tuple(g.shape)} is not ({exciter.shape[0]}, 1, {exciter.shape[2]})")
+            if g.device != exciter.device:
+                raise RuntimeError(f"exciter is on {exciter.device} but grad_out is on {g.device}")
+            film = self.mlp(emb)
+            out = sa.binding().newt_grad(self._wdesc(), exciter, film, g, bool(want_exciter), bool(want_params))
+            g_emb, mg = td_mlp_vjp(emb, self.mlp.net, out[0], want_params)
+            g_exc = out[1] if want_exciter else None
+            if not want_params:
+                return g_exc, g_emb, {}
+            grads = {"mlp.net." + k: v for k, v in mg.items()}
+            grads.update(zip(_NEWT_GRAD_KEYS, out[-len(_NEWT_GRAD_KEYS):]))
+            return g_exc, g_emb, grads
+
     def forward(self, exciter, control_embedding):
         """(B, 64, N) exciter, (B, 128, T) control embedding -> (B, 1, N) (reference shaping.py:67-79): the FiLM-parameter
         MLP (one launch) then FiLM -> shaper -> FiLM -> Conv1d(64 -> 1) on the materialised exciter (one launch)."""
+        if self.differentiable and torch.is_grad_enabled():
+            params = list(self.parameters())
+            if any(isinstance(t, torch.Tensor) and t.requires_grad for t in (exciter, control_embedding, *params)):
+                self._need_backward()
+                e, c = self._checked_pair(exciter.detach(), control_embedding.detach())
+                self._need_backward(e.shape[2] // c.shape[2])
+                if sa.has_hooks(self.waveshaping_index, self.normalising_coeff, self.mixer, self.mixer[0], self._modules.get("shaping_fn")):
+                    raise RuntimeError("NEWT.differentiable: forward hooks on the inner modules (waveshaping_index, shaping_fn, "
+                                       "normalising_coeff, mixer) make the forward run them one by one, and that sequence has no "
+                                       "backward; remove the hooks or clear the flag")
+                return _NEWTFunction.apply(exciter if exciter.is_contiguous() else exciter.contiguous(),
+                                           control_embedding if control_embedding.is_contiguous() else control_embedding.contiguous(),
+                                           self, *params)
         exciter = sa.contiguous(exciter, "exciter")
         if exciter.dim() != 3 or exciter.shape[1] != self.n_waveshapers:
             raise RuntimeError(f"NEWT: expected an exciter of shape (B, {self.n_waveshapers}, N), got {tuple(exciter.shape)}")
@@ -177,6 +285,21 @@ class FastNEWT(NEWT):
 
     def _specialised(self, hop):
         return self.n_waveshapers == sa._lib.N_SHAPERS and self.mixer[0].out_channels == 1 and hop == sa._lib.HOP
+
+    _NO_BACKWARD = ("FastNEWT: the lookup table has no backward (a table lookup has no gradient with respect to the shapers' "
+                    "parameters); training uses the exact NEWT, as the reference does, and the table is built from it afterwards")
+
+    @property
+    def differentiable(self):
+        return False
+
+    @differentiable.setter
+    def differentiable(self, value):
+        if value:
+            raise RuntimeError(self._NO_BACKWARD)
+
+    def vjp(self, grad_out, exciter, control_embedding, want_params=True, want_exciter=True):
+        raise RuntimeError(self._NO_BACKWARD)
 
     def _g_shaper(self):
         return self._g_lut.get(lut=self.lookup_table, lut_min=self.table_min, lut_max=self.table_max)

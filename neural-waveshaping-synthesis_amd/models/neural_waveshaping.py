@@ -9,9 +9,10 @@ Of the reference's Lightning hooks (:92-165) the two that need no backward pass 
 and ``test_step`` return ``stft_loss(recon, audio)`` - ``losses.MultiResolutionSTFTLoss``, the HIP restatement
 of the ``auraloss`` loss the reference logs as ``val/loss`` / ``test/loss`` - through the
 reference's ``_run_step``.  ``stft_loss`` is made on first use (in the reference ``configure_optimizers`` makes
-it).  ``training_step`` and ``configure_optimizers`` raise: the loss, the reverb and the noise branch's filter have a
+it).  ``training_step`` and ``configure_optimizers`` still raise: the loss, the reverb and the noise branch's filter have a
 backward pass, and so have a frame MLP and the control encoder called on their own (3.16, 3.17:
-``ControlModule.differentiable``, ``.vjp``); the oscillator branch has none (SURVEY.md §2 row 1b).  ``pre_reverb`` renders the reverb's input, which is what fitting ``reverb.ir`` alone needs;
+``ControlModule.differentiable``, ``.vjp``) and the oscillator branch (3.18: ``NEWT.differentiable``, ``.vjp``,
+``Conv1x1.differentiable``); ``scripts/fit_newt.py --params model`` composes them, the two hooks are a follow-up.  ``pre_reverb`` renders the reverb's input, which is what fitting ``reverb.ir`` alone needs;
 ``pre_reverb_parts`` renders it in two parts with the noise filter's input, which is what fitting the noise colour
 needs.  Logging (``self.log``, wandb) is left to the caller.
 
@@ -341,22 +342,24 @@ class NeuralWaveshaping(nn.Module):
             return self._run_step(batch)[0]
 
     def training_step(self, batch, batch_idx):
-        raise NotImplementedError("training_step: there is no backward pass in this package for the whole model - the loss "
-                                  "(losses.MultiResolutionSTFTLoss(differentiable=True)), the reverb (Reverb.differentiable, "
-                                  "Reverb.vjp) and the noise branch's filter (FIRNoiseSynth.differentiable, FIRNoiseSynth.vjp: "
-                                  "dL/dH), a frame MLP called on its own (TimeDistributedMLP.differentiable, .vjp, td_mlp_vjp) and "
-                                  "the control encoder (ControlModule.differentiable, .vjp: the recurrence and proj) have one, "
-                                  "the oscillator branch does not; validation_step and test_step "
-                                  "give the reference's loss, scripts/fit_reverb.py fits reverb.ir and scripts/fit_noise.py the "
-                                  "noise colour (h_generator's last bias) or, with --h-generator all, the whole h_generator")
+        raise NotImplementedError("training_step: there is no backward pass in this package behind this hook yet - every link has "
+                                  "one when called on its own: the loss (losses.MultiResolutionSTFTLoss(differentiable=True)), the "
+                                  "reverb (Reverb.differentiable, Reverb.vjp), the noise branch's filter "
+                                  "(FIRNoiseSynth.differentiable, FIRNoiseSynth.vjp: dL/dH), a frame MLP "
+                                  "(TimeDistributedMLP.differentiable, .vjp, td_mlp_vjp), the control encoder "
+                                  "(ControlModule.differentiable, .vjp: the recurrence and proj) and the oscillator branch "
+                                  "(NEWT.differentiable, NEWT.vjp, Conv1x1.differentiable for harmonic_mixer; DESIGN.md 3.18).  "
+                                  "scripts/fit_newt.py --params model composes them into a step over every parameter; "
+                                  "validation_step and test_step give the reference's loss, scripts/fit_reverb.py fits reverb.ir "
+                                  "and scripts/fit_noise.py the noise colour")
 
     def configure_optimizers(self):
-        raise NotImplementedError("configure_optimizers: there is no backward pass in this package for the whole model (the loss, "
-                                  "the reverb, the noise branch's filter, a frame MLP and the control encoder called on their own have one; the "
-                                  "oscillator branch has none, so no gradient of the whole loss reaches the recurrence yet), so the "
-                                  "parameters to optimise are reverb.ir (scripts/fit_reverb.py) and h_generator's last bias or, "
-                                  "with --h-generator all, every h_generator tensor (scripts/fit_noise.py); model.stft_loss is made "
-                                  "on first use instead")
+        raise NotImplementedError("configure_optimizers: there is no backward pass in this package behind the Lightning hooks yet "
+                                  "(the loss, the reverb, the noise branch's filter, a frame MLP, the control encoder and the "
+                                  "oscillator branch - NEWT.differentiable, NEWT.vjp - each have one when called on their own); "
+                                  "scripts/fit_newt.py --params model builds the reference's Adam + StepLR from the model's hparams "
+                                  "and steps every parameter, scripts/fit_reverb.py and scripts/fit_noise.py fit reverb.ir and the "
+                                  "noise colour; model.stft_loss is made on first use instead")
 
     def _sub_module_hooks(self) -> bool:
         """Forward hooks on sub-modules (the reference's users tap stages that way, and so does tests/golden/make_golden.py on
