@@ -35,10 +35,12 @@
 //    of u_t, v_t and u_t (x) x_t as one row of column sums.
 //  * control_gru_grad_whh_kernel (with parameters): dW_hh[i][k] = sum v_t[i] h_{t-1}[k], a contraction over the B T frames on the
 //    matrix pipe; one workgroup = one 32-row strip x one of P ranges of the (utterance, 32-frame chunk) list, P from (B, T) only.
-//  * control_gru_grad_reduce_kernel: out[e] = sum_p part[p][e] in float64 in a fixed order, rounded once (td_mlp_grad.hip's).
+//    The range split, the products of the tile and its write-out are grad_sums.h's (nws_unit_range, dw_tile_step,
+//    dw_tile_store); the two fetches and the staging are this kernel's.
+//  * nws_segment_sum_kernel (grad_sums.h): out[e] = sum_p part[p][e] in float64 in a fixed order, rounded once.
 // Every output element is written by one thread, every sum runs in an order that depends on the sizes only, no atomics: equal
 // inputs give equal bits.  G = 0 without dL/d(h_T) gives zeros: every output is a sum of products with a factor that is zero.
-#include "nws_common.h"
+#include "grad_sums.h"
 
 namespace {
 
@@ -49,8 +51,6 @@ constexpr int kSlice = 48;          // contraction rows per lane slice of the BP
 constexpr int kSlicePad = 52;       // ... and their distance in LDS (floats)
 constexpr int kNcol = 4 * kG;       // one row of column sums: db_ih (384) | db_hh (384) | dW_ih (768)
 constexpr float kSig = -1.4426950408889634f, kTanh = 2.8853900817779268f;
-
-__device__ __forceinline__ int gg_frag_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // workgroup barrier that orders LDS traffic only (control_gru.hip): the dh_t stores are never drained on the critical path
 __device__ __forceinline__ void gg_lds_barrier() {
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void control_gru_coef_kernel(GruW w, const flo
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int r = 4 * j + e;
-      const int unit = 32 * wave + gg_frag_row(r, half);
+      const int unit = 32 * wave + nws_frag_row(r, half);
       const float* wi = w.w_ih + (size_t)unit * 2;
       const float ar = fmaf(wi[1], x1, fmaf(wi[0], x0, w.b_ih[unit])) + (acc[0][r] + w.b_hh[unit]);
       const float az = fmaf(wi[2 * kH + 1], x1, fmaf(wi[2 * kH], x0, w.b_ih[kH + unit])) + (acc[1][r] + w.b_hh[kH + unit]);
@@ -353,8 +353,7 @@ __global__ __launch_bounds__(256) void control_gru_grad_whh_kernel(const float* 
                                                                    float* __restrict__ part) {
   __shared__ float sA[32 * 33];
   __shared__ float sB[kH * 33];
-  const int mt = blockIdx.x, p = blockIdx.y, P = gridDim.y;
-  const int u0 = (int)((long long)p * U / P), u1 = (int)((long long)(p + 1) * U / P);
+  const int mt = blockIdx.x, p = blockIdx.y;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, col = lane & 31;
   const int gate = mt >> 2, ub = 32 * (mt & 3);
@@ -388,54 +387,21 @@ __global__ __launch_bounds__(256) void control_gru_grad_whh_kernel(const float* 
       rb[q] = v;
     }
   };
-  if (u0 < u1) fetch(u0);
-  for (int u = u0; u < u1; ++u) {
+  const UnitRange ur = nws_unit_range(p, gridDim.y, U);
+  if (ur.u0 < ur.u1) fetch(ur.u0);
+  for (int u = ur.u0; u < ur.u1; ++u) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) sA[(tid & 31) * 33 + (tid >> 5) + 8 * q] = ra[q];
 #pragma unroll
     for (int q = 0; q < 16; ++q) sB[(tid & (kH - 1)) * 33 + (tid >> 7) + 2 * q] = rb[q];
     __syncthreads();
-    if (u + 1 < u1) fetch(u + 1);                                   // in flight under this unit's products
-    float av[16], bv[16];
-#pragma unroll
-    for (int s2 = 0; s2 < 16; ++s2) {
-      av[s2] = sA[col * 33 + 16 * half + s2];
-      bv[s2] = sB[(32 * wave + col) * 33 + 16 * half + s2];
-    }
-#pragma unroll
-    for (int s2 = 0; s2 < 16; ++s2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s2], bv[s2], acc, 0, 0, 0);
+    if (u + 1 < ur.u1) fetch(u + 1);                                // in flight under this unit's products
+    float av[16];
+    dw_read16(sA, col, half, av);
+    dw_tile_step(av, sB, 32 * wave + col, half, acc);               // wave w owns the 32-column tile w
     __syncthreads();
   }
-  float* out = part + (size_t)p * kG * kH;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) out[(size_t)(32 * mt + gg_frag_row(r, half)) * kH + 32 * wave + col] = acc[r];
-}
-
-struct GSeg {
-  float* dst;
-  long long off;      // first element of the segment inside a partial row
-  int n;
-};
-struct GSegs {
-  GSeg s[3];
-};
-
-// dst[e] = sum_p part[p * stride + off + e] in float64: thread (e, j) adds p = j, j + 8, ... in turn, then j = 0 .. 7 in order
-__global__ __launch_bounds__(256) void control_gru_grad_reduce_kernel(const float* __restrict__ part, int P, long long stride, GSegs ra) {
-  __shared__ double sums[8][32];
-  const GSeg sg = ra.s[blockIdx.y];
-  if ((int)blockIdx.x * 32 >= sg.n) return;
-  const int e = blockIdx.x * 32 + (threadIdx.x & 31), j = threadIdx.x >> 5;
-  double s = 0.0;
-  if (e < sg.n)
-    for (int p = j; p < P; p += 8) s += (double)part[(size_t)p * stride + sg.off + e];
-  sums[j][threadIdx.x & 31] = s;
-  __syncthreads();
-  if (j == 0 && e < sg.n) {
-    double tot = 0.0;
-    for (int q = 0; q < 8; ++q) tot += sums[q][threadIdx.x & 31];
-    sg.dst[e] = (float)tot;
-  }
+  dw_tile_store(acc, part + (size_t)p * kG * kH, kG, kH, 32 * mt, 32 * wave + col, half);
 }
 
 struct GPlan {
@@ -450,13 +416,12 @@ GPlan make_plan(int B, int T, bool want) {
   if (!pl.ok) return pl;
   pl.ntile = (T + kFT - 1) / kFT;
   const long long U = (long long)B * pl.ntile;
-  if (U > (1ll << 30)) {
+  if (U > kMaxUnits) {
     pl.ok = false;
     return pl;
   }
   pl.U = (int)U;
-  // the number of dW_hh partials: a function of (B, T) only - about eight (utterance, chunk) units each, at most 32
-  pl.P = (int)((U + 7) / 8 < 32 ? (U + 7) / 8 : 32);
+  pl.P = nws_partial_count(U);
   pl.plane = (size_t)B * T * kH;
   pl.off_dh = 5 * pl.plane;
   pl.off_col = 6 * pl.plane;
@@ -502,14 +467,11 @@ extern "C" int nws_control_gru_grad(const NwsWeights* w, const float* control, i
   control_gru_grad_whh_kernel<<<dim3(kG / 32, pl.P), 256, 0, st>>>(h0, gru_out, ws, pl.plane, ws + pl.off_dh, T, pl.ntile, pl.U,
                                                                    ws + pl.off_w);
   NWS_CHECK_LAUNCH();
-  GSegs rw{}, rc{};
-  rw.s[0] = GSeg{grad_w_hh, 0, kG * kH};
-  control_gru_grad_reduce_kernel<<<dim3(kG * kH / 32, 1), 256, 0, st>>>(ws + pl.off_w, pl.P, (long long)kG * kH, rw);
+  const SumSeg rw[1] = {{grad_w_hh, 0, kG * kH}};
+  nws_segment_sums(ws + pl.off_w, pl.P, (long long)kG * kH, rw, 1, st);
   NWS_CHECK_LAUNCH();
-  rc.s[0] = GSeg{grad_b_ih, 0, kG};
-  rc.s[1] = GSeg{grad_b_hh, kG, kG};
-  rc.s[2] = GSeg{grad_w_ih, 2 * kG, 2 * kG};
-  control_gru_grad_reduce_kernel<<<dim3(2 * kG / 32, 3), 256, 0, st>>>(ws + pl.off_col, pl.U, (long long)kNcol, rc);
+  const SumSeg rc[3] = {{grad_b_ih, 0, kG}, {grad_b_hh, kG, kG}, {grad_w_ih, 2 * kG, 2 * kG}};
+  nws_segment_sums(ws + pl.off_col, pl.U, (long long)kNcol, rc, 3, st);
   NWS_CHECK_LAUNCH();
   return NWS_OK;
 }

@@ -38,9 +38,6 @@ struct MlpLds {
   float red[2][4][kFT];
 };
 
-// D-fragment row of accumulator register r for lane half h
-__device__ __forceinline__ int frag_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
 // acc(32 x 32 frames) = W[row0 .. row0+32)[0 .. 2*KH) * X,   K permuted as k(s,h) = KH*h + s.
 // W is row-major with row stride `ldw`; rows >= n_rows contribute zeros.
 template <int KH>
@@ -88,7 +85,7 @@ __device__ __forceinline__ void hidden_layer(MlpLds& L, const float* W, const fl
   float s = 0.0f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    v[r] = acc[r] + bias[32 * wave + frag_row(r, half)];
+    v[r] = acc[r] + bias[32 * wave + nws_frag_row(r, half)];
     s += v[r];
   }
   s += nws_swap_halves(s);
@@ -108,7 +105,7 @@ __device__ __forceinline__ void hidden_layer(MlpLds& L, const float* W, const fl
   const float rstd = 1.0f / sqrtf(var + kLnEps);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int c = 32 * wave + frag_row(r, half);
+    const int c = 32 * wave + nws_frag_row(r, half);
     const float y = (v[r] - mean) * rstd * ln_g[c] + ln_b[c];
     Xout[c * kXS + col] = nws_leaky_relu(y);
   }
@@ -164,7 +161,7 @@ __global__ __launch_bounds__(256) void frame_mlps_kernel(NwsWeights w, const flo
     gemm_tile<64>(w.proj_w, NWS_HIDDEN, 32 * wave, NWS_HIDDEN, L.p0, lane, acc);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int c = 32 * wave + frag_row(r, half);
+      const int c = 32 * wave + nws_frag_row(r, half);
       const float v = acc[r] + w.proj_b[c];
       L.emb[c * kXS + col] = v;
       if (emb_out != nullptr && col < frames_valid) emb_out[((size_t)b * NWS_HIDDEN + c) * T + t0 + col] = v;
@@ -183,7 +180,7 @@ __global__ __launch_bounds__(256) void frame_mlps_kernel(NwsWeights w, const flo
     gemm_tile<64>(w.newt_mlp_w[3], NWS_HIDDEN, c0, NWS_FILM_CH, L.p0, lane, acc);
     float v[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] = acc[r] + w.newt_mlp_b[3][c0 + frag_row(r, half)];
+    for (int r = 0; r < 16; ++r) v[r] = acc[r] + w.newt_mlp_b[3][c0 + nws_frag_row(r, half)];
     store_tile_frame_major(L.stage[wave], v, lane, film_out + ((size_t)b * T + t0) * NWS_FILM_CH + c0, NWS_FILM_CH,
                            frames_valid);
   }
@@ -203,7 +200,7 @@ __global__ __launch_bounds__(256) void frame_mlps_kernel(NwsWeights w, const flo
     gemm_tile<64>(w.hgen_w[3], NWS_HIDDEN, c0, NWS_N_BANDS, L.p0, lane, acc);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int c = c0 + frag_row(r, half);
+      const int c = c0 + nws_frag_row(r, half);
       if (c < NWS_N_BANDS) {
         const float v = acc[r] + w.hgen_b[3][c];
         L.p1[c * kXS + col] = v;
@@ -328,11 +325,11 @@ __device__ __forceinline__ void store_tile_xt(char* xt, int c0, const float v[16
     split4_store(xt, xt + XB, col, c0 + 8 * g + 4 * half, v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
 }
 
-// the 16 per-lane entries (channels 32 wave + frag_row(r, half)) of a per-channel parameter vector
+// the 16 per-lane entries (channels 32 wave + nws_frag_row(r, half)) of a per-channel parameter vector
 __device__ __forceinline__ void load_lane_params(float (&p)[16], const float* __restrict__ vec, int wave, int lane) {
   const int half = lane >> 5;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) p[r] = vec[32 * wave + frag_row(r, half)];
+  for (int r = 0; r < 16; ++r) p[r] = vec[32 * wave + nws_frag_row(r, half)];
 }
 
 // per-wave LayerNorm partials over its 32 channels of frame `col`: mean_w and M2_w = sum (v - mean_w)^2, both exact to
@@ -500,7 +497,7 @@ __global__ __launch_bounds__(512, 4) void frame_mlps16_kernel(NwsWeights w, cons
     store_tile_xt(E, 32 * mt, v, lane);
     if (TAPS && emb_out != nullptr && col < frames_valid) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) emb_out[((size_t)b * NWS_HIDDEN + 32 * mt + frag_row(r, half)) * T + t0 + col] = v[r];
+      for (int r = 0; r < 16; ++r) emb_out[((size_t)b * NWS_HIDDEN + 32 * mt + nws_frag_row(r, half)) * T + t0 + col] = v[r];
     }
   }
   __syncthreads();
@@ -542,7 +539,7 @@ __global__ __launch_bounds__(512, 4) void frame_mlps16_kernel(NwsWeights w, cons
     store_tile_xt(Z, 32 * mt, vh, lane);
     if (TAPS && H_out != nullptr && col < frames_valid) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) H_out[((size_t)b * T + t0 + col) * NWS_N_BANDS + 32 * mt + frag_row(r, half)] = vh[r];
+      for (int r = 0; r < 16; ++r) H_out[((size_t)b * T + t0 + col) * NWS_N_BANDS + 32 * mt + nws_frag_row(r, half)] = vh[r];
     }
     if (mt == 0) {
       // (its own fragment registers, live inside this block only: a conditional reload of A would keep the old contents alive)
@@ -552,7 +549,7 @@ __global__ __launch_bounds__(512, 4) void frame_mlps16_kernel(NwsWeights w, cons
       mma_tile1<8>(A4, Y, lane, acc);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int c = 128 + frag_row(r, half);
+        const int c = 128 + nws_frag_row(r, half);
         vh[r] = c < NWS_N_BANDS ? acc[r] + b128 : 0.0f;   // only row 128 is real
         if (TAPS && H_out != nullptr && c < NWS_N_BANDS && col < frames_valid) H_out[((size_t)b * T + t0 + col) * NWS_N_BANDS + c] = vh[r];
       }
@@ -643,7 +640,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps64_kernel(NwsWeights w, cons
     store_tile_xt<XB>(E + path * kTileB, 32 * mt, v, lane);
     if (TAPS && emb_out != nullptr && 32 * path + col < frames_valid) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) emb_out[((size_t)b * NWS_HIDDEN + 32 * mt + frag_row(r, half)) * T + t0 + 32 * path + col] = v[r];
+      for (int r = 0; r < 16; ++r) emb_out[((size_t)b * NWS_HIDDEN + 32 * mt + nws_frag_row(r, half)) * T + t0 + 32 * path + col] = v[r];
     }
   }
   __syncthreads();
@@ -738,7 +735,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps64_kernel(NwsWeights w, cons
       store_tile_xt<XB>(Z + nt * kTileB, 32 * mt, vh, lane);
       if (TAPS && H_out != nullptr && 32 * nt + col < frames_valid) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) H_out[((size_t)b * T + t0 + 32 * nt + col) * NWS_N_BANDS + 32 * mt + frag_row(r, half)] = vh[r];
+        for (int r = 0; r < 16; ++r) H_out[((size_t)b * T + t0 + 32 * nt + col) * NWS_N_BANDS + 32 * mt + nws_frag_row(r, half)] = vh[r];
       }
     }
     if (mt == 0) {
@@ -751,7 +748,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps64_kernel(NwsWeights w, cons
       for (int nt = 0; nt < 2; ++nt) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int c = 128 + frag_row(r, half);
+          const int c = 128 + nws_frag_row(r, half);
           vh[r] = c < NWS_N_BANDS ? (nt ? acc1[r] : acc0[r]) + b128 : 0.0f;   // only row 128 is real
           if (TAPS && H_out != nullptr && c < NWS_N_BANDS && 32 * nt + col < frames_valid)
             H_out[((size_t)b * T + t0 + 32 * nt + col) * NWS_N_BANDS + c] = vh[r];
@@ -994,7 +991,7 @@ __device__ __forceinline__ void wr_layer_norm(f32x16 (&v)[4], const float* g, co
     }
 }
 
-// a transposed accumulator tile (lane = channel, register r = frame f0 + frag_row(r, half)) -> frame-major rows of LD floats: two
+// a transposed accumulator tile (lane = channel, register r = frame f0 + nws_frag_row(r, half)) -> frame-major rows of LD floats: two
 // full 128 B segments per store instruction.  Buffer stores: ONE per-lane byte offset for every tile of the wave (the tile's
 // channel offset and the row r & 3 ride in the instruction's immediate, the row group r >> 2 in a scalar offset) and the
 // descriptor's size drops the rows of frames >= F - no address arithmetic and no guards on the vector pipe.
@@ -1114,7 +1111,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) emb_out[((size_t)b * NWS_HIDDEN + 32 * mt + frag_row(r, half)) * T + t] = v[mt][r];
+        for (int r = 0; r < 16; ++r) emb_out[((size_t)b * NWS_HIDDEN + 32 * mt + nws_frag_row(r, half)) * T + t] = v[mt][r];
     }
     wr_pack(v, X);
     sync(1);
@@ -1188,7 +1185,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) H_out[(size_t)frame * NWS_N_BANDS + 32 * mt + frag_row(r, half)] = v[mt][r];
+        for (int r = 0; r < 16; ++r) H_out[(size_t)frame * NWS_N_BANDS + 32 * mt + nws_frag_row(r, half)] = v[mt][r];
       if (half == 0) H_out[(size_t)frame * NWS_N_BANDS + 128] = h128;
     }
     wr_pack(v, X);

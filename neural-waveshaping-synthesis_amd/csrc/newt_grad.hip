@@ -19,10 +19,10 @@
 //    and shaper 0 writes) are per-lane accumulators over the wave's units, reduced across the wave once, across the 4 waves
 //    through LDS in wave order, and written as partial row p.
 //  * newt_grad_fold_kernel: dfilm[b][c][t] = the at most six block sums that name frame t, added in float64 in block order.
-//  * newt_grad_reduce_kernel: out[e] = sum_p part[p][e] in float64 in a fixed order, rounded once (td_mlp_grad.hip's form).
+//  * nws_segment_sum_kernel (grad_sums.h): out[e] = sum_p part[p][e] in float64 in a fixed order, rounded once.
 // Every output element is written by one thread and every sum runs in an order that depends on (B, T) only: equal inputs give
 // equal bits.  g = 0 gives zeros: every output is a sum of products with the factor dv = m_s g (or g itself).
-#include "nws_common.h"
+#include "grad_sums.h"
 
 namespace {
 
@@ -281,32 +281,6 @@ __global__ __launch_bounds__(256) void newt_grad_fold_kernel(const float* __rest
   grad_film[idx] = (float)acc;
 }
 
-struct PSeg {
-  float* dst;
-  int off, n;
-};
-struct PArgs {
-  PSeg s[11];
-};
-
-// dst[e] = sum_p part[p * kParStride + off + e] in float64: thread (e, j) adds p = j, j + 8, ... in turn, then j = 0 .. 7 in order
-__global__ __launch_bounds__(256) void newt_grad_reduce_kernel(const float* __restrict__ part, int P, PArgs pa) {
-  __shared__ double sums[8][32];
-  const PSeg sg = pa.s[blockIdx.y];
-  if ((int)blockIdx.x * 32 >= sg.n) return;
-  const int e = blockIdx.x * 32 + (threadIdx.x & 31), j = threadIdx.x >> 5;
-  double sum = 0.0;
-  if (e < sg.n)
-    for (int p = j; p < P; p += 8) sum += (double)part[(size_t)p * kParStride + sg.off + e];
-  sums[j][threadIdx.x & 31] = sum;
-  __syncthreads();
-  if (j == 0 && e < sg.n) {
-    double tot = 0.0;
-    for (int k = 0; k < 8; ++k) tot += sums[k][threadIdx.x & 31];
-    sg.dst[e] = (float)tot;
-  }
-}
-
 struct Plan {
   int U, chunk, P;
   size_t off_par, bytes;      // part_film at 0; offsets in floats
@@ -364,11 +338,11 @@ extern "C" int nws_newt_grad(const NwsWeights* w, const float* exciter, const fl
   newt_grad_fold_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(ws, T, total, grad_film);
   NWS_CHECK_LAUNCH();
   if (!want) return NWS_OK;
-  PArgs pa{};
+  SumSeg segs[11];
   const int offs[11] = {kOffC, kOffW0, kOffB0, kOffW2, kOffB2, kOffW4, kOffB4, kOffW6, kOffB6, kOffM, kOffMB};
   const int ns[11] = {64, 512, 512, 4096, 512, 4096, 512, 512, 64, 64, 1};
-  for (int i = 0; i < 11; ++i) pa.s[i] = PSeg{gp[i], offs[i], ns[i]};
-  newt_grad_reduce_kernel<<<dim3(4096 / 32, 11), 256, 0, st>>>(ws + pl.off_par, pl.P, pa);
+  for (int i = 0; i < 11; ++i) segs[i] = SumSeg{gp[i], offs[i], ns[i]};
+  nws_segment_sums(ws + pl.off_par, pl.P, kParStride, segs, 11, st);
   NWS_CHECK_LAUNCH();
   return NWS_OK;
 }

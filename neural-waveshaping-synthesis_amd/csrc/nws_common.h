@@ -35,6 +35,10 @@ inline bool nws_first_use_on_device(unsigned long long& mask) {
   return true;
 }
 
+// The D fragment of v_mfma_f32_32x32x2_f32 (and of every other 32x32 product): accumulator register r of lane (col, half),
+// col = lane & 31, half = lane >> 5, holds row nws_frag_row(r, half), column col of the 32 x 32 tile.
+__device__ __forceinline__ int nws_frag_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
 // ---------------------------------------------------------------------------------------------
 // F.upsample(x, T*128, mode="linear") of the reference (align_corners=False), bit-exact with
 // ATen's CPU kernel as probed in the build container:  out = fmaf(1-l, x[i0], fl(l*x[i1])).

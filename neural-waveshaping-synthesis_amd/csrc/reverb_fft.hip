@@ -30,8 +30,6 @@
 
 namespace {
 
-__device__ __forceinline__ int frag_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
 struct PlanDev {
   int L, N1, N2, NP, M2;
   int Lc, hist, nblk, P;   // overlap-save: circular length, history per block, blocks per pair, outputs per block (direct: L, 0, 1, L)
@@ -326,7 +324,7 @@ __global__ __launch_bounds__(256) void col_fwd_kernel(const float* __restrict__ 
   }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int row = 32 * mt + frag_row(r, half);
+    const int row = 32 * mt + nws_frag_row(r, half);
     const int is_im = row >= d.NP;
     const int k1 = is_im ? row - d.NP : row;
     if (k1 < d.N1) {
@@ -362,7 +360,7 @@ __global__ __launch_bounds__(256) void col_inv_kernel(const float* __restrict__ 
   }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int row = 32 * mt + frag_row(r, half);
+    const int row = 32 * mt + nws_frag_row(r, half);
     const int is_im = row >= d.NP;
     const int n1 = is_im ? row - d.NP : row;
     const int utt = 2 * p + is_im;

@@ -22,7 +22,6 @@ struct MlpArgs {
 // 32-wide K chunk contracts k0 + 16 h .. k0 + 16 h + 15, the order of a sum being free, so every lane reads 16 consecutive
 // weights of its row) - round 4: the per-thread FMA loop it replaces read every weight through the vector cache once per
 // frame group (0.46 ms per call at 64 x 500 frames of the default sizes; runtime sizes, guards instead of padding).
-__device__ __forceinline__ int td_frag_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 __global__ __launch_bounds__(256) void td_mlp_kernel(MlpArgs a, const float* __restrict__ x, int in_size, int hidden,
                                                      int out_size, int depth, int T, float eps, float slope,
@@ -92,13 +91,13 @@ __global__ __launch_bounds__(256) void td_mlp_kernel(MlpArgs a, const float* __r
         // accumulator register r of lane (col, half) = channel 32 mt + row(r, half), frame t0 + col: 32 lanes = 128 contiguous bytes
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int c = 32 * mt + td_frag_row(r, half);
+          const int c = 32 * mt + nws_frag_row(r, half);
           if (c < cout && live) y[((size_t)b * out_size + c) * T + t] = acc[r] + bias[c];
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int c = 32 * mt + td_frag_row(r, half);
+          const int c = 32 * mt + nws_frag_row(r, half);
           if (c < cout) nxt[c * 33 + col] = acc[r] + bias[c];
         }
       }

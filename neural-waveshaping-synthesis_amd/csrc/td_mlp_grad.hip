@@ -17,12 +17,13 @@
 //    per workgroup, the column sums over its 32 frames of dz_i, dv_i and dv_i n_i (and of g) into the workspace.
 //  * td_mlp_grad_weights_kernel: dW_i[o][k] = sum over frames of dz_i[o] a_{i-1}[k], a contraction over the B T frames on the
 //    matrix pipe.  One workgroup = one 32-row strip of one layer's dW x one of P ranges of the (utterance, 32-frame chunk) list;
-//    P depends on (B, T) only.  The partial strips go to the workspace.
-//  * td_mlp_grad_reduce_kernel: out[e] = sum_p part[p][e] in float64 in a fixed order (eight interleaved sequential sums, then
-//    those eight in order), rounded once.  One launch for the dW partials, one for the column sums.
+//    P depends on (B, T) only.  The partial strips go to the workspace.  The range split, the products of a tile and its
+//    write-out are grad_sums.h's (nws_unit_range, dw_tile_step, dw_tile_store); the two fetches and the staging are this kernel's.
+//  * nws_segment_sum_kernel (grad_sums.h): out[e] = sum_p part[p][e] in float64 in a fixed order, rounded once.  One launch for
+//    the dW partials, one for the column sums.
 // Every output element is written by one thread, every sum runs in an order that depends on the sizes only: equal inputs give
 // equal bits.  g = 0 gives zeros: every output is a sum of products with a factor that is exactly zero.
-#include "nws_common.h"
+#include "grad_sums.h"
 
 namespace {
 
@@ -37,9 +38,6 @@ struct GradArgs {
   const float* ln_g[kMaxDepth];
   const float* ln_b[kMaxDepth];
 };
-
-// accumulator register r of lane (col, half) of a 32x32x2 product holds row td_frag_row(r, half), column col (as in stages.hip)
-__device__ __forceinline__ int td_frag_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // LDS: act [maxw][33] | n_0 .. n_{depth-2} [hidden][33] each | red [2][8][32] | rstd [depth-1][32]
 __global__ __launch_bounds__(256) void td_mlp_grad_data_kernel(GradArgs a, const float* __restrict__ x,
@@ -112,7 +110,7 @@ __global__ __launch_bounds__(256) void td_mlp_grad_data_kernel(GradArgs a, const
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int c = 32 * mt + td_frag_row(r, half);
+        const int c = 32 * mt + nws_frag_row(r, half);
         if (c < cout) np[c * 33 + col] = acc[r] + bias[c];
       }
     }
@@ -200,13 +198,13 @@ __global__ __launch_bounds__(256) void td_mlp_grad_data_kernel(GradArgs a, const
       if (layer == 0) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int c = 32 * mt + td_frag_row(r, half);
+          const int c = 32 * mt + nws_frag_row(r, half);
           if (c < cin && live) grad_x[((size_t)b * in_size + c) * T + t] = acc[r];
         }
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int c = 32 * mt + td_frag_row(r, half);
+          const int c = 32 * mt + nws_frag_row(r, half);
           if (c < cin) {
             const float v = np[c * 33 + col] * gam[c] + bet[c];     // the forward's v, rounding for rounding
             outp[c * 33 + col] = acc[r] * (v > 0.0f ? 1.0f : slope);
@@ -286,8 +284,7 @@ __global__ __launch_bounds__(256) void td_mlp_grad_weights_kernel(WArgs wa, int 
   const float* __restrict__ ap = wa.L[li].a;
   const int cout = wa.L[li].cout, cin = wa.L[li].cin;
   const int mt = blockIdx.x - wa.L[li].strip0;
-  const int p = blockIdx.y, P = gridDim.y;
-  const int u0 = (int)((long long)p * U / P), u1 = (int)((long long)(p + 1) * U / P);
+  const int p = blockIdx.y;
   float* sA = lds;
   float* sB = lds + 32 * 33;
   const int f = threadIdx.x & 31, cg = threadIdx.x >> 5;
@@ -320,75 +317,30 @@ __global__ __launch_bounds__(256) void td_mlp_grad_weights_kernel(WArgs wa, int 
       }
     }
   };
-  if (u0 < u1) fetch(u0);
-  for (int u = u0; u < u1; ++u) {
+  // wave w owns the 32-column tiles w and w + 4; columns beyond cin are computed and not stored
+  const int c0 = 32 * wave + col, c1 = 32 * (wave + 4) + col;
+  const UnitRange ur = nws_unit_range(p, gridDim.y, U);
+  if (ur.u0 < ur.u1) fetch(ur.u0);
+  for (int u = ur.u0; u < ur.u1; ++u) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) sA[(cg + 8 * q) * 33 + f] = ra[q];
 #pragma unroll
     for (int q = 0; q < kMaxWidth / 8; ++q)
       if (cg + 8 * q < cin) sB[(cg + 8 * q) * 33 + f] = rb[q];
     __syncthreads();
-    if (u + 1 < u1) fetch(u + 1);                                   // in flight under this unit's products
-    float av[16], bv[16];
-#pragma unroll
-    for (int s2 = 0; s2 < 16; ++s2) av[s2] = sA[col * 33 + 16 * half + s2];
-    {
-      const int k = 32 * wave + col < cin ? 32 * wave + col : cin - 1;      // columns beyond cin are computed and not stored
-      if (32 * wave < cin) {
-#pragma unroll
-        for (int s2 = 0; s2 < 16; ++s2) bv[s2] = sB[k * 33 + 16 * half + s2];
-#pragma unroll
-        for (int s2 = 0; s2 < 16; ++s2) acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s2], bv[s2], acc0, 0, 0, 0);
-      }
-    }
-    {
-      const int k = 32 * (wave + 4) + col < cin ? 32 * (wave + 4) + col : cin - 1;
-      if (32 * (wave + 4) < cin) {
-#pragma unroll
-        for (int s2 = 0; s2 < 16; ++s2) bv[s2] = sB[k * 33 + 16 * half + s2];
-#pragma unroll
-        for (int s2 = 0; s2 < 16; ++s2) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s2], bv[s2], acc1, 0, 0, 0);
-      }
-    }
+    if (u + 1 < ur.u1) fetch(u + 1);                                // in flight under this unit's products
+    float av[16];
+    dw_read16(sA, col, half, av);
+    if (32 * wave < cin) dw_tile_step(av, sB, c0 < cin ? c0 : cin - 1, half, acc0);
+    if (32 * (wave + 4) < cin) dw_tile_step(av, sB, c1 < cin ? c1 : cin - 1, half, acc1);
     __syncthreads();
   }
   float* out = wa.L[li].part + (size_t)p * wsum;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int o = 32 * mt + td_frag_row(r, half);
-    if (o < cout) {
-      if (32 * wave + col < cin) out[(size_t)o * cin + 32 * wave + col] = acc0[r];
-      if (32 * (wave + 4) + col < cin) out[(size_t)o * cin + 32 * (wave + 4) + col] = acc1[r];
-    }
-  }
+  dw_tile_store(acc0, out, cout, cin, 32 * mt, c0, half);
+  dw_tile_store(acc1, out, cout, cin, 32 * mt, c1, half);
 }
 
-struct RSeg {
-  float* dst;
-  long long off;      // first element of the segment inside a partial row
-  int n;
-};
-struct RArgs {
-  RSeg s[3 * kMaxDepth];
-};
-
-// dst[e] = sum_p part[p * stride + off + e] in float64: thread (e, j) adds p = j, j + 8, ... in turn, then j = 0 .. 7 in order
-__global__ __launch_bounds__(256) void td_mlp_grad_reduce_kernel(const float* __restrict__ part, int P, long long stride, RArgs ra) {
-  __shared__ double sums[8][32];
-  const RSeg sg = ra.s[blockIdx.y];
-  if ((int)blockIdx.x * 32 >= sg.n) return;
-  const int e = blockIdx.x * 32 + (threadIdx.x & 31), j = threadIdx.x >> 5;
-  double s = 0.0;
-  if (e < sg.n)
-    for (int p = j; p < P; p += 8) s += (double)part[(size_t)p * stride + sg.off + e];
-  sums[j][threadIdx.x & 31] = s;
-  __syncthreads();
-  if (j == 0 && e < sg.n) {
-    double tot = 0.0;
-    for (int q = 0; q < 8; ++q) tot += sums[q][threadIdx.x & 31];
-    sg.dst[e] = (float)tot;
-  }
-}
+static_assert(3 * kMaxDepth <= kMaxSumSegs, "the column sums of every layer in one launch");
 
 struct Plan {
   int ntile, U, P, ncol, strips;
@@ -406,10 +358,9 @@ Plan make_plan(int B, int in_size, int hidden, int out_size, int depth, int T) {
   if (pl.lds_data > (size_t)kLdsMax) pl.ok = false;
   pl.ntile = (T + kFT - 1) / kFT;
   const long long U = (long long)B * pl.ntile;
-  if (U > (1ll << 30)) pl.ok = false;
+  if (U > kMaxUnits) pl.ok = false;
   pl.U = (int)U;
-  // the number of dW partials: a function of (B, T) only - about eight (utterance, chunk) units each, at most 32
-  pl.P = (int)((U + 7) / 8 < 32 ? (U + 7) / 8 : 32);
+  pl.P = nws_partial_count(U);
   pl.ncol = 3 * (depth - 1) * hidden + out_size;
   pl.plane = (size_t)B * hidden * T;
   pl.wsum = 0;
@@ -475,9 +426,9 @@ extern "C" int nws_td_mlp_grad(const float* x, const float* grad_y, int B, int i
   if (!want) return NWS_OK;
 
   WArgs wa{};
-  RArgs rw{}, rc{};
+  SumSeg rw[kMaxDepth], rc[3 * kMaxDepth];
   size_t woff = 0;
-  int strip = 0, nc = 0, maxn_w = 0, maxn_c = 0;
+  int strip = 0, nc = 0;
   for (int i = 0; i < depth; ++i) {
     const int cin = i == 0 ? in_size : hidden, cout = i == depth - 1 ? out_size : hidden;
     wa.L[i].dz = i == depth - 1 ? grad_y : ws + pl.off_dz + (size_t)i * pl.plane;
@@ -486,25 +437,22 @@ extern "C" int nws_td_mlp_grad(const float* x, const float* grad_y, int B, int i
     wa.L[i].cout = cout;
     wa.L[i].cin = cin;
     wa.L[i].strip0 = strip;
-    rw.s[i] = RSeg{grad_w[i], (long long)woff, cin * cout};
-    if (cin * cout > maxn_w) maxn_w = cin * cout;
+    rw[i] = SumSeg{grad_w[i], (long long)woff, cin * cout};
     strip += (cout + 31) / 32;
     woff += (size_t)cin * cout;
   }
   td_mlp_grad_weights_kernel<<<dim3(pl.strips, pl.P), 256, pl.lds_w, st>>>(wa, depth, T, pl.ntile, pl.U, (long long)pl.wsum);
   NWS_CHECK_LAUNCH();
-  td_mlp_grad_reduce_kernel<<<dim3((maxn_w + 31) / 32, depth), 256, 0, st>>>(ws + pl.off_w, pl.P, (long long)pl.wsum, rw);
+  nws_segment_sums(ws + pl.off_w, pl.P, (long long)pl.wsum, rw, depth, st);
   NWS_CHECK_LAUNCH();
   // db, dbeta, dgamma: the column sums of all workgroups of the data kernel, one launch
   for (int i = 0; i < depth - 1; ++i) {
-    rc.s[nc++] = RSeg{grad_b[i], (long long)(3 * i) * hidden, hidden};
-    rc.s[nc++] = RSeg{grad_ln_b[i], (long long)(3 * i + 1) * hidden, hidden};
-    rc.s[nc++] = RSeg{grad_ln_g[i], (long long)(3 * i + 2) * hidden, hidden};
-    maxn_c = hidden;
+    rc[nc++] = SumSeg{grad_b[i], (long long)(3 * i) * hidden, hidden};
+    rc[nc++] = SumSeg{grad_ln_b[i], (long long)(3 * i + 1) * hidden, hidden};
+    rc[nc++] = SumSeg{grad_ln_g[i], (long long)(3 * i + 2) * hidden, hidden};
   }
-  rc.s[nc++] = RSeg{grad_b[depth - 1], (long long)3 * (depth - 1) * hidden, out_size};
-  if (out_size > maxn_c) maxn_c = out_size;
-  td_mlp_grad_reduce_kernel<<<dim3((maxn_c + 31) / 32, nc), 256, 0, st>>>(ws + pl.off_col, pl.U, (long long)pl.ncol, rc);
+  rc[nc++] = SumSeg{grad_b[depth - 1], (long long)3 * (depth - 1) * hidden, out_size};
+  nws_segment_sums(ws + pl.off_col, pl.U, (long long)pl.ncol, rc, nc, st);
   NWS_CHECK_LAUNCH();
   return NWS_OK;
 }

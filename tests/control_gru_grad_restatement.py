@@ -25,8 +25,9 @@ import numpy as np
 
 H = 128
 # (B, T): the minimum (h0 is the only history); one carried step; an odd batch, one frame past a 32-frame tile (the only length
-# the backward kernels stage by); the training length; one frame block past the forward's 1024-frame staging
-SHAPES = ((1, 1), (1, 2), (3, 33), (2, 500), (1, 1030))
+# the backward kernels stage by); the training length; one frame block past the forward's 1024-frame staging; 66 (utterance,
+# chunk) units, so nine dW_hh partials: a second trip of the reduction's p += 8 and a count that is no multiple of eight
+SHAPES = ((1, 1), (1, 2), (3, 33), (2, 500), (1, 1030), (3, 700))
 SETS = ("packaged", "default")
 # (parameter set, (B, T), with h0 and grad_hT)
 CASES = tuple((s, bt, st) for s in SETS for bt in SHAPES for st in (True, False))

@@ -31,8 +31,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SETS = ("packaged", "default")
 # (1, 1): the minimum, both lerp edges in one hop; (1, 2): one interior boundary; (3, 3): an odd batch, an interior frame between
-# the clamped edges; (2, 33): several partials; (1, 17): 34 blocks of 64 samples, one frame past the 32 blocks one workgroup covers
-SHAPES = ((1, 1), (1, 2), (3, 3), (2, 33), (1, 17))
+# the clamped edges; (2, 33): several partials; (1, 17): 34 blocks of 64 samples, one frame past the 32 blocks one workgroup covers;
+# (2, 65): 260 blocks, nine partials - a second trip of the reduction's p += 8 and a count that is no multiple of eight
+SHAPES = ((1, 1), (1, 2), (3, 3), (2, 33), (1, 17), (2, 65))
 CASES = tuple((w, bt) for w in SETS for bt in SHAPES)
 IDS = [f"{w}-{b}x{t}" for w, (b, t) in CASES]
 

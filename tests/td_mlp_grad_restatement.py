@@ -26,7 +26,8 @@ MARGIN = 1e-3
 # (in, hidden, out, depth) and the (B, T) each one is run at (tests/test_gpu_td_mlp_grad.py says why)
 PACKAGED = ((128, 128, 129, 4), (128, 128, 256, 4))
 SIZES = PACKAGED + ((5, 7, 3, 3), (40, 72, 33, 3), (6, 6, 9, 1))
-CASES = tuple((s, bt) for s in SIZES for bt in ((1, 1), (3, 33))) + tuple((s, (2, 500)) for s in PACKAGED)
+CASES = (tuple((s, bt) for s in SIZES for bt in ((1, 1), (3, 33))) + tuple((s, (2, 500)) for s in PACKAGED)
+         + (((5, 7, 3, 3), (3, 700)),))
 
 
 def widths(sizes):

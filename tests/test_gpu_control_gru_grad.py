@@ -6,7 +6,8 @@ Parameter sets: 'packaged' = embedding.* of tests/golden/weights_vn.npz under a 
 white noise the packaged recurrence is chaotic and float32 itself is 1e-4 .. 6e-3 from float64); 'default' = torch's default
 initialisation under normal control.  Shapes (B, T): (1, 1) the minimum; (1, 2) one carried step; (3, 33) an odd batch, one frame
 past the 32-frame tile of the parallel kernels; (2, 500) the training length, four dW_hh partials; (1, 1030) one block past the
-forward's 1024-frame staging.  Each once with h0 and grad_hT and once without.
+forward's 1024-frame staging; (3, 700) 66 (utterance, chunk) units, so nine dW_hh partials - the segment sum's second trip of
+p += 8, a count that is no multiple of eight.  Each once with h0 and grad_hT and once without.
 
 Bar, for every returned tensor: the relative L2 from float64 is at most 10 x the distance of torch's float32 CPU autograd from
 the same restatement on the same inputs - the yardstick is computed in the test; the factor and the reasoning are
@@ -25,6 +26,8 @@ kernel distance of the case; "state" = with h0 and grad_hT:
                          none   h0   1.91e-6 | 1.46e-6 | 1.30      W_hh 2.50e-6
               (1, 1030)  state  x    3.90e-6 | 3.60e-6 | 1.08      W_hh 4.20e-6
                          none   W_ih 1.05e-5 | 4.66e-6 | 2.24      b_ih 1.10e-5
+              (3, 700)   state  b_ih 4.19e-6 | 2.53e-6 | 1.66      h0   5.41e-6
+                         none   h0   5.24e-6 | 2.68e-6 | 1.96      W_hh 5.99e-6
     default   (1, 1)     state  b_ih 8.63e-8 | 5.76e-8 | 1.50      x    2.48e-7
                          none   b_hh 9.85e-8 | 6.15e-8 | 1.60      b_hh 9.85e-8
               (1, 2)     state  x    1.54e-7 | 1.12e-7 | 1.37      x    1.54e-7
@@ -35,6 +38,8 @@ kernel distance of the case; "state" = with h0 and grad_hT:
                          none   W_hh 4.80e-7 | 4.51e-7 | 1.06      W_hh 4.80e-7
               (1, 1030)  state  x    2.31e-7 | 2.27e-7 | 1.02      W_hh 4.42e-7
                          none   x    2.34e-7 | 2.28e-7 | 1.03      W_hh 4.20e-7
+              (3, 700)   state  x    2.30e-7 | 2.26e-7 | 1.02      W_hh 4.61e-7
+                         none   x    2.27e-7 | 2.23e-7 | 1.02      W_hh 4.32e-7
 The 8.53: at (1, 2) without h0, dW_hh = v_1 (x) h_0 is one outer product with the forward kernel's h_0 = (1 - z) n; under the default
 initialisation |n| ~ 0.1 and the forward kernel evaluates (1 - z) - 2 (1 - z) s, one rounding at magnitude 1 - ~1e-6 relative to such
 an h_0, where torch rounds tanh itself.  It is the forward's arithmetic and averages out over more frames (2.9 at 33, 1.1 at 500).

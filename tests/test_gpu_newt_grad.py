@@ -4,7 +4,8 @@ scripts/fit_newt.py) against the float64 restatement of its defi
 Input sets: 'packaged' = newt.* of tests/golden/weights_vn.npz under the oracle's exciter and embedding of smooth controls;
 'default' = the modules' own initialisation under normal inputs.  Shapes (B, T): (1, 1) the minimum, both lerp edges in one hop;
 (1, 2) one interior boundary; (3, 3) an odd batch, an interior frame between the clamped edges; (2, 33) several partials; (1, 17)
-34 blocks of 64 samples - a workgroup covers 32, blocks come two to a frame, so this is the first shape past one workgroup.
+34 blocks of 64 samples - a workgroup covers 32, blocks come two to a frame, so this is the first shape past one workgroup; (2, 65)
+260 blocks, nine partial rows - the segment sum's second trip of p += 8, a count that is no multiple of eight.
 
 Bar, for every returned tensor: the relative L2 from float64 is at most 10 x the distance of torch's float32 CPU autograd from the
 same restatement on the same inputs (the yardstick is computed in the test and floored at 2^-24, one float32 rounding), and never

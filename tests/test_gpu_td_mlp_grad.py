@@ -5,7 +5,9 @@ TimeDistributedMLP.differentiable) against the float64 restateme
 Size sets (in, hidden, out, depth): (128, 128, 129, 4) h_generator, one channel past four 32-row tiles; (128, 128, 256, 4) newt.mlp;
 (5, 7, 3, 3) every guard, the scalar weight loads, less than one tile and one K chunk; (40, 72, 33, 3) in != hidden, a partial K
 chunk, a partial tile; (6, 6, 9, 1) a bare convolution.  Shapes (B, T): (1, 1) the minimum; (3, 33) an odd batch and one frame
-past a tile; (2, 500), the training length and more than one K-split partial (4), for the two packaged size sets.
+past a tile; (2, 500), the training length and more than one K-split partial (4), for the two packaged size sets; (3, 700) for
+(5, 7, 3, 3): 66 (utterance, chunk) units, so nine dW partials - the segment sum's second trip of p += 8, a count that is no multiple
+of eight.
 Inputs: td_mlp_grad_restatement.params / inputs (no |v| within 1e-3 of the LeakyReLU's kink).
 
 Bar, for every returned tensor: the relative L2 from float64 is at most 10 x the distance of torch's float32 CPU autograd through
@@ -23,6 +25,7 @@ kernel distance of the case:
                         (2, 500)  gamma0 5.14e-7 | 5.13e-7 | 1.00      gamma1 5.32e-7
     (5, 7, 3, 3)        (1, 1)    b0     2.88e-7 | 4.51e-8 | 6.38      W0     2.97e-7
                         (3, 33)   b2     8.05e-8 | 4.23e-8 | 1.90      x      3.02e-7
+                        (3, 700)  W2     2.55e-7 | 2.03e-7 | 1.25      W0     3.17e-7
     (40, 72, 33, 3)     (1, 1)    W1     2.50e-7 | 1.33e-7 | 1.88      x      3.47e-7
                         (3, 33)   beta1  1.73e-7 | 1.26e-7 | 1.37      gamma1 2.93e-7
     (6, 6, 9, 1)        (1, 1)    W0     2.91e-8 | 2.91e-8 | 1.00      W0     2.91e-8
