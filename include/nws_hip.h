@@ -692,6 +692,35 @@ int nws_stft_grad(const float* x, const float* y, int B, int N, int R, const int
                   size_t workspace_bytes, void* stream);
 
 /*
+ * ---- The optimiser step (csrc/adam_step.hip) -----------------------------------------------------------
+ * torch.nn.utils.clip_grad_norm_(max_norm, 2.0) followed by torch.optim.Adam (weight_decay 0, no amsgrad, no maximize) over n
+ * float32 tensors in two launches (two more for every further NWS_ADAM_TABLE tensors):
+ *   total = sqrt(sum_k sum_i g_k[i]^2)   float64 sums in an order fixed by the sizes, rounded once to float32
+ *   c     = min(max_norm / (total + 1e-6), 1)   in float32 (max_norm = +inf: exactly 1);   gc = c g
+ *   m'    = m + (1 - beta1)(gc - m);   v' = beta2 v + (1 - beta2) gc^2
+ *   p'    = p - (lr / (1 - beta1^step)) m' / (sqrt(v') / sqrt(1 - beta2^step) + eps)
+ * with the bias corrections computed on the host in float64.  param, exp_avg and exp_avg_sq are updated in place; grad is read
+ * and NOT rewritten (clip_grad_norm_ scales it in place; this does not); total_norm: one device float.  No atomics: equal inputs
+ * give equal bits.  NaN and Inf follow the formula.  `tensors` is a HOST array of n records of device pointers (each tensor
+ * contiguous, 4-byte aligned, n elements).  Launches on `stream`, reads nothing back and decides every refusal before the first
+ * launch: NWS_ERR_BAD_ARG for n < 1, a NULL pointer, a tensor of fewer than 1 element, step < 1, or a workspace that is NULL, not
+ * 8-byte aligned or smaller than nws_adam_workspace_bytes (one double per NWS_ADAM_CHUNK elements of every tensor, rounded up per
+ * tensor; 0 for what is refused; only the records' n fields are read); NWS_ERR_UNSUPPORTED for a tensor above 2^40 elements.
+ */
+#define NWS_ADAM_CHUNK 1024 /* elements a workgroup sums and updates */
+#define NWS_ADAM_TABLE 64   /* tensors per launch */
+typedef struct NwsAdamTensor {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  long long n;
+} NwsAdamTensor;
+size_t nws_adam_workspace_bytes(const NwsAdamTensor* tensors, int n);
+int nws_adam_step(const NwsAdamTensor* tensors, int n, long long step, double lr, double beta1, double beta2, double eps,
+                  double max_norm, float* total_norm, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * ---- Runtime-size path (csrc/generic.hip): every gin-configurable size of the reference ------------------------------
  * The fused kernels above are compiled for gin/models/newt.gin.  These entry points take the sizes as arguments and run
  * one plain-fp32 stage kernel each (correct first, stage boundaries materialised); nws_forward_generic chains them into

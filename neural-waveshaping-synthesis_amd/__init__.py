@@ -21,5 +21,6 @@ from .models.modules.generators import FIRNoiseSynth, HarmonicOscillator, add_ch
 from .models.modules.shaping import NEWT, FastNEWT, Reverb, Sine, TrainableNonlinearity  # noqa: F401
 from .pipeline import ForwardPipeline  # noqa: F401
 from .losses import MultiResolutionSTFTLoss, STFTLoss  # noqa: F401
+from . import optim  # noqa: F401,E402
 
 __version__ = "0.1.0"

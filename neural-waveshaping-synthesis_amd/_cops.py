@@ -396,6 +396,47 @@ class CtypesOps:
                                   *[ptr(t) for t in gp], ptr(ws), nbytes, _stream(exciter.device)), "nws_newt_grad")
         return out
 
+    def adam_step(self, params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1, beta2, eps, max_norm):
+        n = len(params)
+        if n < 1:
+            raise RuntimeError("adam_step: no tensors")
+        if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == n):
+            raise RuntimeError(f"adam_step: {n} params but {len(grads)} grads, {len(exp_avgs)} exp_avgs, {len(exp_avg_sqs)} exp_avg_sqs")
+        if step < 1:
+            raise RuntimeError(f"adam_step: step counts from 1, got {step}")
+        recs = (_lib.NwsAdamTensor * n)()
+        for k, (p, g, m, v) in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs)):
+            for name, t in (("param", p), ("grad", g), ("exp_avg", m), ("exp_avg_sq", v)):
+                if not t.is_cuda:
+                    raise RuntimeError(f"{name} lives on {t.device}: the NEWT forward path only runs as HIP kernels on an AMD GPU "
+                                       "(there is no CPU fallback)")
+                if t.dtype != torch.float32:
+                    raise RuntimeError(f"{name}: expected Float, got {t.dtype}")
+                if not t.is_contiguous():
+                    raise RuntimeError(f"{name}: expected a contiguous tensor")
+                if t.device != params[0].device:
+                    raise RuntimeError(f"{name} is on {t.device} but params[0] is on {params[0].device}: all tensors of one call must "
+                                       "live on the same GPU")
+            if not (g.shape == m.shape == v.shape == p.shape):
+                raise RuntimeError(f"adam_step: tensor {k}: param {tuple(p.shape)}, grad {tuple(g.shape)}, exp_avg {tuple(m.shape)}, "
+                                   f"exp_avg_sq {tuple(v.shape)} differ in shape")
+            if p.numel() < 1:
+                raise RuntimeError(f"adam_step: tensor {k} is empty")
+            recs[k] = _lib.NwsAdamTensor(ptr(p), ptr(g), ptr(m), ptr(v), p.numel())
+        L = _lib.lib()
+        nbytes = L.nws_adam_workspace_bytes(recs, n)
+        if nbytes == 0:
+            raise RuntimeError("adam_step: unsupported sizes")
+        like = params[0]
+        with torch.cuda.device(like.device):
+            total = torch.empty((), dtype=torch.float32, device=like.device)
+            ws = _new(like, nbytes // 8, dtype=torch.float64)
+            check(L.nws_adam_step(recs, n, int(step), lr, beta1, beta2, eps, max_norm, ptr(total), ptr(ws), nbytes,
+                                  _stream(like.device)), "nws_adam_step")
+        # the kernels wrote through raw pointers: everything that caches tables derived from the weights keys on ._version
+        torch.autograd.graph.increment_version(list(params) + list(exp_avgs) + list(exp_avg_sqs))
+        return total
+
     # ---- stand-alone stage kernels (csrc/stages.hip) ---------------------------------------------------------------------
     def td_mlp(self, x, weights, biases, ln_w, ln_b, eps, slope):
         B, in_size, T = x.shape

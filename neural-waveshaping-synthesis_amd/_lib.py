@@ -34,6 +34,9 @@ FILM_CH = 256
 SHAPER_WIDTH = 8
 SHAPER_TURNS_ROW = 176
 FIR_DESIGN_COLS = 132
+ADAM_CHUNK = 1024        # elements per workgroup of the optimiser step, and per float64 partial of its norm (NWS_ADAM_CHUNK)
+ADAM_THREADS = 256       # threads that share the sum over the partials (csrc/adam_step.hip)
+ADAM_TABLE = 64          # tensors per launch (NWS_ADAM_TABLE)
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -89,6 +92,11 @@ class NwsGenericModel(C.Structure):
                 ("hgen_w", _fp * 8), ("hgen_b", _fp * 8), ("hgen_ln_g", _fp * 8), ("hgen_ln_b", _fp * 8),
                 ("newt_out_w", _fp), ("newt_out_b", _fp), ("noise_window", _fp), ("ir", _fp),
                 ("shaper", NwsShaperDesc)]
+
+
+class NwsAdamTensor(C.Structure):
+    """one record of nws_adam_step's tensor array: device pointers of a parameter, its gradient and Adam's two states"""
+    _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("n", C.c_longlong)]
 
 
 _PYIN_CFG = (C.c_double, C.c_double, C.c_double, C.c_int, C.c_int)     # sample_rate, fmin, fmax, frame_length, hop
@@ -208,6 +216,9 @@ _PROTOTYPES = {
     "nws_newt_grad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "nws_newt_grad": (C.c_int, [C.POINTER(NwsWeights), _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
                                 _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "nws_adam_workspace_bytes": (C.c_size_t, [C.POINTER(NwsAdamTensor), C.c_int]),
+    "nws_adam_step": (C.c_int, [C.POINTER(NwsAdamTensor), C.c_int, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double,
+                                C.c_double, _fp, _fp, C.c_size_t, _fp]),
     "nws_td_mlp": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),
                              C.POINTER(_fp), C.POINTER(_fp), C.c_float, C.c_float, _fp, _fp]),
     "nws_td_mlp_grad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

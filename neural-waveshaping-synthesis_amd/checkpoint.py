@@ -77,6 +77,55 @@ def write_checkpoint(path, source, replace):
     torch.save({"state_dict": state, "hyper_parameters": hparams}, path)
 
 
+def _to_cpu(obj):
+    """tensors of a nested state dict as compact CPU tensors (a view into a flat state buffer is saved as its own elements)"""
+    if isinstance(obj, torch.Tensor):
+        return obj.detach().cpu().clone()
+    if isinstance(obj, dict):
+        return {k: _to_cpu(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_to_cpu(v) for v in obj)
+    return obj
+
+
+def write_training_checkpoint(path, model, optimizer, scheduler, global_step, epoch, extra=None):
+    """A torch checkpoint with Lightning's keys, everything on the CPU: `state_dict`, `hyper_parameters`, `optimizer_states`
+    ([optimizer.state_dict()], torch.optim.Adam's layout), `lr_schedulers` ([scheduler.state_dict()]), `global_step`, `epoch`, and
+    the entries of `extra`.  `read_checkpoint` / `load_from_checkpoint` read the first two, `read_training_state` the others."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    ck = dict(extra or {})
+    ck.update({"state_dict": _to_cpu(dict(model.state_dict())),
+               "hyper_parameters": {k: v for k, v in dict(model.hparams).items() if k in _HPARAM_KEYS},
+               "optimizer_states": [_to_cpu(optimizer.state_dict())], "lr_schedulers": [_to_cpu(scheduler.state_dict())],
+               "global_step": int(global_step), "epoch": int(epoch)})
+    torch.save(ck, path)
+
+
+def read_training_state(path):
+    """-> (optimizer state dict, scheduler state dict, global_step, epoch) of a checkpoint, None for each one the file lacks: an
+    `.npz` lacks all four, a checkpoint with `optimizer_states: []` (as written without a trainer's state) the first."""
+    if str(path).endswith(".npz"):
+        return None, None, None, None
+    with _lightning_standin():
+        ck = torch.load(path, map_location="cpu", weights_only=False)
+    first = lambda key: (ck.get(key) or [None])[0]
+    number = lambda key: int(ck[key]) if ck.get(key) is not None else None
+    return first("optimizer_states"), first("lr_schedulers"), number("global_step"), number("epoch")
+
+
+_LIGHTNING_KEYS = ("state_dict", "hyper_parameters", "optimizer_states", "lr_schedulers", "global_step", "epoch", "callbacks",
+                   "pytorch-lightning_version")
+
+
+def read_training_extra(path):
+    """the `extra` entries of `write_training_checkpoint` (every top-level key that is not one of Lightning's); {} for an `.npz`"""
+    if str(path).endswith(".npz"):
+        return {}
+    with _lightning_standin():
+        ck = torch.load(path, map_location="cpu", weights_only=False)
+    return {k: v for k, v in ck.items() if k not in _LIGHTNING_KEYS}
+
+
 def load_normalisation(checkpoint_dir):
     """data_mean / data_std rows 0 (f0) and 1 (loudness) as float64 (reference: colab cell 6, 15)."""
     mean = np.load(os.path.join(checkpoint_dir, "data_mean.npy")).astype(np.float64).reshape(-1)

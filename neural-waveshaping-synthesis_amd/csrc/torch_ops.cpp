@@ -715,6 +715,48 @@ std::vector<Tensor> newt_grad(const Tensor& wdesc, const Tensor& exciter, const 
   return out;
 }
 
+// clip_grad_norm_(max_norm, 2.0) + Adam over every listed tensor in two launches (csrc/adam_step.hip): params,
+// exp_avgs and exp_avg_sqs are updated in place and their version counters raised - everything that caches tables derived from
+// the weights keys on Tensor._version - grads are read and not rewritten; returns the gradients' total norm, a 0-dim tensor.
+Tensor adam_step(at::TensorList params, at::TensorList grads, at::TensorList exp_avgs, at::TensorList exp_avg_sqs, int64_t step,
+                 double lr, double beta1, double beta2, double eps, double max_norm) {
+  const size_t n = params.size();
+  TORCH_CHECK(n >= 1, "adam_step: no tensors");
+  TORCH_CHECK(grads.size() == n && exp_avgs.size() == n && exp_avg_sqs.size() == n, "adam_step: ", n, " params but ", grads.size(),
+              " grads, ", exp_avgs.size(), " exp_avgs, ", exp_avg_sqs.size(), " exp_avg_sqs");
+  TORCH_CHECK(step >= 1, "adam_step: step counts from 1, got ", step);
+  std::vector<NwsAdamTensor> recs(n);
+  for (size_t k = 0; k < n; ++k) {
+    check_dev(params[k], "param");
+    check_dev(grads[k], "grad");
+    check_dev(exp_avgs[k], "exp_avg");
+    check_dev(exp_avg_sqs[k], "exp_avg_sq");
+    check_same_device(params[0], "params[0]", params[k], "param");
+    check_same_device(params[k], "param", grads[k], "grad");
+    check_same_device(params[k], "param", exp_avgs[k], "exp_avg");
+    check_same_device(params[k], "param", exp_avg_sqs[k], "exp_avg_sq");
+    TORCH_CHECK(grads[k].sizes() == params[k].sizes() && exp_avgs[k].sizes() == params[k].sizes() &&
+                    exp_avg_sqs[k].sizes() == params[k].sizes(), "adam_step: tensor ", k, ": param ", params[k].sizes(), ", grad ",
+                grads[k].sizes(), ", exp_avg ", exp_avgs[k].sizes(), ", exp_avg_sq ", exp_avg_sqs[k].sizes(), " differ in shape");
+    TORCH_CHECK(params[k].numel() >= 1, "adam_step: tensor ", k, " is empty");
+    recs[k] = NwsAdamTensor{params[k].data_ptr<float>(), grads[k].data_ptr<float>(), exp_avgs[k].data_ptr<float>(),
+                            exp_avg_sqs[k].data_ptr<float>(), (long long)params[k].numel()};
+  }
+  const size_t nbytes = nws_adam_workspace_bytes(recs.data(), (int)n);
+  TORCH_CHECK(nbytes > 0, "adam_step: unsupported sizes");
+  Launch L(params[0]);
+  Tensor total = at::empty({}, params[0].options());
+  Tensor ws = at::empty({(int64_t)(nbytes / 8)}, params[0].options().dtype(at::kDouble));
+  nws_check(nws_adam_step(recs.data(), (int)n, (long long)step, lr, beta1, beta2, eps, max_norm, total.data_ptr<float>(), ws.data_ptr(),
+                          nbytes, L.stream), "nws_adam_step");
+  for (size_t k = 0; k < n; ++k) {
+    params[k].unsafeGetTensorImpl()->bump_version();
+    exp_avgs[k].unsafeGetTensorImpl()->bump_version();
+    exp_avg_sqs[k].unsafeGetTensorImpl()->bump_version();
+  }
+  return total;
+}
+
 // TimeDistributedMLP.forward (dynamic.py:20-40): x (B, in, T); weights[i] (rows_i, cols_i[, 1]), biases[i]; ln_w / ln_b for
 // every layer but the last
 Tensor td_mlp(const Tensor& x, at::TensorList weights, at::TensorList biases, at::TensorList ln_w, at::TensorList ln_b, double eps,
@@ -1515,6 +1557,8 @@ TORCH_LIBRARY(newt_hip, m) {
   m.def("newt_apply(Tensor wdesc, Tensor exciter, Tensor film) -> Tensor", &newt_apply);
   m.def("newt_grad(Tensor wdesc, Tensor exciter, Tensor film, Tensor grad_out, bool want_exciter, bool want_params) -> Tensor[]",
         &newt_grad);
+  m.def("adam_step(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] exp_avgs, Tensor(c!)[] exp_avg_sqs, int step, float lr, "
+        "float beta1, float beta2, float eps, float max_norm) -> Tensor", &adam_step);
   m.def("td_mlp(Tensor x, Tensor[] weights, Tensor[] biases, Tensor[] ln_w, Tensor[] ln_b, float eps, float slope) -> Tensor", &td_mlp);
   m.def("td_mlp_grad(Tensor x, Tensor grad_y, Tensor[] weights, Tensor[] biases, Tensor[] ln_w, Tensor[] ln_b, float eps, float slope, "
         "bool want_params) -> Tensor[]", &td_mlp_grad);

@@ -9,10 +9,12 @@ Of the reference's Lightning hooks (:92-165) the two that need no backward pass 
 and ``test_step`` return ``stft_loss(recon, audio)`` - ``losses.MultiResolutionSTFTLoss``, the HIP restatement
 of the ``auraloss`` loss the reference logs as ``val/loss`` / ``test/loss`` - through the
 reference's ``_run_step``.  ``stft_loss`` is made on first use (in the reference ``configure_optimizers`` makes
-it).  ``training_step`` and ``configure_optimizers`` still raise: the loss, the reverb and the noise branch's filter have a
-backward pass, and so have a frame MLP and the control encoder called on their own (3.16, 3.17:
+it).  ``training_step`` and ``configure_optimizers`` raise on a model as constructed; they are behind the opt-in flag
+``NeuralWaveshaping.differentiable``, which sets the links' own flags: the loss, the reverb and the noise
+branch's filter have a backward pass, and so have a frame MLP and the control encoder (3.16, 3.17:
 ``ControlModule.differentiable``, ``.vjp``) and the oscillator branch (3.18: ``NEWT.differentiable``, ``.vjp``,
-``Conv1x1.differentiable``); ``scripts/fit_newt.py --params model`` composes them, the two hooks are a follow-up.  ``pre_reverb`` renders the reverb's input, which is what fitting ``reverb.ir`` alone needs;
+``Conv1x1.differentiable``); ``pre_reverb_graph`` composes them, for the flagged forward and for ``scripts/fit_newt.py``, and
+``scripts/train.py`` is the training loop.  ``pre_reverb`` renders the reverb's input, which is what fitting ``reverb.ir`` alone needs;
 ``pre_reverb_parts`` renders it in two parts with the noise filter's input, which is what fitting the noise colour
 needs.  Logging (``self.log``, wandb) is left to the caller.
 
@@ -201,6 +203,9 @@ class NeuralWaveshaping(nn.Module):
         return out
 
     def __setattr__(self, name, value):
+        if name == "differentiable":
+            value = bool(value)
+            self._set_differentiable(value)
         super().__setattr__(name, value)
         if name == "newt" and "_engine" in self.__dict__:
             self._engine.invalidate()
@@ -272,7 +277,30 @@ class NeuralWaveshaping(nn.Module):
         noise = _req(noise, "noise", self.control_hop * T - 1)
         return f0, control, phase_u, noise
 
+    # ---- training (opt-in) ------------------------------------------------------------------------
+    _TRAINED = ("newt", "embedding", "harmonic_mixer", "h_generator", "noise_synth", "reverb")
+
+    # ``differentiable`` (default False, also the value of a model unpickled from before the flag existed): nothing carries a
+    # graph and ``training_step`` and ``configure_optimizers`` raise.  Assigning it (``__setattr__``) sets ``differentiable`` of
+    # ``embedding``, ``harmonic_mixer``, ``newt``, ``h_generator``, ``noise_synth``, ``reverb`` and ``stft_loss`` (a ``FastNEWT``
+    # refuses: the lookup table has no backward, and then nothing is changed); False clears them.  Set to True, a forward under
+    # grad mode with some parameter that requires grad runs the links one by one with their backwards attached
+    # (``pre_reverb_graph(self, ..., "model")``, then ``reverb``) with the same two hidden draws in the same order; under
+    # ``no_grad`` it is the fused forward as before, so validation during training stays on the fast path.  The two hooks then
+    # are the reference's (models/neural_waveshaping.py:92-118).
+    differentiable = False
+
+    def _set_differentiable(self, value):
+        for name in self._TRAINED:             # newt first: FastNEWT refuses True before anything has been changed
+            getattr(self, name).differentiable = value
+        self.stft_loss.differentiable = value
+
+    def _wants_graph(self):
+        return self.differentiable and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
     def forward(self, f0, control, *, phase_u=None, noise=None):
+        if self._wants_graph():
+            return self.reverb(pre_reverb_graph(self, f0, control, "model", phase_u=phase_u, noise=noise))
         f0, control, phase_u, noise = self._checked_inputs(f0, control, phase_u, noise)
         if self._sub_module_hooks():
             return self._forward_module_by_module(f0, control, phase_u, noise)
@@ -342,6 +370,9 @@ class NeuralWaveshaping(nn.Module):
             return self._run_step(batch)[0]
 
     def training_step(self, batch, batch_idx):
+        """Under ``differentiable``: reference :114-118 without the logging - the loss of ``_run_step`` with its graph"""
+        if self.differentiable:
+            return self._run_step(batch)[0]
         raise NotImplementedError("training_step: there is no backward pass in this package behind this hook yet - every link has "
                                   "one when called on its own: the loss (losses.MultiResolutionSTFTLoss(differentiable=True)), the "
                                   "reverb (Reverb.differentiable, Reverb.vjp), the noise branch's filter "
@@ -351,15 +382,25 @@ class NeuralWaveshaping(nn.Module):
                                   "(NEWT.differentiable, NEWT.vjp, Conv1x1.differentiable for harmonic_mixer; DESIGN.md 3.18).  "
                                   "scripts/fit_newt.py --params model composes them into a step over every parameter; "
                                   "validation_step and test_step give the reference's loss, scripts/fit_reverb.py fits reverb.ir "
-                                  "and scripts/fit_noise.py the noise colour")
+                                  "and scripts/fit_noise.py the noise colour.  The hook itself is behind an opt-in flag: set "
+                                  "NeuralWaveshaping.differentiable = True (scripts/train.py does)")
 
     def configure_optimizers(self):
+        """Under ``differentiable``: the reference's dictionary (:92-102) - Adam(lr) and StepLR(lr_decay_interval, lr_decay) stepped
+        every optimiser step - with ``optim.Adam``, which also clips (set its ``max_grad_norm``)"""
+        if self.differentiable:
+            from ..optim import Adam
+
+            optimizer = Adam(self.parameters(), lr=self.learning_rate)
+            scheduler = torch.optim.lr_scheduler.StepLR(optimizer, self.lr_decay_interval, self.lr_decay)
+            return {"optimizer": optimizer, "lr_scheduler": {"scheduler": scheduler, "interval": "step"}}
         raise NotImplementedError("configure_optimizers: there is no backward pass in this package behind the Lightning hooks yet "
                                   "(the loss, the reverb, the noise branch's filter, a frame MLP, the control encoder and the "
                                   "oscillator branch - NEWT.differentiable, NEWT.vjp - each have one when called on their own); "
                                   "scripts/fit_newt.py --params model builds the reference's Adam + StepLR from the model's hparams "
                                   "and steps every parameter, scripts/fit_reverb.py and scripts/fit_noise.py fit reverb.ir and the "
-                                  "noise colour; model.stft_loss is made on first use instead")
+                                  "noise colour; model.stft_loss is made on first use instead.  The hook itself is behind an opt-in "
+                                  "flag: set NeuralWaveshaping.differentiable = True (scripts/train.py does)")
 
     def _sub_module_hooks(self) -> bool:
         """Forward hooks on sub-modules (the reference's users tap stages that way, and so does tests/golden/make_golden.py on
@@ -405,6 +446,27 @@ class NeuralWaveshaping(nn.Module):
         if map_location is not None:
             model = model.to(map_location)
         return model
+
+
+def pre_reverb_graph(model, f0, control, mode, phase_u=None, noise=None):
+    """The reverb's input (B, N) with the graph a mode needs, the links called one by one with whatever ``differentiable`` flags
+    the caller has set; draws the two hidden inputs in the forward's order unless they are given.  ``mode`` "model": the control
+    embedding carries its graph into both branches; anything else (scripts/fit_newt.py's "shapers" and "branch"): the embedding and
+    the noise channel are rendered without one and only oscillator bank -> ``harmonic_mixer`` -> ``newt`` carries the gradient."""
+    f0, control, phase_u, noise = model._checked_inputs(f0, control, phase_u, noise)
+    with torch.no_grad():
+        f0_up = upsample_linear(f0, int(model.control_hop))
+        sig = model.osc(f0_up[:, 0], phase_u=phase_u)         # no parameters, and F0 is data: nothing goes further back
+    ctl = control[:, 0:2].contiguous()
+    if mode == "model":
+        emb = model.embedding(ctl)
+        nz = model.noise_synth(model.h_generator(emb), noise=noise)
+    else:
+        with torch.no_grad():
+            emb = model.embedding(ctl)
+            nz = model.noise_synth(model.h_generator(emb), noise=noise)
+    x = model.newt(model.harmonic_mixer(sig), emb)
+    return x[:, 0] + nz[:, 0]
 
 
 def _engine_epoch():

@@ -58,21 +58,8 @@ def fitted_parameters(model, mode):
 
 def pre_reverb(model, f0, control, mode):
     """the reverb's input (B, N) with the graph a mode needs; draws the two hidden inputs in the forward's order"""
-    upsample_linear = importlib.import_module("neural-waveshaping-synthesis_amd.models.modules.dynamic").upsample_linear
-    f0, control, phase_u, noise = model._checked_inputs(f0, control, None, None)
-    with torch.no_grad():
-        f0_up = upsample_linear(f0, int(model.control_hop))
-        sig = model.osc(f0_up[:, 0], phase_u=phase_u)         # no parameters, and F0 is data: nothing goes further back
-    ctl = control[:, 0:2].contiguous()
-    if mode == "model":
-        emb = model.embedding(ctl)
-        nz = model.noise_synth(model.h_generator(emb), noise=noise)
-    else:
-        with torch.no_grad():
-            emb = model.embedding(ctl)
-            nz = model.noise_synth(model.h_generator(emb), noise=noise)
-    x = model.newt(model.harmonic_mixer(sig), emb)
-    return x[:, 0] + nz[:, 0]
+    # the composition NeuralWaveshaping.forward runs under its `differentiable` flag: one copy, in the package
+    return importlib.import_module("neural-waveshaping-synthesis_amd.models.neural_waveshaping").pre_reverb_graph(model, f0, control, mode)
 
 
 @click.command()

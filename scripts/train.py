@@ -1,0 +1,208 @@
+#!/usr/bin/env python
+"""Train a model on a dataset written by scripts/create_dataset.py: the counterpart of the reference's scripts/train.py, on one GPU,
+with every gradient and the optimiser step computed by HIP kernels.
+
+    python scripts/train.py --gin-file neural-waveshaping-synthesis_amd/gin/train/train_newt.gin --dataset-path data/ \\
+        --output-dir run/ [--urmp --instrument vn] [--device 0] [--restore-checkpoint run/last.ckpt] [--max-steps N] \\
+        [--batch-size 8] [--seed 0] [--val-every-epochs 1]
+
+The gin file configures the model and the loop (`trainer_kwargs.max_steps`, `trainer_kwargs.gradient_clip_val`, the batch size as
+`GeneralDataModule.batch_size` / `URMPDataModule.batch_size`); `accelerator = 'dp'` of a reference file is ignored with a note:
+single GPU only.  `--load-data-to-memory` is accepted; `--with-wandb` is refused, there is no wandb logging here.
+
+The loop.  Epoch e walks `ControlDataset(root, "train")` in the order `RandomState(seed + e)` shuffles it into, in batches of items
+of equal length.  Before each step the device generator is seeded with seed + global_step, so the hidden draws of the render are a
+function of the step: a run repeats to the bit and a resumed run continues the same sequence.  A step is `training_step`,
+`backward`, `optimizer.step()` - `nws.optim.Adam` with `max_grad_norm = gradient_clip_val`: clip and update in one operator call -
+`scheduler.step()`, `zero_grad(set_to_none=True)`.  Nothing is read back inside an epoch; at its end (and when `--max-steps` ends
+the run inside one) `validation_step` runs over the `val` split (the fused forward, under the seed --seed) and the steps' losses, the
+last gradient norm, the learning rate and the validation loss are printed.
+
+Checkpoints, in Lightning's layout with the optimiser's and the scheduler's state (checkpoint.write_training_checkpoint):
+`last.ckpt` every epoch, `best.ckpt` when `val/loss` improves, `data_mean.npy` / `data_std.npy` next to them - the output directory
+is what `NeuralWaveshaping.load_from_checkpoint` and scripts/timbre_transfer.py take.  `--restore-checkpoint` restores the weights
+and, where the file has them, the optimiser, the scheduler, the step and the epoch (a reference `last.ckpt` resumes with its own
+Adam state); an `.npz` starts fresh optimiser state from its weights.
+"""
+import importlib
+import math
+import os
+import shutil
+import sys
+
+import click
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _binding(gin, keys, default):
+    for key in keys:
+        try:
+            return gin.query_parameter(key)
+        except ValueError:
+            pass
+    return default
+
+
+def _with_audio(data, split):
+    names = [n for n in data.names if os.path.exists(os.path.join(data.audio_dir, f"audio_{n}.npy"))]
+    if len(names) < len(data):
+        print(f"{len(data) - len(names)} of {len(data)} items of {split!r} have no target audio and are left out")
+    return names
+
+
+def _to_device(batch, dev):
+    return {"audio": torch.from_numpy(np.stack(batch["audio"])).to(dev), "f0": torch.from_numpy(batch["f0"]).to(dev),
+            "control": torch.from_numpy(batch["control"]).to(dev)}
+
+
+def _validate(model, data, names, batch_size, dev, seed):
+    """mean validation_step loss over the split, weighted by items; the hidden draws under --seed: one fixed objective"""
+    torch.cuda.manual_seed(int(seed))
+    losses, sizes = [], []
+    for k, batch in enumerate(data.batches(names, batch_size)):
+        losses.append(model.validation_step(_to_device(batch, dev), k))
+        sizes.append(len(batch["names"]))
+    return float(np.average([float(v) for v in losses], weights=sizes))
+
+
+@click.command()
+@click.option("--gin-file", required=True, help="training gin file (gin/train/train_newt.gin of the package, or a reference one)")
+@click.option("--dataset-path", required=True, help="dataset root: data_mean.npy, data_std.npy, train/, val/")
+@click.option("--urmp", is_flag=True, help="the dataset root is <dataset-path>/<instrument>")
+@click.option("--device", default="0", help="index of the GPU")
+@click.option("--instrument", default="vn")
+@click.option("--load-data-to-memory", is_flag=True, help="accepted; items are read from disk as they are batched")
+@click.option("--with-wandb", is_flag=True, help="refused: there is no wandb logging in this package")
+@click.option("--restore-checkpoint", default="", help="weights and, where present, optimiser, scheduler, step and epoch")
+@click.option("--output-dir", default="checkpoints", help="last.ckpt, best.ckpt and the normalisation files go here")
+@click.option("--max-steps", default=None, type=int, help="optimiser steps in all (overrides trainer_kwargs.max_steps)")
+@click.option("--batch-size", default=None, type=int, help="items per batch (overrides the gin file)")
+@click.option("--seed", default=0, help="shuffling (seed + epoch) and the render's hidden draws (seed + global step)")
+@click.option("--val-every-epochs", default=1, help="validate and consider best.ckpt every this many epochs")
+def main(gin_file, dataset_path, urmp, device, instrument, load_data_to_memory, with_wandb, restore_checkpoint, output_dir, max_steps,
+         batch_size, seed, val_every_epochs):
+    if with_wandb:
+        raise click.ClickException("--with-wandb: there is no wandb logging in this package; the losses are printed once per epoch")
+    nws = importlib.import_module("neural-waveshaping-synthesis_amd")
+    ds_mod = importlib.import_module("neural-waveshaping-synthesis_amd.dataset")
+    ckpt = importlib.import_module("neural-waveshaping-synthesis_amd.checkpoint")
+    gin = nws.gin
+
+    @gin.configurable
+    def get_model(model=nws.NeuralWaveshaping):
+        return model()
+
+    @gin.configurable
+    def trainer_kwargs(**kwargs):
+        return kwargs
+
+    gin.parse_config_file(gin_file)
+    kwargs = trainer_kwargs()
+    clip = kwargs.pop("gradient_clip_val", None)
+    gin_steps = kwargs.pop("max_steps", 0)
+    max_steps = int(gin_steps if max_steps is None else max_steps)
+    if max_steps < 1:
+        raise click.ClickException("no step count: set trainer_kwargs.max_steps in the gin file or pass --max-steps")
+    if "accelerator" in kwargs:
+        print(f"trainer_kwargs.accelerator = {kwargs.pop('accelerator')!r} is ignored: this script trains on one GPU")
+    if kwargs:
+        print(f"trainer_kwargs {sorted(kwargs)} have no meaning here and are ignored")
+    keys = ("URMPDataModule.batch_size", "GeneralDataModule.batch_size")
+    batch_size = int(_binding(gin, keys if urmp else keys[::-1], 8) if batch_size is None else batch_size)
+    root = os.path.join(dataset_path, instrument) if urmp else dataset_path
+
+    dev = torch.device("cuda", int(device))
+    torch.cuda.set_device(dev)
+    torch.manual_seed(int(seed))                              # the initial weights of a run without --restore-checkpoint
+    train = ds_mod.ControlDataset(root, "train")
+    train_names = _with_audio(train, "train")
+    if not train_names:
+        raise click.ClickException(f"no item of 'train' under {root} has target audio: nothing to train on")
+    val, val_names = None, []
+    if os.path.isdir(os.path.join(root, "val", "control")):
+        val = ds_mod.ControlDataset(root, "val")
+        val_names = _with_audio(val, "val")
+    if not val_names:
+        print(f"no 'val' items with audio under {root}: no validation loss, best.ckpt is not written")
+
+    model = get_model()
+    if restore_checkpoint:
+        state, _ = ckpt.read_checkpoint(restore_checkpoint)
+        model.load_state_dict({k: torch.as_tensor(v) for k, v in state.items()})
+    model = model.to(dev)
+    model.differentiable = True
+    configured = model.configure_optimizers()
+    optimizer, scheduler = configured["optimizer"], configured["lr_scheduler"]["scheduler"]
+    optimizer.max_grad_norm = float(clip) if clip else None          # Lightning: gradient_clip_val = 0 means no clipping
+    global_step, epoch, skip, best = 0, 0, 0, math.inf
+    if restore_checkpoint:
+        opt_state, sched_state, step0, epoch0 = ckpt.read_training_state(restore_checkpoint)
+        if opt_state is not None:
+            optimizer.load_state_dict(opt_state)
+            if sched_state is not None:
+                scheduler.load_state_dict(sched_state)
+            global_step, epoch = int(step0 or 0), int(epoch0 or 0)
+            extra = ckpt.read_training_extra(restore_checkpoint)
+            skip, best = int(extra.get("batch_in_epoch", 0)), float(extra.get("best_val_loss", math.inf))
+            print(f"resuming {restore_checkpoint} at step {global_step}, epoch {epoch}, lr {optimizer.param_groups[0]['lr']:.3e}")
+        else:
+            print(f"{restore_checkpoint} carries no optimiser state: fresh Adam state from its weights")
+
+    os.makedirs(output_dir, exist_ok=True)
+    for name in ("data_mean.npy", "data_std.npy"):
+        shutil.copyfile(os.path.join(root, name), os.path.join(output_dir, name))
+
+    def save(name, epoch_, batch_in_epoch):
+        ckpt.write_training_checkpoint(os.path.join(output_dir, name), model, optimizer, scheduler, global_step, epoch_,
+                                       extra={"batch_in_epoch": int(batch_in_epoch), "best_val_loss": float(best)})
+
+    while global_step < max_steps:
+        order = [train_names[i] for i in np.random.RandomState(int(seed) + epoch).permutation(len(train_names))]
+        losses, first_step, done = [], global_step, 0
+        batches = enumerate(train.batches(order, batch_size))
+        for k, batch in batches:
+            if k < skip:                                      # a resumed epoch: these batches were stepped before the checkpoint
+                continue
+            torch.cuda.manual_seed(int(seed) + global_step)
+            loss = model.training_step(_to_device(batch, dev), k)
+            loss.backward()
+            optimizer.step()
+            scheduler.step()
+            optimizer.zero_grad(set_to_none=True)
+            losses.append(loss.detach())
+            global_step += 1
+            done = k + 1
+            if global_step >= max_steps:
+                break
+        skip = 0
+        if not losses:                                        # the checkpoint was written at the very end of its epoch
+            epoch += 1
+            continue
+        finished = next(batches, None) is None                # False: --max-steps ended the run inside the epoch
+        values = [float(v) for v in losses]                   # the epoch's one read-back
+        for i, v in enumerate(values):
+            print(f"  step {first_step + i + 1}: train loss {v:.6f}")
+        val_loss = None
+        if val_names and (epoch + 1) % int(val_every_epochs) == 0:
+            val_loss = _validate(model, val, val_names, batch_size, dev, seed)
+        improved = val_loss is not None and val_loss < best
+        if improved:
+            best = val_loss
+        print(f"epoch {epoch}: step {global_step}  train loss {float(np.mean(values)):.6f}  grad norm "
+              f"{float(optimizer.last_grad_norm):.4f}  lr {optimizer.param_groups[0]['lr']:.3e}  val loss "
+              + (f"{val_loss:.6f}" if val_loss is not None else "-") + ("  (best)" if improved else ""))
+        next_epoch, at = (epoch + 1, 0) if finished else (epoch, done)
+        save("last.ckpt", next_epoch, at)
+        if improved:
+            save("best.ckpt", next_epoch, at)
+        epoch = next_epoch
+        skip = at
+    print(f"wrote {os.path.join(output_dir, 'last.ckpt')} at step {global_step}")
+
+
+if __name__ == "__main__":
+    main()
