@@ -791,6 +791,26 @@ int nws_g_shaper_table(const NwsShaperDesc* d, int table_size, float table_min, 
 /* NEWT.forward before the mixer (shaping.py:68-76): exciter (B,S,N), film (B,4S,T) channel-major -> (B,S,N) */
 int nws_g_film_shaper(const NwsShaperDesc* d, const float* exciter, const float* film, int B, int T, int hop, float* out,
                       void* stream);
+/* The backward of nws_g_film_shaper followed by the Conv1d(S -> 1) mixer - NEWT.forward at any bank size - for grad_out =
+ * dL/d(out) (B, N), N = 128 T (csrc/g_newt_grad.hip): 1 <= n_shapers <= 64, 1 <= width <= 16, 1 <= depth <= 4,
+ * hop 128, one output channel (mix_w (S), mix_b (1)).  grad_film (B, 4S, T), grad_exciter (B, S, N) unless NULL, and, when
+ * param_grads is given with all of its 2 depth + 3 entries, the parameter gradients in the layout of their parameters, in this
+ * order: shaping_fn.input_scale, then net.{2l}.weight, net.{2l}.bias for l = 0 .. depth-1 (the shapes of NwsShaperDesc.w / .b),
+ * then mixer.0.weight (S), mixer.0.bias (1).  Nothing is saved by the forward: it is recomputed per sample from exciter and film;
+ * the gradient is that of the exact expression with the full-range sine (the forward kernel's hardware sine at widths 4 / 8 / 16
+ * is about 4e-7 rad away).  The hidden layers' weight gradients are sums of exact fp32 products on the matrix pipe.  No atomics,
+ * every sum in an order fixed by the sizes: equal inputs give equal bits, grad_out = 0 gives zeros, and neither grad_exciter nor
+ * param_grads changes the other outputs' bits.  Launches on `stream`, reads nothing back and decides every refusal before the
+ * first launch: NWS_ERR_BAD_ARG for a NULL required pointer (d's in_scale / w / b entries below depth included), some but not all
+ * of the 2 depth + 3 parameter gradients, a size < 1, or a workspace that is NULL or smaller than
+ * nws_g_newt_grad_workspace_bytes; NWS_ERR_UNSUPPORTED for a descriptor that carries a table (FastNEWT has no backward),
+ * hop != 128, n_shapers > 64, width > 16, depth > 4, T > 65 535 or B T > 2^28.  nws_g_newt_grad_workspace_bytes: 0 for sizes that
+ * are refused. */
+size_t nws_g_newt_grad_workspace_bytes(const NwsShaperDesc* d, int B, int T, int want_params);
+int nws_g_newt_grad(const NwsShaperDesc* d, const float* mix_w, const float* mix_b, const float* exciter, const float* film,
+                    const float* grad_out, int B, int T, int hop, float* grad_exciter /* may be NULL */, float* grad_film,
+                    float* const* param_grads /* NULL, or a HOST array of 2 depth + 3 device pointers */, void* workspace,
+                    size_t workspace_bytes, void* stream);
 /* FIRNoiseSynth (generators.py:21-35) for any even ir_length >= hop: H (B, L/2+1, T) -> taps (B, T, L); then the noise
  * branch (+ the sum over `add_channels` channels of add_in (B, add_channels, N), NULL = none) -> out (B, N) */
 int nws_g_fir_design(const float* H, const float* window, int fir_len, int B, int T, float* fir_out, void* stream);

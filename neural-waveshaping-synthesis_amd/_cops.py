@@ -773,6 +773,43 @@ class CtypesOps:
             check(_lib.lib().nws_g_conv1x1(ptr(shaped), ptr(mix_w), ptr(mix_b), B, S, O, N, ptr(out), st), "nws_g_conv1x1")
         return out
 
+    def g_newt_grad(self, sdesc, exciter, film, grad_out, mix_w, mix_b, want_exciter, want_params):
+        d = _struct(sdesc, NwsShaperDesc)
+        B, _, N = exciter.shape
+        S, W, D = d.n_shapers, d.width, d.depth
+        T = film.shape[2]
+        if exciter.shape[1] != S or tuple(film.shape) != (B, 4 * S, T) or N != T * HOP:
+            raise RuntimeError(f"NEWT: exciter {tuple(exciter.shape)} and FiLM parameters {tuple(film.shape)} disagree "
+                               f"({S} shapers, hop {HOP})")
+        if B < 1 or T < 1:
+            raise RuntimeError("g_newt_grad: need at least one utterance and one frame")
+        if grad_out.numel() != B * N or grad_out.shape[0] != B:
+            raise RuntimeError(f"g_newt_grad: grad_out {tuple(grad_out.shape)} is not ({B}, 1, {N})")
+        if d.lut:
+            raise RuntimeError("g_newt_grad: the lookup table has no backward")
+        if mix_w.numel() != S or mix_b.numel() != 1:
+            raise RuntimeError(f"g_newt_grad: one output channel only: mixer weight {tuple(mix_w.shape)} / bias {tuple(mix_b.shape)} "
+                               f"for {S} shapers")
+        L = _lib.lib()
+        nbytes = L.nws_g_newt_grad_workspace_bytes(C.byref(d), B, T, 1 if want_params else 0) if max(B, T) < 2 ** 30 else 0
+        if nbytes == 0:
+            raise RuntimeError(f"g_newt_grad: unsupported size ({S} shapers of width {W} and depth {D}, B {B}, T {T}): at most 64 "
+                               "shapers of width 16 and depth 4, T <= 65535, B T <= 2^28")
+        with torch.cuda.device(exciter.device):
+            out = [_new(exciter, B, 4 * S, T)]
+            ge = torch.empty_like(exciter) if want_exciter else None
+            if want_exciter:
+                out.append(ge)
+            gp = []
+            if want_params:
+                gp = [_new(exciter, *sh) for sh in _lib.g_newt_grad_shapes(S, W, D)]
+                out += gp
+            ws = _new(exciter, nbytes, dtype=torch.uint8)
+            check(L.nws_g_newt_grad(C.byref(d), ptr(mix_w), ptr(mix_b), ptr(exciter), ptr(film), ptr(grad_out), B, T, HOP, ptr(ge),
+                                    ptr(out[0]), _ptrs(gp) if want_params else None, ptr(ws), nbytes, _stream(exciter.device)),
+                  "nws_g_newt_grad")
+        return out
+
     def g_fir_noise(self, H, window, noise, hop):
         B, _, T = H.shape
         Lf = window.numel()

@@ -41,6 +41,17 @@ ADAM_TABLE = 64          # tensors per launch (NWS_ADAM_TABLE)
 _fp = C.c_void_p  # device pointers travel as integers
 
 
+def g_newt_grad_shapes(S, W, D):
+    """the 2 D + 3 parameter gradients of nws_g_newt_grad in its order, each in the shape of its parameter: shaping_fn.input_scale,
+    net.{2l}.weight and net.{2l}.bias for l < D, mixer.0.weight, mixer.0.bias"""
+    shapes = [(1, S, 1)]
+    for l in range(D):
+        last = l == D - 1
+        cin, cout = (1 if l == 0 else W), (1 if last else W)
+        shapes += [(S * cout, cin, 1), (S * cout,)]
+    return shapes + [(1, S, 1), (1,)]
+
+
 class NwsWeights(C.Structure):
     _fields_ = [
         ("gru_w_ih", _fp), ("gru_w_hh", _fp), ("gru_b_ih", _fp), ("gru_b_hh", _fp),
@@ -239,6 +250,9 @@ _PROTOTYPES = {
     "nws_g_shaper_apply": (C.c_int, [C.POINTER(NwsShaperDesc), _fp, C.c_int64, C.c_int64, _fp, _fp]),
     "nws_g_shaper_table": (C.c_int, [C.POINTER(NwsShaperDesc), C.c_int, C.c_float, C.c_float, _fp, _fp]),
     "nws_g_film_shaper": (C.c_int, [C.POINTER(NwsShaperDesc), _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "nws_g_newt_grad_workspace_bytes": (C.c_size_t, [C.POINTER(NwsShaperDesc), C.c_int, C.c_int, C.c_int]),
+    "nws_g_newt_grad": (C.c_int, [C.POINTER(NwsShaperDesc), _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp,
+                                  C.POINTER(_fp), _fp, C.c_size_t, _fp]),
     "nws_g_fir_design": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "nws_g_fir_noise": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp]),
     "nws_g_reverb_direct": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),

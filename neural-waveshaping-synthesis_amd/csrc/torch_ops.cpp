@@ -1377,6 +1377,66 @@ Tensor g_newt_apply(const Tensor& sdesc, const Tensor& exciter, const Tensor& fi
   return out;
 }
 
+// The backward of g_newt_apply with one output channel for grad_out = dL/d(out) (B, 1, N) (csrc/g_newt_grad.hip):
+// [grad_film (B, 4S, T)], then grad_exciter (B, S, N) when wanted, then with want_params the 2 D + 3 parameter gradients in the
+// shapes of their parameters: input_scale, net.{2l}.weight and net.{2l}.bias for l < D, mixer.0.weight, mixer.0.bias.  Nothing was
+// saved by the forward; the workspace comes from torch's allocator.
+std::vector<Tensor> g_newt_grad(const Tensor& sdesc, const Tensor& exciter, const Tensor& film, const Tensor& grad_out, const Tensor& mix_w,
+                                const Tensor& mix_b, bool want_exciter, bool want_params) {
+  const NwsShaperDesc* d = struct_of<NwsShaperDesc>(sdesc, "sdesc");
+  check_dev(exciter, "exciter");
+  check_dev(film, "film_params");
+  check_dev(grad_out, "grad_out");
+  check_dev(mix_w, "mixer weight");
+  check_dev(mix_b, "mixer bias");
+  check_same_device(exciter, "exciter", film, "control embedding");
+  check_same_device(exciter, "exciter", grad_out, "grad_out");
+  check_same_device(exciter, "exciter", mix_w, "newt.mixer");
+  const int64_t S = d->n_shapers, W = d->width, D = d->depth;
+  TORCH_CHECK(exciter.dim() == 3, "NEWT: expected an exciter of shape (B, ", S, ", N), got ", exciter.sizes());
+  const int64_t B = exciter.size(0), N = exciter.size(2);
+  TORCH_CHECK(film.dim() == 3, "NEWT: expected FiLM parameters of shape (B, ", 4 * S, ", T), got ", film.sizes());
+  const int64_t T = film.size(2);
+  TORCH_CHECK(exciter.size(1) == S && film.size(0) == B && film.size(1) == 4 * S && N == T * NWS_HOP, "NEWT: exciter ", exciter.sizes(),
+              " and FiLM parameters ", film.sizes(), " disagree (", S, " shapers, hop ", NWS_HOP, ")");
+  TORCH_CHECK(B >= 1 && T >= 1, "g_newt_grad: need at least one utterance and one frame");
+  TORCH_CHECK(grad_out.numel() == B * N && grad_out.size(0) == B, "g_newt_grad: grad_out ", grad_out.sizes(), " is not (", B, ", 1, ", N, ")");
+  TORCH_CHECK(d->lut == nullptr, "g_newt_grad: the lookup table has no backward");
+  TORCH_CHECK(mix_w.numel() == S && mix_b.numel() == 1, "g_newt_grad: one output channel only: mixer weight ", mix_w.sizes(), " / bias ",
+              mix_b.sizes(), " for ", S, " shapers");
+  const size_t nbytes = B < (1 << 30) && T < (1 << 30) ? nws_g_newt_grad_workspace_bytes(d, (int)B, (int)T, want_params ? 1 : 0) : 0;
+  TORCH_CHECK(nbytes > 0, "g_newt_grad: unsupported size (", S, " shapers of width ", W, " and depth ", D, ", B ", B, ", T ", T,
+              "): at most 64 shapers of width 16 and depth 4, T <= 65535, B T <= 2^28");
+  Launch L(exciter);
+  auto opt = exciter.options();
+  std::vector<Tensor> out{at::empty({B, 4 * S, T}, opt)};
+  float* ge = nullptr;
+  if (want_exciter) {
+    out.push_back(at::empty_like(exciter));
+    ge = out.back().data_ptr<float>();
+  }
+  std::vector<float*> gp;
+  if (want_params) {
+    auto add = [&](std::vector<int64_t> shape) {
+      out.push_back(at::empty(shape, opt));
+      gp.push_back(out.back().data_ptr<float>());
+    };
+    add({1, S, 1});
+    for (int64_t l = 0; l < D; ++l) {
+      const int64_t cin = l == 0 ? 1 : W, cout = l == D - 1 ? 1 : W;
+      add({S * cout, cin, 1});
+      add({S * cout});
+    }
+    add({1, S, 1});
+    add({1});
+  }
+  Tensor ws = at::empty({(int64_t)nbytes}, opt.dtype(at::kByte));
+  nws_check(nws_g_newt_grad(d, mix_w.data_ptr<float>(), mix_b.data_ptr<float>(), exciter.data_ptr<float>(), film.data_ptr<float>(),
+                            grad_out.data_ptr<float>(), (int)B, (int)T, NWS_HOP, ge, out[0].data_ptr<float>(),
+                            want_params ? gp.data() : nullptr, ws.data_ptr(), nbytes, L.stream), "nws_g_newt_grad");
+  return out;
+}
+
 // FIRNoiseSynth.forward for any even ir_length >= hop: H (B, L/2+1, T) -> (B, hop * T)
 Tensor g_fir_noise(const Tensor& H, const Tensor& window, const Tensor& noise, int64_t hop) {
   check_dev(H, "H");
@@ -1575,6 +1635,8 @@ TORCH_LIBRARY(newt_hip, m) {
   m.def("g_shaper_apply(Tensor sdesc, Tensor x) -> Tensor", &g_shaper_apply);
   m.def("g_shaper_table(Tensor sdesc, Tensor like, int size, float tmin, float tmax) -> Tensor", &g_shaper_table);
   m.def("g_newt_apply(Tensor sdesc, Tensor exciter, Tensor film, Tensor mix_w, Tensor mix_b) -> Tensor", &g_newt_apply);
+  m.def("g_newt_grad(Tensor sdesc, Tensor exciter, Tensor film, Tensor grad_out, Tensor mix_w, Tensor mix_b, bool want_exciter, "
+        "bool want_params) -> Tensor[]", &g_newt_grad);
   m.def("g_fir_noise(Tensor H, Tensor window, Tensor noise, int hop) -> Tensor", &g_fir_noise);
   m.def("g_reverb_direct(Tensor x, Tensor ir) -> Tensor", &g_reverb_direct);
   m.def("stream_step(Tensor wdesc, Tensor fir_design, Tensor? plan, Tensor? reverb_tables, Tensor? reverb_spectrum, Tensor(a!) state, "

@@ -82,13 +82,15 @@ class TrainableNonlinearity(nn.Module):
         return sa.call("shaper_apply", self._desc.get(sa.shaper_fields(self)), x)
 
 
-_NEWT_GRAD_KEYS = ("shaping_fn.input_scale", "shaping_fn.net.0.weight", "shaping_fn.net.0.bias", "shaping_fn.net.2.weight",
-                   "shaping_fn.net.2.bias", "shaping_fn.net.4.weight", "shaping_fn.net.4.bias", "shaping_fn.net.6.weight",
-                   "shaping_fn.net.6.bias", "mixer.0.weight", "mixer.0.bias")       # the op's eleven, in its order
+def _newt_grad_keys(depth):
+    """the 2 depth + 3 keys of the sample-rate part's parameter gradients, in the order of the newt_grad / g_newt_grad ops"""
+    return ("shaping_fn.input_scale", *(f"shaping_fn.net.{2 * l}.{k}" for l in range(depth) for k in ("weight", "bias")),
+            "mixer.0.weight", "mixer.0.bias")
 
 
 class _NEWTFunction(torch.autograd.Function):
-    """NEWT.forward with its backward attached (csrc/newt_grad.hip): saves the two inputs; backward is
+    """NEWT.forward with its backward attached (csrc/newt_grad.hip; any other bank size csrc/g_newt_grad.hip,
+    DESIGN.md 3.20): saves the two inputs; backward is
     ``NEWT.vjp`` and hands gradients to the exciter, the control embedding and every parameter that requires grad"""
 
     @staticmethod
@@ -113,11 +115,12 @@ class _NEWTFunction(torch.autograd.Function):
 
 @gin.configurable
 class NEWT(nn.Module):
-    """``differentiable`` (a plain attribute, default False): forward only, as the stage kernels are.  Set to True (packaged
-    sizes only: 64 shapers of width 8 and depth 4, hop 128, one output channel), a forward under grad mode whose exciter,
-    control embedding or parameters require grad returns the same bits with a ``torch.autograd.Function`` attached that saves
-    the two inputs; its backward hands gradients to both and to each of the 25 parameters that requires grad.  ``vjp`` is the
-    same gradient without autograd."""
+    """``differentiable`` (a plain attribute, default False): forward only, as the stage kernels are.  Set to True (hop 128,
+    one output channel, sine activations; up to 64 shapers of width up to 16 and depth up to 4), a forward under grad mode whose
+    exciter, control embedding or parameters require grad returns the same bits with a ``torch.autograd.Function`` attached that
+    saves the two inputs; its backward hands gradients to both and to each of the parameters that requires grad (25 at depth 4).
+    ``vjp`` is the same gradient without autograd.  The packaged size set (64 shapers of width 8 and depth 4) runs
+    csrc/newt_grad.hip, every other one csrc/g_newt_grad.hip."""
 
     differentiable = False      # also the value of a module unpickled from before the flag existed
 
@@ -157,16 +160,34 @@ class NEWT(nn.Module):
         mb = sa._req(self.mixer[0].bias.detach(), "newt.mixer.0.bias")
         return sa.call("g_newt_apply", self._g_shaper(), exciter, film, mw, mb)
 
-    def _need_backward(self, hop=None):
-        """the backward kernel serves the packaged sizes, and a forward that carries it never calls the inner modules"""
+    def _need_backward(self, hop=None, device=None):
+        """True for the packaged size set (csrc/newt_grad.hip), False for another one the runtime-size backward serves
+        (csrc/g_newt_grad.hip); raises for everything else.  A forward that carries a backward never calls the inner modules.
+        ``device``: of the exciter - on the runtime-size path the refusal of a CPU tensor names the size set."""
         sh = self._modules["shaping_fn"]
-        if not NEWT._specialised(self, sa._lib.HOP if hop is None else hop):
-            raise RuntimeError("NEWT: the backward (csrc/newt_grad.hip) exists for 64 shapers of width 8 and depth 4, hop 128 and one "
-                               f"output channel only; this is {self.n_waveshapers} shapers of width {sh.width} and depth {sh.depth}, "
-                               f"hop {sa._lib.HOP if hop is None else hop}, {self.mixer[0].out_channels} output channel(s), which "
-                               "runs on the runtime-size path and has no backward")
+        hop = sa._lib.HOP if hop is None else hop
+        sizes = f"this is {self.n_waveshapers} shapers of width {sh.width} and depth {sh.depth}"
+        packaged = NEWT._specialised(self, sa._lib.HOP)
         if not all(isinstance(m, Sine) for m in list(sh.net)[1::2]):
             raise RuntimeError("NEWT: the backward implements the sine activations NEWT configures (nonlinearity=Sine)")
+        if hop != sa._lib.HOP or self.mixer[0].out_channels != 1:
+            raise RuntimeError(f"NEWT: the backward exists for hop {sa._lib.HOP} and one output channel only (the noise branch and the "
+                               f"GRU fix the hop: their runtime-size forms have no backward); {sizes}, hop {hop}, "
+                               f"{self.mixer[0].out_channels} output channel(s)")
+        if not packaged and device is not None and device.type != "cuda":
+            raise RuntimeError(f"NEWT: the backward needs tensors on an AMD GPU (no CPU fallback), the exciter is on {device}; {sizes}, "
+                               "which runs on the runtime-size path (csrc/g_newt_grad.hip)")
+        if not packaged and not (1 <= self.n_waveshapers <= 64 and 1 <= sh.width <= 16 and 1 <= sh.depth <= 4):
+            raise RuntimeError("NEWT: the runtime-size backward (csrc/g_newt_grad.hip) exists for at most 64 shapers of width at most 16 "
+                               f"and depth at most 4; {sizes}")
+        return packaged
+
+    def _need_backward_for(self, exciter, control_embedding):
+        """``_need_backward`` on the unchecked pair: the hop where the shapes give one, and the exciter's device"""
+        hop = None
+        if getattr(exciter, "ndim", 0) == 3 and getattr(control_embedding, "ndim", 0) == 3 and control_embedding.shape[2] >= 1:
+            hop = exciter.shape[2] // control_embedding.shape[2]
+        return self._need_backward(hop, exciter.device if isinstance(exciter, torch.Tensor) else None)
 
     def _checked_pair(self, exciter, control_embedding):
         exciter = sa.contiguous(exciter, "exciter")
@@ -185,34 +206,43 @@ class NEWT(nn.Module):
         return self._newt_desc.get(tensors, scalars)
 
     def _forward_detached(self, exciter, control_embedding):
-        """the forward of the packaged sizes on checked, detached inputs (callers hold no_grad): the two launches of ``forward``"""
+        """the forward on checked, detached inputs (callers hold no_grad): the launches of ``forward`` for the module's size set"""
         film = self.mlp(control_embedding)
+        if not NEWT._specialised(self, exciter.shape[2] // film.shape[2]):
+            return self._forward_generic(exciter, film)
         return sa.call("newt_apply", self._wdesc(), exciter, film)
 
     def vjp(self, grad_out, exciter, control_embedding, want_params=True, want_exciter=True):
-        """(dL/d(exciter) (B, 64, N) | None, dL/d(control_embedding) (B, 128, T), {state-dict key relative to this module:
-        gradient}) of ``forward`` at (exciter, control_embedding) for grad_out = dL/d(out) (B, 1, N); the 25 keys ``mlp.net.*``,
-        ``shaping_fn.*`` and ``mixer.0.*``, an empty dict without ``want_params``.  Reruns ``self.mlp`` for the FiLM parameters,
-        takes their gradient and the sample-rate part from the ``newt_grad`` op (csrc/newt_grad.hip) and the
-        MLP's part from ``td_mlp_vjp``.  Whatever ``differentiable`` and the grad mode say; autograd is not involved and the
-        results carry no graph."""
+        """(dL/d(exciter) (B, S, N) | None, dL/d(control_embedding) (B, 128, T), {state-dict key relative to this module:
+        gradient}) of ``forward`` at (exciter, control_embedding) for grad_out = dL/d(out) (B, 1, N); the keys ``mlp.net.*``,
+        ``shaping_fn.*`` and ``mixer.0.*`` (25 at depth 4), an empty dict without ``want_params``.  Reruns ``self.mlp`` for the FiLM
+        parameters, takes their gradient and the sample-rate part from the ``newt_grad`` op (csrc/newt_grad.hip, DESIGN.md 3.18;
+        the packaged size set) or the ``g_newt_grad`` op (csrc/g_newt_grad.hip; any other) and the MLP's part from
+        ``td_mlp_vjp``.  Whatever ``differentiable`` and the grad mode say; autograd is not involved and the results carry no
+        graph."""
         with torch.no_grad():
-            self._need_backward()
+            self._need_backward_for(exciter, control_embedding)
             exciter, emb = self._checked_pair(exciter.detach(), control_embedding.detach())
             g = sa.contiguous(grad_out.detach(), "grad_out")
-            self._need_backward(exciter.shape[2] // emb.shape[2])
+            packaged = self._need_backward(exciter.shape[2] // emb.shape[2])
             if g.numel() != exciter.shape[0] * exciter.shape[2] or g.shape[0] != exciter.shape[0]:
                 raise RuntimeError(f"NEWT: grad_out {tuple(g.shape)} is not ({exciter.shape[0]}, 1, {exciter.shape[2]})")
             if g.device != exciter.device:
                 raise RuntimeError(f"exciter is on {exciter.device} but grad_out is on {g.device}")
             film = self.mlp(emb)
-            out = sa.binding().newt_grad(self._wdesc(), exciter, film, g, bool(want_exciter), bool(want_params))
+            if packaged:
+                out = sa.binding().newt_grad(self._wdesc(), exciter, film, g, bool(want_exciter), bool(want_params))
+            else:
+                mw = sa._req(self.mixer[0].weight.detach(), "newt.mixer.0.weight")
+                mb = sa._req(self.mixer[0].bias.detach(), "newt.mixer.0.bias")
+                out = sa.binding().g_newt_grad(self._g_shaper(), exciter, film, g, mw, mb, bool(want_exciter), bool(want_params))
             g_emb, mg = td_mlp_vjp(emb, self.mlp.net, out[0], want_params)
             g_exc = out[1] if want_exciter else None
             if not want_params:
                 return g_exc, g_emb, {}
+            keys = _newt_grad_keys(self._modules["shaping_fn"].depth)
             grads = {"mlp.net." + k: v for k, v in mg.items()}
-            grads.update(zip(_NEWT_GRAD_KEYS, out[-len(_NEWT_GRAD_KEYS):]))
+            grads.update(zip(keys, out[-len(keys):]))
             return g_exc, g_emb, grads
 
     def forward(self, exciter, control_embedding):
@@ -221,7 +251,7 @@ class NEWT(nn.Module):
         if self.differentiable and torch.is_grad_enabled():
             params = list(self.parameters())
             if any(isinstance(t, torch.Tensor) and t.requires_grad for t in (exciter, control_embedding, *params)):
-                self._need_backward()
+                self._need_backward_for(exciter, control_embedding)
                 e, c = self._checked_pair(exciter.detach(), control_embedding.detach())
                 self._need_backward(e.shape[2] // c.shape[2])
                 if sa.has_hooks(self.waveshaping_index, self.normalising_coeff, self.mixer, self.mixer[0], self._modules.get("shaping_fn")):

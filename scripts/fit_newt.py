@@ -22,6 +22,10 @@ draws of the render (phase offsets, noise excitation) come from the device gener
 step: the printed losses are values of one fixed objective and a run repeats to the bit.  There is no FastNEWT option: the lookup
 table has no backward and training uses the exact shapers, as the reference does.  The output is written in the input's format and
 differs from the input checkpoint in exactly the fitted keys; `NeuralWaveshaping.load_from_checkpoint` reads it.
+
+`--model-gin` names the model's gin file when it is not the packaged one.  A model with another waveshaper bank (up to 64 shapers of
+width up to 16 and depth up to 4), harmonic count, sample rate or reverb length fits in all three modes: its oscillator branch's
+backward is csrc/g_newt_grad.hip, and the tensor counts above change with the shapers' depth.
 """
 import importlib
 import os
