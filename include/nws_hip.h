@@ -830,6 +830,33 @@ int nws_forward_generic(const NwsGenericModel* m, const float* f0, const float* 
                         const void* reverb_tables, const void* reverb_spectrum, void* reverb_workspace,
                         size_t reverb_workspace_bytes, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * ---- Stateful streaming on the runtime-size path (csrc/generic.hip): nws_stream_step's contract for any model
+ * nws_forward_generic takes whose control hop is 128, whose noise filter has 256 taps under a window symmetric about tap 128
+ * (the caller checks the window, as for nws_frame_mlps) and whose impulse response fits the ring (ir_len < 32 768).  The
+ * argument list is nws_stream_step's with the model descriptor in place of NwsWeights; the design matrix, the impulse response
+ * and its length come from the descriptor.  nws_stream_reset, nws_stream_out_samples, nws_stream_noise_draws and
+ * nws_stream_noise_start serve both paths; the state blob has its own layout (nws_g_stream_state_bytes, nws_g_stream_reverb_tail).
+ * One call is one chunk of K <= max_frames frames: out (B, M), M = nws_stream_out_samples(K, first, final); phase_u and
+ * rand_phase hold n_harmonics values; out_channels > 1 are summed (models/neural_waveshaping.py:84-86).  Nothing is allocated,
+ * read back or synchronised, and every refusal is decided before the first launch, with outputs and state untouched:
+ * NWS_ERR_BAD_ARG for a NULL required pointer, an incomplete descriptor, B < 1, K < 1, K > max_frames, C < control_size, both or
+ * neither of noise_new / noise_all, `first` disagreeing with frames_seen == 0, or a chunk beyond 2048 samples without a plan that
+ * holds ir_len + M samples; NWS_ERR_UNSUPPORTED for another hop or filter length, ir_len >= 32 768, B > 65 535 or layer widths
+ * the stage kernels refuse; NWS_ERR_WORKSPACE for a state blob smaller than nws_g_stream_state_bytes (which is 0 for every
+ * size that is refused).
+ */
+size_t nws_g_stream_state_bytes(const NwsGenericModel* m, int B, int max_frames, int ir_len, const NwsReverbPlan* plan);
+int nws_g_stream_step(const NwsGenericModel* m, const NwsReverbPlan* plan, const void* reverb_tables, const void* reverb_spectrum,
+                      void* state, size_t state_bytes, int B, int max_frames, const float* f0 /* (B,K) */,
+                      const float* control /* (B,C,K) */, int C, int K, int first, int final, long long frames_seen,
+                      long long nz_prev_start, float sample_rate, const float* phase_u, const float* rand_phase,
+                      const float* noise_new, const float* noise_all, int noise_all_len, float* out /* (B, M) */,
+                      float* pre_out /* optional (B, M) */, void* stream);
+int nws_g_stream_reverb_tail(const NwsGenericModel* m, const NwsReverbPlan* plan, const void* reverb_tables,
+                             const void* reverb_spectrum, void* state, size_t state_bytes, int B, int max_frames,
+                             float* tail_out /* (B, ir_len + 1) */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Diagnostic entry points (kernel ablations for timing, the co-execution hazard probes) are declared in nws_hip_debug.h: they are
  * exported by the same library but are not part of the product ABI. */
 

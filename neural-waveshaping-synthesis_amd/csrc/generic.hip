@@ -1805,3 +1805,303 @@ int nws_forward_generic(const NwsGenericModel* m, const float* f0, const float* 
 }
 
 }  // extern "C"
+
+// ---- stateful streaming on the runtime-size path (the contract of stream.hip's nws_stream_step) --------------
+// One chunk of K frames on the window [previous frame | K new frames]: nws_g_gru with carried state, the frame MLPs on the new
+// frames, the windows (channel-major FiLM rows, half-tap rows, the shared noise window), the phase with the carried float64
+// sum, g_exciter_newt_fused on the window, and the noise branch, residue, reverb-input ring and reverb of stream.hip.
+namespace {
+
+constexpr int kGsRing = NWS_STREAM_RING;
+constexpr int kGsMaxDirect = 2048;       // samples per step of the time-domain reverb (stream.hip)
+constexpr int kGsHalf = NWS_FIR_LEN / 2;
+
+struct GsLayout {
+  size_t h, h_next, prev_f0, prev_film, prev_fir, S, residue, ring, counters, nzwin;                         // state
+  size_t gru_ws, gru_bth, gru_bht, emb, film_new, H, fir_new, dmat, f0_w, film_w, fir_w, f0_up, phase, tab;   // scratch
+  size_t newt, newt_sum, exciter, shaped, osc, noise_w, pre, partial, x_lin, y_lin, rv_ws;
+  size_t gru_ws_bytes, rv_ws_bytes, total;
+  int parts;
+  bool stages;
+};
+
+// what the hop's launchers would refuse, asked before anything is launched
+bool gs_serves(const NwsGenericModel* m, int B) {
+  if (m->hop != NWS_HOP || m->fir_len != NWS_FIR_LEN || m->ir_len >= kGsRing / 2 || B > 65535) return false;
+  if (m->n_harmonics > 65535 || m->n_shapers > 65535 || (m->out_channels + 7) / 8 > 65535) return false;
+  if (g_gru_stream_lds(m->gru_hidden, m->control_size) > 160 * 1024) return false;
+  auto mlp_fits = [](int in_size, int hidden) {
+    const int maxw = in_size > hidden ? in_size : hidden;
+    return ((size_t)2 * maxw * 33 + 512) * sizeof(float) <= 160 * 1024;      // nws_td_mlp's staging
+  };
+  if (!mlp_fits(m->gru_hidden, m->embedding) || !mlp_fits(m->embedding, m->embedding) || !mlp_fits(m->embedding, m->hgen_hidden))
+    return false;
+  return shaper_lds(&m->shaper) <= 160 * 1024;
+}
+
+GsLayout gs_layout(const NwsGenericModel* m, int B, int max_frames, int ir_len, size_t fft_ws_bytes) {
+  GsLayout L{};
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += al(bytes);
+    return at;
+  };
+  const size_t K = max_frames, Tw = K + 1, Nw = 128 * Tw;
+  const size_t Hh = m->gru_hidden, E = m->embedding, FC = (size_t)4 * m->n_shapers, S = m->n_shapers, OC = m->out_channels;
+  L.h = take(B * Hh * 4);
+  L.h_next = take(B * Hh * 4);
+  L.prev_f0 = take((size_t)B * 4);
+  L.prev_film = take(B * FC * 4);
+  L.prev_fir = take((size_t)B * kGsHalf * 4);
+  L.S = take((size_t)B * 8);
+  L.residue = take((size_t)B * 64 * 4);
+  L.ring = take((size_t)B * kGsRing * 4);
+  L.counters = take(64);
+  L.nzwin = take((Nw + 128 + 8) * 4);
+  L.gru_ws_bytes = nws_g_gru_workspace_bytes(m->gru_hidden);
+  L.gru_ws = take(L.gru_ws_bytes);
+  L.gru_bth = take(B * K * Hh * 4);
+  L.gru_bht = take(B * K * Hh * 4);
+  L.emb = take(B * K * E * 4);
+  L.film_new = take(B * K * FC * 4);
+  L.H = take((size_t)B * K * (kGsHalf + 1) * 4);
+  L.fir_new = take((size_t)B * K * kGsHalf * 4);
+  L.dmat = take((size_t)NWS_FIR_LEN * 132 * 4);
+  L.f0_w = take((size_t)B * Tw * 4);
+  L.film_w = take(B * Tw * FC * 4);
+  L.fir_w = take((size_t)B * Tw * kGsHalf * 4);
+  L.f0_up = take((size_t)B * Nw * 4);
+  L.phase = take((size_t)B * Nw * 4);
+  L.tab = take(g_tab_floats(m) * 4);
+  L.newt = take(B * OC * Nw * 4);
+  L.newt_sum = OC > 1 ? take((size_t)B * Nw * 4) : L.newt;
+  // the sizes decide the kernel family, not the window length: the stage kernels need the oscillator bank in memory
+  L.stages = g_exciter_plan(m->n_shapers, m->n_harmonics, m->out_channels, m->hop, m->shaper.lut == nullptr, B, 128).family == kGExcStages;
+  if (L.stages || m->shaper.lut == nullptr) {
+    L.exciter = take(B * S * Nw * 4);
+    L.shaped = take(B * S * Nw * 4);
+  }
+  if (L.stages) L.osc = take((size_t)B * m->n_harmonics * Nw * 4);
+  L.noise_w = take((size_t)B * Nw * 4);
+  L.pre = take((size_t)B * Nw * 4);
+  L.parts = (ir_len + 255) / 256;
+  L.partial = take((size_t)L.parts * B * (Nw < (size_t)kGsMaxDirect ? Nw : (size_t)kGsMaxDirect) * 4);
+  if (Nw > (size_t)kGsMaxDirect) {
+    L.x_lin = take((size_t)B * (ir_len + Nw) * 4);
+    L.y_lin = take((size_t)B * (ir_len + Nw) * 4);
+    L.rv_ws_bytes = fft_ws_bytes;
+    L.rv_ws = take(fft_ws_bytes);
+  }
+  L.total = o;
+  return L;
+}
+
+// The runtime-size counterpart of stream_prep_kernel.  blocks 0..B-1: one utterance each - the F0 window (B, Tw), the FiLM window
+// (B, FC, Tw) CHANNEL-major as the runtime-size kernels read it, the half-tap window (B, Tw, 128), each the previous frame
+// followed by the new ones; the last frame saved for the next chunk; the GRU state handed over.  block B: the shared noise
+// window and the previous step's pending counters.
+__global__ __launch_bounds__(256) void g_stream_windows_kernel(const float* __restrict__ f0_new, const float* __restrict__ film_new,
+                                                               const float* __restrict__ fir_new, int K, int first, int B, int FC, int Hh,
+                                                               float* __restrict__ prev_f0, float* __restrict__ prev_film,
+                                                               float* __restrict__ prev_fir, float* __restrict__ h,
+                                                               const float* __restrict__ h_next, float* __restrict__ f0_w,
+                                                               float* __restrict__ film_w, float* __restrict__ fir_w, NwsStreamNoiseWin Z) {
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x;
+  if (b == B) {
+    nws_stream_noise_window_block<256>(Z, tid);
+    return;
+  }
+  const int off = first ? 0 : 1, Tw = K + off;
+  for (int i = tid; i < Tw; i += 256) f0_w[(size_t)b * Tw + i] = (i < off) ? prev_f0[b] : f0_new[(size_t)b * K + i - off];
+  for (int i = tid; i < FC * Tw; i += 256) {
+    const int c = i / Tw, t = i - c * Tw;
+    film_w[(size_t)b * FC * Tw + i] = (t < off) ? prev_film[(size_t)b * FC + c] : film_new[((size_t)b * FC + c) * K + t - off];
+  }
+  for (int i = tid; i < Tw * kGsHalf; i += 256) {
+    const int t = i / kGsHalf, c = i - t * kGsHalf;
+    fir_w[(size_t)b * Tw * kGsHalf + i] = (t < off) ? prev_fir[(size_t)b * kGsHalf + c] : fir_new[((size_t)b * K + t - off) * kGsHalf + c];
+  }
+  for (int j = tid; j < Hh; j += 256) h[(size_t)b * Hh + j] = h_next[(size_t)b * Hh + j];
+  __syncthreads();   // the windows are complete and prev_* has been consumed
+  if (tid == 0) prev_f0[b] = f0_new[(size_t)b * K + K - 1];
+  for (int c = tid; c < FC; c += 256) prev_film[(size_t)b * FC + c] = film_new[((size_t)b * FC + c) * K + K - 1];
+  for (int c = tid; c < kGsHalf; c += 256) prev_fir[(size_t)b * kGsHalf + c] = fir_new[((size_t)b * K + K - 1) * kGsHalf + c];
+}
+
+// g_phase_kernel on a stream's window of N = 128 Tw samples: the inclusive float64 sum starts from the carried S[b] at sample
+// `lo` (0 in the stream's first window, else 64: the first sample not yet emitted - samples in front of it were interpolated with
+// a left clamp the one-shot never applied there and contribute nothing; their phase is a placeholder that is not emitted) and
+// S[b] becomes the sum through sample hi - 1, the last one this step emits.  Sums of fp32 values in float64 are exact, so the
+// sum at every emitted sample is the one-shot forward's whatever the chunking; the fp32 chain behind it is g_phase_kernel's.
+__global__ __launch_bounds__(1024) void g_stream_phase_kernel(const float* __restrict__ f0_w, int Tw, int N, float sample_rate, int lo,
+                                                              int hi, int keep, double* __restrict__ S, float* __restrict__ f0_up_out,
+                                                              float* __restrict__ phase_out) {
+  __shared__ double tot[1024];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int per = (N + 1023) / 1024;
+  const int n0 = tid * per, n1 = n0 + per < N ? n0 + per : N;
+  const float* x = f0_w + (size_t)b * Tw;
+  const float scale = (float)Tw / (float)N;
+  const double s0 = S[b];
+  auto value = [&](int n) {
+    const GLerp L = g_lerp_coeff(n, Tw, scale);
+    return fmaf(L.w0, x[L.i0], L.w1 * x[L.i1]);
+  };
+  double s = 0.0;
+  for (int n = n0; n < n1; ++n) s += n >= lo ? (double)value(n) : 0.0;
+  tot[tid] = s;
+  __syncthreads();   // (every thread has read S[b])
+  for (int off = 1; off < 1024; off <<= 1) {
+    const double v = tid >= off ? tot[tid - off] : 0.0;
+    __syncthreads();
+    tot[tid] += v;
+    __syncthreads();
+  }
+  double run = s0 + (tid > 0 ? tot[tid - 1] : 0.0);
+  for (int n = n0; n < n1; ++n) {
+    const float v = value(n);
+    if (n >= lo) run += (double)v;
+    const float c = (float)run;
+    const float tc = kTauF * c;
+    phase_out[(size_t)b * N + n] = __fdiv_rn(tc, sample_rate);
+    f0_up_out[(size_t)b * N + n] = v;
+    if (keep && n == hi - 1) S[b] = run;
+  }
+}
+
+// sum over the NEWT output channels (models/neural_waveshaping.py:84-86 sums them with the noise branch): (B, OC, N) -> (B, N)
+__global__ __launch_bounds__(256) void g_channel_sum_kernel(const float* __restrict__ x, int OC, int N, float* __restrict__ y) {
+  const int b = blockIdx.y;
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  float acc = x[(size_t)b * OC * N + n];
+  for (int c = 1; c < OC; ++c) acc += x[((size_t)b * OC + c) * N + n];
+  y[(size_t)b * N + n] = acc;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nws_g_stream_state_bytes(const NwsGenericModel* m, int B, int max_frames, int ir_len, const NwsReverbPlan* plan) {
+  if (!model_ok(m) || B <= 0 || max_frames <= 0 || max_frames > (1 << 20) || ir_len != m->ir_len || !gs_serves(m, B)) return 0;
+  return gs_layout(m, B, max_frames, ir_len, plan ? nws_reverb_workspace_bytes(plan, B) : 0).total;
+}
+
+int nws_g_stream_step(const NwsGenericModel* m, const NwsReverbPlan* plan, const void* reverb_tables, const void* reverb_spectrum,
+                      void* state, size_t state_bytes, int B, int max_frames, const float* f0, const float* control, int C, int K,
+                      int first, int final, long long frames_seen, long long nz_prev_start, float sample_rate, const float* phase_u,
+                      const float* rand_phase, const float* noise_new, const float* noise_all, int noise_all_len, float* out,
+                      float* pre_out, void* stream) {
+  if (!model_ok(m) || !state || !f0 || !control || !phase_u || !rand_phase || !out) return NWS_ERR_BAD_ARG;
+  if (B <= 0 || K <= 0 || max_frames <= 0 || max_frames > (1 << 20) || K > max_frames || C < m->control_size || !(sample_rate > 0.0f))
+    return NWS_ERR_BAD_ARG;
+  if ((noise_new == nullptr) == (noise_all == nullptr)) return NWS_ERR_BAD_ARG;
+  if ((first != 0) != (frames_seen == 0)) return NWS_ERR_BAD_ARG;
+  if (!gs_serves(m, B)) return NWS_ERR_UNSUPPORTED;
+  const GsLayout L = gs_layout(m, B, max_frames, m->ir_len, plan ? nws_reverb_workspace_bytes(plan, B) : 0);
+  if (L.total > state_bytes) return NWS_ERR_WORKSPACE;
+  const int Tw = first ? K : K + 1, Nw = 128 * Tw;
+  const int lo = first ? 0 : 64, hi = final ? Nw : Nw - 64, M = hi - lo;
+  if (M > kGsMaxDirect) {
+    if (!plan || !reverb_tables || !reverb_spectrum || L.x_lin == 0) return NWS_ERR_BAD_ARG;
+    if (m->ir_len + M > plan->L || plan->Lc != 0) return NWS_ERR_BAD_ARG;
+  }
+  const long long nz_start = nws_stream_noise_start(first, frames_seen);
+  const long long have = first ? 0 : 128 * (frames_seen - 1) + 129;       // absolute end of what the noise window holds now
+  const int n_new = noise_new ? nws_stream_noise_draws(K, first, frames_seen) : 0;
+  const int nz_keep = first ? 0 : (int)(have - nz_start);
+  const int nz_shift = first ? 0 : (int)(nz_start - nz_prev_start);
+  if (nz_shift < 0 || nz_keep < 0 || nz_keep + nz_shift > 128 * (max_frames + 1) + 129) return NWS_ERR_BAD_ARG;
+  // frame t of the window covers nzwin[128 t - origin, +256): see stream.hip
+  const long long A0 = first ? 0 : frames_seen - 1;
+  const int origin = A0 == 0 ? 128 : 0;
+  const int n_have = (int)(128 * (A0 + Tw - 1) + 129 - nz_start);
+  const int n_len = final ? (int)(128 * (A0 + Tw) - 1 - nz_start) : n_have;
+  if (n_len < 2) return NWS_ERR_BAD_ARG;
+
+  char* base = static_cast<char*>(state);
+  auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+  long long* counters = reinterpret_cast<long long*>(base + L.counters);
+  double* S = reinterpret_cast<double*>(base + L.S);
+  hipStream_t st = (hipStream_t)stream;
+  const int Sn = m->n_shapers, Kh = m->n_harmonics, OC = m->out_channels, FC = 4 * Sn, Hh = m->gru_hidden, E = m->embedding;
+  int rc;
+#define G(call)                  \
+  do {                           \
+    rc = (call);                 \
+    if (rc != NWS_OK) return rc; \
+  } while (0)
+  // 1. control encoder on the new frames, state carried; proj and both frame MLPs on the new frames only
+  G(nws_g_gru(m->gru_w_ih, m->gru_w_hh, m->gru_b_ih, m->gru_b_hh, control, B, C, m->control_size, Hh, K, first ? nullptr : F(L.h),
+              F(L.gru_bth), F(L.h_next), base + L.gru_ws, L.gru_ws_bytes, stream));
+  G(nws_g_bth_to_bht(F(L.gru_bth), B, K, Hh, F(L.gru_bht), stream));
+  {
+    const float* w1[1] = {m->proj_w};
+    const float* b1[1] = {m->proj_b};
+    const float* none[1] = {nullptr};
+    G(nws_td_mlp(F(L.gru_bht), B, Hh, E, E, 1, K, w1, b1, none, none, m->ln_eps, m->leaky_slope, F(L.emb), stream));
+  }
+  G(nws_td_mlp(F(L.emb), B, E, E, FC, m->newt_mlp_depth, K, m->newt_mlp_w, m->newt_mlp_b, m->newt_ln_g, m->newt_ln_b, m->ln_eps,
+               m->leaky_slope, F(L.film_new), stream));
+  G(nws_td_mlp(F(L.emb), B, E, m->hgen_hidden, kGsHalf + 1, m->hgen_depth, K, m->hgen_w, m->hgen_b, m->hgen_ln_g, m->hgen_ln_b,
+               m->ln_eps, m->leaky_slope, F(L.H), stream));
+  // half-taps of the new frames: the design matrix of the model's own window (symmetric about tap 128: the caller's check)
+  G(nws_fir_design_matrix(m->noise_window, F(L.dmat), stream));
+  G(nws_fir_from_h(F(L.H), F(L.dmat), B, K, F(L.fir_new), stream));
+  // 2. windows, previous frame, GRU state hand-over, noise window, pending counters
+  const NwsStreamNoiseWin Z{F(L.nzwin), noise_new, noise_all, counters, nz_shift, nz_keep, n_new, noise_all_len, first, K};
+  g_stream_windows_kernel<<<B + 1, 256, 0, st>>>(f0, F(L.film_new), F(L.fir_new), K, first, B, FC, Hh, F(L.prev_f0), F(L.prev_film),
+                                                 F(L.prev_fir), F(L.h), F(L.h_next), F(L.f0_w), F(L.film_w), F(L.fir_w), Z);
+  NWS_CHECK_LAUNCH();
+  // 3. phase with the carried float64 sum
+  g_stream_phase_kernel<<<B, 1024, 0, st>>>(F(L.f0_w), Tw, Nw, sample_rate, lo, hi, final ? 0 : 1, S, F(L.f0_up), F(L.phase));
+  NWS_CHECK_LAUNCH();
+  // 4. oscillator bank -> NEWT output on the window (its FiLM upsample clamps at the window's edges: samples outside [lo, hi))
+  float* exciter = L.exciter ? F(L.exciter) : nullptr;
+  float* shaped = L.shaped ? F(L.shaped) : nullptr;
+  rc = L.stages ? NWS_ERR_UNSUPPORTED
+                : g_exciter_newt_fused(m, F(L.f0_up), F(L.phase), phase_u, rand_phase, F(L.film_w), B, Tw, Nw, sample_rate, F(L.tab),
+                                       F(L.newt), exciter, shaped, stream);
+  if (rc == NWS_ERR_UNSUPPORTED && L.stages) {
+    G(nws_g_oscillator(F(L.f0_up), F(L.phase), phase_u, rand_phase, Kh, B, Nw, sample_rate, F(L.osc), stream));
+    G(nws_g_conv1x1(F(L.osc), m->mixer_w, m->mixer_b, B, Kh, Sn, Nw, exciter, stream));
+    G(nws_g_film_shaper(&m->shaper, exciter, F(L.film_w), B, Tw, m->hop, shaped, stream));
+    G(nws_g_conv1x1(shaped, m->newt_out_w, m->newt_out_b, B, Sn, OC, Nw, F(L.newt), stream));
+  } else if (rc != NWS_OK) {
+    return rc;
+  }
+  if (OC > 1) {
+    g_channel_sum_kernel<<<dim3((Nw + 255) / 256, B), 256, 0, st>>>(F(L.newt), OC, Nw, F(L.newt_sum));
+    NWS_CHECK_LAUNCH();
+  }
+  // 5. noise branch on the same window, then the emitted samples, the residue, the ring and the linear reverb (stream.hip)
+  G(nws_fir_noise_window(F(L.fir_w), F(L.nzwin), n_len, origin, nullptr, B, Tw, F(L.noise_w), stream));
+#undef G
+  const int R0 = first ? 0 : 64, noise_off = first ? 0 : 128;
+  const NwsPreSrc P{F(L.newt_sum), F(L.noise_w), F(L.residue), Nw, lo, R0, noise_off, nullptr};
+  const int tail_from = noise_off + M - R0;
+  const NwsStreamEmit Em{F(L.ring), F(L.residue), counters, F(L.partial), L.parts, L.x_lin ? F(L.x_lin) : nullptr,
+                         L.y_lin ? F(L.y_lin) : nullptr, base + L.rv_ws, L.rv_ws_bytes};
+  return nws_stream_emit(&P, &Em, plan, reverb_tables, reverb_spectrum, m->ir, m->ir_len, B, K, M, final, tail_from, out,
+                         pre_out ? pre_out : F(L.pre), stream);
+}
+
+int nws_g_stream_reverb_tail(const NwsGenericModel* m, const NwsReverbPlan* plan, const void* reverb_tables,
+                             const void* reverb_spectrum, void* state, size_t state_bytes, int B, int max_frames, float* tail_out,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  if (!model_ok(m) || !plan || !reverb_tables || !reverb_spectrum || !state || !tail_out || !workspace || B <= 0 || max_frames <= 0 ||
+      max_frames > (1 << 20))
+    return NWS_ERR_BAD_ARG;
+  if (!gs_serves(m, B)) return NWS_ERR_UNSUPPORTED;
+  // (only the state part of the blob is touched)
+  const GsLayout L = gs_layout(m, B, max_frames, m->ir_len, 0);
+  if (L.nzwin > state_bytes) return NWS_ERR_WORKSPACE;
+  char* base = static_cast<char*>(state);
+  return nws_stream_ring_tail(plan, reverb_tables, reverb_spectrum, reinterpret_cast<float*>(base + L.ring),
+                              reinterpret_cast<long long*>(base + L.counters), B, m->ir_len, tail_out, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"

@@ -529,6 +529,30 @@ __device__ __forceinline__ void nws_stream_head_block(const NwsStreamSide& H, in
   if (!H.final && tid == 0) H.S[b] = cb[nch - 2];    // through the last emitted sample (128 Tw - 64)
 }
 
+// stream.hip: the closing launches of a step on buffers the caller names - the time-domain reverb (partial sums + fixed-order
+// reduction) for M <= 2048, the FFT reverb on ring history above (x_lin == NULL: not provided for) - which also write the ring,
+// the noise residue and the pending counters.  nws_stream_ring_tail: nws_stream_reverb_tail on the ring and counters themselves.
+// Both for nws_g_stream_step (generic.hip), whose state blob has its own layout.  Internal to the library.
+struct NwsStreamEmit {
+  float* ring;
+  float* residue;
+  long long* counters;
+  float* partial;
+  int parts;
+  float* x_lin;
+  float* y_lin;
+  void* rv_ws;
+  size_t rv_ws_bytes;
+};
+extern "C" __attribute__((visibility("hidden"))) int nws_stream_emit(const NwsPreSrc* P, const NwsStreamEmit* E, const NwsReverbPlan* plan,
+                                                                     const void* reverb_tables, const void* reverb_spectrum,
+                                                                     const float* ir, int ir_len, int B, int K, int M, int final,
+                                                                     int tail_from, float* out, float* pre, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int nws_stream_ring_tail(const NwsReverbPlan* plan, const void* reverb_tables,
+                                                                          const void* reverb_spectrum, const float* ring,
+                                                                          const long long* counters, int B, int ir_len,
+                                                                          float* tail_out, void* workspace, size_t workspace_bytes,
+                                                                          void* stream);
 // fir_noise.hip: nws_fir_noise_window with per-row reflection bounds (x: first, y: last noise-window index of the row's voice) and
 // first window frame (z) - the slot mode of a streaming hop.  Internal to the library.
 extern "C" __attribute__((visibility("hidden"))) int nws_fir_noise_window_rows(const float* fir, const float* noise, int origin,

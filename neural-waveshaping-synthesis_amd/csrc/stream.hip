@@ -395,6 +395,40 @@ int nws_stream_noise_draws(int K, int first, long long frames_seen) {
 
 }  // extern "C"
 
+// The closing launches of a step that no earlier launch has taken a share of (nws_common.h): the time-domain reverb in two launches
+// for M <= 2048 emitted samples, the four-step FFT on [ir_len samples of ring history | the M new ones] above.  Shared by
+// nws_stream_step and the runtime-size nws_g_stream_step (generic.hip), whose state blobs differ only in where these buffers sit.
+extern "C" int nws_stream_emit(const NwsPreSrc* Pp, const NwsStreamEmit* E, const NwsReverbPlan* plan, const void* reverb_tables,
+                               const void* reverb_spectrum, const float* ir, int ir_len, int B, int K, int M, int final,
+                               int tail_from, float* out, float* pre, void* stream) {
+  const PreSrc P = *Pp;
+  hipStream_t st = (hipStream_t)stream;
+  if (M <= kMaxDirect) {
+    // two launches: 125 x B workgroups of partial sums, then the fixed-order reduction that also closes the step
+    stream_reverb_partial_kernel<<<dim3(E->parts, (M + 255) / 256, B), 256, 0, st>>>(E->ring, P, ir, ir_len, M, B, E->partial, E->counters);
+    NWS_CHECK_LAUNCH();
+    stream_reverb_reduce_kernel<false><<<dim3((M + 255) / 256, B), 256, 0, st>>>(E->partial, E->parts, P, M, B, K, final, tail_from, out,
+                                                                                 pre, E->ring, E->residue, E->counters, ir, ir_len,
+                                                                                 StreamTail{});
+    NWS_CHECK_LAUNCH();
+    return NWS_OK;
+  }
+  if (!plan || !reverb_tables || !reverb_spectrum || E->x_lin == nullptr) return NWS_ERR_BAD_ARG;
+  const int N = ir_len + M;
+  if (N > plan->L || plan->Lc != 0) return NWS_ERR_BAD_ARG;
+  stream_combine_kernel<<<dim3((M + 255) / 256, B), 256, 0, st>>>(P, M, pre, E->ring, E->counters);
+  NWS_CHECK_LAUNCH();
+  stream_gather_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(E->ring, ir_len, M, N, 0, E->x_lin, E->counters);
+  NWS_CHECK_LAUNCH();
+  const int rc = nws_reverb(plan, reverb_tables, reverb_spectrum, E->x_lin, B, N, E->y_lin, E->rv_ws, E->rv_ws_bytes, stream);
+  if (rc != NWS_OK) return rc;
+  stream_take_kernel<<<dim3((M + 255) / 256, B), 256, 0, st>>>(E->y_lin, N, ir_len, M, out);
+  NWS_CHECK_LAUNCH();
+  stream_close_kernel<<<B + 1, 64, 0, st>>>(P.noise_w, P.Nw, tail_from, final, B, M, K, E->residue, E->counters);
+  NWS_CHECK_LAUNCH();
+  return NWS_OK;
+}
+
 namespace {
 
 // ev != NULL: slot mode (nws_stream_step_slots) - the seven-launch form whatever K, with the per-row events in the windows, the
@@ -544,28 +578,10 @@ int stream_step(const NwsWeights* w, const float* fir_design, const NwsReverbPla
     stream_reverb_reduce_kernel<true><<<dim3(1, B), 256, 0, st>>>(F(L.partial), L.parts, P, M, B, K, final, tail_from, out, pre, F(L.ring),
                                                                   F(L.residue), counters, ir, ir_len, tail);
     NWS_CHECK_LAUNCH();
-  } else if (M <= kMaxDirect) {
-    // two launches: 125 x B workgroups of partial sums, then the fixed-order reduction that also closes the step
-    stream_reverb_partial_kernel<<<dim3(L.parts, (M + 255) / 256, B), 256, 0, st>>>(F(L.ring), P, ir, ir_len, M, B, F(L.partial), counters);
-    NWS_CHECK_LAUNCH();
-    stream_reverb_reduce_kernel<false><<<dim3((M + 255) / 256, B), 256, 0, st>>>(F(L.partial), L.parts, P, M, B, K, final, tail_from, out,
-                                                                                 pre, F(L.ring), F(L.residue), counters, ir, ir_len,
-                                                                                 StreamTail{});
-    NWS_CHECK_LAUNCH();
   } else {
-    if (!plan || !reverb_tables || !reverb_spectrum || L.x_lin == 0) return NWS_ERR_BAD_ARG;
-    const int N = ir_len + M;
-    if (N > plan->L || plan->Lc != 0) return NWS_ERR_BAD_ARG;
-    stream_combine_kernel<<<dim3((M + 255) / 256, B), 256, 0, st>>>(P, M, pre, F(L.ring), counters);
-    NWS_CHECK_LAUNCH();
-    stream_gather_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(F(L.ring), ir_len, M, N, 0, F(L.x_lin), counters);
-    NWS_CHECK_LAUNCH();
-    rc = nws_reverb(plan, reverb_tables, reverb_spectrum, F(L.x_lin), B, N, F(L.y_lin), base + L.rv_ws, L.rv_ws_bytes, stream);
-    if (rc != NWS_OK) return rc;
-    stream_take_kernel<<<dim3((M + 255) / 256, B), 256, 0, st>>>(F(L.y_lin), N, ir_len, M, out);
-    NWS_CHECK_LAUNCH();
-    stream_close_kernel<<<B + 1, 64, 0, st>>>(F(L.noise_w), Nw, tail_from, final, B, M, K, F(L.residue), counters);
-    NWS_CHECK_LAUNCH();
+    const NwsStreamEmit E{F(L.ring), F(L.residue), counters, F(L.partial), L.parts, L.x_lin ? F(L.x_lin) : nullptr, F(L.y_lin),
+                          base + L.rv_ws, L.rv_ws_bytes};
+    return nws_stream_emit(&P, &E, plan, reverb_tables, reverb_spectrum, ir, ir_len, B, K, M, final, tail_from, out, pre, stream);
   }
   return NWS_OK;
 }
@@ -610,19 +626,27 @@ int nws_stream_reverb_tail(const NwsReverbPlan* plan, const void* reverb_tables,
   // (the state blob may have been sized without the FFT scratch of long chunks: only the state part is touched here)
   const Layout L = layout(B, max_frames, ir_len, 0);
   if (L.nzwin > state_bytes) return NWS_ERR_WORKSPACE;
+  char* base = static_cast<char*>(state);
+  return nws_stream_ring_tail(plan, reverb_tables, reverb_spectrum, reinterpret_cast<float*>(base + L.ring),
+                              reinterpret_cast<long long*>(base + L.counters), B, ir_len, tail_out, workspace, workspace_bytes, stream);
+}
+
+// the same on the ring and the counters themselves (nws_common.h): nws_g_stream_reverb_tail finds them in its own layout
+int nws_stream_ring_tail(const NwsReverbPlan* plan, const void* reverb_tables, const void* reverb_spectrum, const float* ring,
+                         const long long* counters, int B, int ir_len, float* tail_out, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  if (!plan || !reverb_tables || !reverb_spectrum || !ring || !counters || !tail_out || !workspace || B <= 0) return NWS_ERR_BAD_ARG;
   const int N = 2 * ir_len + 1;
   if (N > plan->L || plan->Lc != 0) return NWS_ERR_BAD_ARG;
   const size_t lin = al((size_t)B * N * sizeof(float));
   const size_t rvb = nws_reverb_workspace_bytes(plan, B);
   if (workspace_bytes < 2 * lin + rvb) return NWS_ERR_WORKSPACE;
-  char* base = static_cast<char*>(state);
   char* ws = static_cast<char*>(workspace);
   float* x_lin = reinterpret_cast<float*>(ws);
   float* y_lin = reinterpret_cast<float*>(ws + lin);
   hipStream_t st = (hipStream_t)stream;
   // the last step's sample count is still pending: history = [pos + pending - ir_len, pos + pending), then ir_len + 1 zeros
-  stream_gather_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(reinterpret_cast<float*>(base + L.ring), ir_len, ir_len + 1, ir_len, 1,
-                                                                 x_lin, reinterpret_cast<long long*>(base + L.counters));
+  stream_gather_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(ring, ir_len, ir_len + 1, ir_len, 1, x_lin, counters);
   NWS_CHECK_LAUNCH();
   const int rc = nws_reverb(plan, reverb_tables, reverb_spectrum, x_lin, B, N, y_lin, ws + 2 * lin, rvb, stream);
   if (rc != NWS_OK) return rc;

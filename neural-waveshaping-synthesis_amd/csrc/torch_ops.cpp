@@ -1475,20 +1475,21 @@ struct StepDims {
   int64_t B, K, C;
 };
 
-StepDims check_step_tensors(const char* op, const Tensor& f0, const Tensor& control, const Tensor& fir_design, const Tensor& state,
-                            const Tensor& phase_u, const Tensor& rand_phase, const Tensor& ir, const Tensor& out) {
+// (fir_design / ir: NULL for g_stream_step, whose descriptor carries both)
+StepDims check_step_tensors(const char* op, const Tensor& f0, const Tensor& control, const Tensor* fir_design, const Tensor& state,
+                            const Tensor& phase_u, const Tensor& rand_phase, const Tensor* ir, const Tensor& out) {
   check_dev(f0, "f0");
   check_dev(control, "control");
-  check_dev(fir_design, "fir_design");
+  if (fir_design) check_dev(*fir_design, "fir_design");
   check_dev(state, "state", at::kByte);
   check_dev(phase_u, "phase_u");
   check_dev(rand_phase, "rand_phase");
-  check_dev(ir, "reverb.ir");
+  if (ir) check_dev(*ir, "reverb.ir");
   check_dev(out, "out");
   check_same_device(f0, "f0", control, "control");
   check_same_device(f0, "f0", state, "state");
   check_same_device(f0, "f0", out, "out");
-  check_same_device(f0, "f0", ir, "reverb.ir");
+  if (ir) check_same_device(f0, "f0", *ir, "reverb.ir");
   TORCH_CHECK(f0.dim() == 2 && control.dim() == 3 && control.size(0) == f0.size(0) && control.size(2) == f0.size(1) && control.size(1) >= 2,
               op, ": f0 (B, K), control (B, C>=2, K); got ", f0.sizes(), " / ", control.sizes());
   return {f0.size(0), f0.size(1), control.size(1)};
@@ -1496,8 +1497,9 @@ StepDims check_step_tensors(const char* op, const Tensor& f0, const Tensor& cont
 
 void check_step_io(const char* op, const StepDims& d, bool first, bool final, int64_t frames_seen, const Tensor& phase_u,
                    const Tensor& rand_phase, const OptTensor& noise_new, const OptTensor& noise_all, const Tensor& out,
-                   const OptTensor& pre_out) {
-  TORCH_CHECK(phase_u.numel() == NWS_N_HARMONICS && rand_phase.numel() == NWS_N_HARMONICS, "phase_u / rand_phase: 101 elements each");
+                   const OptTensor& pre_out, int64_t n_harmonics = NWS_N_HARMONICS) {
+  TORCH_CHECK(phase_u.numel() == n_harmonics && rand_phase.numel() == n_harmonics, "phase_u / rand_phase: ", n_harmonics,
+              " elements each");
   TORCH_CHECK(noise_new.has_value() != noise_all.has_value(), op, ": give exactly one of noise_new and noise_all");
   const int M = nws_stream_out_samples((int)d.K, first, final);
   TORCH_CHECK(out.numel() == d.B * M, "out: expected (", d.B, ", ", M, "), got ", out.sizes());
@@ -1521,7 +1523,7 @@ void stream_step(const Tensor& wdesc, const Tensor& fir_design, const OptTensor&
                  const Tensor& rand_phase, const OptTensor& noise_new, const OptTensor& noise_all, const Tensor& ir, Tensor& out,
                  const OptTensor& pre_out) {
   const NwsWeights* w = weights_of(wdesc);
-  const StepDims d = check_step_tensors("stream_step", f0, control, fir_design, state, phase_u, rand_phase, ir, out);
+  const StepDims d = check_step_tensors("stream_step", f0, control, &fir_design, state, phase_u, rand_phase, &ir, out);
   const int64_t B = d.B, K = d.K, C = d.C;
   TORCH_CHECK(K >= 1 && K <= max_frames, "stream_step: chunk of ", K, " frames, the stream was sized for ", max_frames);
   check_step_io("stream_step", d, first, final, frames_seen, phase_u, rand_phase, noise_new, noise_all, out, pre_out);
@@ -1553,7 +1555,7 @@ void stream_step_slots(const Tensor& wdesc, const Tensor& fir_design, Tensor& st
                        const Tensor& rand_phase, const OptTensor& noise_new, const OptTensor& noise_all, const Tensor& ir,
                        const Tensor& events, Tensor& out, const OptTensor& pre_out) {
   const NwsWeights* w = weights_of(wdesc);
-  const StepDims d = check_step_tensors("stream_step_slots", f0, control, fir_design, state, phase_u, rand_phase, ir, out);
+  const StepDims d = check_step_tensors("stream_step_slots", f0, control, &fir_design, state, phase_u, rand_phase, &ir, out);
   const int64_t B = d.B, K = d.K, C = d.C;
   check_dev(events, "events", at::kInt);
   check_same_device(f0, "f0", events, "events");
@@ -1570,6 +1572,40 @@ void stream_step_slots(const Tensor& wdesc, const Tensor& fir_design, Tensor& st
                                   ir.data_ptr<float>(), (int)ir.numel(), events.data_ptr<int>(), out.data_ptr<float>(),
                                   pre_out.has_value() ? pre_out->data_ptr<float>() : nullptr, L.stream),
             "nws_stream_step_slots");
+}
+
+// ---- the same step on the runtime-size path (csrc/generic.hip nws_g_stream_step): the model descriptor in place of the weights ----
+void g_stream_step(const Tensor& gdesc, const OptTensor& plan_t, const OptTensor& tables, const OptTensor& spectrum, Tensor& state,
+                   int64_t max_frames, const Tensor& f0, const Tensor& control, bool first, bool final, int64_t frames_seen,
+                   int64_t nz_prev_start, double sample_rate, const Tensor& phase_u, const Tensor& rand_phase,
+                   const OptTensor& noise_new, const OptTensor& noise_all, Tensor& out, const OptTensor& pre_out) {
+  const NwsGenericModel* m = struct_of<NwsGenericModel>(gdesc, "gdesc");
+  TORCH_CHECK(m->hop > 0 && m->n_harmonics > 0, "gdesc: not a NwsGenericModel");
+  const StepDims d = check_step_tensors("g_stream_step", f0, control, nullptr, state, phase_u, rand_phase, nullptr, out);
+  const int64_t B = d.B, K = d.K, C = d.C;
+  TORCH_CHECK(K >= 1 && K <= max_frames, "g_stream_step: chunk of ", K, " frames, the stream was sized for ", max_frames);
+  check_step_io("g_stream_step", d, first, final, frames_seen, phase_u, rand_phase, noise_new, noise_all, out, pre_out, m->n_harmonics);
+  NwsReverbPlan plan{};
+  const bool fft = plan_t.has_value();
+  if (fft) {
+    TORCH_CHECK(tables.has_value() && spectrum.has_value(), "g_stream_step: plan without tables / spectrum");
+    plan = plan_of(*plan_t);
+    check_dev(*tables, "reverb_tables");
+    check_dev(*spectrum, "reverb_spectrum");
+    check_reverb_buffers(plan, *tables, *spectrum);
+  }
+  const size_t need = nws_g_stream_state_bytes(m, (int)B, (int)max_frames, m->ir_len, fft ? &plan : nullptr);
+  TORCH_CHECK(need != 0, "g_stream_step: the runtime-size stream does not serve this model (control hop 128, 256 noise taps, an "
+              "impulse response below 32768 taps)");
+  TORCH_CHECK((size_t)state.numel() >= need, "g_stream_step: state blob too small");
+  Launch L(f0);
+  nws_check(nws_g_stream_step(m, fft ? &plan : nullptr, fft ? tables->data_ptr() : nullptr, fft ? spectrum->data_ptr() : nullptr,
+                              state.data_ptr(), (size_t)state.numel(), (int)B, (int)max_frames, f0.data_ptr<float>(),
+                              control.data_ptr<float>(), (int)C, (int)K, first ? 1 : 0, final ? 1 : 0, (long long)frames_seen,
+                              (long long)nz_prev_start, (float)sample_rate, phase_u.data_ptr<float>(), rand_phase.data_ptr<float>(),
+                              fptr(noise_new), fptr(noise_all), noise_all.has_value() ? (int)noise_all->numel() : 0,
+                              out.data_ptr<float>(), pre_out.has_value() ? pre_out->data_ptr<float>() : nullptr, L.stream),
+            "nws_g_stream_step");
 }
 
 int64_t abi_version() { return nws_abi_version(); }
@@ -1647,6 +1683,10 @@ TORCH_LIBRARY(newt_hip, m) {
         "int nz_prev_start, float sample_rate, Tensor phase_u, Tensor rand_phase, Tensor? noise_new, Tensor? noise_all, Tensor ir, "
         "Tensor events, Tensor(b!) out, Tensor(c!)? pre_out) -> ()",
         &stream_step_slots);
+  m.def("g_stream_step(Tensor gdesc, Tensor? plan, Tensor? reverb_tables, Tensor? reverb_spectrum, Tensor(a!) state, int max_frames, "
+        "Tensor f0, Tensor control, bool first, bool final, int frames_seen, int nz_prev_start, float sample_rate, Tensor phase_u, "
+        "Tensor rand_phase, Tensor? noise_new, Tensor? noise_all, Tensor(b!) out, Tensor(c!)? pre_out) -> ()",
+        &g_stream_step);
   m.def("loudness(Tensor audio, Tensor dft, int n_fft, int hop, float amin, float top_db, bool normalise) -> Tensor", &loudness);
   m.def("pyin_table(float sample_rate, float fmin, float fmax, int frame_length, int hop) -> Tensor", &pyin_table);
   m.def("pyin_cmnd(Tensor audio, float sample_rate, float fmin, float fmax, int frame_length, int hop) -> Tensor", &pyin_cmnd);

@@ -484,13 +484,15 @@ def ensure_default_config():
 
 
 def _stream(self, batch_size: int = 1, *, phase_u=None, noise=None, slots: bool = False, **kw):
-    """Stateful streaming synthesiser bound to this model (see streaming.NewtStream; kw: max_chunk_frames, graph).
-    slots=True: B voice slots that start and stop on their own (streaming.VoiceStream; kw: graph)."""
-    from ..streaming import NewtStream, VoiceStream
+    """Stateful streaming synthesiser bound to this model (see streaming.NewtStream; kw: max_chunk_frames, graph).  A model of
+    another architecture than gin/models/newt.gin gets the same stream on the runtime-size kernels (streaming.GenericNewtStream).
+    slots=True: B voice slots that start and stop on their own (streaming.VoiceStream; kw: graph; the packaged architecture only)."""
+    from ..streaming import GenericNewtStream, NewtStream, VoiceStream
 
     if slots:
         return VoiceStream(self, batch_size, phase_u=phase_u, noise=noise, **kw)
-    return NewtStream(self, batch_size, phase_u=phase_u, noise=noise, **kw)
+    cls = NewtStream if self._engine.specialised() else GenericNewtStream
+    return cls(self, batch_size, phase_u=phase_u, noise=noise, **kw)
 
 
 NeuralWaveshaping.stream = _stream

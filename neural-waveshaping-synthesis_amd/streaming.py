@@ -22,6 +22,9 @@ hipGraph and replayed (`graph=True`, the default): a 256-sample hop is then one 
     RMS, not bit for bit (hops of one or two frames take another frame-MLP kernel than longer chunks, chunks beyond 2048
     samples sum the reverb in another order).
 
+`GenericNewtStream` is the same stream for a model of another architecture (bank, harmonics, layer sizes, sample rate, reverb
+length): one push = one `g_stream_step` (`nws_g_stream_step`, the runtime-size kernels); `model.stream` picks the class.
+
 `VoiceStream` (`model.stream(B, slots=True)`, `nws_stream_step_slots`) is the slot mode: B voices that start and stop on their
 own in one batched stream, with per-slot events as device data; its docstring states the contract.
 """
@@ -93,47 +96,57 @@ class _StreamBase:
         250 ms of wall-clock (a full fingerprint walk costs ~12 us of host time: too much for every 256-sample hop, nothing once
         per sixteen 16 ms hops).  So for up to 250 ms after such an update graph=True and graph=False streams differ; `refresh()`
         closes that window on demand."""
-        eng = self.eng
         now = time.monotonic()
         if now - self.__dict__.get("_last_walk", 0.0) >= 0.25:
             self._last_walk = now
-            if eng._w is not None and eng._fingerprint() != eng._fp:
-                eng._wd()                              # rebuilds (drains the device first)
-        if eng._w is not self.__dict__.get("_w_seen"):
+            self._rewalk()
+        rec = self._record()
+        if rec is not self.__dict__.get("_w_seen"):
             if self._graphs:
                 torch.cuda.synchronize(self.dev)
                 self._graphs.clear()
                 self._steady_runs.clear()
-            self._w_seen = eng._w
+            self._w_seen = rec
+
+    def _record(self):
+        """The engine's current record of pointers and derived tables (replaced, never edited, on a rebuild)."""
+        return self.eng._w
+
+    def _rewalk(self):
+        """One fingerprint walk; rebuilds the record if a parameter changed (drains the device first)."""
+        eng = self.eng
+        if eng._w is not None and eng._fingerprint() != eng._fp:
+            eng._wd()
+
+    def _tail_call(self, L, plan, tables, spec, tail, ws, nb):
+        return L.nws_stream_reverb_tail(C.byref(plan), tables.data_ptr(), spec.data_ptr(), self._state.data_ptr(),
+                                        self._state.numel(), self.B, self.max_frames, self._ir_len, tail.data_ptr(),
+                                        ws.data_ptr(), nb, stream_ptr(self.dev)), "nws_stream_reverb_tail"
 
     def reverb_tail(self) -> torch.Tensor:
         """The remaining (B, ir_len + 1) reverb tail of every row after the last chunk (what a linear reverb still rings out)."""
-        eng = self.eng
-        eng._wd()
-        plan, tables, spec, _ = eng._reverb_aux(self._plan_n)
+        plan, tables, spec, _ = self._reverb_plan()
         L = _lib.lib()
         with torch.cuda.device(self.dev):
             tail = torch.empty((self.B, self.tail_len), dtype=torch.float32, device=self.dev)
             nb = 2 * ((self.B * (2 * self._ir_len + 1) * 4 + 255) // 256 * 256) + L.nws_reverb_workspace_bytes(C.byref(plan), self.B)
             ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
-            _lib.check(L.nws_stream_reverb_tail(C.byref(plan), tables.data_ptr(), spec.data_ptr(), self._state.data_ptr(),
-                                                self._state.numel(), self.B, self.max_frames, self._ir_len, tail.data_ptr(),
-                                                ws.data_ptr(), nb, stream_ptr(self.dev)), "nws_stream_reverb_tail")
+            _lib.check(*self._tail_call(L, plan, tables, spec, tail, ws, nb))
         return tail
+
+    def _reverb_plan(self):
+        """(plan, tables, IR spectrum, plan tensor) of the stream's FFT reverb length, for the current weights."""
+        self.eng._wd()
+        return self.eng._reverb_aux(self._plan_n)
 
 
 class NewtStream(_StreamBase):
     def __init__(self, model, batch_size: int, phase_u: torch.Tensor | None = None, noise: torch.Tensor | None = None,
                  max_chunk_frames: int = _MAX_CHUNK_FRAMES, graph: bool = True):
-        if not model._engine.specialised():
-            raise RuntimeError("stateful streaming runs on the fused kernels: the model must have the architecture of "
-                               "gin/models/newt.gin")
         self.model = model
         self.eng = model._engine
-        w, _, dev = self.eng.weights()
-        self.dev = dev
         self.B = int(batch_size)
-        self._ir_len = int(self.eng.ir().numel())
+        self._bind()               # self.dev, self._ir_len, self._n_harmonics: from the path's own record of the model
         self.tail_len = self._ir_len + 1
         if self._ir_len >= _RING // 2:
             raise RuntimeError(f"stateful streaming keeps {_RING // 2 - 1} samples of reverb history per utterance; this model's impulse "
@@ -145,7 +158,7 @@ class NewtStream(_StreamBase):
         fit = (self._plan_n - self._ir_len) // HOP - 1
         self.max_frames = int(min(max(1, max_chunk_frames), fit))
         self.phase_u = _req((phase_u if phase_u is not None else torch.rand_like(model.osc.rand_phase)).reshape(-1),
-                            "phase_u", _lib.N_HARMONICS)
+                            "phase_u", self._n_harmonics)
         self._noise_all = _req(noise, "noise") if noise is not None else None    # parity mode: the reference's whole draw
         self.frames_seen = 0
         self.samples_emitted = 0
@@ -153,8 +166,9 @@ class NewtStream(_StreamBase):
         self._nz_prev_start = 0
         self._need_fft = HOP * (self.max_frames + 1) > 2048
         L = _lib.lib()
-        plan = self.eng.reverb_aux(self._plan_n)[0] if self._need_fft else None
-        nbytes = L.nws_stream_state_bytes(self.B, self.max_frames, self._ir_len, C.byref(plan) if plan is not None else None)
+        plan = self._reverb_plan()[0] if self._need_fft else None
+        nbytes = self._state_bytes(L, C.byref(plan) if plan is not None else None)
+        dev = self.dev
         with torch.cuda.device(dev):
             self._state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             _lib.check(L.nws_stream_reset(self._state.data_ptr(), nbytes, stream_ptr(dev)), "nws_stream_reset")
@@ -163,6 +177,17 @@ class NewtStream(_StreamBase):
         self._steady_runs = {}     # (K, channels) -> CONSECUTIVE steady-state pushes seen
         self._last_K = None
         self._last_pre = None
+
+    def _bind(self):
+        if not self.eng.specialised():
+            raise RuntimeError("stateful streaming runs on the fused kernels: the model must have the architecture of "
+                               "gin/models/newt.gin")
+        _, _, self.dev = self.eng.weights()
+        self._ir_len = int(self.eng.ir().numel())
+        self._n_harmonics = _lib.N_HARMONICS
+
+    def _state_bytes(self, L, plan_ref):
+        return L.nws_stream_state_bytes(self.B, self.max_frames, self._ir_len, plan_ref)
 
     # ---- one call of the binding ------------------------------------------------------------------------------------
     def _step(self, f0_2d, control, first, final, noise_new, out, pre):
@@ -258,6 +283,75 @@ class NewtStream(_StreamBase):
         self.samples_emitted += M
         self._last_K = K
         self.finished = bool(final)
+
+
+class GenericNewtStream(NewtStream):
+    """NewtStream for a model that `Engine.specialised()` turns down (another bank, harmonic count, GRU / MLP size, sample rate,
+    reverb length, several NEWT output channels): the same contract and methods, one push = one `g_stream_step` of the binding
+    (`nws_g_stream_step`, csrc/generic.hip) - the runtime-size stage kernels on the window, the noise branch,
+    ring and reverb of csrc/stream.hip.  The noise branch, the ring and the 64-sample emission delay are the packaged stream's,
+    so three sizes are fixed: control hop 128, 256 noise taps, a window symmetric about tap 128.  What it watches for weight
+    updates is the GenericEngine's descriptor record."""
+
+    def _bind(self):
+        m, eng = self.model, self.eng
+        ns = m.noise_synth
+        if int(m.control_hop) != HOP or int(ns.hop_length) != HOP:
+            raise RuntimeError(f"stateful streaming runs at a control hop of {HOP} samples: this model has control_hop = "
+                               f"{int(m.control_hop)}, FIRNoiseSynth.hop_length = {int(ns.hop_length)} - render it with the one-shot "
+                               f"forward, which serves every hop")
+        if int(ns.ir_length) != _lib.FIR_LEN:
+            raise RuntimeError(f"stateful streaming filters the noise with {_lib.FIR_LEN} taps per frame: this model has "
+                               f"FIRNoiseSynth.ir_length = {int(ns.ir_length)} - render it with the one-shot forward, which serves "
+                               f"every even length")
+        if not eng._window_symmetric():
+            w = ns.window.detach().float().cpu()
+            asym = float((w[1:HOP] - w[HOP + 1:].flip(0)).abs().max())
+            raise RuntimeError(f"stateful streaming hands half of every frame's noise taps on: the window must be symmetric about tap "
+                               f"{HOP} with window[0] = 0, this model's has window[0] = {float(w[0]):.6g} and differs by up to "
+                               f"{asym:.3g} between mirrored taps - render it with the one-shot forward, which serves every window")
+        r = eng.generic.model_desc()
+        self.dev = r.device
+        self._ir_len = int(r.ir.numel())
+        self._n_harmonics = int(r.struct.n_harmonics)
+
+    def _state_bytes(self, L, plan_ref):
+        r = self.eng.generic.model_desc()
+        nbytes = L.nws_g_stream_state_bytes(C.byref(r.struct), self.B, self.max_frames, self._ir_len, plan_ref)
+        if nbytes == 0:
+            raise RuntimeError("stateful streaming: the runtime-size kernels do not serve this model's layer sizes - render it "
+                               "with the one-shot forward")
+        return nbytes
+
+    def _record(self):
+        return self.eng.generic._cache
+
+    def _rewalk(self):
+        self.eng.generic.model_desc()
+
+    def _reverb_plan(self):
+        g = self.eng.generic
+        r = g.model_desc()
+        return g._reverb_aux(self._plan_n, r.device, r.ir)
+
+    def _capture(self, K, C_in):
+        self.eng.generic.model_desc()     # a rebuild synchronises: in front of the capture, never inside it
+        return super()._capture(K, C_in)
+
+    def _tail_call(self, L, plan, tables, spec, tail, ws, nb):
+        r = self.eng.generic.model_desc()
+        return L.nws_g_stream_reverb_tail(C.byref(r.struct), C.byref(plan), tables.data_ptr(), spec.data_ptr(), self._state.data_ptr(),
+                                          self._state.numel(), self.B, self.max_frames, tail.data_ptr(), ws.data_ptr(), nb,
+                                          stream_ptr(self.dev)), "nws_g_stream_reverb_tail"
+
+    def _step(self, f0_2d, control, first, final, noise_new, out, pre):
+        g = self.eng.generic
+        r = g.model_desc()
+        _, tables, spec, plan_t = g._reverb_aux(self._plan_n, r.device, r.ir) if self._need_fft else (None, None, None, None)
+        binding().g_stream_step(r.gdesc, plan_t, tables, spec, self._state, self.max_frames, f0_2d, control, bool(first), bool(final),
+                                int(self.frames_seen), int(self._nz_prev_start), self.eng.osc_sample_rate(), self.phase_u,
+                                r.rand_phase, noise_new, self._noise_all, out, pre)
+
 
 # ---- slot mode: B voices with their own lifetimes in one batched stream ------------------------------------------------
 SLOT_START, SLOT_STOP, SLOT_RELEASE, SLOT_ACTIVE = 1, 2, 4, 8   # include/nws_hip.h NWS_SLOT_*

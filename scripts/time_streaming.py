@@ -5,7 +5,10 @@ every push carries GRU / phase / noise / reverb state and applies the 2 s reverb
 (csrc/stream.hip); steady-state hops replay a hipGraph unless --no-graph.  Host wall-clock per push is reported beside the
 HIP-event latency (a push returns a fresh tensor: input copy + graph launch + output copy).
 --slots: the slot mode (model.stream(B, slots=True)) under a random note-on / note-off schedule (every hop each idle slot starts
-with probability --note-on, each active one stops with probability --note-off); same timing, events written every hop."""
+with probability --note-on, each active one stops with probability --note-off); same timing, events written every hop.
+--model-gin FILE: a model of another architecture (its stream runs on the runtime-size kernels), with the weights
+of --checkpoint, or seeded random ones when none is named: the hop's latency depends on the sizes, not on the values.
+--runtime-size: the packaged model on the runtime-size stream, to compare the two paths on one set of sizes."""
 import importlib
 import os
 import sys
@@ -19,7 +22,9 @@ sys.path.insert(0, ROOT)
 
 
 @click.command()
-@click.option("--checkpoint", default=os.path.join(ROOT, "tests", "golden", "weights_vn.npz"))
+@click.option("--checkpoint", default=None, help="default: the packaged weights, or seeded random ones with --model-gin")
+@click.option("--model-gin", default=None, help="the model's gin file when it is not the packaged one")
+@click.option("--runtime-size", is_flag=True, default=False, help="force the runtime-size stream (GenericNewtStream)")
 @click.option("--batch-size", default=1)
 @click.option("--hop-frames", default=2)
 @click.option("--num-hops", default=500)
@@ -34,11 +39,17 @@ sys.path.insert(0, ROOT)
 @click.option("--seed", default=0)
 @click.option("--gc/--no-gc", "keep_gc", default=True, help="--no-gc: Python's cyclic garbage collector off during the timed hops "
               "(what a host with a real-time audio callback does); reported in the result")
-def main(checkpoint, batch_size, hop_frames, num_hops, use_fast_newt, graph, static_io, json_out, slots, note_on, note_off, seed,
-         keep_gc):
+def main(checkpoint, model_gin, runtime_size, batch_size, hop_frames, num_hops, use_fast_newt, graph, static_io, json_out, slots, note_on,
+         note_off, seed, keep_gc):
     nws = importlib.import_module("neural-waveshaping-synthesis_amd")
     nws.ensure_default_config()
-    model = nws.NeuralWaveshaping.load_from_checkpoint(checkpoint).cuda().eval()
+    if model_gin:
+        nws.gin.parse_config_file(model_gin)
+    if checkpoint is None and model_gin:
+        torch.manual_seed(seed)
+        model = nws.NeuralWaveshaping().cuda().eval()
+    else:
+        model = nws.NeuralWaveshaping.load_from_checkpoint(checkpoint or os.path.join(ROOT, "tests", "golden", "weights_vn.npz")).cuda().eval()
     if use_fast_newt:
         model.newt = nws.FastNEWT(model.newt)
     K = hop_frames
@@ -56,7 +67,10 @@ def main(checkpoint, batch_size, hop_frames, num_hops, use_fast_newt, graph, sta
         return {"start": start, "stop": stop}
 
     with torch.no_grad():
-        s = model.stream(batch_size, graph=graph, slots=True) if slots else model.stream(batch_size, graph=graph)
+        if runtime_size and not slots:
+            s = importlib.import_module("neural-waveshaping-synthesis_amd.streaming").GenericNewtStream(model, batch_size, graph=graph)
+        else:
+            s = model.stream(batch_size, graph=graph, slots=True) if slots else model.stream(batch_size, graph=graph)
         for _ in range(20):
             s.push(f0, control, **events())
         if static_io:
@@ -87,13 +101,13 @@ def main(checkpoint, batch_size, hop_frames, num_hops, use_fast_newt, graph, sta
             lat.append(e0.elapsed_time(e1) * 1e3)
     gc.enable()
     lat, wall = np.array(lat), np.array(wall)
-    period = K * 128 / 16000.0 * 1e6
-    res = {"batch": batch_size, "hop_samples": K * 128, "graph": bool(graph), "static_io": bool(static_io), "hops": num_hops, "python_gc": bool(keep_gc),
+    period = K * 128 / float(model.sample_rate) * 1e6
+    res = {"stream": type(s).__name__, "batch": batch_size, "hop_samples": K * 128, "graph": bool(graph), "static_io": bool(static_io), "hops": num_hops, "python_gc": bool(keep_gc),
            "slots": bool(slots), "events": n_events,
            "p50_us": float(np.percentile(lat, 50)), "p99_us": float(np.percentile(lat, 99)), "max_us": float(lat.max()),
            "wall_p50_us": float(np.percentile(wall, 50)), "wall_p99_us": float(np.percentile(wall, 99)),
            "x_realtime_p50": period / float(np.percentile(lat, 50))}
-    print(f"stateful streaming{' (slots, %d events)' % n_events if slots else ''}, batch {batch_size}, hop {K * 128} samples ({period / 1e3:.1f} ms), graph={graph}, static_io={static_io}, gc={keep_gc}: p50 {res['p50_us']:.1f} us  "
+    print(f"{type(s).__name__}: stateful streaming{' (slots, %d events)' % n_events if slots else ''}, batch {batch_size}, hop {K * 128} samples ({period / 1e3:.1f} ms), graph={graph}, static_io={static_io}, gc={keep_gc}: p50 {res['p50_us']:.1f} us  "
           f"p99 {res['p99_us']:.1f} us  (host wall p50 {res['wall_p50_us']:.1f} / p99 {res['wall_p99_us']:.1f} us)  -> "
           f"{res['x_realtime_p50']:.1f}x real-time")
     if json_out:
