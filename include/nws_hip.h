@@ -721,6 +721,30 @@ int nws_adam_step(const NwsAdamTensor* tensors, int n, long long step, double lr
                   double max_norm, float* total_norm, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * ---- Gradient averaging for data-parallel training (csrc/grad_reduce.hip) -------------------------------
+ * The ranks' gradients travel as rows of one (world, row_stride) buffer (an all-gather: data only); the mean is formed here in
+ * rank order, so every rank holds the same bits whatever carried the rows.  No atomics, every output element written by one
+ * thread.  Both launch on `stream`, read nothing back and decide every refusal before the first launch.
+ *
+ * nws_grad_pack: the n tensors (a HOST array of records of device pointers; each tensor contiguous, 4-byte aligned) copied one
+ * after the other into dst[0 .. sum n); at most NWS_ADAM_TABLE tensors per launch.  NWS_ERR_BAD_ARG for n < 1, a NULL pointer, a
+ * tensor of fewer than 1 element or dst_elems < sum n; NWS_ERR_UNSUPPORTED for a tensor above 2^40 elements.
+ *
+ * nws_grad_reduce: for i < n
+ *   out[i] = (float)((sum_{r = 0 .. world-1} (double)rows[r row_stride + i]) / (double)world)
+ * the sum in float64 in ascending r, divided once in float64, rounded once to float32; NaN and Inf follow the formula; world = 1
+ * returns the row's own bits.  NWS_ERR_BAD_ARG for a NULL pointer, world < 1, n < 1, row_stride < n, or out[0 .. n) overlapping
+ * [rows, rows + world row_stride); NWS_ERR_UNSUPPORTED for world > NWS_GRAD_MAX_WORLD or a row_stride above 2^40.
+ */
+#define NWS_GRAD_MAX_WORLD 1024
+typedef struct NwsGradTensor {
+  const float* src;
+  size_t n;
+} NwsGradTensor;
+int nws_grad_pack(const NwsGradTensor* tensors, int n, float* dst, size_t dst_elems, void* stream);
+int nws_grad_reduce(const float* rows, int world, size_t n, size_t row_stride, float* out, void* stream);
+
+/*
  * ---- Runtime-size path (csrc/generic.hip): every gin-configurable size of the reference ------------------------------
  * The fused kernels above are compiled for gin/models/newt.gin.  These entry points take the sizes as arguments and run
  * one plain-fp32 stage kernel each (correct first, stage boundaries materialised); nws_forward_generic chains them into

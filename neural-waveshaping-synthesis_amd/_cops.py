@@ -86,6 +86,19 @@ def _mfcc_dims(sample_rate, n_fft, n_mfcc, n_mels):
     return tuple(dims)
 
 
+def _check_dev(name, t, like=None, like_name="out"):
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} lives on {t.device}: the NEWT forward path only runs as HIP kernels on an AMD GPU "
+                           "(there is no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name}: expected Float, got {t.dtype}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name}: expected a contiguous tensor")
+    if like is not None and t.device != like.device:
+        raise RuntimeError(f"{like_name} is on {like.device} but {name} is on {t.device}: all tensors of one call must live on "
+                           "the same GPU")
+
+
 class CtypesOps:
     def abi_version(self):
         return int(_lib.lib().nws_abi_version())
@@ -436,6 +449,39 @@ class CtypesOps:
         # the kernels wrote through raw pointers: everything that caches tables derived from the weights keys on ._version
         torch.autograd.graph.increment_version(list(params) + list(exp_avgs) + list(exp_avg_sqs))
         return total
+
+    def grad_pack(self, tensors, out):
+        n = len(tensors)
+        if n < 1:
+            raise RuntimeError("grad_pack: no tensors")
+        _check_dev("out", out)
+        if out.dim() != 1:
+            raise RuntimeError(f"grad_pack: out: expected a 1-D tensor, got {tuple(out.shape)}")
+        recs = (_lib.NwsGradTensor * n)()
+        for k, t in enumerate(tensors):
+            _check_dev("tensor", t, out)
+            if t.numel() < 1:
+                raise RuntimeError(f"grad_pack: tensor {k} is empty")
+            recs[k] = _lib.NwsGradTensor(ptr(t), t.numel())
+        total = sum(t.numel() for t in tensors)
+        if out.numel() < total:
+            raise RuntimeError(f"grad_pack: out holds {out.numel()} elements, the tensors have {total}")
+        with torch.cuda.device(out.device):
+            check(_lib.lib().nws_grad_pack(recs, n, ptr(out), out.numel(), _stream(out.device)), "nws_grad_pack")
+        torch.autograd.graph.increment_version(out)          # written through a raw pointer
+
+    def grad_reduce(self, rows, out):
+        _check_dev("rows", rows)
+        _check_dev("out", out, rows, "rows")
+        if rows.dim() != 2 or rows.shape[0] < 1:
+            raise RuntimeError(f"grad_reduce: rows: expected (world, stride), got {tuple(rows.shape)}")
+        if out.dim() != 1 or not 1 <= out.numel() <= rows.shape[1]:
+            raise RuntimeError(f"grad_reduce: out: expected a 1-D tensor of 1 .. {rows.shape[1]} elements (the rows' stride), got "
+                               f"{tuple(out.shape)}")
+        with torch.cuda.device(rows.device):
+            check(_lib.lib().nws_grad_reduce(ptr(rows), min(int(rows.shape[0]), 1 << 30), out.numel(), int(rows.shape[1]), ptr(out),
+                                             _stream(rows.device)), "nws_grad_reduce")
+        torch.autograd.graph.increment_version(out)          # written through a raw pointer
 
     # ---- stand-alone stage kernels (csrc/stages.hip) ---------------------------------------------------------------------
     def td_mlp(self, x, weights, biases, ln_w, ln_b, eps, slope):

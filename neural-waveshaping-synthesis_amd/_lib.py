@@ -37,6 +37,7 @@ FIR_DESIGN_COLS = 132
 ADAM_CHUNK = 1024        # elements per workgroup of the optimiser step, and per float64 partial of its norm (NWS_ADAM_CHUNK)
 ADAM_THREADS = 256       # threads that share the sum over the partials (csrc/adam_step.hip)
 ADAM_TABLE = 64          # tensors per launch (NWS_ADAM_TABLE)
+GRAD_MAX_WORLD = 1024    # ranks nws_grad_reduce averages (NWS_GRAD_MAX_WORLD)
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -110,7 +111,12 @@ class NwsAdamTensor(C.Structure):
     _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("n", C.c_longlong)]
 
 
-_PYIN_CFG = (C.c_double, C.c_double, C.c_double, C.c_int, C.c_int)     # sample_rate, fmin, fmax, frame_length, hop
+class NwsGradTensor(C.Structure):
+    """one record of nws_grad_pack's tensor array: the device pointer of a tensor and its element count"""
+    _fields_ = [("src", _fp), ("n", C.c_size_t)]
+
+
+_PYIN_CFG =(C.c_double, C.c_double, C.c_double, C.c_int, C.c_int)     # sample_rate, fmin, fmax, frame_length, hop
 
 _MFCC_CFG = (C.c_double, C.c_int, C.c_int, C.c_int)                       # sample_rate, n_fft, n_mfcc, n_mels
 
@@ -230,6 +236,8 @@ _PROTOTYPES = {
     "nws_adam_workspace_bytes": (C.c_size_t, [C.POINTER(NwsAdamTensor), C.c_int]),
     "nws_adam_step": (C.c_int, [C.POINTER(NwsAdamTensor), C.c_int, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double,
                                 C.c_double, _fp, _fp, C.c_size_t, _fp]),
+    "nws_grad_pack": (C.c_int, [C.POINTER(NwsGradTensor), C.c_int, _fp, C.c_size_t, _fp]),
+    "nws_grad_reduce": (C.c_int, [_fp, C.c_int, C.c_size_t, C.c_size_t, _fp, _fp]),
     "nws_td_mlp": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),
                              C.POINTER(_fp), C.POINTER(_fp), C.c_float, C.c_float, _fp, _fp]),
     "nws_td_mlp_grad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

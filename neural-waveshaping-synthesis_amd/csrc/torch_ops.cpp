@@ -757,6 +757,40 @@ Tensor adam_step(at::TensorList params, at::TensorList grads, at::TensorList exp
   return total;
 }
 
+// Data-parallel training (csrc/grad_reduce.hip).  grad_pack: the listed tensors one after the other into the
+// front of `out` (a 1-D tensor, usually one rank's row of the exchange buffer).  grad_reduce: out[i] = mean over the rows of
+// rows[:, i] for i < out.numel(), summed in float64 in row order.  Both write `out` only, which no cache keys on.
+void grad_pack(at::TensorList tensors, Tensor& out) {
+  const size_t n = tensors.size();
+  TORCH_CHECK(n >= 1, "grad_pack: no tensors");
+  check_dev(out, "out");
+  TORCH_CHECK(out.dim() == 1, "grad_pack: out: expected a 1-D tensor, got ", out.sizes());
+  std::vector<NwsGradTensor> recs(n);
+  int64_t total = 0;
+  for (size_t k = 0; k < n; ++k) {
+    check_dev(tensors[k], "tensor");
+    check_same_device(out, "out", tensors[k], "tensor");
+    TORCH_CHECK(tensors[k].numel() >= 1, "grad_pack: tensor ", k, " is empty");
+    recs[k] = NwsGradTensor{tensors[k].data_ptr<float>(), (size_t)tensors[k].numel()};
+    total += tensors[k].numel();
+  }
+  TORCH_CHECK(out.numel() >= total, "grad_pack: out holds ", out.numel(), " elements, the tensors have ", total);
+  Launch L(out);
+  nws_check(nws_grad_pack(recs.data(), (int)n, out.data_ptr<float>(), (size_t)out.numel(), L.stream), "nws_grad_pack");
+}
+
+void grad_reduce(const Tensor& rows, Tensor& out) {
+  check_dev(rows, "rows");
+  check_dev(out, "out");
+  check_same_device(rows, "rows", out, "out");
+  TORCH_CHECK(rows.dim() == 2 && rows.size(0) >= 1, "grad_reduce: rows: expected (world, stride), got ", rows.sizes());
+  TORCH_CHECK(out.dim() == 1 && out.numel() >= 1 && out.numel() <= rows.size(1), "grad_reduce: out: expected a 1-D tensor of 1 .. ",
+              rows.size(1), " elements (the rows' stride), got ", out.sizes());
+  Launch L(rows);
+  nws_check(nws_grad_reduce(rows.data_ptr<float>(), (int)std::min<int64_t>(rows.size(0), 1 << 30), (size_t)out.numel(),
+                            (size_t)rows.size(1), out.data_ptr<float>(), L.stream), "nws_grad_reduce");
+}
+
 // TimeDistributedMLP.forward (dynamic.py:20-40): x (B, in, T); weights[i] (rows_i, cols_i[, 1]), biases[i]; ln_w / ln_b for
 // every layer but the last
 Tensor td_mlp(const Tensor& x, at::TensorList weights, at::TensorList biases, at::TensorList ln_w, at::TensorList ln_b, double eps,
@@ -1655,6 +1689,8 @@ TORCH_LIBRARY(newt_hip, m) {
         &newt_grad);
   m.def("adam_step(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] exp_avgs, Tensor(c!)[] exp_avg_sqs, int step, float lr, "
         "float beta1, float beta2, float eps, float max_norm) -> Tensor", &adam_step);
+  m.def("grad_pack(Tensor[] tensors, Tensor(a!) out) -> ()", &grad_pack);
+  m.def("grad_reduce(Tensor rows, Tensor(a!) out) -> ()", &grad_reduce);
   m.def("td_mlp(Tensor x, Tensor[] weights, Tensor[] biases, Tensor[] ln_w, Tensor[] ln_b, float eps, float slope) -> Tensor", &td_mlp);
   m.def("td_mlp_grad(Tensor x, Tensor grad_y, Tensor[] weights, Tensor[] biases, Tensor[] ln_w, Tensor[] ln_b, float eps, float slope, "
         "bool want_params) -> Tensor[]", &td_mlp_grad);

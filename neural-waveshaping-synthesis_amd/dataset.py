@@ -42,16 +42,44 @@ class ControlDataset:
         """Round-robin split of the (sorted) item list: independent objects, no collective needed."""
         return self.names[rank::world]
 
+    def groups(self, names, batch_size: int):
+        """The names of every batch `batches` yields, without loading the items (`group_names` over the items' frame counts)."""
+        frames = {n: np.load(os.path.join(self.control_dir, f"control_{n}.npy"), mmap_mode="r").shape[-1] for n in names}
+        return group_names(names, frames, batch_size)
+
+    def collate(self, names):
+        """One batch of the named items (of equal frame count)."""
+        items = [self.item(n) for n in names]
+        return {"names": [it["name"] for it in items],
+                "f0": np.stack([it["f0"] for it in items]),
+                "control": np.stack([it["control"] for it in items]),
+                "audio": [it.get("audio") for it in items]}
+
     def batches(self, names, batch_size: int):
         """Group items of equal frame count (forward needs a rectangular batch), keep file order inside a group."""
-        by_len = defaultdict(list)
-        for n in names:
-            by_len[np.load(os.path.join(self.control_dir, f"control_{n}.npy"), mmap_mode="r").shape[-1]].append(n)
-        for T in sorted(by_len):
-            group = by_len[T]
-            for i in range(0, len(group), batch_size):
-                items = [self.item(n) for n in group[i:i + batch_size]]
-                yield {"names": [it["name"] for it in items],
-                       "f0": np.stack([it["f0"] for it in items]),
-                       "control": np.stack([it["control"] for it in items]),
-                       "audio": [it.get("audio") for it in items]}
+        for group in self.groups(names, batch_size):
+            yield self.collate(group)
+
+
+def group_names(names, frames, batch_size: int):
+    """`names` grouped by frame count (`frames[name]`, ascending), the given order kept inside a group, in runs of at most
+    `batch_size`: the batches of `ControlDataset.batches` as lists of names."""
+    by_len = defaultdict(list)
+    for n in names:
+        by_len[frames[n]].append(n)
+    return [by_len[T][i:i + batch_size] for T in sorted(by_len) for i in range(0, len(by_len[T]), batch_size)]
+
+
+def rank_batches(groups, world: int, rank: int):
+    """Data-parallel training (scripts/train.py --gpus N): `groups` are the global batches, `group_names(order, frames, W b)`.
+    Rank `rank` takes the items `shard_bounds(n, world, rank)` of a global batch of n items; a global batch with n < world is left
+    out on every rank, so every rank takes the same number of steps and none gets an empty batch.
+    -> (this rank's batches as lists of names, the number of global batches left out); world = 1 gives `groups` back."""
+    from .parallel import shard_bounds
+
+    kept = [g for g in groups if len(g) >= world]
+    mine = []
+    for g in kept:
+        lo, hi = shard_bounds(len(g), world, rank)
+        mine.append(list(g[lo:hi]))
+    return mine, len(groups) - len(kept)

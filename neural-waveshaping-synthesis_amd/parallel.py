@@ -575,3 +575,124 @@ class PeerCopyAllGather:
         self._claim(slot)
         self._push(y, slot, self.rank * self.rows)
         return self._signal(slot)
+
+
+class GradientAverager:
+    """Data-parallel training: the ranks' gradients averaged in RANK ORDER by a HIP kernel, the exchange moving
+    data only.  ``GradientAverager(params, group=None, extra=1, kernels=None)``
+
+    A ring all-reduce sums in an order its library chooses (algorithm, channel count, world size); every sum of this package's
+    backward and optimiser step runs in an order fixed by the sizes.  So each rank packs its gradients into its row of one
+    ``(W, stride)`` buffer (``grad_pack``), the rows are all-gathered, and ``grad_reduce`` forms
+    ``float32(sum_r float64(rows[r]) / float64(W))`` with r ascending.  Every rank then holds the same bits: the result does not
+    depend on the backend, the ranks' parameters cannot drift apart (no broadcast after the start), and a W-rank run equals a
+    one-process emulation that packs the W gradients into the rows itself.
+
+    ``params``: the tensors that take part, in a fixed order (the order ``configure_optimizers`` hands to the optimiser), or
+    ``(name, tensor)`` pairs as ``named_parameters()`` yields them - the names are for messages.  ``P = sum numel``;
+    ``stride = P + extra`` rounded up to a multiple of 4.  ``W`` and the rank come from ``group``; with no initialised process
+    group ``W = 1`` and nothing is exchanged.  ``extra``: floats that travel behind the gradients (the loop's detached loss).
+    ``kernels``: an object with ``grad_pack(tensors, out)`` and ``grad_reduce(rows, out)``; default the binding's operators - a
+    parameter for the reason ``render_fn`` is one in this file: a CPU test drives the class over gloo with the numpy restatement.
+
+    Construction ends with ``check_in_sync()``: every rank builds the model from the same seed and checkpoint, and the check holds
+    it to that.  No asynchronous form, no buckets, no overlap with the backward: a row of the packaged model is 1 MB."""
+
+    def __init__(self, params, group=None, extra: int = 1, kernels=None):
+        items = list(params)
+        if not items:
+            raise ValueError("GradientAverager: no parameters")
+        if isinstance(items[0], (tuple, list)):
+            self.names, self.params = [str(n) for n, _ in items], [p for _, p in items]
+        else:
+            self.names, self.params = [f"parameter {k} {tuple(p.shape)}" for k, p in enumerate(items)], items
+        self.group = group
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        self.backend = dist.get_backend(group) if dist.is_initialized() else None
+        self.device = self.params[0].device
+        for name, p in zip(self.names, self.params):
+            self._check(name, p, "it")
+        self.extra = int(extra)
+        if self.extra < 0:
+            raise ValueError(f"GradientAverager: extra = {extra}")
+        self.sizes = [p.numel() for p in self.params]
+        self.P = sum(self.sizes)
+        self.stride = -(-(self.P + self.extra) // 4) * 4
+        self.rows = torch.zeros((self.world, self.stride), dtype=torch.float32, device=self.device)
+        self.mean = torch.zeros(self.stride, dtype=torch.float32, device=self.device)
+        self._no_extra = torch.zeros(self.extra, dtype=torch.float32, device=self.device)
+        if kernels is None:
+            from .engine import binding
+
+            kernels = binding()
+        self.kernels = kernels
+        self.check_in_sync()
+
+    def _check(self, name, t, what):
+        if t is None:
+            raise RuntimeError(f"GradientAverager: {name} has no gradient (.grad is None): every parameter takes part in every step")
+        if t.device != self.device:
+            raise RuntimeError(f"GradientAverager: {name}: {what} lives on {t.device}, the exchange buffer on {self.device}")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"GradientAverager: {name}: {what} is {t.dtype}, expected torch.float32")
+
+    def _tail(self, extra):
+        if extra is None:
+            return [self._no_extra] if self.extra else []
+        if extra.dim() != 1 or extra.numel() != self.extra or extra.device != self.device or extra.dtype != torch.float32:
+            raise RuntimeError(f"GradientAverager: extra: expected a 1-D float32 tensor of {self.extra} elements on {self.device}, got "
+                               f"{tuple(extra.shape)} {extra.dtype} on {extra.device}")
+        return [extra] if self.extra else []
+
+    def _gather(self):
+        """rows[rank] of every rank into rows[r] of every rank; nothing at world size 1"""
+        if self.world == 1:
+            return
+        if self.backend == "nccl":          # in place, on the current stream
+            dist.all_gather_into_tensor(self.rows.view(-1), self.rows[self.rank], group=self.group)
+        else:                               # gloo: the list-of-views form, whose input must not alias its outputs
+            dist.all_gather([self.rows[r] for r in range(self.world)], self.rows[self.rank].clone(), group=self.group)
+
+    @torch.no_grad()
+    def average(self, extra=None):
+        """``p.grad`` of every parameter becomes the mean over the ranks, a view into one buffer; returns the mean of ``extra``
+        (``extra`` floats; the loop passes the detached loss and gets the mean loss back).  Everything is checked before anything
+        is packed or exchanged: a rank that raises has not entered the collective."""
+        grads = [p.grad for p in self.params]
+        for name, g in zip(self.names, grads):
+            self._check(name, g, "its gradient")
+        tail = self._tail(extra)
+        self.kernels.grad_pack([g.contiguous() for g in grads] + tail, self.rows[self.rank])
+        self._gather()
+        self.kernels.grad_reduce(self.rows, self.mean[:self.P + self.extra])
+        off = 0
+        for p, n in zip(self.params, self.sizes):
+            p.grad = self.mean[off:off + n].view_as(p)
+            off += n
+        return self.mean[self.P:self.P + self.extra]
+
+    @torch.no_grad()
+    def check_in_sync(self, tensors=None):
+        """Every rank holds the same bits in ``tensors`` (default: the parameters): they are packed into the row, gathered and
+        compared with rank 0's row on the device; ONE read-back, of the number of differing elements.  Raises RuntimeError naming
+        the first differing parameter - on every rank, since every rank sees the same rows."""
+        tensors = [p.detach() for p in self.params] if tensors is None else list(tensors)
+        if [t.numel() for t in tensors] != self.sizes:
+            raise ValueError("GradientAverager.check_in_sync: the tensors do not have the parameters' sizes")
+        for name, t in zip(self.names, tensors):
+            self._check(name, t, "the tensor")
+        self.kernels.grad_pack([t.contiguous() for t in tensors] + self._tail(None), self.rows[self.rank])
+        self._gather()
+        if self.world == 1:
+            return
+        differs = (self.rows.view(torch.int32)[1:, :self.P] != self.rows.view(torch.int32)[:1, :self.P]).any(dim=0)
+        count = int(differs.sum())          # the read-back
+        if count:
+            first = int(torch.nonzero(differs)[0])
+            k, off = 0, 0
+            while off + self.sizes[k] <= first:
+                off += self.sizes[k]
+                k += 1
+            raise RuntimeError(f"GradientAverager: the ranks are out of sync: {count} elements differ from rank 0's, the first in "
+                               f"{self.names[k]} (element {first - off}): every rank must start from the same seed and checkpoint")

@@ -10,7 +10,11 @@ operator (two launches); `clip_grad_norm_` + `torch.optim.Adam(foreach=True)`; t
 each timed on its own with the same method: the forward link by link, the loss, the backward link by link through the `vjp`
 methods (the chain `training_step` + `backward` run through autograd), and the optimiser.
 
-    python scripts/time_adam_step.py [--training-step] [--batch-size 8] [--frames 500]
+--grad-exchange: the two kernels of data-parallel training (csrc/grad_reduce.hip) on the same tensors in the same
+windows, with the optimiser step beside them: `grad_pack` of the 48 gradients and one loss element into a row, `grad_reduce` of
+W = 2 and W = 8 such rows.  The all-gather between them is not here: one process, one GPU.
+
+    python scripts/time_adam_step.py [--training-step] [--grad-exchange] [--batch-size 8] [--frames 500]
 """
 import importlib
 import json
@@ -95,6 +99,28 @@ def optimiser_variants(nws, model):
             "the same, .grad restored first (foreach)": theirs(foreach=True)}
 
 
+def grad_exchange_variants(nws, model):
+    from importlib import import_module
+
+    b = import_module("neural-waveshaping-synthesis_amd.engine").binding()
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    ps = [torch.nn.Parameter(p.detach().clone()) for p in model.parameters()]
+    for p in ps:
+        p.grad = 1e-3 * torch.randn(p.shape, device="cuda", generator=gen)
+    loss = torch.ones(1, device="cuda")
+    P = sum(p.numel() for p in ps)
+    stride = -(-(P + 1) // 4) * 4
+    rows = {W: torch.randn(W, stride, device="cuda", generator=gen) for W in (2, 8)}
+    mean = torch.zeros(stride, device="cuda")
+    tensors = [p.grad for p in ps] + [loss]
+    opt = nws.optim.Adam(ps, lr=1e-3, max_grad_norm=2.0)
+    out = {"grad_pack (48 gradients + loss into a row)": lambda: b.grad_pack(tensors, rows[2][0])}
+    for W in (2, 8):
+        out[f"grad_reduce W = {W}, P = {P + 1}"] = lambda W=W: b.grad_reduce(rows[W], mean[:P + 1])
+    out["adam_step (nws.optim.Adam.step)"] = opt.step
+    return out
+
+
 def training_step_variants(nws, model, B, T):
     dyn = importlib.import_module("neural-waveshaping-synthesis_amd.models.modules.dynamic")
     gen = torch.Generator(device="cuda").manual_seed(0)
@@ -171,13 +197,14 @@ def training_step_variants(nws, model, B, T):
 
 @click.command()
 @click.option("--training-step", is_flag=True, help="also take one training step apart, link by link")
+@click.option("--grad-exchange", is_flag=True, help="also time grad_pack and grad_reduce (W = 2, 8) beside the optimiser step")
 @click.option("--batch-size", default=8)
 @click.option("--frames", default=500)
 @click.option("--inner", default=3, help="calls per timed window")
 @click.option("--windows", default=7, help="timed windows per variant")
 @click.option("--warmup", default=2)
 @click.option("--json-out", default=None, help="also write the tables as JSON")
-def main(training_step, batch_size, frames, inner, windows, warmup, json_out):
+def main(training_step, grad_exchange, batch_size, frames, inner, windows, warmup, json_out):
     nws = importlib.import_module("neural-waveshaping-synthesis_amd")
     if not torch.cuda.is_available():
         raise SystemExit("time_adam_step: needs the GPU (a CPU run cannot give a time)")
@@ -187,6 +214,9 @@ def main(training_step, batch_size, frames, inner, windows, warmup, json_out):
     print(f"the optimiser step on {len(list(model.parameters()))} tensors, {sum(p.numel() for p in model.parameters())} floats; "
           f"{windows} windows of {inner} calls; ms per call")
     out["optimiser"] = report(timed(optimiser_variants(nws, model), inner, windows, warmup))
+    if grad_exchange:
+        print(f"the gradient exchange's kernels beside the optimiser step; {windows} windows of {inner} calls; ms per call")
+        out["grad_exchange"] = report(timed(grad_exchange_variants(nws, model), inner, windows, warmup))
     if training_step:
         model.differentiable = True
         print(f"one training step at ({batch_size}, {frames}), link by link; ms per call")

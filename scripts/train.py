@@ -1,14 +1,16 @@
 #!/usr/bin/env python
 """Train a model on a dataset written by scripts/create_dataset.py: the counterpart of the reference's scripts/train.py, on one GPU,
-with every gradient and the optimiser step computed by HIP kernels.
+with every gradient and the optimiser step computed by HIP kernels; `--gpus N` trains data-parallel on N
+GPUs of one node.
 
     python scripts/train.py --gin-file neural-waveshaping-synthesis_amd/gin/train/train_newt.gin --dataset-path data/ \\
         --output-dir run/ [--urmp --instrument vn] [--device 0] [--restore-checkpoint run/last.ckpt] [--max-steps N] \\
-        [--batch-size 8] [--seed 0] [--val-every-epochs 1]
+        [--batch-size 8] [--seed 0] [--val-every-epochs 1] [--gpus 1]
 
 The gin file configures the model and the loop (`trainer_kwargs.max_steps`, `trainer_kwargs.gradient_clip_val`, the batch size as
 `GeneralDataModule.batch_size` / `URMPDataModule.batch_size`); `accelerator = 'dp'` of a reference file is ignored with a note:
-single GPU only.  `--load-data-to-memory` is accepted; `--with-wandb` is refused, there is no wandb logging here.
+`--gpus` selects the mode, not the gin file.  `--load-data-to-memory` is accepted; `--with-wandb` is refused, there is no wandb
+logging here.
 
 The loop.  Epoch e walks `ControlDataset(root, "train")` in the order `RandomState(seed + e)` shuffles it into, in batches of items
 of equal length.  Before each step the device generator is seeded with seed + global_step, so the hidden draws of the render are a
@@ -23,11 +25,39 @@ Checkpoints, in Lightning's layout with the optimiser's and the scheduler's stat
 is what `NeuralWaveshaping.load_from_checkpoint` and scripts/timbre_transfer.py take.  `--restore-checkpoint` restores the weights
 and, where the file has them, the optimiser, the scheduler, the step and the epoch (a reference `last.ckpt` resumes with its own
 Adam state); an `.npz` starts fresh optimiser state from its weights.
+
+`--gpus N`, N > 1: data-parallel over N GPUs of this node, what `accelerator = 'dp'` does in the reference.  Typed by hand (no
+WORLD_SIZE in the environment) the script starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node=N` on itself as a
+child process and returns its status; under a launcher WORLD_SIZE and `--gpus` must agree.  N above the GPU count is refused
+(status 2).  Rank r uses GPU LOCAL_RANK, the process group is "nccl" (RCCL) with a timeout of 120 s; a rank that raises exits
+non-zero, the launcher ends its peers, nothing retries.  (NWS_TRAIN_SHARE_GPU=1, for tests: every rank uses cuda:0 and the
+process group is gloo - the N > 1 code path on a machine with one GPU.)
+  * `--batch-size b` is PER RANK, as under Lightning's `dp`.  Epoch e is ordered by `RandomState(seed + e)` as above; the global
+    batches are what `ControlDataset.batches(order, N b)` yields, and rank r takes the items `shard_bounds(n, N, r)` of a global
+    batch of n items.  A global batch with n < N is left out on every rank (the count is printed once per epoch), so every rank
+    takes the same number of steps.
+  * The step's objective is the MEAN OF THE RANKS' LOSSES, which is what `dp` computes - not the loss of the concatenated batch:
+    the spectral-convergence term is a ratio of norms over a batch and does not decompose over items.  With ragged shards the
+    ranks weigh equally, whatever their item counts; this is not corrected for.
+  * Every rank seeds its device generator with seed + global_step before the step, so the hidden draws agree across ranks with no
+    collective.
+  * One step: `training_step` on the shard, `backward`, `GradientAverager.average(loss)` - the ranks' gradients and losses packed
+    into one row each, all-gathered, and averaged IN RANK ORDER by one HIP kernel, so every rank holds the same bits whatever
+    carried the rows, the ranks' parameters cannot drift apart, and an N-rank run equals a one-process emulation of it to the bit
+    - then `optimizer.step()`, `scheduler.step()`, `zero_grad`.  The printed train loss is the mean over the ranks, read back
+    once per epoch.  The ranks' parameters are compared on the device at the start and at the end of every epoch.
+  * Every rank validates the whole `val` split under --seed (the fused forward: cheap, and the same value everywhere, so the
+    best.ckpt decision needs no collective).  Rank 0 alone prints and writes; `batch_in_epoch` counts global batches and
+    `world_size` goes into the checkpoint.  A resume at another world size or batch size continues, with a note that the position
+    in the epoch means other items.  The run ends with a barrier after rank 0's last write.
 """
+import datetime
 import importlib
 import math
 import os
 import shutil
+import socket
+import subprocess
 import sys
 
 import click
@@ -69,6 +99,20 @@ def _validate(model, data, names, batch_size, dev, seed):
     return float(np.average([float(v) for v in losses], weights=sizes))
 
 
+def _launch_ranks(gpus, share):
+    """`--gpus N` typed by hand: N ranks under torch.distributed.run, as a fresh child process; -> its exit status"""
+    have = torch.cuda.device_count()
+    if have < gpus and not share:
+        print(f"train.py: --gpus {gpus} needs {gpus} GPUs, this machine has {have}", file=sys.stderr)
+        return 2
+    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:          # a free port: bound and released
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
+    return subprocess.run(cmd).returncode
+
+
 @click.command()
 @click.option("--gin-file", required=True, help="training gin file (gin/train/train_newt.gin of the package, or a reference one)")
 @click.option("--dataset-path", required=True, help="dataset root: data_mean.npy, data_std.npy, train/, val/")
@@ -83,10 +127,24 @@ def _validate(model, data, names, batch_size, dev, seed):
 @click.option("--batch-size", default=None, type=int, help="items per batch (overrides the gin file)")
 @click.option("--seed", default=0, help="shuffling (seed + epoch) and the render's hidden draws (seed + global step)")
 @click.option("--val-every-epochs", default=1, help="validate and consider best.ckpt every this many epochs")
+@click.option("--gpus", default=1, help="data-parallel over this many GPUs of the node; --batch-size is then per rank")
 def main(gin_file, dataset_path, urmp, device, instrument, load_data_to_memory, with_wandb, restore_checkpoint, output_dir, max_steps,
-         batch_size, seed, val_every_epochs):
+         batch_size, seed, val_every_epochs, gpus):
     if with_wandb:
         raise click.ClickException("--with-wandb: there is no wandb logging in this package; the losses are printed once per epoch")
+    gpus, share = int(gpus), os.environ.get("NWS_TRAIN_SHARE_GPU") == "1"
+    if gpus < 1:
+        print(f"train.py: --gpus {gpus}: at least 1", file=sys.stderr)
+        sys.exit(2)
+    if gpus > 1 and os.environ.get("WORLD_SIZE") is None:
+        sys.exit(_launch_ranks(gpus, share))
+    world = int(os.environ.get("WORLD_SIZE") or 1)
+    if world != gpus:
+        print(f"train.py: launched with WORLD_SIZE={world} but --gpus {gpus}: the two must agree", file=sys.stderr)
+        sys.exit(2)
+    rank = int(os.environ.get("RANK", "0")) if world > 1 else 0
+    if rank != 0:
+        sys.stdout = open(os.devnull, "w")                    # rank 0 alone prints; errors still reach stderr
     nws = importlib.import_module("neural-waveshaping-synthesis_amd")
     ds_mod = importlib.import_module("neural-waveshaping-synthesis_amd.dataset")
     ckpt = importlib.import_module("neural-waveshaping-synthesis_amd.checkpoint")
@@ -108,7 +166,8 @@ def main(gin_file, dataset_path, urmp, device, instrument, load_data_to_memory, 
     if max_steps < 1:
         raise click.ClickException("no step count: set trainer_kwargs.max_steps in the gin file or pass --max-steps")
     if "accelerator" in kwargs:
-        print(f"trainer_kwargs.accelerator = {kwargs.pop('accelerator')!r} is ignored: this script trains on one GPU")
+        print(f"trainer_kwargs.accelerator = {kwargs.pop('accelerator')!r} is ignored: "
+              + ("this script trains on one GPU" if world == 1 else f"--gpus {gpus} selects data-parallel training, not the gin file"))
     if kwargs:
         print(f"trainer_kwargs {sorted(kwargs)} have no meaning here and are ignored")
     keys = ("URMPDataModule.batch_size", "GeneralDataModule.batch_size")
@@ -116,7 +175,21 @@ def main(gin_file, dataset_path, urmp, device, instrument, load_data_to_memory, 
     root = os.path.join(dataset_path, instrument) if urmp else dataset_path
 
     dev = torch.device("cuda", int(device))
+    if world > 1:
+        import torch.distributed as dist
+
+        local = int(os.environ.get("LOCAL_RANK", "0"))
+        if not share and local >= torch.cuda.device_count():
+            print(f"train.py: rank {rank} needs GPU {local}, this machine has {torch.cuda.device_count()}", file=sys.stderr)
+            sys.exit(2)
+        dev = torch.device("cuda", 0 if share else local)
     torch.cuda.set_device(dev)
+    if world > 1:
+        limit = datetime.timedelta(seconds=120)
+        if share:
+            dist.init_process_group("gloo", timeout=limit)
+        else:
+            dist.init_process_group("nccl", timeout=limit, device_id=dev)
     torch.manual_seed(int(seed))                              # the initial weights of a run without --restore-checkpoint
     train = ds_mod.ControlDataset(root, "train")
     train_names = _with_audio(train, "train")
@@ -138,6 +211,12 @@ def main(gin_file, dataset_path, urmp, device, instrument, load_data_to_memory, 
     configured = model.configure_optimizers()
     optimizer, scheduler = configured["optimizer"], configured["lr_scheduler"]["scheduler"]
     optimizer.max_grad_norm = float(clip) if clip else None          # Lightning: gradient_clip_val = 0 means no clipping
+    averager = None
+    if world > 1:
+        par = importlib.import_module("neural-waveshaping-synthesis_amd.parallel")
+        names = {id(p): k for k, p in model.named_parameters()}
+        # the optimiser's order; construction compares the ranks' parameters: same seed, same checkpoint, same bits
+        averager = par.GradientAverager([(names[id(p)], p) for g in optimizer.param_groups for p in g["params"]], extra=1)
     global_step, epoch, skip, best = 0, 0, 0, math.inf
     if restore_checkpoint:
         opt_state, sched_state, step0, epoch0 = ckpt.read_training_state(restore_checkpoint)
@@ -149,27 +228,46 @@ def main(gin_file, dataset_path, urmp, device, instrument, load_data_to_memory, 
             extra = ckpt.read_training_extra(restore_checkpoint)
             skip, best = int(extra.get("batch_in_epoch", 0)), float(extra.get("best_val_loss", math.inf))
             print(f"resuming {restore_checkpoint} at step {global_step}, epoch {epoch}, lr {optimizer.param_groups[0]['lr']:.3e}")
+            was = (int(extra.get("world_size", world)), int(extra.get("batch_size", batch_size)))
+            if skip and was != (world, batch_size):
+                print(f"  it was written at world size {was[0]}, batch size {was[1]}; this run has {world} and {batch_size}: batch "
+                      f"{skip} of the epoch means other items")
         else:
             print(f"{restore_checkpoint} carries no optimiser state: fresh Adam state from its weights")
 
-    os.makedirs(output_dir, exist_ok=True)
-    for name in ("data_mean.npy", "data_std.npy"):
-        shutil.copyfile(os.path.join(root, name), os.path.join(output_dir, name))
+    if rank == 0:
+        os.makedirs(output_dir, exist_ok=True)
+        for name in ("data_mean.npy", "data_std.npy"):
+            shutil.copyfile(os.path.join(root, name), os.path.join(output_dir, name))
 
     def save(name, epoch_, batch_in_epoch):
+        if rank != 0:
+            return
         ckpt.write_training_checkpoint(os.path.join(output_dir, name), model, optimizer, scheduler, global_step, epoch_,
-                                       extra={"batch_in_epoch": int(batch_in_epoch), "best_val_loss": float(best)})
+                                       extra={"batch_in_epoch": int(batch_in_epoch), "best_val_loss": float(best),
+                                              "world_size": int(world), "batch_size": int(batch_size)})
+
+    def epoch_batches(order):
+        """(k, batch) over the epoch: the batches of one GPU, or this rank's shard of every global batch of world * batch_size"""
+        if world == 1:
+            return enumerate(train.batches(order, batch_size))
+        mine, left_out = ds_mod.rank_batches(train.groups(order, world * batch_size), world, rank)
+        if left_out:
+            print(f"epoch {epoch}: {left_out} global batches of fewer than {world} items are left out")
+        return enumerate(train.collate(g) for g in mine)
 
     while global_step < max_steps:
         order = [train_names[i] for i in np.random.RandomState(int(seed) + epoch).permutation(len(train_names))]
         losses, first_step, done = [], global_step, 0
-        batches = enumerate(train.batches(order, batch_size))
+        batches = epoch_batches(order)
         for k, batch in batches:
             if k < skip:                                      # a resumed epoch: these batches were stepped before the checkpoint
                 continue
             torch.cuda.manual_seed(int(seed) + global_step)
             loss = model.training_step(_to_device(batch, dev), k)
             loss.backward()
+            if averager is not None:                          # .grad: the ranks' mean; loss: the mean of the ranks' losses
+                loss = averager.average(loss.detach().reshape(1)).clone()
             optimizer.step()
             scheduler.step()
             optimizer.zero_grad(set_to_none=True)
@@ -201,6 +299,11 @@ def main(gin_file, dataset_path, urmp, device, instrument, load_data_to_memory, 
             save("best.ckpt", next_epoch, at)
         epoch = next_epoch
         skip = at
+        if averager is not None:
+            averager.check_in_sync()
+    if world > 1:
+        dist.barrier()                                        # rank 0's last write is behind every rank
+        dist.destroy_process_group()
     print(f"wrote {os.path.join(output_dir, 'last.ckpt')} at step {global_step}")
 
 
