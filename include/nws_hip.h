@@ -626,6 +626,41 @@ int nws_resample_bank(int sr_in, int sr_out, float* bank_host);
 int nws_resample(const float* x, int B, int N, int sr_in, int sr_out, const float* bank_dev, float* y, void* stream);
 
 /*
+ * Streaming sample-rate converter: nws_resample on chunks with the state carried between calls, so that a stream at one rate
+ * can feed, or be fed by, a device at another (DESIGN.md 3.23 is the definition; symbols as above).  A stream is made for
+ * (B, sr_in, sr_out) and keeps per row two 64-bit counters: n_seen (input samples consumed) and t_next (outputs emitted).
+ * Output t = row (t M) mod L of the bank against x[n - left + 1 .. n + right], n = (t M) / L, x = all samples pushed so far and
+ * zero before sample 0.  It is emitted once x[n + right] has been pushed: after n_seen samples
+ *   E(n_seen) = 0 for n_seen <= right, else ceil((n_seen - right) L / M)
+ * outputs have left, and a step of n samples emits outputs [t_next, E(n_seen + n)) - possibly none.  A step with `final` (n may be
+ * 0) treats x as zero beyond its end and emits up to the offline length (n_seen L) / M; the stream is then finished until the next
+ * reset.  Latency: `right` input samples.  Any chunking of the same input gives the same output bits (the order in which an
+ * output's taps are summed depends on the rates alone); the bits are not those of nws_resample, which sums in another order.
+ * State blob (nws_resample_stream_state_bytes, a multiple of 16; device memory, 8-byte aligned):
+ *   B x {int64 n_seen, int64 t_next} | B x (taps - 1) floats: the last taps - 1 input samples of each row | padding to 16 bytes.
+ * Limits: B <= 65 535; a step's n <= nws_resample_stream_max_chunk (taps - 1 + n + right floats fit 64 KB of LDS:
+ * 16 195 samples at 16 -> 48 kHz, 11 707 at 192 -> 8 kHz with its 3 119 taps); rates nws_resample_dims refuses, taps - 1 + right >= 16 384, or (16 386 L + M) >= 2^31:
+ * NWS_ERR_UNSUPPORTED / 0 bytes / 0 samples.  NULL state, bank or y, NULL x with n > 0, B < 1, n < 0, n = 0 without `final`,
+ * y_stride below nws_resample_stream_max_out, a state smaller than nws_resample_stream_state_bytes: NWS_ERR_BAD_ARG.  Every
+ * refusal is decided before the launch; nothing is read back; everything runs on `stream`.
+ *   nws_resample_stream_reset    zeroes the blob: n_seen = t_next = 0, a history of zeros.
+ *   nws_resample_stream_emitted  host arithmetic: E(n_seen), with `final` the offline length (n_seen L) / M; -1: unsupported rates,
+ *                                n_seen < 0 or beyond 64-bit arithmetic.
+ *   nws_resample_stream_max_out  host arithmetic: the most outputs one step of n samples can emit whatever the stream has seen:
+ *                                ceil(n L / M), with `final` ((n + right) L) / M; -1: unsupported rates, n < 0.
+ *   nws_resample_stream_step     one launch, one workgroup per row: x (B, n) -> row b of y (B, y_stride) receives its outputs from
+ *                                column 0, the rest is left untouched; `bank_dev` is the device copy of nws_resample_bank.  The
+ *                                caller mirrors the counters with nws_resample_stream_emitted to know how many columns are new.
+ */
+size_t nws_resample_stream_state_bytes(int B, int sr_in, int sr_out);
+int nws_resample_stream_max_chunk(int sr_in, int sr_out);
+int nws_resample_stream_reset(void* state, size_t bytes, int B, int sr_in, int sr_out, void* stream);
+int64_t nws_resample_stream_emitted(int64_t n_seen, int sr_in, int sr_out, int final);
+int nws_resample_stream_max_out(int n, int sr_in, int sr_out, int final);
+int nws_resample_stream_step(void* state, size_t bytes, const float* x, int B, int n, int sr_in, int sr_out, const float* bank_dev,
+                             int final, float* y, int y_stride, void* stream);
+
+/*
  * MFCC feature, the remaining analysis feature of the reference's control files:
  * neural_waveshaping_synthesis/data/utils/mfcc_extraction.py:7-13 (extract_mfcc -> librosa.feature.mfcc with librosa 0.8.0's
  * defaults) = power STFT (the loudness feature's: periodic hann, centre / reflect padding, T = 1 + N / hop frames), Slaney mel

@@ -99,6 +99,19 @@ def _check_dev(name, t, like=None, like_name="out"):
                            "the same GPU")
 
 
+def _check_state(t, like=None):
+    """a state blob: a contiguous uint8 tensor on the GPU (of `like`, the call's chunk)"""
+    if not t.is_cuda:
+        raise RuntimeError(f"state lives on {t.device}: the NEWT forward path only runs as HIP kernels on an AMD GPU "
+                           "(there is no CPU fallback)")
+    if t.dtype != torch.uint8:
+        raise RuntimeError(f"state: expected Byte, got {t.dtype}")
+    if not t.is_contiguous():
+        raise RuntimeError("state: expected a contiguous tensor")
+    if like is not None and t.device != like.device:
+        raise RuntimeError(f"chunk is on {like.device} but state is on {t.device}: all tensors of one call must live on the same GPU")
+
+
 class CtypesOps:
     def abi_version(self):
         return int(_lib.lib().nws_abi_version())
@@ -631,6 +644,56 @@ class CtypesOps:
             y = _new(audio, B, n_out)
             check(_lib.lib().nws_resample(ptr(audio), B, N, sr_in, sr_out, ptr(bank), ptr(y), _stream(audio.device)), "nws_resample")
         return y
+
+    # ---- streaming sample-rate converter (csrc/resample_stream.hip): the state blob is a uint8 tensor on the device ----------
+    @staticmethod
+    def _resample_stream_bytes(op, dims, B, sr_in, sr_out):
+        nbytes = _lib.lib().nws_resample_stream_state_bytes(B, sr_in, sr_out) if 1 <= B <= 65535 else 0
+        if nbytes == 0:
+            raise RuntimeError(f"{op}: unsupported stream (B {B}, {sr_in} -> {sr_out} Hz): 1 <= B <= 65535, and the {dims[2] - 1} "
+                               f"samples of history and {dims[4]} of look-ahead must leave room for a chunk in 64 KB of LDS")
+        return nbytes
+
+    def resample_stream_reset(self, state, B, sr_in, sr_out):
+        _check_state(state)
+        nbytes = self._resample_stream_bytes("resample_stream_reset", _resample_dims(sr_in, sr_out), B, sr_in, sr_out)
+        if state.numel() < nbytes:
+            raise RuntimeError(f"resample_stream_reset: state blob too small (expected {nbytes} bytes for B = {B}, got {state.numel()})")
+        with torch.cuda.device(state.device):
+            check(_lib.lib().nws_resample_stream_reset(ptr(state), state.numel(), B, sr_in, sr_out, _stream(state.device)),
+                  "nws_resample_stream_reset")
+
+    def resample_stream_step(self, state, bank, sr_in, sr_out, chunk, final, out):
+        _check_dev("chunk", chunk)
+        _check_dev("bank", bank, chunk, "chunk")
+        _check_dev("out", out, chunk, "chunk")
+        _check_state(state, chunk)
+        dims = _resample_dims(sr_in, sr_out)
+        L, _, taps = dims[:3]
+        if chunk.dim() != 2 or chunk.shape[0] < 1:
+            raise RuntimeError(f"resample_stream_step: expected a (B, n) chunk, got {tuple(chunk.shape)}")
+        if tuple(bank.shape) != (L, taps):
+            raise RuntimeError(f"resample_stream_step: bank does not belong to these rates (expected ({L}, {taps}), got "
+                               f"{tuple(bank.shape)})")
+        B, n = chunk.shape
+        lib = _lib.lib()
+        nbytes = self._resample_stream_bytes("resample_stream_step", dims, B, sr_in, sr_out)
+        if state.numel() != nbytes:
+            raise RuntimeError(f"resample_stream_step: state does not belong to a stream of B = {B} rows at these rates (expected "
+                               f"{nbytes} bytes, got {state.numel()})")
+        max_chunk = lib.nws_resample_stream_max_chunk(sr_in, sr_out)
+        if n < 1 and not final:
+            raise RuntimeError("resample_stream_step: empty chunk (only a final step may carry no samples)")
+        if n > max_chunk:
+            raise RuntimeError(f"resample_stream_step: a step takes at most {max_chunk} samples at these rates, got {n}")
+        max_out = lib.nws_resample_stream_max_out(n, sr_in, sr_out, 1 if final else 0)
+        if out.dim() != 2 or out.shape[0] != B or not max_out <= out.shape[1] < 2 ** 31:
+            raise RuntimeError(f"resample_stream_step: out: expected ({B}, >= {max_out}) for a {'final ' if final else ''}step of {n} "
+                               f"samples, got {tuple(out.shape)}")
+        with torch.cuda.device(chunk.device):
+            check(lib.nws_resample_stream_step(ptr(state), state.numel(), ptr(chunk) if n > 0 else None, B, n, sr_in, sr_out,
+                                               ptr(bank), 1 if final else 0, ptr(out), out.shape[1], _stream(chunk.device)),
+                  "nws_resample_stream_step")
 
     # ---- MFCC feature (csrc/mfcc.hip) --------------------------------------------------------------------------------------
     def mfcc_table(self, sample_rate, n_fft, n_mfcc, n_mels):

@@ -213,6 +213,13 @@ _PROTOTYPES = {
     "nws_resample_bank_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "nws_resample_bank": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),          # a HOST buffer of floats
     "nws_resample": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "nws_resample_stream_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nws_resample_stream_max_chunk": (C.c_int, [C.c_int, C.c_int]),
+    "nws_resample_stream_reset": (C.c_int, [_fp, C.c_size_t, C.c_int, C.c_int, C.c_int, _fp]),
+    "nws_resample_stream_emitted": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "nws_resample_stream_max_out": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nws_resample_stream_step": (C.c_int, [_fp, C.c_size_t, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int,
+                                           _fp]),
     "nws_mfcc_dims": (C.c_int, [*_MFCC_CFG, C.POINTER(C.c_int32)]),
     "nws_mfcc_table_bytes": (C.c_size_t, [*_MFCC_CFG]),
     "nws_mfcc_table": (C.c_int, [*_MFCC_CFG, C.c_void_p]),          # a HOST buffer of 4-byte words

@@ -1104,6 +1104,56 @@ Tensor resample(const Tensor& audio, const Tensor& bank, int64_t sr_in, int64_t 
   return y;
 }
 
+// ---- streaming sample-rate converter (csrc/resample_stream.hip): the state blob is a uint8 tensor on the device -------------
+size_t resample_stream_bytes(const char* op, const ResampleCfg& c, int64_t B) {
+  const size_t nbytes = B >= 1 && B <= 65535 ? nws_resample_stream_state_bytes((int)B, c.sr_in, c.sr_out) : 0;
+  TORCH_CHECK(nbytes > 0, op, ": unsupported stream (B ", B, ", ", c.sr_in, " -> ", c.sr_out, " Hz): 1 <= B <= 65535, and the ",
+              c.dims[2] - 1, " samples of history and ", c.dims[4], " of look-ahead must leave room for a chunk in 64 KB of LDS");
+  return nbytes;
+}
+
+void resample_stream_reset(Tensor& state, int64_t B, int64_t sr_in, int64_t sr_out) {
+  check_dev(state, "state", at::kByte);
+  ResampleCfg c(sr_in, sr_out);
+  const size_t nbytes = resample_stream_bytes("resample_stream_reset", c, B);
+  TORCH_CHECK((size_t)state.numel() >= nbytes, "resample_stream_reset: state blob too small (expected ", nbytes, " bytes for B = ", B,
+              ", got ", state.numel(), ")");
+  Launch L(state);
+  nws_check(nws_resample_stream_reset(state.data_ptr(), (size_t)state.numel(), (int)B, c.sr_in, c.sr_out, L.stream),
+            "nws_resample_stream_reset");
+}
+
+void resample_stream_step(Tensor& state, const Tensor& bank, int64_t sr_in, int64_t sr_out, const Tensor& chunk, bool final,
+                          Tensor& out) {
+  check_dev(chunk, "chunk");
+  check_dev(bank, "bank");
+  check_dev(out, "out");
+  check_dev(state, "state", at::kByte);
+  check_same_device(chunk, "chunk", bank, "bank");
+  check_same_device(chunk, "chunk", out, "out");
+  check_same_device(chunk, "chunk", state, "state");
+  ResampleCfg c(sr_in, sr_out);
+  TORCH_CHECK(chunk.dim() == 2 && chunk.size(0) >= 1, "resample_stream_step: expected a (B, n) chunk, got ", chunk.sizes());
+  TORCH_CHECK(bank.dim() == 2 && bank.size(0) == c.dims[0] && bank.size(1) == c.dims[2],
+              "resample_stream_step: bank does not belong to these rates (expected (", c.dims[0], ", ", c.dims[2], "), got ",
+              bank.sizes(), ")");
+  const int64_t B = chunk.size(0), n = chunk.size(1);
+  const size_t nbytes = resample_stream_bytes("resample_stream_step", c, B);
+  TORCH_CHECK((size_t)state.numel() == nbytes, "resample_stream_step: state does not belong to a stream of B = ", B, " rows at these "
+              "rates (expected ", nbytes, " bytes, got ", state.numel(), ")");
+  const int64_t max_chunk = nws_resample_stream_max_chunk(c.sr_in, c.sr_out);
+  TORCH_CHECK(final || n >= 1, "resample_stream_step: empty chunk (only a final step may carry no samples)");
+  TORCH_CHECK(n <= max_chunk, "resample_stream_step: a step takes at most ", max_chunk, " samples at these rates, got ", n);
+  const int64_t max_out = nws_resample_stream_max_out((int)n, c.sr_in, c.sr_out, final ? 1 : 0);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == B && out.size(1) >= max_out && out.size(1) <= INT32_MAX,
+              "resample_stream_step: out: expected (", B, ", >= ", max_out, ") for a ", final ? "final " : "", "step of ", n,
+              " samples, got ", out.sizes());
+  Launch L(chunk);
+  nws_check(nws_resample_stream_step(state.data_ptr(), (size_t)state.numel(), n > 0 ? chunk.data_ptr<float>() : nullptr, (int)B,
+                                     (int)n, c.sr_in, c.sr_out, bank.data_ptr<float>(), final ? 1 : 0, out.data_ptr<float>(),
+                                     (int)out.size(1), L.stream), "nws_resample_stream_step");
+}
+
 // ---- MFCC feature (csrc/mfcc.hip; data/utils/mfcc_extraction.py:7-13) ------------------------------------------------------
 struct MfccCfg {
   double sr;
@@ -1734,6 +1784,9 @@ TORCH_LIBRARY(newt_hip, m) {
         "float fill_value) -> (Tensor, Tensor, Tensor)", &pyin);
   m.def("resample_bank(int sr_in, int sr_out) -> Tensor", &resample_bank);
   m.def("resample(Tensor audio, Tensor bank, int sr_in, int sr_out) -> Tensor", &resample);
+  m.def("resample_stream_reset(Tensor(a!) state, int B, int sr_in, int sr_out) -> ()", &resample_stream_reset);
+  m.def("resample_stream_step(Tensor(a!) state, Tensor bank, int sr_in, int sr_out, Tensor chunk, bool final, Tensor(b!) out) -> ()",
+        &resample_stream_step);
   m.def("mfcc_table(float sample_rate, int n_fft, int n_mfcc, int n_mels) -> Tensor", &mfcc_table);
   m.def("stft_loss_dft(int n_fft, int win_length) -> Tensor", &stft_loss_dft);
   m.def("stft_loss(Tensor x, Tensor y, Tensor[] dfts, int[] n_ffts, int[] hops, int[] win_lengths, float w_sc, float w_log_mag, "

@@ -637,3 +637,159 @@ class VoiceStream(_StreamBase):
         self.check()
         self._graphs.clear()
         self.finished = True
+
+
+# ---- streaming sample-rate converter: a stream at one rate feeds, or is fed by, a device at another ----------------------
+class StreamResampler:
+    """Band-limited sample-rate conversion of a stream, chunk by chunk (`binding().resample_stream_step` ->
+    `nws_resample_stream_step`, csrc/resample_stream.hip): the concatenation of everything `push` and `flush`
+    return is `resample_audio` of the concatenated input - to the converter's accuracy, and bit for bit the same whatever the
+    chunk sizes.  The stream runs `latency_samples` (= right, 4 ms) input samples behind its input; the chunk marked `final`
+    (or `flush()`) releases the remainder against a zero extension, like the offline converter's right edge.
+
+    The two counters of every row (samples consumed, outputs emitted) live in the device state blob, so a step's launch has no
+    changing argument: `static_io(n)` captures the step of n samples ONCE into a hipGraph and `hop()` replays it.  How many of a
+    step's output columns are new (705 or 706 per 256 samples at 16 -> 44.1 kHz) comes from the host's own mirror of the
+    counters, plain Python ints, never from a read-back; `check()` compares mirror and device on demand."""
+
+    def __init__(self, sr_in, sr_out, batch_size: int, device=None, max_chunk: int = 4096, graph: bool = True):
+        from .data.utils.preprocess_audio import _bank, _rate
+
+        self.sr_in, self.sr_out = _rate(sr_in, "sr_in"), _rate(sr_out, "sr_out")
+        self.B = int(batch_size)
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise _lib.NwsError(f"StreamResampler on {dev}: the converter only runs as a HIP kernel on an AMD GPU; there is no CPU fallback.")
+        self.dev = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        L = _lib.lib()
+        in_range = max(self.sr_in, self.sr_out) < 2 ** 31 and 1 <= self.B <= 65535
+        nbytes = L.nws_resample_stream_state_bytes(self.B, self.sr_in, self.sr_out) if in_range else 0
+        if nbytes == 0:
+            raise RuntimeError(f"StreamResampler: unsupported stream (B {self.B}, {self.sr_in} -> {self.sr_out} Hz): 1 <= B <= 65535, "
+                               "rates the offline converter serves, and a filter whose history and look-ahead leave room for a chunk "
+                               "in 64 KB of LDS")
+        dims = (C.c_int32 * 6)()
+        _lib.check(L.nws_resample_dims(self.sr_in, self.sr_out, dims), "nws_resample_dims")
+        self.taps, self._right = int(dims[2]), int(dims[4])
+        self.max_chunk = int(min(max(1, int(max_chunk)), L.nws_resample_stream_max_chunk(self.sr_in, self.sr_out)))
+        self._bank = _bank(self.sr_in, self.sr_out, self.dev)
+        with torch.cuda.device(self.dev):
+            self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        self._use_graph = bool(graph)
+        self._graphs = {}          # n -> (graph or None, x_in, out)
+        self._static_n = None
+        self.reset()
+
+    # ---- the host's mirror of the device counters ---------------------------------------------------------------------
+    @property
+    def latency_samples(self) -> int:
+        return self._right
+
+    @property
+    def samples_in(self) -> int:
+        return self._n_seen
+
+    @property
+    def samples_out(self) -> int:
+        return self._t_next
+
+    def _emits(self, n: int, final: bool) -> int:
+        """columns a step of n samples adds: E(n_seen + n) - t_next, with `final` up to the offline length"""
+        return int(_lib.lib().nws_resample_stream_emitted(self._n_seen + n, self.sr_in, self.sr_out, int(final))) - self._t_next
+
+    def _advance(self, n: int, m: int, final: bool):
+        self._n_seen += n
+        self._t_next += m
+        self.finished = bool(final)
+
+    def reset(self):
+        """Back to the initial state: nothing consumed, nothing emitted, a history of zeros (the captured steps stay valid)."""
+        binding().resample_stream_reset(self._state, self.B, self.sr_in, self.sr_out)
+        self._n_seen = 0
+        self._t_next = 0
+        self.finished = False
+
+    # ---- one chunk ----------------------------------------------------------------------------------------------------
+    def _step(self, x, final, out):
+        binding().resample_stream_step(self._state, self._bank, self.sr_in, self.sr_out, x, bool(final), out)
+
+    def push(self, x: torch.Tensor, final: bool = False) -> torch.Tensor:
+        """x (B, n) float32 at sr_in -> (B, m) at sr_out: the outputs whose last tap this chunk delivered (m may be 0).  `final`
+        ends the stream (n may be 0 then): the remaining outputs up to (samples_in L) // M, against zeros beyond the end."""
+        if self.finished:
+            raise RuntimeError("stream already finished")
+        if isinstance(x, torch.Tensor) and x.is_cuda and not x.is_contiguous():
+            x = x.contiguous()
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise RuntimeError(f"expected a ({self.B}, n) chunk, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+        n = int(x.shape[1])
+        if n < 1 and not final:
+            raise RuntimeError("empty chunk")
+        if n > self.max_chunk:                           # long chunks: process in pieces (state makes that exact)
+            outs = []
+            for k0 in range(0, n, self.max_chunk):
+                k1 = min(n, k0 + self.max_chunk)
+                outs.append(self.push(x[:, k0:k1], final and k1 == n))
+            return torch.cat(outs, dim=1)
+        m = self._emits(n, final)
+        width = int(_lib.lib().nws_resample_stream_max_out(n, self.sr_in, self.sr_out, int(final)))
+        with torch.cuda.device(self.dev):
+            out = torch.empty((self.B, width), dtype=torch.float32, device=self.dev)
+        self._step(x, final, out)                        # the binding checks device, dtype and sizes, and raises before a launch
+        self._advance(n, m, final)
+        return out[:, :m]
+
+    def flush(self) -> torch.Tensor:
+        """The stream's remaining outputs: `push` of an empty chunk with final=True."""
+        with torch.cuda.device(self.dev):
+            return self.push(torch.empty((self.B, 0), dtype=torch.float32, device=self.dev), final=True)
+
+    # ---- zero-copy hops: the caller writes into the captured step's own input buffer and reads its output buffer -----------
+    def static_io(self, n: int):
+        """(x_in (B, n), out (B, max_out)) of the captured step of n samples - the buffers `hop()` consumes and fills.  One
+        kernel, no parallel branches, no changing argument: captured once, valid for the life of the stream (across reset())."""
+        n = int(n)
+        if self.finished:
+            raise RuntimeError("stream already finished")
+        if not 1 <= n <= self.max_chunk:
+            raise RuntimeError(f"static_io({n}): a captured step takes 1 .. {self.max_chunk} samples")
+        hit = self._graphs.get(n)
+        if hit is None:
+            width = int(_lib.lib().nws_resample_stream_max_out(n, self.sr_in, self.sr_out, 0))
+            with torch.cuda.device(self.dev):
+                x_in = torch.zeros((self.B, n), dtype=torch.float32, device=self.dev)
+                out = torch.zeros((self.B, width), dtype=torch.float32, device=self.dev)
+                g = None
+                if self._use_graph:
+                    g = torch.cuda.CUDAGraph()
+                    torch.cuda.synchronize(self.dev)
+                    with torch.cuda.graph(g):
+                        self._step(x_in, False, out)     # capture records, it does not run: the state has not advanced
+            hit = self._graphs[n] = (g, x_in, out)
+        self._static_n = n
+        return hit[1], hit[2]
+
+    def hop(self) -> torch.Tensor:
+        """Run the captured step on whatever the caller left in static_io(n)'s input buffer; returns the new columns
+        out[:, :m] of the static output buffer (overwritten by the next hop)."""
+        hit = self._graphs.get(self._static_n)
+        if hit is None:
+            raise RuntimeError("hop(): call static_io(n) first")
+        if self.finished:
+            raise RuntimeError("stream already finished")
+        n = self._static_n
+        m = self._emits(n, False)
+        if hit[0] is not None:
+            hit[0].replay()
+        else:
+            self._step(hit[1], False, hit[2])
+        self._advance(n, m, False)
+        return hit[2][:, :m]
+
+    def check(self) -> None:
+        """Read the device counters back once (synchronises) and compare them with the host's mirror; for tests and debugging."""
+        cnt = self._state[:16 * self.B].cpu().view(torch.int64).reshape(self.B, 2)
+        want = torch.tensor([self._n_seen, self._t_next], dtype=torch.int64).expand(self.B, 2)
+        if not torch.equal(cnt, want):
+            raise RuntimeError(f"StreamResampler: device counters {cnt.tolist()} differ from the host's mirror "
+                               f"(n_seen {self._n_seen}, t_next {self._t_next})")

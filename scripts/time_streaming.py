@@ -8,7 +8,10 @@ HIP-event latency (a push returns a fresh tensor: input copy + graph launch + ou
 with probability --note-on, each active one stops with probability --note-off); same timing, events written every hop.
 --model-gin FILE: a model of another architecture (its stream runs on the runtime-size kernels), with the weights
 of --checkpoint, or seeded random ones when none is named: the hop's latency depends on the sizes, not on the values.
---runtime-size: the packaged model on the runtime-size stream, to compare the two paths on one set of sizes."""
+--runtime-size: the packaged model on the runtime-size stream, to compare the two paths on one set of sizes.
+--output-rate R: after every hop its samples go through a StreamResampler(model rate -> R) (csrc/resample_stream.hip, DESIGN.md
+3.23), with --static-io through its captured hop: the hop's latency with and without the converter, the converter's own time
+and the output sample count are reported beside the figures above.  Not with --slots."""
 import importlib
 import os
 import sys
@@ -37,10 +40,13 @@ sys.path.insert(0, ROOT)
 @click.option("--note-on", default=0.2, help="--slots: per-hop start probability of an idle slot")
 @click.option("--note-off", default=0.1, help="--slots: per-hop stop probability of an active slot")
 @click.option("--seed", default=0)
+@click.option("--output-rate", default=None, type=int, help="convert every hop to this sample rate with a StreamResampler and time it")
 @click.option("--gc/--no-gc", "keep_gc", default=True, help="--no-gc: Python's cyclic garbage collector off during the timed hops "
               "(what a host with a real-time audio callback does); reported in the result")
 def main(checkpoint, model_gin, runtime_size, batch_size, hop_frames, num_hops, use_fast_newt, graph, static_io, json_out, slots, note_on,
-         note_off, seed, keep_gc):
+         note_off, seed, output_rate, keep_gc):
+    if output_rate is not None and slots:
+        raise click.UsageError("--output-rate times the converter behind model.stream(B); it does not combine with --slots")
     nws = importlib.import_module("neural-waveshaping-synthesis_amd")
     nws.ensure_default_config()
     if model_gin:
@@ -71,16 +77,24 @@ def main(checkpoint, model_gin, runtime_size, batch_size, hop_frames, num_hops, 
             s = importlib.import_module("neural-waveshaping-synthesis_amd.streaming").GenericNewtStream(model, batch_size, graph=graph)
         else:
             s = model.stream(batch_size, graph=graph, slots=True) if slots else model.stream(batch_size, graph=graph)
+        conv = None
+        if output_rate is not None:
+            conv = importlib.import_module("neural-waveshaping-synthesis_amd.streaming").StreamResampler(
+                int(model.sample_rate), output_rate, batch_size, graph=graph)
         for _ in range(20):
-            s.push(f0, control, **events())
+            y = s.push(f0, control, **events())
+            if conv is not None:
+                conv.push(y)
         if static_io:
             f0_in, c_in = s.static_io(K)[:2]
             f0_in.copy_(f0[:, 0])
             c_in.copy_(control)
+            if conv is not None:
+                x_in = conv.static_io(K * 128)[0]
         torch.cuda.synchronize()
         import gc
         import time
-        lat, wall = [], []
+        lat, wall, lat_conv, lat_both, out_samples = [], [], [], [], 0
         if not keep_gc:
             gc.collect()
             gc.disable()
@@ -91,12 +105,22 @@ def main(checkpoint, model_gin, runtime_size, batch_size, hop_frames, num_hops, 
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0 = time.perf_counter()
             e0.record()
-            if static_io:
-                s.hop(K, **ev)
-            else:
-                s.push(f0, control, **ev)
+            y = s.hop(K, **ev) if static_io else s.push(f0, control, **ev)
             e1.record()
-            e1.synchronize()
+            if conv is not None:
+                # the hop's samples through the converter on the same stream; e1 splits the pair
+                e2 = torch.cuda.Event(enable_timing=True)
+                if static_io:
+                    x_in.copy_(y)
+                    out_samples += conv.hop().shape[1]
+                else:
+                    out_samples += conv.push(y).shape[1]
+                e2.record()
+                e2.synchronize()
+                lat_conv.append(e1.elapsed_time(e2) * 1e3)
+                lat_both.append(e0.elapsed_time(e2) * 1e3)
+            else:
+                e1.synchronize()
             wall.append((time.perf_counter() - t0) * 1e6)
             lat.append(e0.elapsed_time(e1) * 1e3)
     gc.enable()
@@ -110,6 +134,15 @@ def main(checkpoint, model_gin, runtime_size, batch_size, hop_frames, num_hops, 
     print(f"{type(s).__name__}: stateful streaming{' (slots, %d events)' % n_events if slots else ''}, batch {batch_size}, hop {K * 128} samples ({period / 1e3:.1f} ms), graph={graph}, static_io={static_io}, gc={keep_gc}: p50 {res['p50_us']:.1f} us  "
           f"p99 {res['p99_us']:.1f} us  (host wall p50 {res['wall_p50_us']:.1f} / p99 {res['wall_p99_us']:.1f} us)  -> "
           f"{res['x_realtime_p50']:.1f}x real-time")
+    if conv is not None:
+        lat_conv, lat_both = np.array(lat_conv), np.array(lat_both)
+        res.update({"output_rate": int(output_rate), "output_samples": int(out_samples),
+                    "converter_p50_us": float(np.percentile(lat_conv, 50)), "converter_p99_us": float(np.percentile(lat_conv, 99)),
+                    "p50_with_converter_us": float(np.percentile(lat_both, 50)), "p99_with_converter_us": float(np.percentile(lat_both, 99))})
+        print(f"  + StreamResampler {int(model.sample_rate)} -> {output_rate} Hz ({'captured hop' if static_io else 'push'}): converter p50 "
+              f"{res['converter_p50_us']:.1f} us  p99 {res['converter_p99_us']:.1f} us; hop with converter p50 "
+              f"{res['p50_with_converter_us']:.1f} us  p99 {res['p99_with_converter_us']:.1f} us; {out_samples} samples out "
+              f"(host wall above includes the converter)")
     if json_out:
         import json
         with open(json_out, "a") as f:
