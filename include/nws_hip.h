@@ -605,6 +605,56 @@ int nws_pyin(const float* audio, int B, int N, double sample_rate, double fmin, 
              void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Fixed-lag pYIN stream: F0 from chunked audio with a bounded delay (DESIGN.md 3.24 is the definition; symbols as above,
+ * W = frame_length / 2).  It is nws_pyin's forward pass - the same CMND, observations, value vectors V and backpointers, bit for
+ * bit, whatever the chunking - read out by another backtrace.  A stream is made for (B, configuration); all rows advance in
+ * lock-step.  After n samples
+ *   F(n) = 0 for n <= W, else 1 + (n - W) / hop     frames are computed (frame t as soon as all its samples exist), and
+ *   E(n) = max(0, F(n) - lag)                       frames have left: frame e is the state at e of the backtrace that starts at
+ *                                                   argmax V_{e + lag} (lowest index on ties), 0 <= lag <= 255.
+ * A step with `final` (n may be 0) ends the stream at N = n_seen + n; it is the step without `final` followed by a flush: the
+ * frames F(N) .. T - 1, T = 1 + N / hop, are computed with the right edge reflected about N, and every frame not yet emitted
+ * leaves from argmax V_{T - 1}.  With lag >= T - 1 nothing leaves before `final` and the output is nws_pyin's, bit for bit.
+ * Per emitted frame: states (int32, [voiced bins | unvoiced bins]), f0 (fill_unvoiced as in nws_pyin_viterbi) and voiced_prob,
+ * all three delayed alike; row b's new frames go to columns 0 .. of row b of the (B, out_stride) outputs, the rest is untouched.
+ * Latency: W + lag hop samples.
+ * State blob (nws_pyin_stream_state_bytes; device memory, 8-byte aligned), B rows of
+ *   int64 n_seen, frames computed, frames emitted, finished | double max V_last, int64 argmax V_last |
+ *   double [2 n_pitch_bins] V_last - log rowsum, as the offline kernel keeps V between steps | double [512] voiced_prob ring |
+ *   int32 [512] jump-word ring (argmax V_{t-1} at frame t) | float [frame_length] sample history: what the frames still to come and a
+ *   flush need, fewer than frame_length samples | uint8 [512][2 n_pitch_bins] backpointer ring, frame t at slot t % 512;
+ *   each part padded to 8 bytes.
+ * The caller mirrors n_seen and passes it to every step, so that all sizes and refusals are decided on the host before the first
+ * launch; nothing is read back.  The kernels compare it with the blob's counters and leave state and outputs untouched when they
+ * differ - a stream that was never reset, or one that has had `final`: it accepts nothing until the next reset.
+ * V is never renormalised (that would change bits): a frame lowers max V by less than 1500, so up to 2^21 frames one ulp of V
+ * stays below 1e-6; a stream is refused beyond 2^21 hop samples (4.6 h at hop 128 / 16 kHz).
+ * Limits (NWS_ERR_UNSUPPORTED / 0 / -1): a configuration nws_pyin_dims refuses or with more than 256 hops in W, B > 65 535,
+ * n > nws_pyin_stream_max_chunk = 256 hop, more than 2^21 hop samples in all.  NULL state, table, workspace or output, NULL x
+ * with n > 0, B < 1, n < 0, n_seen < 0, n = 0 without `final`, `final` with N <= W, out_stride below the step's emission, a state
+ * below nws_pyin_stream_state_bytes, a workspace below nws_pyin_stream_workspace_bytes, lag outside 0 .. 255: NWS_ERR_BAD_ARG.
+ * Every refusal leaves state and outputs untouched; everything runs on `stream`, four launches a pass (a final step with samples
+ * is two passes), one when the pass computes no frame.
+ *   nws_pyin_stream_frames           host arithmetic: F(n_seen), with `final` T (-1: unsupported, n_seen < 0, `final` with N <= W).
+ *   nws_pyin_stream_emitted          host arithmetic: E(n_seen), with `final` T; a step emits the difference (-1 as above).
+ *   nws_pyin_stream_workspace_bytes  scratch of a step of n samples, whatever the stream has seen.
+ *   nws_pyin_stream_reset            zeroes the blob.
+ */
+size_t nws_pyin_stream_state_bytes(int B, double sample_rate, double fmin, double fmax, int frame_length, int hop);
+int nws_pyin_stream_max_chunk(double sample_rate, double fmin, double fmax, int frame_length, int hop);
+size_t nws_pyin_stream_workspace_bytes(int B, int n, double sample_rate, double fmin, double fmax, int frame_length, int hop,
+                                       int final);
+int64_t nws_pyin_stream_frames(int64_t n_seen, double sample_rate, double fmin, double fmax, int frame_length, int hop, int final);
+int64_t nws_pyin_stream_emitted(int64_t n_seen, double sample_rate, double fmin, double fmax, int frame_length, int hop, int lag,
+                                int final);
+int nws_pyin_stream_reset(void* state, size_t bytes, int B, double sample_rate, double fmin, double fmax, int frame_length, int hop,
+                          void* stream);
+int nws_pyin_stream_step(void* state, size_t bytes, const float* x, int B, int n, int64_t n_seen, double sample_rate, double fmin,
+                         double fmax, int frame_length, int hop, int lag, const double* table_dev, int final, int fill_unvoiced,
+                         float fill_value, float* f0, double* voiced_prob, int* states, int out_stride, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/*
  * Band-limited sample-rate converter, the step in front of the two analysis features:
  * neural_waveshaping_synthesis/data/utils/preprocess_audio.py:65-66 (resample_audio -> resampy.resample, filter kaiser_best).
  * DESIGN.md 3.10 is the definition (resampy 0.2.2's interpolation with n_out = (N L) / M in integers and the exact rational

@@ -624,6 +624,71 @@ class CtypesOps:
                              ptr(states), ptr(ws), nbytes, _stream(audio.device)), "nws_pyin")
         return f0, voiced_prob, states
 
+    # ---- fixed-lag pYIN stream (csrc/pyin_stream.hip): the state blob is a uint8 tensor on the device ------------------------
+    @staticmethod
+    def _pyin_stream_bytes(op, B, cfg):
+        _pyin_dims(cfg)
+        nbytes = _lib.lib().nws_pyin_stream_state_bytes(B, *cfg) if 1 <= B <= 65535 else 0
+        if nbytes == 0:
+            raise RuntimeError(f"{op}: unsupported stream (B {B}, frame_length {cfg[3]}, hop {cfg[4]}): 1 <= B <= 65535 and at most "
+                               "256 hops in half a frame")
+        return nbytes
+
+    def pyin_stream_reset(self, state, B, sample_rate, fmin, fmax, frame_length, hop):
+        _check_state(state)
+        cfg = (sample_rate, fmin, fmax, frame_length, hop)
+        nbytes = self._pyin_stream_bytes("pyin_stream_reset", B, cfg)
+        if state.numel() < nbytes:
+            raise RuntimeError(f"pyin_stream_reset: state blob too small (expected {nbytes} bytes for B = {B}, got {state.numel()})")
+        with torch.cuda.device(state.device):
+            check(_lib.lib().nws_pyin_stream_reset(ptr(state), state.numel(), B, *cfg, _stream(state.device)), "nws_pyin_stream_reset")
+
+    def pyin_stream_step(self, state, table, sample_rate, fmin, fmax, frame_length, hop, lag, chunk, n_seen, final, fill_unvoiced,
+                         fill_value, f0, voiced_prob, states):
+        _check_dev("chunk", chunk)
+        _check_dev("f0", f0, chunk, "chunk")
+        _check_state(state, chunk)
+        cfg = (sample_rate, fmin, fmax, frame_length, hop)
+        _pyin_dims(cfg, table)
+        if table.device != chunk.device:
+            raise RuntimeError(f"chunk is on {chunk.device} but table is on {table.device}: all tensors of one call must live on the "
+                               "same GPU")
+        if chunk.dim() != 2 or chunk.shape[0] < 1:
+            raise RuntimeError(f"pyin_stream_step: expected a (B, n) chunk, got {tuple(chunk.shape)}")
+        B, n = chunk.shape
+        lib = _lib.lib()
+        nbytes = self._pyin_stream_bytes("pyin_stream_step", B, cfg)
+        if state.numel() != nbytes:
+            raise RuntimeError(f"pyin_stream_step: state does not belong to a stream of B = {B} rows of this configuration (expected "
+                               f"{nbytes} bytes, got {state.numel()})")
+        if not 0 <= lag <= 255:
+            raise RuntimeError(f"pyin_stream_step: lag {lag} outside 0 .. 255")
+        if n < 1 and not final:
+            raise RuntimeError("pyin_stream_step: empty chunk (only a final step may carry no samples)")
+        max_chunk = lib.nws_pyin_stream_max_chunk(*cfg)
+        if n > max_chunk:
+            raise RuntimeError(f"pyin_stream_step: a step takes at most {max_chunk} samples at this hop, got {n}")
+        if final and n_seen + n <= frame_length // 2:
+            raise RuntimeError(f"pyin_stream_step: a stream of {n_seen + n} samples cannot end: the reflect padding needs more than "
+                               f"frame_length / 2 = {frame_length // 2}")
+        before = lib.nws_pyin_stream_emitted(n_seen, *cfg, lag, 0) if n_seen >= 0 else -1
+        after = lib.nws_pyin_stream_emitted(n_seen + n, *cfg, lag, 1 if final else 0) if n_seen >= 0 else -1
+        if before < 0 or after < 0:
+            raise RuntimeError(f"pyin_stream_step: n_seen {n_seen} + {n} samples outside 0 .. 2^21 hops")
+        m = after - before
+        for name, t, dt in (("f0", f0, torch.float32), ("voiced_prob", voiced_prob, torch.float64), ("states", states, torch.int32)):
+            if (not t.is_cuda or t.device != chunk.device or t.dtype != dt or not t.is_contiguous() or t.dim() != 2 or t.shape[0] != B
+                    or t.shape[1] != f0.shape[1] or not max(m, 1) <= t.shape[1] < 2 ** 31):
+                raise RuntimeError(f"pyin_stream_step: {name}: expected a contiguous ({B}, >= {max(m, 1)}) {dt} tensor on the chunk's GPU, the "
+                                   f"same width for all three outputs, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        with torch.cuda.device(chunk.device):
+            ws_bytes = lib.nws_pyin_stream_workspace_bytes(B, n, *cfg, 1 if final else 0)
+            ws = _new(chunk, ws_bytes, dtype=torch.uint8)
+            check(lib.nws_pyin_stream_step(ptr(state), state.numel(), ptr(chunk) if n > 0 else None, B, n, n_seen, *cfg, lag, ptr(table),
+                                           1 if final else 0, 1 if fill_unvoiced else 0, fill_value, ptr(f0), ptr(voiced_prob),
+                                           ptr(states), f0.shape[1], ptr(ws), ws_bytes, _stream(chunk.device)),
+                  "nws_pyin_stream_step")
+
     # ---- sample-rate converter (csrc/resample.hip) ------------------------------------------------------------------------
     def resample_bank(self, sr_in, sr_out):
         L, _, taps = _resample_dims(sr_in, sr_out)[:3]

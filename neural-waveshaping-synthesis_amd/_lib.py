@@ -208,6 +208,14 @@ _PROTOTYPES = {
     "nws_pyin_viterbi": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, *_PYIN_CFG, _fp, C.c_int, C.c_float, _fp, _fp, _fp,
                                    C.c_size_t, _fp]),
     "nws_pyin": (C.c_int, [_fp, C.c_int, C.c_int, *_PYIN_CFG, _fp, C.c_int, C.c_float, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "nws_pyin_stream_state_bytes": (C.c_size_t, [C.c_int, *_PYIN_CFG]),
+    "nws_pyin_stream_max_chunk": (C.c_int, [*_PYIN_CFG]),
+    "nws_pyin_stream_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, *_PYIN_CFG, C.c_int]),
+    "nws_pyin_stream_frames": (C.c_int64, [C.c_int64, *_PYIN_CFG, C.c_int]),
+    "nws_pyin_stream_emitted": (C.c_int64, [C.c_int64, *_PYIN_CFG, C.c_int, C.c_int]),
+    "nws_pyin_stream_reset": (C.c_int, [_fp, C.c_size_t, C.c_int, *_PYIN_CFG, _fp]),
+    "nws_pyin_stream_step": (C.c_int, [_fp, C.c_size_t, _fp, C.c_int, C.c_int, C.c_int64, *_PYIN_CFG, C.c_int, _fp, C.c_int, C.c_int,
+                                       C.c_float, _fp, _fp, _fp, C.c_int, _fp, C.c_size_t, _fp]),
     "nws_resample_dims": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "nws_resample_length": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "nws_resample_bank_bytes": (C.c_size_t, [C.c_int, C.c_int]),

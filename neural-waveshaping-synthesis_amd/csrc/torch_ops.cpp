@@ -1067,6 +1067,71 @@ std::tuple<Tensor, Tensor, Tensor> pyin(const Tensor& audio, const Tensor& table
   return {f0, voiced_prob, states};
 }
 
+// ---- fixed-lag pYIN stream (csrc/pyin_stream.hip): the state blob is a uint8 tensor on the device ---------------------------
+size_t pyin_stream_bytes(const char* op, const PyinCfg& c, int64_t B) {
+  const size_t nbytes = B >= 1 && B <= 65535 ? nws_pyin_stream_state_bytes((int)B, c.sr, c.fmin, c.fmax, c.fl, c.hop) : 0;
+  TORCH_CHECK(nbytes > 0, op, ": unsupported stream (B ", B, ", frame_length ", c.fl, ", hop ", c.hop,
+              "): 1 <= B <= 65535 and at most 256 hops in half a frame");
+  return nbytes;
+}
+
+void pyin_stream_reset(Tensor& state, int64_t B, double sample_rate, double fmin, double fmax, int64_t frame_length, int64_t hop) {
+  check_dev(state, "state", at::kByte);
+  PyinCfg c(sample_rate, fmin, fmax, frame_length, hop);
+  const size_t nbytes = pyin_stream_bytes("pyin_stream_reset", c, B);
+  TORCH_CHECK((size_t)state.numel() >= nbytes, "pyin_stream_reset: state blob too small (expected ", nbytes, " bytes for B = ", B,
+              ", got ", state.numel(), ")");
+  Launch L(state);
+  nws_check(nws_pyin_stream_reset(state.data_ptr(), (size_t)state.numel(), (int)B, c.sr, c.fmin, c.fmax, c.fl, c.hop, L.stream),
+            "nws_pyin_stream_reset");
+}
+
+void pyin_stream_step(Tensor& state, const Tensor& table, double sample_rate, double fmin, double fmax, int64_t frame_length,
+                      int64_t hop, int64_t lag, const Tensor& chunk, int64_t n_seen, bool final, bool fill_unvoiced, double fill_value,
+                      Tensor& f0, Tensor& voiced_prob, Tensor& states) {
+  check_dev(chunk, "chunk");
+  check_dev(f0, "f0");
+  check_same_device(chunk, "chunk", f0, "f0");
+  check_dev(state, "state", at::kByte);
+  check_same_device(chunk, "chunk", state, "state");
+  PyinCfg c(sample_rate, fmin, fmax, frame_length, hop);
+  c.check_table(table);
+  check_same_device(chunk, "chunk", table, "table");
+  TORCH_CHECK(chunk.dim() == 2 && chunk.size(0) >= 1, "pyin_stream_step: expected a (B, n) chunk, got ", chunk.sizes());
+  const int64_t B = chunk.size(0), n = chunk.size(1);
+  const size_t nbytes = pyin_stream_bytes("pyin_stream_step", c, B);
+  TORCH_CHECK((size_t)state.numel() == nbytes, "pyin_stream_step: state does not belong to a stream of B = ", B,
+              " rows of this configuration (expected ", nbytes, " bytes, got ", state.numel(), ")");
+  TORCH_CHECK(lag >= 0 && lag <= 255, "pyin_stream_step: lag ", lag, " outside 0 .. 255");
+  TORCH_CHECK(final || n >= 1, "pyin_stream_step: empty chunk (only a final step may carry no samples)");
+  const int64_t max_chunk = nws_pyin_stream_max_chunk(c.sr, c.fmin, c.fmax, c.fl, c.hop);
+  TORCH_CHECK(n <= max_chunk, "pyin_stream_step: a step takes at most ", max_chunk, " samples at this hop, got ", n);
+  TORCH_CHECK(!final || n_seen + n > c.fl / 2, "pyin_stream_step: a stream of ", n_seen + n,
+              " samples cannot end: the reflect padding needs more than frame_length / 2 = ", c.fl / 2);
+  const int64_t before = n_seen >= 0 ? nws_pyin_stream_emitted(n_seen, c.sr, c.fmin, c.fmax, c.fl, c.hop, (int)lag, 0) : -1;
+  const int64_t after =
+      n_seen >= 0 ? nws_pyin_stream_emitted(n_seen + n, c.sr, c.fmin, c.fmax, c.fl, c.hop, (int)lag, final ? 1 : 0) : -1;
+  TORCH_CHECK(before >= 0 && after >= 0, "pyin_stream_step: n_seen ", n_seen, " + ", n, " samples outside 0 .. 2^21 hops");
+  const int64_t m = std::max<int64_t>(after - before, 1);
+  const std::tuple<const char*, const Tensor*, at::ScalarType> outs[3] = {
+      {"f0", &f0, at::kFloat}, {"voiced_prob", &voiced_prob, at::kDouble}, {"states", &states, at::kInt}};
+  for (const auto& [name, t, st] : outs) {
+    TORCH_CHECK(t->is_cuda() && t->device() == chunk.device() && t->scalar_type() == st && t->is_contiguous() && t->dim() == 2 &&
+                    t->size(0) == B && t->size(1) == f0.size(1) && t->size(1) >= m && t->size(1) <= INT32_MAX,
+                "pyin_stream_step: ", name, ": expected a contiguous (", B, ", >= ", m, ") ", st,
+                " tensor on the chunk's GPU, the same width for all three outputs, got ", t->sizes(), " ", t->scalar_type(), " on ",
+                t->device());
+  }
+  Launch L(chunk);
+  const size_t ws_bytes = nws_pyin_stream_workspace_bytes((int)B, (int)n, c.sr, c.fmin, c.fmax, c.fl, c.hop, final ? 1 : 0);
+  Tensor ws = at::empty({(int64_t)ws_bytes}, chunk.options().dtype(at::kByte));
+  nws_check(nws_pyin_stream_step(state.data_ptr(), (size_t)state.numel(), n > 0 ? chunk.data_ptr<float>() : nullptr, (int)B, (int)n,
+                                 n_seen, c.sr, c.fmin, c.fmax, c.fl, c.hop, (int)lag, table.data_ptr<double>(), final ? 1 : 0,
+                                 fill_unvoiced ? 1 : 0, (float)fill_value, f0.data_ptr<float>(), voiced_prob.data_ptr<double>(),
+                                 states.data_ptr<int32_t>(), (int)f0.size(1), ws.data_ptr(), ws_bytes, L.stream),
+            "nws_pyin_stream_step");
+}
+
 
 // ---- sample-rate converter (csrc/resample.hip; data/utils/preprocess_audio.py:65-66) ---------------------------------------
 struct ResampleCfg {
@@ -1782,6 +1847,11 @@ TORCH_LIBRARY(newt_hip, m) {
         "float fmin, float fmax, int frame_length, int hop, bool fill_unvoiced, float fill_value) -> (Tensor, Tensor)", &pyin_viterbi);
   m.def("pyin(Tensor audio, Tensor table, float sample_rate, float fmin, float fmax, int frame_length, int hop, bool fill_unvoiced, "
         "float fill_value) -> (Tensor, Tensor, Tensor)", &pyin);
+  m.def("pyin_stream_reset(Tensor(a!) state, int B, float sample_rate, float fmin, float fmax, int frame_length, int hop) -> ()",
+        &pyin_stream_reset);
+  m.def("pyin_stream_step(Tensor(a!) state, Tensor table, float sample_rate, float fmin, float fmax, int frame_length, int hop, "
+        "int lag, Tensor chunk, int n_seen, bool final, bool fill_unvoiced, float fill_value, Tensor(b!) f0, "
+        "Tensor(c!) voiced_prob, Tensor(d!) states) -> ()", &pyin_stream_step);
   m.def("resample_bank(int sr_in, int sr_out) -> Tensor", &resample_bank);
   m.def("resample(Tensor audio, Tensor bank, int sr_in, int sr_out) -> Tensor", &resample);
   m.def("resample_stream_reset(Tensor(a!) state, int B, int sr_in, int sr_out) -> ()", &resample_stream_reset);

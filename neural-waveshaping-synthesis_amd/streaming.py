@@ -793,3 +793,122 @@ class StreamResampler:
         if not torch.equal(cnt, want):
             raise RuntimeError(f"StreamResampler: device counters {cnt.tolist()} differ from the host's mirror "
                                f"(n_seen {self._n_seen}, t_next {self._t_next})")
+
+
+# ---- fixed-lag pYIN stream: F0 from chunked audio with a bounded delay ---------------------------------------------------
+class StreamF0:
+    """pYIN F0 of a stream, chunk by chunk (`binding().pyin_stream_step` -> `nws_pyin_stream_step`, csrc/pyin_stream.hip;
+    DESIGN.md 3.24), with the offline extractor's names and defaults.  The stream runs the offline forward pass as the samples
+    arrive and emits frame e once frame e + lag exists, as the state at e of the best path that ends in frame e + lag;
+    `final` (or `flush()`) computes the last frames against the reflected right edge and releases the rest.  With a lag of
+    at least the clip's frame count the result is `pyin_frames` of the whole clip, bit for bit; at lag 4 it agreed with it
+    on every frame of the project's test signals (DESIGN.md 3.24 has the table).  The output runs `latency_samples` =
+    frame_length / 2 + lag hop_length samples behind the input.
+
+    The counters live in the device state blob; the host keeps a mirror (plain ints) and hands its sample count to every
+    step, so nothing is read back; `check()` compares mirror and device on demand."""
+
+    def __init__(self, batch_size: int, sample_rate: float = 16000, minimum_frequency: float = 65.0,
+                 maximum_frequency: float = 2093.0, frame_length: int = 1024, hop_length: int = 128, lag: int = 8,
+                 fill_unvoiced=None, device=None):
+        from .data.utils.f0_extraction import _config, _table
+
+        self.B = int(batch_size)
+        self.cfg = _config(sample_rate, minimum_frequency, maximum_frequency, frame_length, hop_length)
+        self.frame_length, self.hop_length, self.lag = self.cfg[3], self.cfg[4], int(lag)
+        self.fill_unvoiced = None if fill_unvoiced is None else float(fill_unvoiced)
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise _lib.NwsError(f"StreamF0 on {dev}: the extractor only runs as HIP kernels on an AMD GPU; there is no CPU fallback.")
+        self.dev = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        if not 0 <= self.lag <= 255:
+            raise RuntimeError(f"StreamF0: lag {self.lag} outside 0 .. 255")
+        L = _lib.lib()
+        nbytes = L.nws_pyin_stream_state_bytes(self.B, *self.cfg) if 1 <= self.B <= 65535 else 0
+        if nbytes == 0:
+            raise RuntimeError(f"StreamF0: unsupported stream (B {self.B}, configuration {self.cfg}): 1 <= B <= 65535, a "
+                               "configuration the offline extractor serves, and at most 256 hops in half a frame")
+        self.max_chunk = int(L.nws_pyin_stream_max_chunk(*self.cfg))
+        self._table = _table(self.cfg, self.dev)
+        with torch.cuda.device(self.dev):
+            self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        self.reset()
+
+    # ---- the host's mirror of the device counters ---------------------------------------------------------------------
+    @property
+    def latency_samples(self) -> int:
+        return self.frame_length // 2 + self.lag * self.hop_length
+
+    @property
+    def samples_in(self) -> int:
+        return self._n_seen
+
+    @property
+    def frames_out(self) -> int:
+        return self._emitted
+
+    def _emitted_after(self, n_seen: int, final: bool) -> int:
+        return int(_lib.lib().nws_pyin_stream_emitted(n_seen, *self.cfg, self.lag, int(final)))
+
+    def reset(self):
+        """Back to the initial state: nothing consumed, nothing emitted."""
+        binding().pyin_stream_reset(self._state, self.B, *self.cfg)
+        self._n_seen = 0
+        self._emitted = 0
+        self.finished = False
+
+    def push(self, x: torch.Tensor, final: bool = False):
+        """x (B, n) or (n,) float32 CUDA -> (f0 (B, m) fp32, voiced_prob (B, m) fp64, states (B, m) int32): the m >= 0 frames this
+        chunk released.  `final` ends the stream (n may be 0 then): the remaining frames up to 1 + samples_in // hop_length."""
+        if self.finished:
+            raise RuntimeError("stream already finished")
+        if isinstance(x, torch.Tensor) and x.dim() == 1 and self.B == 1:
+            x = x.unsqueeze(0)
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != self.B:
+            raise RuntimeError(f"expected a ({self.B}, n) chunk, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+        if not x.is_cuda:
+            raise _lib.NwsError(f"chunk lives on {x.device}: the extractor only runs as HIP kernels on an AMD GPU; there is no CPU fallback.")
+        if not x.is_contiguous():
+            x = x.contiguous()
+        n = int(x.shape[1])
+        if n < 1 and not final:
+            raise RuntimeError("empty chunk")
+        if n > self.max_chunk:                           # long chunks: process in pieces (state makes that exact)
+            outs = []
+            for k0 in range(0, n, self.max_chunk):
+                k1 = min(n, k0 + self.max_chunk)
+                outs.append(self.push(x[:, k0:k1], final and k1 == n))
+            return tuple(torch.cat([o[i] for o in outs], dim=1) for i in range(3))
+        if final and self._n_seen + n <= self.frame_length // 2:
+            raise RuntimeError(f"a stream of {self._n_seen + n} samples cannot end: the reflect padding needs more than "
+                               f"frame_length / 2 = {self.frame_length // 2}")
+        after = self._emitted_after(self._n_seen + n, final)
+        if after < 0:
+            raise RuntimeError("StreamF0: the stream is limited to 2^21 hops; reset() it")
+        m = after - self._emitted
+        with torch.cuda.device(self.dev):
+            f0 = torch.empty((self.B, max(m, 1)), dtype=torch.float32, device=self.dev)
+            voiced_prob = torch.empty((self.B, max(m, 1)), dtype=torch.float64, device=self.dev)
+            states = torch.empty((self.B, max(m, 1)), dtype=torch.int32, device=self.dev)
+        binding().pyin_stream_step(self._state, self._table, *self.cfg, self.lag, x, self._n_seen, bool(final),
+                                   self.fill_unvoiced is not None, self.fill_unvoiced if self.fill_unvoiced is not None else 0.0,
+                                   f0, voiced_prob, states)
+        self._n_seen += n
+        self._emitted = after
+        self.finished = bool(final)
+        return f0[:, :m], voiced_prob[:, :m], states[:, :m]
+
+    def flush(self):
+        """The stream's remaining frames: `push` of an empty chunk with final=True."""
+        with torch.cuda.device(self.dev):
+            return self.push(torch.empty((self.B, 0), dtype=torch.float32, device=self.dev), final=True)
+
+    def check(self) -> None:
+        """Read the device counters back once (synchronises) and compare them with the host's mirror; for tests and debugging."""
+        row = self._state.numel() // self.B
+        cnt = self._state.view(self.B, row)[:, :32].cpu().contiguous().view(torch.int64)
+        frames = -1 if self._n_seen <= self.frame_length // 2 and self.finished else int(
+            _lib.lib().nws_pyin_stream_frames(self._n_seen, *self.cfg, int(self.finished)))
+        want = torch.tensor([self._n_seen, frames, self._emitted, int(self.finished)], dtype=torch.int64).expand(self.B, 4)
+        if not torch.equal(cnt, want):
+            raise RuntimeError(f"StreamF0: device counters {cnt.tolist()} differ from the host's mirror {want[0].tolist()}")

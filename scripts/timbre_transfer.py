@@ -4,11 +4,15 @@ features normalised with the checkpoint's statistics -> the model -> wav.  The c
 data/utils/preprocess_audio.py followed by its inference notebook, on the GPU end to end.
 
     python scripts/timbre_transfer.py in.wav out.wav --model-checkpoint ckpt [--normalisation-dir dir] [--use-fastnewt]
-                                      [--resample] [--output-rate R]
+                                      [--resample] [--output-rate R] [--stream-f0 LAG [--chunk N]] [--seed S]
 
 Without --resample the wav must already be at the model's sample rate and mono.  With it the file may be at any rate and
 stereo: the left channel is kept and converted to the model's rate on the GPU (csrc/resample.hip), and the output has the
 converted length.  --output-rate converts the model's output to another rate with the same kernel.
+--stream-f0 LAG takes F0 from the fixed-lag stream (streaming.StreamF0) fed --chunk samples at a time, as a live
+input would deliver them, instead of from the offline extractor: everything else runs as without it, so the output lets one
+hear what a lag of LAG frames costs (a lag of the whole clip's frame count, at most 255, gives the same file when both runs
+fix the model's two random draws - the oscillators' start phases and the noise - with the same --seed).
 """
 import importlib
 import os
@@ -58,6 +62,16 @@ def normalisation(ck, checkpoint, directory):
     raise click.BadParameter(f"no data_mean.npy / data_std.npy in {directory}: pass --normalisation-dir")
 
 
+def stream_f0_frames(audio, sr, hop, lag, chunk):
+    """F0 and voiced probability of every frame through streaming.StreamF0, `chunk` samples a push; numpy like the offline call"""
+    streaming = importlib.import_module("neural-waveshaping-synthesis_amd.streaming")
+    s = streaming.StreamF0(1, sample_rate=sr, frame_length=1024, hop_length=hop, lag=lag)
+    x = torch.from_numpy(audio).cuda().unsqueeze(0)
+    outs = [s.push(x[:, at:at + chunk], final=at + chunk >= audio.size) for at in range(0, audio.size, chunk)]
+    f0 = torch.cat([o[0] for o in outs], dim=1)[0].cpu().numpy().astype(np.float64)
+    return f0, torch.cat([o[1] for o in outs], dim=1)[0].cpu().numpy()
+
+
 @click.command()
 @click.argument("input_wav", type=click.Path(exists=True))
 @click.argument("output_wav", type=click.Path())
@@ -68,7 +82,11 @@ def normalisation(ck, checkpoint, directory):
 @click.option("--octave-shift", default=0, type=int, help="transpose the extracted F0 by whole octaves")
 @click.option("--resample", is_flag=True, help="accept any sample rate and stereo: keep the left channel, convert to the model's rate")
 @click.option("--output-rate", default=None, type=int, help="convert the model's output to this sample rate")
-def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, use_fastnewt, octave_shift, resample, output_rate):
+@click.option("--stream-f0", default=None, type=click.IntRange(0, 255), help="F0 from the fixed-lag stream with this lag in frames")
+@click.option("--chunk", default=128, type=click.IntRange(1), show_default=True, help="samples per push of --stream-f0")
+@click.option("--seed", default=None, type=int, help="seed torch's generators, so that two runs draw the same start phases and noise")
+def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, use_fastnewt, octave_shift, resample, output_rate,
+         stream_f0, chunk, seed):
     nws = importlib.import_module("neural-waveshaping-synthesis_amd")
     ck = importlib.import_module("neural-waveshaping-synthesis_amd.checkpoint")
     f0x = importlib.import_module("neural-waveshaping-synthesis_amd.data.utils.f0_extraction")
@@ -86,10 +104,15 @@ def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, 
     mean, std = normalisation(ck, model_checkpoint, normalisation_dir)
     audio = read_any(input_wav, sr, pre) if resample else read_mono(input_wav, sr)
     # frame-rate features, one frame per control hop: T = 1 + N // hop for both
-    f0, voiced_prob = f0x.extract_f0_with_pyin(audio, sr, frame_length=1024, hop_length=hop, interpolate_fn=None)
+    if stream_f0 is None:
+        f0, voiced_prob = f0x.extract_f0_with_pyin(audio, sr, frame_length=1024, hop_length=hop, interpolate_fn=None)
+    else:
+        f0, voiced_prob = stream_f0_frames(audio, sr, hop, stream_f0, chunk)
     loudness = ldx.extract_perceptual_loudness(audio, sr, n_fft=1024, hop_length=hop, interpolate_fn=None)
     f0 = f0 * 2.0 ** octave_shift
     f0_t, control = ck.make_control(f0, loudness, mean, std)
+    if seed is not None:
+        torch.manual_seed(seed)
     with torch.no_grad():
         out = model(f0_t.unsqueeze(0).cuda(), control.unsqueeze(0).cuda())
     y = out[0, :audio.size].cpu().numpy().astype(np.float32)
