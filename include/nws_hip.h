@@ -19,7 +19,7 @@
  *   - the analysis front end in front of the forward path (data/utils/ of the reference) takes audio (B, N) of any
  *     length: nws_resample (any integer sample rate to any other), nws_loudness, nws_pyin, nws_mfcc.  Their constant
  *     operands (weight bank, DFT matrix, fp64 table, filter table) are built once per configuration by the entry points
- *     beside them.
+ *     beside them.  Chunked audio: nws_resample_stream_*, nws_pyin_stream_* and nws_loudness_stream_* keep their state in a blob.
  */
 #ifndef NWS_HIP_H
 #define NWS_HIP_H
@@ -565,6 +565,54 @@ int nws_loudness_frames(int N, int hop);
 size_t nws_loudness_workspace_bytes(int B, int N, int n_fft, int hop);
 int nws_loudness(const float* audio, int B, int N, int n_fft, int hop, const float* dft, float amin, float top_db,
                  int normalise, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* The clip maximum nws_loudness normalises by, as power_out (B) floats on the device: the power pass alone (workspace and
+ * refusals as nws_loudness).  A calibration value for a loudness stream's fixed reference. */
+int nws_loudness_peak_power(const float* audio, int B, int N, int n_fft, int hop, const float* dft, float* power_out,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Loudness stream: the feature above from chunked audio with a bounded delay and a causal reference level (DESIGN.md 3.25 is the
+ * definition; W = n_fft / 2).  Frames and emission are the pYIN stream's below: after n samples F(n) = 0 for n <= W, else
+ * 1 + (n - W) / hop frames are computed and E(n) = max(0, F(n) - lag) have left, 0 <= lag <= 255; a step with `final` (n may be
+ * 0) ends the stream at N = n_seen + n, computes the frames F(N) .. T - 1, T = 1 + N / hop, with the right edge reflected about
+ * N and releases the rest.  P(t, k), the power of bin k of frame t, has the bits nws_loudness computes for that frame of the
+ * whole signal, whatever the chunking; p(t) = max_k P(t, k).
+ * Reference level: a row carries one float M.  nws_loudness_stream_reset sets it to initial_power[b] >= 0 (device memory) and
+ * fixes `track`: with it M(t) = max(M(t - 1), p(t)), without it M(t) = initial_power.  A frame e that leaves in a step without
+ * `final` is measured against ref(e) = M(e + lag), one the flush releases against M(T - 1):
+ *   db(k) = 10 log10(max(amin^2, P(e, k))) - 10 log10(max(amin^2, ref(e))),  loudness = mean_k max(db(k), -top_db) [, (l + 80) / 80]
+ * term for term nws_loudness's dB pass, the sum over k in order.  Without `track` a signal louder than its reference gives
+ * values above 0 dB (above 1 normalised); they are not clipped.  track with initial_power 0 is the running reference; no track
+ * with nws_loudness_peak_power of the clip is nws_loudness of the clip, bit for bit, at any lag and chunking; so is the
+ * running reference at lag >= T - 1.  The maximum does not decay: one click pins the reference until the next reset.
+ * Row b's new frames go to columns 0 .. of row b of the (B, out_stride) outputs loudness_out and ref_out (the reference power
+ * each frame was measured against); the rest is untouched.  Latency: W + lag hop samples.
+ * State blob (nws_loudness_stream_state_bytes; device memory, 8-byte aligned), B rows of
+ *   int64 n_seen, frames computed, frames emitted, finished | float M, int32 track | float [n_fft] sample history (the pYIN
+ *   stream's rule) | float [512] ring of M(t) at t % 512 | float [n_fft / 2 + 1][512] ring of P(t, k) at k 512 + t % 512;
+ *   each part padded to 8 bytes.
+ * The caller mirrors n_seen and passes it to every step; all sizes and refusals are decided on the host before the first launch,
+ * nothing is read back.  The kernels compare n_seen with the blob's counters and leave state and outputs untouched when they
+ * differ (a stream never reset, or one that has had `final`).  Two launches and one memset a pass (a final step with samples is
+ * two passes), one launch when the pass computes no frame.
+ * Limits (NWS_ERR_UNSUPPORTED / 0 / -1): n_fft and hop nws_loudness refuses or with more than 256 hops in W, B > 65 535,
+ * n > nws_loudness_stream_max_chunk = 256 hop, more than 2^21 hop samples in all.  NULL state, dft, initial_power, workspace or
+ * output, NULL x with n > 0, B < 1, n < 0, n_seen < 0, n = 0 without `final`, `final` with N <= W, out_stride below the step's
+ * emission, a state below nws_loudness_stream_state_bytes, a workspace below nws_loudness_stream_workspace_bytes, lag outside
+ * 0 .. 255, amin <= 0, top_db < 0: NWS_ERR_BAD_ARG.  Every refusal leaves state and outputs untouched.
+ *   nws_loudness_stream_frames / _emitted   host arithmetic: F(n_seen) / E(n_seen), with `final` T (-1: refused).
+ *   nws_loudness_stream_workspace_bytes     scratch of a step of n samples, whatever the stream has seen.
+ */
+size_t nws_loudness_stream_state_bytes(int B, int n_fft, int hop);
+int nws_loudness_stream_max_chunk(int n_fft, int hop);
+size_t nws_loudness_stream_workspace_bytes(int B, int n, int n_fft, int hop, int final);
+int64_t nws_loudness_stream_frames(int64_t n_seen, int n_fft, int hop, int final);
+int64_t nws_loudness_stream_emitted(int64_t n_seen, int n_fft, int hop, int lag, int final);
+int nws_loudness_stream_reset(void* state, size_t bytes, int B, int n_fft, int hop, const float* initial_power, int track,
+                              void* stream);
+int nws_loudness_stream_step(void* state, size_t bytes, const float* x, int B, int n, int64_t n_seen, int n_fft, int hop, int lag,
+                             const float* dft, float amin, float top_db, int normalise, int final, float* loudness_out,
+                             float* ref_out, int out_stride, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * pYIN F0 extractor, the other analysis feature in front of the synthesis path:

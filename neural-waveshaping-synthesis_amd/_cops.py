@@ -559,6 +559,99 @@ class CtypesOps:
                                  ws.numel(), _stream(audio.device)), "nws_loudness")
         return out
 
+    @staticmethod
+    def _check_loudness_sizes(op, dft, n_fft, hop):
+        L = _lib.lib()
+        if L.nws_loudness_workspace_bytes(1, 1, n_fft, hop) == 0:
+            raise RuntimeError(f"{op}: unsupported n_fft / hop_length ({n_fft}, {hop}): n_fft must be a power of two in [64, 2048], "
+                               "1 <= hop <= n_fft and 31 hop + n_fft samples must fit 160 KB of LDS")
+        if dft.numel() * 4 != L.nws_loudness_dft_bytes(n_fft):
+            raise RuntimeError(f"{op}: dft does not belong to n_fft = {n_fft}")
+
+    def loudness_peak_power(self, audio, dft, n_fft, hop):
+        _check_dev("audio", audio)
+        _check_dev("dft", dft, audio, "audio")
+        if audio.dim() != 2 or audio.shape[0] < 1:
+            raise RuntimeError(f"loudness_peak_power: expected (B, N), got {tuple(audio.shape)}")
+        B, N = audio.shape
+        self._check_loudness_sizes("loudness_peak_power", dft, n_fft, hop)
+        if N <= n_fft // 2:
+            raise RuntimeError(f"loudness_peak_power: N = {N}: the reflect padding needs more than n_fft / 2 = {n_fft // 2} samples")
+        L = _lib.lib()
+        with torch.cuda.device(audio.device):
+            nbytes = L.nws_loudness_workspace_bytes(B, N, n_fft, hop)
+            ws = _new(audio, nbytes, dtype=torch.uint8)
+            out = _new(audio, B)
+            check(L.nws_loudness_peak_power(ptr(audio), B, N, n_fft, hop, ptr(dft), ptr(out), ptr(ws), nbytes, _stream(audio.device)),
+                  "nws_loudness_peak_power")
+        return out
+
+    # ---- loudness stream (csrc/loudness_stream.hip): the state blob is a uint8 tensor on the device --------------------------
+    @staticmethod
+    def _loudness_stream_bytes(op, B, n_fft, hop):
+        nbytes = _lib.lib().nws_loudness_stream_state_bytes(B, n_fft, hop) if 1 <= B <= 65535 else 0
+        if nbytes == 0:
+            raise RuntimeError(f"{op}: unsupported stream (B {B}, n_fft {n_fft}, hop {hop}): 1 <= B <= 65535, sizes the offline "
+                               "extractor serves and at most 256 hops in half a frame")
+        return nbytes
+
+    def loudness_stream_reset(self, state, B, n_fft, hop, initial_power, track):
+        _check_state(state)
+        _check_dev("initial_power", initial_power, state, "state")
+        nbytes = self._loudness_stream_bytes("loudness_stream_reset", B, n_fft, hop)
+        if state.numel() < nbytes:
+            raise RuntimeError(f"loudness_stream_reset: state blob too small (expected {nbytes} bytes for B = {B}, got {state.numel()})")
+        if initial_power.dim() != 1 or initial_power.shape[0] != B:
+            raise RuntimeError(f"loudness_stream_reset: initial_power: expected ({B}), got {tuple(initial_power.shape)}")
+        with torch.cuda.device(state.device):
+            check(_lib.lib().nws_loudness_stream_reset(ptr(state), state.numel(), B, n_fft, hop, ptr(initial_power), 1 if track else 0,
+                                                       _stream(state.device)), "nws_loudness_stream_reset")
+
+    def loudness_stream_step(self, state, dft, n_fft, hop, lag, chunk, n_seen, final, amin, top_db, normalise, loudness,
+                             reference_power):
+        _check_dev("chunk", chunk)
+        _check_dev("loudness", loudness, chunk, "chunk")
+        _check_state(state, chunk)
+        _check_dev("dft", dft, chunk, "chunk")
+        if chunk.dim() != 2 or chunk.shape[0] < 1:
+            raise RuntimeError(f"loudness_stream_step: expected a (B, n) chunk, got {tuple(chunk.shape)}")
+        B, n = chunk.shape
+        lib = _lib.lib()
+        nbytes = self._loudness_stream_bytes("loudness_stream_step", B, n_fft, hop)
+        if state.numel() != nbytes:
+            raise RuntimeError(f"loudness_stream_step: state does not belong to a stream of B = {B} rows of this configuration "
+                               f"(expected {nbytes} bytes, got {state.numel()})")
+        self._check_loudness_sizes("loudness_stream_step", dft, n_fft, hop)
+        if not 0 <= lag <= 255:
+            raise RuntimeError(f"loudness_stream_step: lag {lag} outside 0 .. 255")
+        if not (amin > 0.0 and top_db >= 0.0):
+            raise RuntimeError("loudness_stream_step: amin must be positive and top_db non-negative")
+        if n < 1 and not final:
+            raise RuntimeError("loudness_stream_step: empty chunk (only a final step may carry no samples)")
+        max_chunk = lib.nws_loudness_stream_max_chunk(n_fft, hop)
+        if n > max_chunk:
+            raise RuntimeError(f"loudness_stream_step: a step takes at most {max_chunk} samples at this hop, got {n}")
+        if final and n_seen + n <= n_fft // 2:
+            raise RuntimeError(f"loudness_stream_step: a stream of {n_seen + n} samples cannot end: the reflect padding needs more "
+                               f"than n_fft / 2 = {n_fft // 2}")
+        before = lib.nws_loudness_stream_emitted(n_seen, n_fft, hop, lag, 0) if n_seen >= 0 else -1
+        after = lib.nws_loudness_stream_emitted(n_seen + n, n_fft, hop, lag, 1 if final else 0) if n_seen >= 0 else -1
+        if before < 0 or after < 0:
+            raise RuntimeError(f"loudness_stream_step: n_seen {n_seen} + {n} samples outside 0 .. 2^21 hops")
+        m = after - before
+        for name, t in (("loudness", loudness), ("reference_power", reference_power)):
+            if (not t.is_cuda or t.device != chunk.device or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2
+                    or t.shape[0] != B or t.shape[1] != loudness.shape[1] or not max(m, 1) <= t.shape[1] < 2 ** 31):
+                raise RuntimeError(f"loudness_stream_step: {name}: expected a contiguous ({B}, >= {max(m, 1)}) Float tensor on the "
+                                   f"chunk's GPU, the same width for both outputs, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        with torch.cuda.device(chunk.device):
+            ws_bytes = lib.nws_loudness_stream_workspace_bytes(B, n, n_fft, hop, 1 if final else 0)
+            ws = _new(chunk, ws_bytes, dtype=torch.uint8)
+            check(lib.nws_loudness_stream_step(ptr(state), state.numel(), ptr(chunk) if n > 0 else None, B, n, n_seen, n_fft, hop, lag,
+                                               ptr(dft), amin, top_db, 1 if normalise else 0, 1 if final else 0, ptr(loudness),
+                                               ptr(reference_power), loudness.shape[1], ptr(ws), ws_bytes, _stream(chunk.device)),
+                  "nws_loudness_stream_step")
+
     # ---- pYIN F0 extractor (csrc/pyin.hip) -------------------------------------------------------------------------------
     def pyin_table(self, sample_rate, fmin, fmax, frame_length, hop):
         cfg = (sample_rate, fmin, fmax, frame_length, hop)

@@ -198,6 +198,15 @@ _PROTOTYPES = {
     "nws_loudness_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "nws_loudness": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_float, C.c_float, C.c_int, _fp, _fp,
                                C.c_size_t, _fp]),
+    "nws_loudness_peak_power": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "nws_loudness_stream_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nws_loudness_stream_max_chunk": (C.c_int, [C.c_int, C.c_int]),
+    "nws_loudness_stream_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nws_loudness_stream_frames": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int]),
+    "nws_loudness_stream_emitted": (C.c_int64, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nws_loudness_stream_reset": (C.c_int, [_fp, C.c_size_t, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp]),
+    "nws_loudness_stream_step": (C.c_int, [_fp, C.c_size_t, _fp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _fp, C.c_float,
+                                           C.c_float, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, C.c_size_t, _fp]),
     "nws_pyin_frames": (C.c_int, [C.c_int, C.c_int]),
     "nws_pyin_dims": (C.c_int, [*_PYIN_CFG, C.POINTER(C.c_int32)]),
     "nws_pyin_table_bytes": (C.c_size_t, [*_PYIN_CFG]),

@@ -13,6 +13,7 @@
 // The dB reference is the maximum over the WHOLE spectrogram of an utterance: pass 1 leaves it in one word per utterance
 // (atomicMax on the float bits, valid for non-negative values), pass 2 clips, averages and normalises.
 #include "stft_tile.h"  // the tile, its limits and the operand's size: shared with stft_loss.hip and stft_grad.hip
+#include "loudness_db.h"  // the dB pass of one frame: shared with loudness_stream.hip
 
 namespace {
 
@@ -49,19 +50,8 @@ __global__ void loudness_db_kernel(const float* __restrict__ power, const unsign
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
   if (t >= frames) return;
-  const float k10 = 3.0102999566398120f;  // 10 / log2(10)
-  const float floor_p = amin * amin;
-  const float ref_db = k10 * __log2f(fmaxf(floor_p, __uint_as_float(max_bits[b])));
-  // log_spec.max() is max(floor, max power) - ref = 0 by construction, so the top_db clip sits at -top_db
-  const float* p = power + (size_t)b * bins * frames_pad + t;
-  float s = 0.0f;
-  for (int k = 0; k < bins; ++k) {
-    const float db = k10 * __log2f(fmaxf(floor_p, p[(size_t)k * frames_pad])) - ref_db;
-    s += fmaxf(db, -top_db);
-  }
-  float l = s / (float)bins;
-  if (normalise) l = (l + 80.0f) / 80.0f;
-  out[(size_t)b * frames + t] = l;
+  out[(size_t)b * frames + t] = loudness_frame_db(power + (size_t)b * bins * frames_pad + t, frames_pad, bins,
+                                                  __uint_as_float(max_bits[b]), amin, top_db, normalise);
 }
 
 // the shared limits (stft_tile.h) for one staged signal, and hop <= n_fft: e.g. n_fft 2048 allows hop <= 1250, n_fft 1024 hop <= 1024
@@ -133,6 +123,23 @@ int nws_loudness(const float* audio, int B, int N, int n_fft, int hop, const flo
   loudness_db_kernel<<<g2, 256, 0, st>>>(power, max_bits, bins, frames, frames_pad, amin, top_db, normalise, out);
   NWS_CHECK_LAUNCH();
   return NWS_OK;
+}
+
+// The power pass alone, handed out as power_out (B) floats: the clip maximum nws_loudness normalises by.  A loudness stream with
+// this value as its fixed reference is nws_loudness of the clip; measured on a sound check it is a calibration.
+int nws_loudness_peak_power(const float* audio, int B, int N, int n_fft, int hop, const float* dft, float* power_out,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  if (!audio || !dft || !power_out || !workspace || B <= 0 || !fft_ok(n_fft, hop)) return NWS_ERR_BAD_ARG;
+  if (N <= n_fft / 2) return NWS_ERR_BAD_ARG;
+  if (B > 65535) return NWS_ERR_UNSUPPORTED;
+  if (workspace_bytes < nws_loudness_workspace_bytes(B, N, n_fft, hop)) return NWS_ERR_WORKSPACE;
+  const size_t max_bytes = ((size_t)B * sizeof(unsigned) + 255) & ~size_t(255);
+  unsigned* max_bits = static_cast<unsigned*>(workspace);
+  float* power = reinterpret_cast<float*>(static_cast<char*>(workspace) + max_bytes);
+  const int rc = nws_stft_power_pass(audio, B, N, n_fft, hop, dft, power, max_bits, stream);
+  if (rc != NWS_OK) return rc;
+  const hipError_t e = hipMemcpyAsync(power_out, max_bits, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  return e == hipSuccess ? NWS_OK : (int)e;
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@
 // 2 |log(tiny)| + log(2 n_pitch_bins) < 1500, so after 2^21 frames |V| < 3.2e9 and one ulp of V is below 1e-6, four orders under
 // the smallest difference between two transition weights: streams are refused beyond 2^21 frames (4.6 h at hop 128 / 16 kHz).
 #include "pyin_frame.h"
+#include "frame_stream.h"  // frames_done, hist_start: shared with loudness_stream.hip
 
 namespace {
 
@@ -49,14 +50,6 @@ __host__ __device__ inline StreamLayout stream_layout(int npb, int fl) {
   l.bp = l.hist + (((size_t)fl * sizeof(float) + 7) & ~size_t(7));   // uint8 [kRing][2 npb] backpointers
   l.row = l.bp + (((size_t)kRing * 2 * npb + 7) & ~size_t(7));
   return l;
-}
-
-__host__ __device__ inline long long frames_done(long long n, int W, int hop) { return n <= W ? 0 : 1 + (n - W) / hop; }
-// first sample the history keeps: what the frames still to come need, and what a flush reflects about n
-__host__ __device__ inline long long hist_start(long long n, int W, int hop) {
-  const long long a = hop * frames_done(n, W, hop) - W, b = n - W - 1;
-  const long long s = a < b ? a : b;
-  return s < 0 ? 0 : s;
 }
 
 __host__ bool stream_dims(double sr, double fmin, double fmax, int fl, int hop, PyinDims* d) {

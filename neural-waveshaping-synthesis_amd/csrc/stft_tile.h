@@ -38,6 +38,17 @@ __device__ __forceinline__ void tile_stage(const float* const (&rows)[S], int N,
   __syncthreads();
 }
 
+// The same tile of ONE signal that is not a row in memory: sample(i) is position i of the padded row (a stream's
+// [history | chunk], with the reflections resolved by the caller and 0 where a sample does not exist yet); frames t0 .. t0 + 31.
+// Every thread of the workgroup; ends in a barrier.  tile_transform<1> reads what this leaves exactly as it reads tile_stage's.
+template <class Sample>
+__device__ __forceinline__ void tile_stage_from(Sample sample, int n_fft, int hop, long long t0, float* lds) {
+  const int span = (kFrames - 1) * hop + n_fft;
+  const long long first = (long long)hop * t0 - n_fft / 2;
+  for (int j = threadIdx.x; j < span; j += 256) lds[skew(j)] = sample(first + j);
+  __syncthreads();
+}
+
 // the accumulators of a wave's M-tile: x of the first signal, y of the second (S == 2 only).  Two named vectors: the compiler
 // keeps an ARRAY of accumulators apart less well (the K loop then comes out scheduled differently)
 struct TileAcc {

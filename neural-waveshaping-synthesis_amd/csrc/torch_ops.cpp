@@ -955,6 +955,96 @@ Tensor loudness(const Tensor& audio, const Tensor& dft, int64_t n_fft, int64_t h
   return out;
 }
 
+void check_loudness_sizes(const char* op, const Tensor& dft, int64_t n_fft, int64_t hop) {
+  TORCH_CHECK(nws_loudness_workspace_bytes(1, 1, (int)n_fft, (int)hop) > 0, op, ": unsupported n_fft / hop_length (", n_fft, ", ", hop,
+              "): n_fft must be a power of two in [64, 2048], 1 <= hop <= n_fft and 31 hop + n_fft samples must fit 160 KB of LDS");
+  TORCH_CHECK((size_t)dft.numel() * sizeof(float) == nws_loudness_dft_bytes((int)n_fft), op, ": dft does not belong to n_fft = ", n_fft);
+}
+
+// the clip maximum `loudness` normalises by: audio (B, N) -> (B) powers
+Tensor loudness_peak_power(const Tensor& audio, const Tensor& dft, int64_t n_fft, int64_t hop) {
+  check_dev(audio, "audio");
+  check_dev(dft, "dft");
+  check_same_device(audio, "audio", dft, "dft");
+  TORCH_CHECK(audio.dim() == 2 && audio.size(0) >= 1, "loudness_peak_power: expected (B, N), got ", audio.sizes());
+  const int64_t B = audio.size(0), N = audio.size(1);
+  check_loudness_sizes("loudness_peak_power", dft, n_fft, hop);
+  TORCH_CHECK(N > n_fft / 2, "loudness_peak_power: N = ", N, ": the reflect padding needs more than n_fft / 2 = ", n_fft / 2, " samples");
+  const size_t nbytes = nws_loudness_workspace_bytes((int)B, (int)N, (int)n_fft, (int)hop);
+  Launch L(audio);
+  Tensor ws = at::empty({(int64_t)nbytes}, audio.options().dtype(at::kByte));
+  Tensor out = at::empty({B}, audio.options());
+  nws_check(nws_loudness_peak_power(audio.data_ptr<float>(), (int)B, (int)N, (int)n_fft, (int)hop, dft.data_ptr<float>(),
+                                    out.data_ptr<float>(), ws.data_ptr(), nbytes, L.stream), "nws_loudness_peak_power");
+  return out;
+}
+
+// ---- loudness stream (csrc/loudness_stream.hip): the state blob is a uint8 tensor on the device ----------------------------
+size_t loudness_stream_bytes(const char* op, int64_t B, int64_t n_fft, int64_t hop) {
+  const size_t nbytes = B >= 1 && B <= 65535 ? nws_loudness_stream_state_bytes((int)B, (int)n_fft, (int)hop) : 0;
+  TORCH_CHECK(nbytes > 0, op, ": unsupported stream (B ", B, ", n_fft ", n_fft, ", hop ", hop,
+              "): 1 <= B <= 65535, sizes the offline extractor serves and at most 256 hops in half a frame");
+  return nbytes;
+}
+
+void loudness_stream_reset(Tensor& state, int64_t B, int64_t n_fft, int64_t hop, const Tensor& initial_power, bool track) {
+  check_dev(state, "state", at::kByte);
+  check_dev(initial_power, "initial_power");
+  check_same_device(state, "state", initial_power, "initial_power");
+  const size_t nbytes = loudness_stream_bytes("loudness_stream_reset", B, n_fft, hop);
+  TORCH_CHECK((size_t)state.numel() >= nbytes, "loudness_stream_reset: state blob too small (expected ", nbytes, " bytes for B = ", B,
+              ", got ", state.numel(), ")");
+  TORCH_CHECK(initial_power.dim() == 1 && initial_power.size(0) == B, "loudness_stream_reset: initial_power: expected (", B, "), got ",
+              initial_power.sizes());
+  Launch L(state);
+  nws_check(nws_loudness_stream_reset(state.data_ptr(), (size_t)state.numel(), (int)B, (int)n_fft, (int)hop,
+                                      initial_power.data_ptr<float>(), track ? 1 : 0, L.stream), "nws_loudness_stream_reset");
+}
+
+void loudness_stream_step(Tensor& state, const Tensor& dft, int64_t n_fft, int64_t hop, int64_t lag, const Tensor& chunk, int64_t n_seen,
+                          bool final, double amin, double top_db, bool normalise, Tensor& loudness, Tensor& reference_power) {
+  check_dev(chunk, "chunk");
+  check_dev(loudness, "loudness");
+  check_same_device(chunk, "chunk", loudness, "loudness");
+  check_dev(state, "state", at::kByte);
+  check_same_device(chunk, "chunk", state, "state");
+  check_dev(dft, "dft");
+  check_same_device(chunk, "chunk", dft, "dft");
+  TORCH_CHECK(chunk.dim() == 2 && chunk.size(0) >= 1, "loudness_stream_step: expected a (B, n) chunk, got ", chunk.sizes());
+  const int64_t B = chunk.size(0), n = chunk.size(1);
+  const size_t nbytes = loudness_stream_bytes("loudness_stream_step", B, n_fft, hop);
+  TORCH_CHECK((size_t)state.numel() == nbytes, "loudness_stream_step: state does not belong to a stream of B = ", B,
+              " rows of this configuration (expected ", nbytes, " bytes, got ", state.numel(), ")");
+  check_loudness_sizes("loudness_stream_step", dft, n_fft, hop);
+  TORCH_CHECK(lag >= 0 && lag <= 255, "loudness_stream_step: lag ", lag, " outside 0 .. 255");
+  TORCH_CHECK(amin > 0.0 && top_db >= 0.0, "loudness_stream_step: amin must be positive and top_db non-negative");
+  TORCH_CHECK(final || n >= 1, "loudness_stream_step: empty chunk (only a final step may carry no samples)");
+  const int64_t max_chunk = nws_loudness_stream_max_chunk((int)n_fft, (int)hop);
+  TORCH_CHECK(n <= max_chunk, "loudness_stream_step: a step takes at most ", max_chunk, " samples at this hop, got ", n);
+  TORCH_CHECK(!final || n_seen + n > n_fft / 2, "loudness_stream_step: a stream of ", n_seen + n,
+              " samples cannot end: the reflect padding needs more than n_fft / 2 = ", n_fft / 2);
+  const int64_t before = n_seen >= 0 ? nws_loudness_stream_emitted(n_seen, (int)n_fft, (int)hop, (int)lag, 0) : -1;
+  const int64_t after = n_seen >= 0 ? nws_loudness_stream_emitted(n_seen + n, (int)n_fft, (int)hop, (int)lag, final ? 1 : 0) : -1;
+  TORCH_CHECK(before >= 0 && after >= 0, "loudness_stream_step: n_seen ", n_seen, " + ", n, " samples outside 0 .. 2^21 hops");
+  const int64_t m = std::max<int64_t>(after - before, 1);
+  const std::pair<const char*, const Tensor*> outs[2] = {{"loudness", &loudness}, {"reference_power", &reference_power}};
+  for (const auto& [name, t] : outs) {
+    TORCH_CHECK(t->is_cuda() && t->device() == chunk.device() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 2 &&
+                    t->size(0) == B && t->size(1) == loudness.size(1) && t->size(1) >= m && t->size(1) <= INT32_MAX,
+                "loudness_stream_step: ", name, ": expected a contiguous (", B, ", >= ", m,
+                ") Float tensor on the chunk's GPU, the same width for both outputs, got ", t->sizes(), " ", t->scalar_type(), " on ",
+                t->device());
+  }
+  Launch L(chunk);
+  const size_t ws_bytes = nws_loudness_stream_workspace_bytes((int)B, (int)n, (int)n_fft, (int)hop, final ? 1 : 0);
+  Tensor ws = at::empty({(int64_t)ws_bytes}, chunk.options().dtype(at::kByte));
+  nws_check(nws_loudness_stream_step(state.data_ptr(), (size_t)state.numel(), n > 0 ? chunk.data_ptr<float>() : nullptr, (int)B, (int)n,
+                                     n_seen, (int)n_fft, (int)hop, (int)lag, dft.data_ptr<float>(), (float)amin, (float)top_db,
+                                     normalise ? 1 : 0, final ? 1 : 0, loudness.data_ptr<float>(), reference_power.data_ptr<float>(),
+                                     (int)loudness.size(1), ws.data_ptr(), ws_bytes, L.stream),
+            "nws_loudness_stream_step");
+}
+
 // ---- pYIN F0 extractor (csrc/pyin.hip; data/utils/f0_extraction.py:61-92) ------------------------------------------------
 struct PyinCfg {
   double sr, fmin, fmax;
@@ -1839,6 +1929,11 @@ TORCH_LIBRARY(newt_hip, m) {
         "Tensor rand_phase, Tensor? noise_new, Tensor? noise_all, Tensor(b!) out, Tensor(c!)? pre_out) -> ()",
         &g_stream_step);
   m.def("loudness(Tensor audio, Tensor dft, int n_fft, int hop, float amin, float top_db, bool normalise) -> Tensor", &loudness);
+  m.def("loudness_peak_power(Tensor audio, Tensor dft, int n_fft, int hop) -> Tensor", &loudness_peak_power);
+  m.def("loudness_stream_reset(Tensor(a!) state, int B, int n_fft, int hop, Tensor initial_power, bool track) -> ()",
+        &loudness_stream_reset);
+  m.def("loudness_stream_step(Tensor(a!) state, Tensor dft, int n_fft, int hop, int lag, Tensor chunk, int n_seen, bool final, "
+        "float amin, float top_db, bool normalise, Tensor(b!) loudness, Tensor(c!) reference_power) -> ()", &loudness_stream_step);
   m.def("pyin_table(float sample_rate, float fmin, float fmax, int frame_length, int hop) -> Tensor", &pyin_table);
   m.def("pyin_cmnd(Tensor audio, float sample_rate, float fmin, float fmax, int frame_length, int hop) -> Tensor", &pyin_cmnd);
   m.def("pyin_observe(Tensor yin, Tensor table, float sample_rate, float fmin, float fmax, int frame_length, int hop) -> "

@@ -42,6 +42,16 @@ def loudness_frames(audio: torch.Tensor, n_fft: int, hop_length: int, epsilon: f
     return binding().loudness(audio, dft, int(n_fft), int(hop_length), float(epsilon), float(top_db), bool(normalise))
 
 
+def peak_power(audio: torch.Tensor, n_fft: int, hop_length: int) -> torch.Tensor:
+    """(B, N) fp32 CUDA tensor -> (B,) fp32 CUDA: the largest power of a bin of the clip's STFT, the reference `loudness_frames`
+    normalises by.  As `reference` of a `streaming.StreamLoudness` it makes the stream equal `loudness_frames` of the clip;
+    measured on a sound check it is a calibration."""
+    if not isinstance(audio, torch.Tensor) or not audio.is_cuda or audio.dtype != torch.float32 or audio.dim() != 2:
+        raise RuntimeError("audio: expected a (B, N) float32 CUDA tensor (no CPU fallback)")
+    audio = audio.contiguous()
+    return binding().loudness_peak_power(audio, _dft_operand(n_fft, audio.device), int(n_fft), int(hop_length))
+
+
 @gin.configurable
 def extract_perceptual_loudness(audio, sample_rate: float = 16000, n_fft: int = 2048, hop_length: int = 512,
                                 window: str = "hann", epsilon: float = 1e-5,

@@ -795,8 +795,89 @@ class StreamResampler:
                                f"(n_seen {self._n_seen}, t_next {self._t_next})")
 
 
-# ---- fixed-lag pYIN stream: F0 from chunked audio with a bounded delay ---------------------------------------------------
-class StreamF0:
+# ---- analysis streams: frame-rate features from chunked audio with a bounded delay -----------------------------------------
+class _FrameStream:
+    """What `StreamF0` and `StreamLoudness` share: frames of 2 W samples every hop_length, frame e released once frame e + lag
+    exists (DESIGN.md 3.24 has the arithmetic), the counters in the device state blob with a mirror of plain ints on the host
+    that is handed to every step, so nothing is read back; `check()` compares mirror and device on demand.
+    A subclass sets B, dev, frame_length, hop_length, lag, max_chunk, _state and _half (its name for 2 W in messages), and has
+    `reset()`, `_emitted_after`, `_frames_after` and `_step(x, final, m) -> its output tensors, (B, >= m) each`."""
+
+    def _device(self, device):
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise _lib.NwsError(f"{type(self).__name__} on {dev}: the extractor only runs as HIP kernels on an AMD GPU; there is no CPU fallback.")
+        return torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+
+    @property
+    def latency_samples(self) -> int:
+        return self.frame_length // 2 + self.lag * self.hop_length
+
+    @property
+    def samples_in(self) -> int:
+        return self._n_seen
+
+    @property
+    def frames_out(self) -> int:
+        return self._emitted
+
+    def _restart(self):
+        self._n_seen = 0
+        self._emitted = 0
+        self.finished = False
+
+    def push(self, x: torch.Tensor, final: bool = False):
+        """x (B, n) or (n,) float32 CUDA -> the subclass's outputs, (B, m) each: the m >= 0 frames this chunk released.
+        `final` ends the stream (n may be 0 then): the remaining frames up to 1 + samples_in // hop_length."""
+        if self.finished:
+            raise RuntimeError("stream already finished")
+        if isinstance(x, torch.Tensor) and x.dim() == 1 and self.B == 1:
+            x = x.unsqueeze(0)
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != self.B:
+            raise RuntimeError(f"expected a ({self.B}, n) chunk, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+        if not x.is_cuda:
+            raise _lib.NwsError(f"chunk lives on {x.device}: the extractor only runs as HIP kernels on an AMD GPU; there is no CPU fallback.")
+        if not x.is_contiguous():
+            x = x.contiguous()
+        n = int(x.shape[1])
+        if n < 1 and not final:
+            raise RuntimeError("empty chunk")
+        if n > self.max_chunk:                           # long chunks: process in pieces (state makes that exact)
+            outs = []
+            for k0 in range(0, n, self.max_chunk):
+                k1 = min(n, k0 + self.max_chunk)
+                outs.append(self.push(x[:, k0:k1], final and k1 == n))
+            return tuple(torch.cat(o, dim=1) for o in zip(*outs))
+        if final and self._n_seen + n <= self.frame_length // 2:
+            raise RuntimeError(f"a stream of {self._n_seen + n} samples cannot end: the reflect padding needs more than "
+                               f"{self._half} / 2 = {self.frame_length // 2}")
+        after = self._emitted_after(self._n_seen + n, final)
+        if after < 0:
+            raise RuntimeError(f"{type(self).__name__}: the stream is limited to 2^21 hops; reset() it")
+        m = after - self._emitted
+        with torch.cuda.device(self.dev):
+            outs = self._step(x, bool(final), m)
+        self._n_seen += n
+        self._emitted = after
+        self.finished = bool(final)
+        return tuple(o[:, :m] for o in outs)
+
+    def flush(self):
+        """The stream's remaining frames: `push` of an empty chunk with final=True."""
+        with torch.cuda.device(self.dev):
+            return self.push(torch.empty((self.B, 0), dtype=torch.float32, device=self.dev), final=True)
+
+    def check(self) -> None:
+        """Read the device counters back once (synchronises) and compare them with the host's mirror; for tests and debugging."""
+        row = self._state.numel() // self.B
+        cnt = self._state.view(self.B, row)[:, :32].cpu().contiguous().view(torch.int64)
+        frames = -1 if self._n_seen <= self.frame_length // 2 and self.finished else self._frames_after(self._n_seen, self.finished)
+        want = torch.tensor([self._n_seen, frames, self._emitted, int(self.finished)], dtype=torch.int64).expand(self.B, 4)
+        if not torch.equal(cnt, want):
+            raise RuntimeError(f"{type(self).__name__}: device counters {cnt.tolist()} differ from the host's mirror {want[0].tolist()}")
+
+
+class StreamF0(_FrameStream):
     """pYIN F0 of a stream, chunk by chunk (`binding().pyin_stream_step` -> `nws_pyin_stream_step`, csrc/pyin_stream.hip;
     DESIGN.md 3.24), with the offline extractor's names and defaults.  The stream runs the offline forward pass as the samples
     arrive and emits frame e once frame e + lag exists, as the state at e of the best path that ends in frame e + lag;
@@ -817,10 +898,7 @@ class StreamF0:
         self.cfg = _config(sample_rate, minimum_frequency, maximum_frequency, frame_length, hop_length)
         self.frame_length, self.hop_length, self.lag = self.cfg[3], self.cfg[4], int(lag)
         self.fill_unvoiced = None if fill_unvoiced is None else float(fill_unvoiced)
-        dev = torch.device("cuda" if device is None else device)
-        if dev.type != "cuda":
-            raise _lib.NwsError(f"StreamF0 on {dev}: the extractor only runs as HIP kernels on an AMD GPU; there is no CPU fallback.")
-        self.dev = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        self.dev = self._device(device)
         if not 0 <= self.lag <= 255:
             raise RuntimeError(f"StreamF0: lag {self.lag} outside 0 .. 255")
         L = _lib.lib()
@@ -834,81 +912,166 @@ class StreamF0:
             self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
         self.reset()
 
-    # ---- the host's mirror of the device counters ---------------------------------------------------------------------
-    @property
-    def latency_samples(self) -> int:
-        return self.frame_length // 2 + self.lag * self.hop_length
-
-    @property
-    def samples_in(self) -> int:
-        return self._n_seen
-
-    @property
-    def frames_out(self) -> int:
-        return self._emitted
+    _half = "frame_length"
 
     def _emitted_after(self, n_seen: int, final: bool) -> int:
         return int(_lib.lib().nws_pyin_stream_emitted(n_seen, *self.cfg, self.lag, int(final)))
 
+    def _frames_after(self, n_seen: int, final: bool) -> int:
+        return int(_lib.lib().nws_pyin_stream_frames(n_seen, *self.cfg, int(final)))
+
     def reset(self):
         """Back to the initial state: nothing consumed, nothing emitted."""
         binding().pyin_stream_reset(self._state, self.B, *self.cfg)
-        self._n_seen = 0
-        self._emitted = 0
-        self.finished = False
+        self._restart()
 
-    def push(self, x: torch.Tensor, final: bool = False):
-        """x (B, n) or (n,) float32 CUDA -> (f0 (B, m) fp32, voiced_prob (B, m) fp64, states (B, m) int32): the m >= 0 frames this
-        chunk released.  `final` ends the stream (n may be 0 then): the remaining frames up to 1 + samples_in // hop_length."""
-        if self.finished:
-            raise RuntimeError("stream already finished")
-        if isinstance(x, torch.Tensor) and x.dim() == 1 and self.B == 1:
-            x = x.unsqueeze(0)
-        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != self.B:
-            raise RuntimeError(f"expected a ({self.B}, n) chunk, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
-        if not x.is_cuda:
-            raise _lib.NwsError(f"chunk lives on {x.device}: the extractor only runs as HIP kernels on an AMD GPU; there is no CPU fallback.")
-        if not x.is_contiguous():
-            x = x.contiguous()
-        n = int(x.shape[1])
-        if n < 1 and not final:
-            raise RuntimeError("empty chunk")
-        if n > self.max_chunk:                           # long chunks: process in pieces (state makes that exact)
-            outs = []
-            for k0 in range(0, n, self.max_chunk):
-                k1 = min(n, k0 + self.max_chunk)
-                outs.append(self.push(x[:, k0:k1], final and k1 == n))
-            return tuple(torch.cat([o[i] for o in outs], dim=1) for i in range(3))
-        if final and self._n_seen + n <= self.frame_length // 2:
-            raise RuntimeError(f"a stream of {self._n_seen + n} samples cannot end: the reflect padding needs more than "
-                               f"frame_length / 2 = {self.frame_length // 2}")
-        after = self._emitted_after(self._n_seen + n, final)
-        if after < 0:
-            raise RuntimeError("StreamF0: the stream is limited to 2^21 hops; reset() it")
-        m = after - self._emitted
-        with torch.cuda.device(self.dev):
-            f0 = torch.empty((self.B, max(m, 1)), dtype=torch.float32, device=self.dev)
-            voiced_prob = torch.empty((self.B, max(m, 1)), dtype=torch.float64, device=self.dev)
-            states = torch.empty((self.B, max(m, 1)), dtype=torch.int32, device=self.dev)
-        binding().pyin_stream_step(self._state, self._table, *self.cfg, self.lag, x, self._n_seen, bool(final),
+    def _step(self, x, final, m):
+        """-> (f0 fp32, voiced_prob fp64, states int32)"""
+        f0 = torch.empty((self.B, max(m, 1)), dtype=torch.float32, device=self.dev)
+        voiced_prob = torch.empty((self.B, max(m, 1)), dtype=torch.float64, device=self.dev)
+        states = torch.empty((self.B, max(m, 1)), dtype=torch.int32, device=self.dev)
+        binding().pyin_stream_step(self._state, self._table, *self.cfg, self.lag, x, self._n_seen, final,
                                    self.fill_unvoiced is not None, self.fill_unvoiced if self.fill_unvoiced is not None else 0.0,
                                    f0, voiced_prob, states)
-        self._n_seen += n
-        self._emitted = after
-        self.finished = bool(final)
-        return f0[:, :m], voiced_prob[:, :m], states[:, :m]
+        return f0, voiced_prob, states
+
+
+# ---- loudness stream: the loudness feature with a causal reference level ----------------------------------------------------
+class StreamLoudness(_FrameStream):
+    """Perceptual loudness of a stream, chunk by chunk (`binding().loudness_stream_step` -> `nws_loudness_stream_step`,
+    csrc/loudness_stream.hip), with the offline extractor's names and the pipeline's defaults
+    (gin/data/urmp_4second_pyin.gin), which pair it with a `StreamF0`: both emit the same number of frames on every push.
+
+    The offline feature is measured against the loudest bin of the WHOLE clip, which a stream does not know.  Here frame e
+    leaves once frame e + lag exists and is measured against a reference power that depends on e, the lag and the signal alone,
+    never on the chunking:
+      * reference="running": the largest power heard up to frame e + lag (at the flush: up to the last frame).  Quiet starts
+        are rendered too loud until the signal's peak has been heard; from then on the frames are the offline ones, bit for bit.
+        The maximum does not decay: one click pins the reference until `reset()`.
+      * reference=a float or a (B,) tensor of powers: fixed, a calibration - `loudness_extraction.peak_power` of a sound check,
+        for example.  With the clip's own peak power the stream is `loudness_frames` of the clip, bit for bit.  A signal louder
+        than its reference gives values above 1 (above 0 dB without `normalise`); they are not clipped.
+      * floor_power (with "running"): the running maximum starts at this power instead of 0, so that the room noise in front of
+        the first note is not rendered at 0 dB.
+    `push` returns (loudness (B, m) fp32, reference_power (B, m) fp32): the frames released and the reference each was measured
+    against.  `final` (or `flush()`) computes the last frames against the reflected right edge and releases the rest.  The
+    output runs `latency_samples` = n_fft / 2 + lag hop_length samples behind the input."""
+
+    _half = "n_fft"
+
+    def __init__(self, batch_size: int, n_fft: int = 1024, hop_length: int = 128, lag: int = 8, reference="running",
+                 floor_power=None, epsilon: float = 1e-5, normalise: bool = True, device=None):
+        from .data.utils.loudness_extraction import _dft_operand
+
+        self.B = int(batch_size)
+        self.n_fft = self.frame_length = int(n_fft)
+        self.hop_length, self.lag = int(hop_length), int(lag)
+        self.epsilon, self.normalise = float(epsilon), bool(normalise)
+        self.dev = self._device(device)
+        if not 0 <= self.lag <= 255:
+            raise RuntimeError(f"StreamLoudness: lag {self.lag} outside 0 .. 255")
+        if not self.epsilon > 0.0:
+            raise RuntimeError(f"StreamLoudness: epsilon {self.epsilon} must be positive")
+        L = _lib.lib()
+        nbytes = L.nws_loudness_stream_state_bytes(self.B, self.n_fft, self.hop_length) if 1 <= self.B <= 65535 else 0
+        if nbytes == 0:
+            raise RuntimeError(f"StreamLoudness: unsupported stream (B {self.B}, n_fft {self.n_fft}, hop_length {self.hop_length}): "
+                               "1 <= B <= 65535, sizes the offline extractor serves (n_fft a power of two in [64, 2048], "
+                               "1 <= hop_length <= n_fft, 31 hop_length + n_fft samples within 160 KB of LDS), and at most 256 hops "
+                               "in half a frame")
+        self.max_chunk = int(L.nws_loudness_stream_max_chunk(self.n_fft, self.hop_length))
+        self.track = isinstance(reference, str)
+        if self.track:
+            if reference != "running":
+                raise RuntimeError(f"StreamLoudness: reference {reference!r}: expected 'running', a power or a (B,) tensor of powers")
+            self._initial = self._powers(0.0 if floor_power is None else floor_power, "floor_power")
+        else:
+            if floor_power is not None:
+                raise RuntimeError("StreamLoudness: floor_power belongs to reference='running'; a fixed reference has no floor")
+            self._initial = self._powers(reference, "reference")
+        self._dft = _dft_operand(self.n_fft, self.dev)
+        with torch.cuda.device(self.dev):
+            self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        self.reset()
+
+    def _powers(self, value, name) -> torch.Tensor:
+        """a power or a (B,) tensor of powers -> (B,) fp32 on the stream's GPU; checked once, here (this reads a tensor back)"""
+        if isinstance(value, torch.Tensor):
+            p = value.detach().to(device=self.dev, dtype=torch.float32).reshape(-1).contiguous()
+            if p.numel() != self.B:
+                raise RuntimeError(f"StreamLoudness: {name}: expected ({self.B},) powers, got {tuple(value.shape)}")
+        else:
+            p = torch.full((self.B,), float(value), dtype=torch.float32, device=self.dev)
+        if not bool((torch.isfinite(p) & (p >= 0)).all()):
+            raise RuntimeError(f"StreamLoudness: {name}: powers must be finite and >= 0")
+        return p
+
+    def _emitted_after(self, n_seen: int, final: bool) -> int:
+        return int(_lib.lib().nws_loudness_stream_emitted(n_seen, self.n_fft, self.hop_length, self.lag, int(final)))
+
+    def _frames_after(self, n_seen: int, final: bool) -> int:
+        return int(_lib.lib().nws_loudness_stream_frames(n_seen, self.n_fft, self.hop_length, int(final)))
+
+    def reset(self):
+        """Back to the initial state: nothing consumed, nothing emitted, the reference level at its initial power."""
+        binding().loudness_stream_reset(self._state, self.B, self.n_fft, self.hop_length, self._initial, self.track)
+        self._restart()
+
+    def _step(self, x, final, m):
+        """-> (loudness fp32, reference_power fp32)"""
+        loudness = torch.empty((self.B, max(m, 1)), dtype=torch.float32, device=self.dev)
+        reference_power = torch.empty((self.B, max(m, 1)), dtype=torch.float32, device=self.dev)
+        binding().loudness_stream_step(self._state, self._dft, self.n_fft, self.hop_length, self.lag, x, self._n_seen, final,
+                                       self.epsilon, 80.0, self.normalise, loudness, reference_power)
+        return loudness, reference_power
+
+
+class StreamControl:
+    """Chunked audio -> the model's two inputs: one `StreamF0` and one `StreamLoudness` on the model's sample rate and control
+    hop (frames of 1024 samples, the same lag), and `checkpoint.make_control` on what they release - in float64 on the device,
+    cast to fp32 at the end, so the values are the bits of `make_control` on the two streams' frames.  `reference` and
+    `floor_power` are `StreamLoudness`'s, `fill_unvoiced` is `StreamF0`'s; `mean` / `std` are the dataset statistics of the
+    checkpoint ((f0, loudness) each; None: the features as they are); `octave_shift` transposes F0 by whole octaves.
+    `push(x, final=False)` -> (f0 (B, 1, m) Hz, control (B, 2, m)), ready for `model.stream(B).push` whenever m > 0."""
+
+    def __init__(self, model, batch_size: int, lag: int = 8, reference="running", floor_power=None, mean=None, std=None,
+                 octave_shift: int = 0, fill_unvoiced=None):
+        dev = next(model.parameters()).device
+        sr, hop = float(model.sample_rate), int(model.control_hop)
+        self.f0 = StreamF0(batch_size, sample_rate=sr, frame_length=1024, hop_length=hop, lag=lag, fill_unvoiced=fill_unvoiced,
+                           device=dev)
+        self.loudness = StreamLoudness(batch_size, n_fft=1024, hop_length=hop, lag=lag, reference=reference,
+                                       floor_power=floor_power, device=dev)
+        self.mean = (0.0, 0.0) if mean is None else (float(mean[0]), float(mean[1]))
+        self.std = (1.0, 1.0) if std is None else (float(std[0]), float(std[1]))
+        self.scale = 2.0 ** int(octave_shift)
+
+    @property
+    def latency_samples(self) -> int:
+        return self.f0.latency_samples
+
+    @property
+    def finished(self) -> bool:
+        return self.f0.finished
+
+    def push(self, x: torch.Tensor, final: bool = False):
+        f0 = self.f0.push(x, final)[0]
+        loudness = self.loudness.push(x, final)[0]
+        if f0.shape != loudness.shape:
+            raise RuntimeError(f"StreamControl: the two streams released {f0.shape[1]} and {loudness.shape[1]} frames")
+        f0 = f0.double() * self.scale
+        control = torch.stack([(f0 - self.mean[0]) / self.std[0], (loudness.double() - self.mean[1]) / self.std[1]], dim=-2)
+        return f0.float().unsqueeze(-2), control.float()
 
     def flush(self):
-        """The stream's remaining frames: `push` of an empty chunk with final=True."""
-        with torch.cuda.device(self.dev):
-            return self.push(torch.empty((self.B, 0), dtype=torch.float32, device=self.dev), final=True)
+        """The remaining frames of both streams."""
+        with torch.cuda.device(self.f0.dev):
+            return self.push(torch.empty((self.f0.B, 0), dtype=torch.float32, device=self.f0.dev), final=True)
+
+    def reset(self):
+        self.f0.reset()
+        self.loudness.reset()
 
     def check(self) -> None:
-        """Read the device counters back once (synchronises) and compare them with the host's mirror; for tests and debugging."""
-        row = self._state.numel() // self.B
-        cnt = self._state.view(self.B, row)[:, :32].cpu().contiguous().view(torch.int64)
-        frames = -1 if self._n_seen <= self.frame_length // 2 and self.finished else int(
-            _lib.lib().nws_pyin_stream_frames(self._n_seen, *self.cfg, int(self.finished)))
-        want = torch.tensor([self._n_seen, frames, self._emitted, int(self.finished)], dtype=torch.int64).expand(self.B, 4)
-        if not torch.equal(cnt, want):
-            raise RuntimeError(f"StreamF0: device counters {cnt.tolist()} differ from the host's mirror {want[0].tolist()}")
+        self.f0.check()
+        self.loudness.check()
