@@ -584,7 +584,8 @@ int nws_loudness_peak_power(const float* audio, int B, int N, int n_fft, int hop
  * term for term nws_loudness's dB pass, the sum over k in order.  Without `track` a signal louder than its reference gives
  * values above 0 dB (above 1 normalised); they are not clipped.  track with initial_power 0 is the running reference; no track
  * with nws_loudness_peak_power of the clip is nws_loudness of the clip, bit for bit, at any lag and chunking; so is the
- * running reference at lag >= T - 1.  The maximum does not decay: one click pins the reference until the next reset.
+ * running reference at lag >= T - 1.  The maximum does not decay here: one click pins the reference until the next reset (the _release
+ * entry points below add a decay).
  * Row b's new frames go to columns 0 .. of row b of the (B, out_stride) outputs loudness_out and ref_out (the reference power
  * each frame was measured against); the rest is untouched.  Latency: W + lag hop samples.
  * State blob (nws_loudness_stream_state_bytes; device memory, 8-byte aligned), B rows of
@@ -613,6 +614,44 @@ int nws_loudness_stream_reset(void* state, size_t bytes, int B, int n_fft, int h
 int nws_loudness_stream_step(void* state, size_t bytes, const float* x, int B, int n, int64_t n_seen, int n_fft, int hop, int lag,
                              const float* dft, float amin, float top_db, int normalise, int final, float* loudness_out,
                              float* ref_out, int out_stride, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Loudness stream with a release: the tracked level falls by a constant factor per frame, so a click no longer
+ * pins the reference.  release_factor rho = float(10^(-release_db_per_s hop / (10 sample_rate))), 0 < rho <= 1, computed by the
+ * caller in double and rounded once; F = floor_power[b] >= 0.  In fp32, one product, nothing fused:
+ *   d = rho M(t - 1);  if d < 2^-126: d = 0;  M(t) = max(p(t), F, d);  M(-1) = F
+ * A decaying M is not monotone, so a frame e that leaves in a step without `final` is measured against
+ * ref(e) = max_{t = e .. e + lag} M(t), one the flush releases against max_{t = e .. T - 1} M(t); ref(e) >= p(e) always.  At
+ * rho = 1 this is the stream above, bit for bit (nothing is flushed there).  The bits depend on the signal, lag and rho alone, never
+ * on the chunking.
+ *   nws_loudness_stream_release_state_bytes  the blob of a releasing stream: the B rows above, then float F[B] padded to 8 bytes.
+ *   nws_loudness_stream_reset_release        a tracking stream at M = F with the floors stored; its rows carry track = 3.
+ *   nws_loudness_stream_step_release         nws_loudness_stream_step with release_factor; `track` is the caller's mirror of how the
+ *     stream was reset.  At release_factor 1 it is nws_loudness_stream_step on either kind of blob.  Below 1 the blob must come from
+ *     nws_loudness_stream_reset_release (the kernels compare the rows' track word and leave everything untouched otherwise).
+ * Further refusals (NWS_ERR_BAD_ARG, before any launch): release_factor NaN or outside (0, 1]; release_factor < 1 without track;
+ * release_factor < 1 on a blob below nws_loudness_stream_release_state_bytes.
+ */
+size_t nws_loudness_stream_release_state_bytes(int B, int n_fft, int hop);
+int nws_loudness_stream_reset_release(void* state, size_t bytes, int B, int n_fft, int hop, const float* floor_power, void* stream);
+int nws_loudness_stream_step_release(void* state, size_t bytes, const float* x, int B, int n, int64_t n_seen, int n_fft, int hop,
+                                     int lag, float release_factor, int track, const float* dft, float amin, float top_db,
+                                     int normalise, int final, float* loudness_out, float* ref_out, int out_stride, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+
+/*
+ * The loudness stream's feature of a whole clip in one call: audio (B, N) -> loudness_out, ref_out, peak_out (B, 1 + N / hop) each,
+ * the concatenated outputs of a stream over the clip (any chunking, then the flush), bit for bit, and p(t).  Frames
+ * e < F(N) - lag take the window e .. e + lag, the rest the window e .. T - 1.  track: the running (releasing) reference from
+ * floor_power (device memory, B floats; NULL: 0); no track: floor_power is the fixed reference.
+ * Refusals: nws_loudness's, lag outside 0 .. 255, release_factor as above, NULL floor_power without track (NWS_ERR_BAD_ARG); sizes
+ * the stream refuses or a clip beyond 2^21 hops (NWS_ERR_UNSUPPORTED); a workspace below nws_loudness_causal_workspace_bytes
+ * (NWS_ERR_WORKSPACE).
+ */
+size_t nws_loudness_causal_workspace_bytes(int B, int N, int n_fft, int hop);
+int nws_loudness_causal(const float* audio, int B, int N, int n_fft, int hop, const float* dft, int lag, float release_factor,
+                        const float* floor_power, int track, float amin, float top_db, int normalise, float* loudness_out,
+                        float* ref_out, float* peak_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * pYIN F0 extractor, the other analysis feature in front of the synthesis path:

@@ -607,50 +607,124 @@ class CtypesOps:
             check(_lib.lib().nws_loudness_stream_reset(ptr(state), state.numel(), B, n_fft, hop, ptr(initial_power), 1 if track else 0,
                                                        _stream(state.device)), "nws_loudness_stream_reset")
 
+    def loudness_stream_reset_release(self, state, B, n_fft, hop, floor_power):
+        _check_state(state)
+        _check_dev("floor_power", floor_power, state, "state")
+        self._loudness_stream_bytes("loudness_stream_reset_release", B, n_fft, hop)
+        nbytes = _lib.lib().nws_loudness_stream_release_state_bytes(B, n_fft, hop)
+        if state.numel() < nbytes:
+            raise RuntimeError(f"loudness_stream_reset_release: state blob too small (expected {nbytes} bytes for B = {B}, got {state.numel()})")
+        if floor_power.dim() != 1 or floor_power.shape[0] != B:
+            raise RuntimeError(f"loudness_stream_reset_release: floor_power: expected ({B}), got {tuple(floor_power.shape)}")
+        with torch.cuda.device(state.device):
+            check(_lib.lib().nws_loudness_stream_reset_release(ptr(state), state.numel(), B, n_fft, hop, ptr(floor_power),
+                                                               _stream(state.device)), "nws_loudness_stream_reset_release")
+
     def loudness_stream_step(self, state, dft, n_fft, hop, lag, chunk, n_seen, final, amin, top_db, normalise, loudness,
                              reference_power):
+        self._loudness_stream_step("loudness_stream_step", False, state, dft, n_fft, hop, lag, 1.0, True, chunk, n_seen, final, amin,
+                                   top_db, normalise, loudness, reference_power)
+
+    def loudness_stream_step_release(self, state, dft, n_fft, hop, lag, release_factor, track, chunk, n_seen, final, amin, top_db,
+                                     normalise, loudness, reference_power):
+        self._loudness_stream_step("loudness_stream_step_release", True, state, dft, n_fft, hop, lag, release_factor, track, chunk,
+                                   n_seen, final, amin, top_db, normalise, loudness, reference_power)
+
+    def _loudness_stream_step(self, op, with_release, state, dft, n_fft, hop, lag, release_factor, track, chunk, n_seen, final, amin,
+                              top_db, normalise, loudness, reference_power):
+        """the step of both ops.  with_release: loudness_stream_step_release, whose release_factor 1 is loudness_stream_step on either
+        kind of blob; below 1 the blob is loudness_stream_reset_release's, hence track"""
         _check_dev("chunk", chunk)
         _check_dev("loudness", loudness, chunk, "chunk")
         _check_state(state, chunk)
         _check_dev("dft", dft, chunk, "chunk")
         if chunk.dim() != 2 or chunk.shape[0] < 1:
-            raise RuntimeError(f"loudness_stream_step: expected a (B, n) chunk, got {tuple(chunk.shape)}")
+            raise RuntimeError(f"{op}: expected a (B, n) chunk, got {tuple(chunk.shape)}")
         B, n = chunk.shape
         lib = _lib.lib()
-        nbytes = self._loudness_stream_bytes("loudness_stream_step", B, n_fft, hop)
-        if state.numel() != nbytes:
-            raise RuntimeError(f"loudness_stream_step: state does not belong to a stream of B = {B} rows of this configuration "
-                               f"(expected {nbytes} bytes, got {state.numel()})")
-        self._check_loudness_sizes("loudness_stream_step", dft, n_fft, hop)
+        nbytes = self._loudness_stream_bytes(op, B, n_fft, hop)
+        releasing = release_factor < 1.0
+        rbytes = lib.nws_loudness_stream_release_state_bytes(B, n_fft, hop)
+        if with_release:
+            if not 0.0 < release_factor <= 1.0:
+                raise RuntimeError(f"{op}: release_factor {release_factor} outside (0, 1]")
+            if releasing and not track:
+                raise RuntimeError(f"{op}: a release needs a tracked reference")
+        have = state.numel()
+        if not (have == rbytes if releasing else have == nbytes or (with_release and have == rbytes)):
+            raise RuntimeError(f"{op}: state does not belong to a stream of B = {B} rows of this configuration "
+                               f"(expected {rbytes if releasing else nbytes} bytes, got {state.numel()})")
+        self._check_loudness_sizes(op, dft, n_fft, hop)
         if not 0 <= lag <= 255:
-            raise RuntimeError(f"loudness_stream_step: lag {lag} outside 0 .. 255")
+            raise RuntimeError(f"{op}: lag {lag} outside 0 .. 255")
         if not (amin > 0.0 and top_db >= 0.0):
-            raise RuntimeError("loudness_stream_step: amin must be positive and top_db non-negative")
+            raise RuntimeError(f"{op}: amin must be positive and top_db non-negative")
         if n < 1 and not final:
-            raise RuntimeError("loudness_stream_step: empty chunk (only a final step may carry no samples)")
+            raise RuntimeError(f"{op}: empty chunk (only a final step may carry no samples)")
         max_chunk = lib.nws_loudness_stream_max_chunk(n_fft, hop)
         if n > max_chunk:
-            raise RuntimeError(f"loudness_stream_step: a step takes at most {max_chunk} samples at this hop, got {n}")
+            raise RuntimeError(f"{op}: a step takes at most {max_chunk} samples at this hop, got {n}")
         if final and n_seen + n <= n_fft // 2:
-            raise RuntimeError(f"loudness_stream_step: a stream of {n_seen + n} samples cannot end: the reflect padding needs more "
+            raise RuntimeError(f"{op}: a stream of {n_seen + n} samples cannot end: the reflect padding needs more "
                                f"than n_fft / 2 = {n_fft // 2}")
         before = lib.nws_loudness_stream_emitted(n_seen, n_fft, hop, lag, 0) if n_seen >= 0 else -1
         after = lib.nws_loudness_stream_emitted(n_seen + n, n_fft, hop, lag, 1 if final else 0) if n_seen >= 0 else -1
         if before < 0 or after < 0:
-            raise RuntimeError(f"loudness_stream_step: n_seen {n_seen} + {n} samples outside 0 .. 2^21 hops")
+            raise RuntimeError(f"{op}: n_seen {n_seen} + {n} samples outside 0 .. 2^21 hops")
         m = after - before
         for name, t in (("loudness", loudness), ("reference_power", reference_power)):
             if (not t.is_cuda or t.device != chunk.device or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2
                     or t.shape[0] != B or t.shape[1] != loudness.shape[1] or not max(m, 1) <= t.shape[1] < 2 ** 31):
-                raise RuntimeError(f"loudness_stream_step: {name}: expected a contiguous ({B}, >= {max(m, 1)}) Float tensor on the "
+                raise RuntimeError(f"{op}: {name}: expected a contiguous ({B}, >= {max(m, 1)}) Float tensor on the "
                                    f"chunk's GPU, the same width for both outputs, got {tuple(t.shape)} {t.dtype} on {t.device}")
         with torch.cuda.device(chunk.device):
             ws_bytes = lib.nws_loudness_stream_workspace_bytes(B, n, n_fft, hop, 1 if final else 0)
             ws = _new(chunk, ws_bytes, dtype=torch.uint8)
-            check(lib.nws_loudness_stream_step(ptr(state), state.numel(), ptr(chunk) if n > 0 else None, B, n, n_seen, n_fft, hop, lag,
-                                               ptr(dft), amin, top_db, 1 if normalise else 0, 1 if final else 0, ptr(loudness),
-                                               ptr(reference_power), loudness.shape[1], ptr(ws), ws_bytes, _stream(chunk.device)),
-                  "nws_loudness_stream_step")
+            x = ptr(chunk) if n > 0 else None
+            if with_release:
+                check(lib.nws_loudness_stream_step_release(ptr(state), state.numel(), x, B, n, n_seen, n_fft, hop, lag, release_factor,
+                                                           1 if track else 0, ptr(dft), amin, top_db, 1 if normalise else 0,
+                                                           1 if final else 0, ptr(loudness), ptr(reference_power), loudness.shape[1],
+                                                           ptr(ws), ws_bytes, _stream(chunk.device)), "nws_loudness_stream_step_release")
+            else:
+                check(lib.nws_loudness_stream_step(ptr(state), state.numel(), x, B, n, n_seen, n_fft, hop, lag, ptr(dft), amin, top_db,
+                                                   1 if normalise else 0, 1 if final else 0, ptr(loudness), ptr(reference_power),
+                                                   loudness.shape[1], ptr(ws), ws_bytes, _stream(chunk.device)),
+                      "nws_loudness_stream_step")
+
+    def loudness_causal(self, audio, dft, n_fft, hop, lag, release_factor, floor_power, track, amin, top_db, normalise):
+        _check_dev("audio", audio)
+        _check_dev("dft", dft, audio, "audio")
+        _check_dev("floor_power", floor_power, audio, "audio")
+        if audio.dim() != 2 or audio.shape[0] < 1:
+            raise RuntimeError(f"loudness_causal: expected (B, N), got {tuple(audio.shape)}")
+        B, N = audio.shape
+        self._check_loudness_sizes("loudness_causal", dft, n_fft, hop)
+        if N <= n_fft // 2:
+            raise RuntimeError(f"loudness_causal: N = {N}: the reflect padding needs more than n_fft / 2 = {n_fft // 2} samples")
+        if not 0 <= lag <= 255:
+            raise RuntimeError(f"loudness_causal: lag {lag} outside 0 .. 255")
+        if not (amin > 0.0 and top_db >= 0.0):
+            raise RuntimeError("loudness_causal: amin must be positive and top_db non-negative")
+        if not 0.0 < release_factor <= 1.0:
+            raise RuntimeError(f"loudness_causal: release_factor {release_factor} outside (0, 1]")
+        if release_factor != 1.0 and not track:
+            raise RuntimeError("loudness_causal: a release needs a tracked reference")
+        if floor_power.dim() != 1 or floor_power.shape[0] != B:
+            raise RuntimeError(f"loudness_causal: floor_power: expected ({B}), got {tuple(floor_power.shape)}")
+        L = _lib.lib()
+        nbytes = L.nws_loudness_causal_workspace_bytes(B, N, n_fft, hop) if B <= 65535 and N < 2 ** 31 else 0
+        if nbytes == 0:
+            raise RuntimeError(f"loudness_causal: unsupported clip (B {B}, N {N}, n_fft {n_fft}, hop {hop}): 1 <= B <= 65535, sizes the "
+                               "loudness stream serves (at most 256 hops in half a frame) and at most 2^21 hops")
+        with torch.cuda.device(audio.device):
+            ws = _new(audio, nbytes, dtype=torch.uint8)
+            T = L.nws_loudness_frames(N, hop)
+            loud, ref, peak = _new(audio, B, T), _new(audio, B, T), _new(audio, B, T)
+            check(L.nws_loudness_causal(ptr(audio), B, N, n_fft, hop, ptr(dft), lag, release_factor, ptr(floor_power), 1 if track else 0,
+                                        amin, top_db, 1 if normalise else 0, ptr(loud), ptr(ref), ptr(peak), ptr(ws), nbytes,
+                                        _stream(audio.device)), "nws_loudness_causal")
+        return loud, ref, peak
 
     # ---- pYIN F0 extractor (csrc/pyin.hip) -------------------------------------------------------------------------------
     def pyin_table(self, sample_rate, fmin, fmax, frame_length, hop):

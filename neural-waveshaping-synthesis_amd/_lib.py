@@ -207,6 +207,14 @@ _PROTOTYPES = {
     "nws_loudness_stream_reset": (C.c_int, [_fp, C.c_size_t, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp]),
     "nws_loudness_stream_step": (C.c_int, [_fp, C.c_size_t, _fp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _fp, C.c_float,
                                            C.c_float, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, C.c_size_t, _fp]),
+    "nws_loudness_stream_release_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nws_loudness_stream_reset_release": (C.c_int, [_fp, C.c_size_t, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "nws_loudness_stream_step_release": (C.c_int, [_fp, C.c_size_t, _fp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                                   C.c_float, C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_int, _fp, _fp, C.c_int,
+                                                   _fp, C.c_size_t, _fp]),
+    "nws_loudness_causal_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "nws_loudness_causal": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_float, _fp, C.c_int, C.c_float,
+                                      C.c_float, C.c_int, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
     "nws_pyin_frames": (C.c_int, [C.c_int, C.c_int]),
     "nws_pyin_dims": (C.c_int, [*_PYIN_CFG, C.POINTER(C.c_int32)]),
     "nws_pyin_table_bytes": (C.c_size_t, [*_PYIN_CFG]),

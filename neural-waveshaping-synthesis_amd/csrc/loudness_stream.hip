@@ -23,8 +23,14 @@
 // A pass without new frames launches the second only.  Nothing is read back, no workgroup waits for another.  The host passes
 // n_seen (its mirror of the row counter) so that every size and refusal is decided before the first launch; both kernels compare
 // it with the device's counters and leave state and outputs untouched if they differ.
+//
+// With a release (the _release entry points) M decays by the factor rho per frame, never below the row's floor F:
+// loudness_level.h has the step.  M is no longer monotone then, so frame e is measured against the maximum of M over e .. e + L
+// (on a flush over e .. T - 1), which at rho = 1 is the M(e + L) above.  The floors live behind the B rows of the blob
+// (nws_loudness_stream_release_state_bytes), so a row keeps the layout above; such a row carries track = 3.
 #include "stft_tile.h"
 #include "loudness_db.h"
+#include "loudness_level.h"
 #include "frame_stream.h"  // frames_done, hist_start: shared with pyin_stream.hip
 
 namespace {
@@ -65,16 +71,25 @@ __host__ int pass_frames_bound(int n, int n_fft, int hop, int final) {
 
 __host__ size_t stream_ws_bytes(int B, int frames) { return ((size_t)B * frames * sizeof(unsigned) + 255) & ~size_t(255); }
 
+constexpr int kTrackRelease = 3;         // the row's track word after nws_loudness_stream_reset_release: tracking, floors in the blob
+
+// the floors F[B] of a releasing stream follow the B rows
+__host__ inline size_t release_bytes(int B, int n_fft) { return (size_t)B * loud_layout(n_fft).row + (((size_t)B * sizeof(float) + 7) & ~size_t(7)); }
+
 struct LoudPass {
   int B, n, flush, lag;
+  int track;                        // the track word the caller expects of every row; -1: any
+  float rho;                        // release factor, 1: none
   long long n_seen, n_total;        // samples before and after the pass
   long long hs0, hs1;               // hist_start before and after
   int f0, f1, e0, e1;               // frames computed / emitted before and after
   int out_off, out_stride;
 };
 
-__device__ __forceinline__ bool stream_state_matches(const long long* cnt, const LoudPass& g) {
-  return cnt[0] == g.n_seen && cnt[1] == g.f0 && cnt[2] == g.e0 && cnt[3] == 0;
+__device__ __forceinline__ bool stream_state_matches(const unsigned char* rs, const LoudLayout& l, const LoudPass& g) {
+  const long long* cnt = reinterpret_cast<const long long*>(rs + l.cnt);
+  const int track = *reinterpret_cast<const int*>(rs + l.ref + 4);
+  return cnt[0] == g.n_seen && cnt[1] == g.f0 && cnt[2] == g.e0 && cnt[3] == 0 && (g.track < 0 || track == g.track);
 }
 
 // grid (tiles of 32 new frames, groups of 4 M-tiles, B); pmax (B, f1 - f0) zeroed
@@ -85,7 +100,7 @@ __global__ __launch_bounds__(256) void loudness_stream_power_kernel(unsigned cha
   const TileCoord c;
   const LoudLayout l = loud_layout(n_fft);
   unsigned char* rs = state + (size_t)c.b * l.row;
-  if (!stream_state_matches(reinterpret_cast<const long long*>(rs + l.cnt), g)) return;   // workgroup-uniform, in front of the barrier
+  if (!stream_state_matches(rs, l, g)) return;   // workgroup-uniform, in front of the barrier
   const float* hist = reinterpret_cast<const float*>(rs + l.hist);
   const float* xr = x + (size_t)c.b * g.n;
   const long long N = g.n_total;
@@ -122,26 +137,28 @@ __global__ __launch_bounds__(256) void loudness_stream_power_kernel(unsigned cha
 __global__ __launch_bounds__(256) void loudness_stream_emit_kernel(unsigned char* __restrict__ state, const float* __restrict__ x,
                                                                    LoudPass g, int n_fft, const unsigned* __restrict__ pmax,
                                                                    float amin, float top_db, int normalise,
-                                                                   float* __restrict__ loud, float* __restrict__ ref_out) {
+                                                                   const float* __restrict__ floors, float* __restrict__ loud,
+                                                                   float* __restrict__ ref_out) {
   extern __shared__ float hs[];     // [n_fft] the row's new history, then [kStepFrames + 1] M of the pass's new frames
   float* sm = hs + n_fft;
   const int tid = threadIdx.x, b = blockIdx.x, bins = n_fft / 2 + 1, nf = g.f1 - g.f0;
   const LoudLayout l = loud_layout(n_fft);
   unsigned char* rs = state + (size_t)b * l.row;
   long long* cnt = reinterpret_cast<long long*>(rs + l.cnt);
-  if (!stream_state_matches(cnt, g)) return;    // workgroup-uniform, in front of every barrier
+  if (!stream_state_matches(rs, l, g)) return;    // workgroup-uniform, in front of every barrier
   float* Mp = reinterpret_cast<float*>(rs + l.ref);
   const int track = *reinterpret_cast<const int*>(rs + l.ref + 4);
   float* hist = reinterpret_cast<float*>(rs + l.hist);
   float* mring = reinterpret_cast<float*>(rs + l.mring);
   const float* pring = reinterpret_cast<const float*>(rs + l.pring);
-  // the M ring grows by the new frames: a serial prefix maximum (track) or the constant (fixed reference)
+  // the M ring grows by the new frames: the serial level recurrence (track) or the constant (fixed reference)
   for (int i = tid; i < nf; i += 256) sm[i] = __uint_as_float(pmax[(size_t)b * nf + i]);
   __syncthreads();
   if (tid == 0 && nf > 0) {
     float M = *Mp;
+    const float F = floors ? floors[b] : 0.0f;   // read at rho < 1 only, and then it is there
     for (int i = 0; i < nf; ++i) {
-      if (track) M = fmaxf(M, sm[i]);
+      if (track) M = loudness_level_step(M, sm[i], F, g.rho);
       sm[i] = M;
     }
     *Mp = M;
@@ -151,7 +168,10 @@ __global__ __launch_bounds__(256) void loudness_stream_emit_kernel(unsigned char
   // M(t) of a frame this pass computed is in LDS, of an earlier one in the ring
   auto M_of = [&](int t) { return t >= g.f0 ? sm[t - g.f0] : mring[t & (kRing - 1)]; };
   for (int e = g.e0 + tid; e < g.e1; e += 256) {
-    const float ref = M_of(g.flush ? g.f1 - 1 : e + g.lag);
+    const int end = g.flush ? g.f1 - 1 : e + g.lag;
+    float ref = M_of(end);
+    if (g.rho < 1.0f)   // a decaying M is not monotone: the largest level the frame's window holds (<= 511 frames, all in LDS or ring)
+      for (int t = e; t < end; ++t) ref = fmaxf(ref, M_of(t));
     const size_t o = (size_t)b * g.out_stride + g.out_off + (e - g.e0);
     loud[o] = loudness_frame_db(pring + (e & (kRing - 1)), kRing, bins, ref, amin, top_db, normalise);
     ref_out[o] = ref;
@@ -176,13 +196,14 @@ __global__ __launch_bounds__(256) void loudness_stream_emit_kernel(unsigned char
   }
 }
 
-// after the blob was zeroed: M = initial_power of the row, track as given
+// after the blob was zeroed: M = initial_power of the row, track as given; floors (a releasing stream) = initial_power too
 __global__ void loudness_stream_init_kernel(unsigned char* __restrict__ state, int B, size_t row, size_t ref_off,
-                                            const float* __restrict__ initial_power, int track) {
+                                            const float* __restrict__ initial_power, int track, float* __restrict__ floors) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   *reinterpret_cast<float*>(state + (size_t)b * row + ref_off) = initial_power[b];
   *reinterpret_cast<int*>(state + (size_t)b * row + ref_off + 4) = track;
+  if (floors) floors[b] = initial_power[b];
 }
 
 __host__ int run_pass(unsigned char* state, const float* x, const LoudPass& g, int n_fft, int hop, const float* dft, float amin,
@@ -197,8 +218,9 @@ __host__ int run_pass(unsigned char* state, const float* x, const LoudPass& g, i
     loudness_stream_power_kernel<<<grid, 256, tile_lds_bytes(n_fft, hop, 1), stream>>>(state, x, g, n_fft, hop, dft, m_tiles, pmax);
     NWS_CHECK_LAUNCH();
   }
+  const float* floors = g.rho < 1.0f ? reinterpret_cast<const float*>(state + (size_t)g.B * loud_layout(n_fft).row) : nullptr;
   loudness_stream_emit_kernel<<<g.B, 256, (size_t)(n_fft + kStepFrames + 1) * sizeof(float), stream>>>(
-      state, x, g, n_fft, pmax, amin, top_db, normalise, loud, ref_out);
+      state, x, g, n_fft, pmax, amin, top_db, normalise, floors, loud, ref_out);
   NWS_CHECK_LAUNCH();
   return NWS_OK;
 }
@@ -237,24 +259,35 @@ int64_t nws_loudness_stream_emitted(int64_t n_seen, int n_fft, int hop, int lag,
   return emitted_after(n_seen, n_fft, hop, lag, final ? 1 : 0);
 }
 
-int nws_loudness_stream_reset(void* state, size_t bytes, int B, int n_fft, int hop, const float* initial_power, int track,
-                              void* stream) {
+size_t nws_loudness_stream_release_state_bytes(int B, int n_fft, int hop) {
+  if (B < 1 || B > 65535 || !stream_ok(n_fft, hop)) return 0;
+  return release_bytes(B, n_fft);
+}
+
+}  // extern "C"
+
+namespace {
+
+// track: 0 / 1 of nws_loudness_stream_reset, kTrackRelease of nws_loudness_stream_reset_release (the blob holds the floors then)
+__host__ int reset_impl(void* state, size_t bytes, int B, int n_fft, int hop, const float* initial_power, int track, void* stream) {
   if (!state || !initial_power || B < 1) return NWS_ERR_BAD_ARG;
   if (B > 65535 || !stream_ok(n_fft, hop)) return NWS_ERR_UNSUPPORTED;
   const LoudLayout l = loud_layout(n_fft);
-  const size_t need = (size_t)B * l.row;
+  const size_t rows = (size_t)B * l.row, need = track == kTrackRelease ? release_bytes(B, n_fft) : rows;
   if (bytes < need) return NWS_ERR_BAD_ARG;
   const hipError_t e = hipMemsetAsync(state, 0, need, (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
-  loudness_stream_init_kernel<<<(B + 255) / 256, 256, 0, (hipStream_t)stream>>>(static_cast<unsigned char*>(state), B, l.row, l.ref,
-                                                                               initial_power, track ? 1 : 0);
+  unsigned char* st = static_cast<unsigned char*>(state);
+  loudness_stream_init_kernel<<<(B + 255) / 256, 256, 0, (hipStream_t)stream>>>(
+      st, B, l.row, l.ref, initial_power, track, track == kTrackRelease ? reinterpret_cast<float*>(st + rows) : nullptr);
   NWS_CHECK_LAUNCH();
   return NWS_OK;
 }
 
-int nws_loudness_stream_step(void* state, size_t bytes, const float* x, int B, int n, int64_t n_seen, int n_fft, int hop, int lag,
-                             const float* dft, float amin, float top_db, int normalise, int final, float* loudness_out,
-                             float* ref_out, int out_stride, void* workspace, size_t workspace_bytes, void* stream) {
+// track -1: whatever the rows carry (the step without a release); rho < 1 needs the floors, so kTrackRelease
+__host__ int step_impl(void* state, size_t bytes, const float* x, int B, int n, int64_t n_seen, int n_fft, int hop, int lag, int track,
+                       float rho, const float* dft, float amin, float top_db, int normalise, int final, float* loudness_out,
+                       float* ref_out, int out_stride, void* workspace, size_t workspace_bytes, void* stream) {
   if (!state || !dft || !loudness_out || !ref_out || !workspace || B < 1 || n < 0 || n_seen < 0 || (n == 0 && !final) ||
       (n > 0 && !x) || lag < 0 || lag > kMaxLag || !(amin > 0.0f) || !(top_db >= 0.0f))
     return NWS_ERR_BAD_ARG;
@@ -265,7 +298,7 @@ int nws_loudness_stream_step(void* state, size_t bytes, const float* x, int B, i
   const long long e_before = emitted_after(n_seen, n_fft, hop, lag, 0), e_mid = emitted_after(N, n_fft, hop, lag, 0);
   const long long e_after = final ? emitted_after(N, n_fft, hop, lag, 1) : e_mid;
   if (out_stride < e_after - e_before) return NWS_ERR_BAD_ARG;
-  if (bytes < (size_t)B * loud_layout(n_fft).row) return NWS_ERR_BAD_ARG;
+  if (bytes < (rho < 1.0f ? release_bytes(B, n_fft) : (size_t)B * loud_layout(n_fft).row)) return NWS_ERR_BAD_ARG;
   if (workspace_bytes < stream_ws_bytes(B, pass_frames_bound(n, n_fft, hop, final ? 1 : 0))) return NWS_ERR_BAD_ARG;
   static unsigned long long attr_devices = 0;
   if (nws_first_use_on_device(attr_devices)) {
@@ -276,18 +309,47 @@ int nws_loudness_stream_step(void* state, size_t bytes, const float* x, int B, i
   unsigned char* st = static_cast<unsigned char*>(state);
   const int norm = normalise ? 1 : 0;
   if (n > 0) {
-    const LoudPass g{B, n, 0, lag, n_seen, N, hist_start(n_seen, W, hop), hist_start(N, W, hop), (int)frames_done(n_seen, W, hop),
+    const LoudPass g{B, n, 0, lag, track, rho, n_seen, N, hist_start(n_seen, W, hop), hist_start(N, W, hop), (int)frames_done(n_seen, W, hop),
                      (int)frames_done(N, W, hop), (int)e_before, (int)e_mid, 0, out_stride};
     const int rc = run_pass(st, x, g, n_fft, hop, dft, amin, top_db, norm, loudness_out, ref_out, workspace, (hipStream_t)stream);
     if (rc != NWS_OK) return rc;
   }
   if (final) {
     const long long hs = hist_start(N, W, hop);
-    const LoudPass g{B, 0, 1, lag, N, N, hs, hs, (int)frames_done(N, W, hop), (int)(1 + N / hop), (int)e_mid, (int)e_after,
+    const LoudPass g{B, 0, 1, lag, track, rho, N, N, hs, hs, (int)frames_done(N, W, hop), (int)(1 + N / hop), (int)e_mid, (int)e_after,
                      (int)(e_mid - e_before), out_stride};
     return run_pass(st, x, g, n_fft, hop, dft, amin, top_db, norm, loudness_out, ref_out, workspace, (hipStream_t)stream);
   }
   return NWS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nws_loudness_stream_reset(void* state, size_t bytes, int B, int n_fft, int hop, const float* initial_power, int track,
+                              void* stream) {
+  return reset_impl(state, bytes, B, n_fft, hop, initial_power, track ? 1 : 0, stream);
+}
+
+int nws_loudness_stream_reset_release(void* state, size_t bytes, int B, int n_fft, int hop, const float* floor_power, void* stream) {
+  return reset_impl(state, bytes, B, n_fft, hop, floor_power, kTrackRelease, stream);
+}
+
+int nws_loudness_stream_step(void* state, size_t bytes, const float* x, int B, int n, int64_t n_seen, int n_fft, int hop, int lag,
+                             const float* dft, float amin, float top_db, int normalise, int final, float* loudness_out,
+                             float* ref_out, int out_stride, void* workspace, size_t workspace_bytes, void* stream) {
+  return step_impl(state, bytes, x, B, n, n_seen, n_fft, hop, lag, -1, 1.0f, dft, amin, top_db, normalise, final, loudness_out, ref_out,
+                   out_stride, workspace, workspace_bytes, stream);
+}
+
+int nws_loudness_stream_step_release(void* state, size_t bytes, const float* x, int B, int n, int64_t n_seen, int n_fft, int hop,
+                                     int lag, float release_factor, int track, const float* dft, float amin, float top_db,
+                                     int normalise, int final, float* loudness_out, float* ref_out, int out_stride, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  if (!(release_factor > 0.0f && release_factor <= 1.0f) || (release_factor < 1.0f && !track)) return NWS_ERR_BAD_ARG;
+  return step_impl(state, bytes, x, B, n, n_seen, n_fft, hop, lag, release_factor < 1.0f ? kTrackRelease : -1, release_factor, dft,
+                   amin, top_db, normalise, final, loudness_out, ref_out, out_stride, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

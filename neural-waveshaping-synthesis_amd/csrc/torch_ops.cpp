@@ -1001,8 +1001,27 @@ void loudness_stream_reset(Tensor& state, int64_t B, int64_t n_fft, int64_t hop,
                                       initial_power.data_ptr<float>(), track ? 1 : 0, L.stream), "nws_loudness_stream_reset");
 }
 
-void loudness_stream_step(Tensor& state, const Tensor& dft, int64_t n_fft, int64_t hop, int64_t lag, const Tensor& chunk, int64_t n_seen,
-                          bool final, double amin, double top_db, bool normalise, Tensor& loudness, Tensor& reference_power) {
+// a releasing stream: tracking, M = floor_power, the floors kept behind the rows of the larger blob
+void loudness_stream_reset_release(Tensor& state, int64_t B, int64_t n_fft, int64_t hop, const Tensor& floor_power) {
+  check_dev(state, "state", at::kByte);
+  check_dev(floor_power, "floor_power");
+  check_same_device(state, "state", floor_power, "floor_power");
+  loudness_stream_bytes("loudness_stream_reset_release", B, n_fft, hop);
+  const size_t nbytes = nws_loudness_stream_release_state_bytes((int)B, (int)n_fft, (int)hop);
+  TORCH_CHECK((size_t)state.numel() >= nbytes, "loudness_stream_reset_release: state blob too small (expected ", nbytes, " bytes for B = ", B,
+              ", got ", state.numel(), ")");
+  TORCH_CHECK(floor_power.dim() == 1 && floor_power.size(0) == B, "loudness_stream_reset_release: floor_power: expected (", B, "), got ",
+              floor_power.sizes());
+  Launch L(state);
+  nws_check(nws_loudness_stream_reset_release(state.data_ptr(), (size_t)state.numel(), (int)B, (int)n_fft, (int)hop,
+                                              floor_power.data_ptr<float>(), L.stream), "nws_loudness_stream_reset_release");
+}
+
+// the step of both ops.  with_release: loudness_stream_step_release, whose release_factor 1 is loudness_stream_step on either kind
+// of blob; below 1 the blob is loudness_stream_reset_release's, hence track
+void loudness_stream_step_impl(const char* op, bool with_release, Tensor& state, const Tensor& dft, int64_t n_fft, int64_t hop, int64_t lag,
+                               double release_factor, bool track, const Tensor& chunk, int64_t n_seen, bool final, double amin,
+                               double top_db, bool normalise, Tensor& loudness, Tensor& reference_power) {
   check_dev(chunk, "chunk");
   check_dev(loudness, "loudness");
   check_same_device(chunk, "chunk", loudness, "loudness");
@@ -1010,39 +1029,101 @@ void loudness_stream_step(Tensor& state, const Tensor& dft, int64_t n_fft, int64
   check_same_device(chunk, "chunk", state, "state");
   check_dev(dft, "dft");
   check_same_device(chunk, "chunk", dft, "dft");
-  TORCH_CHECK(chunk.dim() == 2 && chunk.size(0) >= 1, "loudness_stream_step: expected a (B, n) chunk, got ", chunk.sizes());
+  TORCH_CHECK(chunk.dim() == 2 && chunk.size(0) >= 1, op, ": expected a (B, n) chunk, got ", chunk.sizes());
   const int64_t B = chunk.size(0), n = chunk.size(1);
-  const size_t nbytes = loudness_stream_bytes("loudness_stream_step", B, n_fft, hop);
-  TORCH_CHECK((size_t)state.numel() == nbytes, "loudness_stream_step: state does not belong to a stream of B = ", B,
-              " rows of this configuration (expected ", nbytes, " bytes, got ", state.numel(), ")");
-  check_loudness_sizes("loudness_stream_step", dft, n_fft, hop);
-  TORCH_CHECK(lag >= 0 && lag <= 255, "loudness_stream_step: lag ", lag, " outside 0 .. 255");
-  TORCH_CHECK(amin > 0.0 && top_db >= 0.0, "loudness_stream_step: amin must be positive and top_db non-negative");
-  TORCH_CHECK(final || n >= 1, "loudness_stream_step: empty chunk (only a final step may carry no samples)");
+  const size_t nbytes = loudness_stream_bytes(op, B, n_fft, hop);
+  const bool releasing = release_factor < 1.0;
+  const size_t rbytes = nws_loudness_stream_release_state_bytes((int)B, (int)n_fft, (int)hop);
+  if (with_release) {
+    TORCH_CHECK(release_factor > 0.0 && release_factor <= 1.0, op, ": release_factor ", release_factor, " outside (0, 1]");
+    TORCH_CHECK(!releasing || track, op, ": a release needs a tracked reference");
+  }
+  const size_t have = (size_t)state.numel();
+  TORCH_CHECK(releasing ? have == rbytes : have == nbytes || (with_release && have == rbytes), op,
+              ": state does not belong to a stream of B = ", B, " rows of this configuration (expected ", releasing ? rbytes : nbytes,
+              " bytes, got ", state.numel(), ")");
+  check_loudness_sizes(op, dft, n_fft, hop);
+  TORCH_CHECK(lag >= 0 && lag <= 255, op, ": lag ", lag, " outside 0 .. 255");
+  TORCH_CHECK(amin > 0.0 && top_db >= 0.0, op, ": amin must be positive and top_db non-negative");
+  TORCH_CHECK(final || n >= 1, op, ": empty chunk (only a final step may carry no samples)");
   const int64_t max_chunk = nws_loudness_stream_max_chunk((int)n_fft, (int)hop);
-  TORCH_CHECK(n <= max_chunk, "loudness_stream_step: a step takes at most ", max_chunk, " samples at this hop, got ", n);
-  TORCH_CHECK(!final || n_seen + n > n_fft / 2, "loudness_stream_step: a stream of ", n_seen + n,
+  TORCH_CHECK(n <= max_chunk, op, ": a step takes at most ", max_chunk, " samples at this hop, got ", n);
+  TORCH_CHECK(!final || n_seen + n > n_fft / 2, op, ": a stream of ", n_seen + n,
               " samples cannot end: the reflect padding needs more than n_fft / 2 = ", n_fft / 2);
   const int64_t before = n_seen >= 0 ? nws_loudness_stream_emitted(n_seen, (int)n_fft, (int)hop, (int)lag, 0) : -1;
   const int64_t after = n_seen >= 0 ? nws_loudness_stream_emitted(n_seen + n, (int)n_fft, (int)hop, (int)lag, final ? 1 : 0) : -1;
-  TORCH_CHECK(before >= 0 && after >= 0, "loudness_stream_step: n_seen ", n_seen, " + ", n, " samples outside 0 .. 2^21 hops");
+  TORCH_CHECK(before >= 0 && after >= 0, op, ": n_seen ", n_seen, " + ", n, " samples outside 0 .. 2^21 hops");
   const int64_t m = std::max<int64_t>(after - before, 1);
   const std::pair<const char*, const Tensor*> outs[2] = {{"loudness", &loudness}, {"reference_power", &reference_power}};
   for (const auto& [name, t] : outs) {
     TORCH_CHECK(t->is_cuda() && t->device() == chunk.device() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->dim() == 2 &&
                     t->size(0) == B && t->size(1) == loudness.size(1) && t->size(1) >= m && t->size(1) <= INT32_MAX,
-                "loudness_stream_step: ", name, ": expected a contiguous (", B, ", >= ", m,
+                op, ": ", name, ": expected a contiguous (", B, ", >= ", m,
                 ") Float tensor on the chunk's GPU, the same width for both outputs, got ", t->sizes(), " ", t->scalar_type(), " on ",
                 t->device());
   }
   Launch L(chunk);
   const size_t ws_bytes = nws_loudness_stream_workspace_bytes((int)B, (int)n, (int)n_fft, (int)hop, final ? 1 : 0);
   Tensor ws = at::empty({(int64_t)ws_bytes}, chunk.options().dtype(at::kByte));
-  nws_check(nws_loudness_stream_step(state.data_ptr(), (size_t)state.numel(), n > 0 ? chunk.data_ptr<float>() : nullptr, (int)B, (int)n,
-                                     n_seen, (int)n_fft, (int)hop, (int)lag, dft.data_ptr<float>(), (float)amin, (float)top_db,
-                                     normalise ? 1 : 0, final ? 1 : 0, loudness.data_ptr<float>(), reference_power.data_ptr<float>(),
-                                     (int)loudness.size(1), ws.data_ptr(), ws_bytes, L.stream),
-            "nws_loudness_stream_step");
+  const float* x = n > 0 ? chunk.data_ptr<float>() : nullptr;
+  if (with_release)
+    nws_check(nws_loudness_stream_step_release(state.data_ptr(), (size_t)state.numel(), x, (int)B, (int)n, n_seen, (int)n_fft, (int)hop,
+                                               (int)lag, (float)release_factor, track ? 1 : 0, dft.data_ptr<float>(), (float)amin,
+                                               (float)top_db, normalise ? 1 : 0, final ? 1 : 0, loudness.data_ptr<float>(),
+                                               reference_power.data_ptr<float>(), (int)loudness.size(1), ws.data_ptr(), ws_bytes,
+                                               L.stream), "nws_loudness_stream_step_release");
+  else
+    nws_check(nws_loudness_stream_step(state.data_ptr(), (size_t)state.numel(), x, (int)B, (int)n, n_seen, (int)n_fft, (int)hop, (int)lag,
+                                       dft.data_ptr<float>(), (float)amin, (float)top_db, normalise ? 1 : 0, final ? 1 : 0,
+                                       loudness.data_ptr<float>(), reference_power.data_ptr<float>(), (int)loudness.size(1),
+                                       ws.data_ptr(), ws_bytes, L.stream), "nws_loudness_stream_step");
+}
+
+void loudness_stream_step(Tensor& state, const Tensor& dft, int64_t n_fft, int64_t hop, int64_t lag, const Tensor& chunk, int64_t n_seen,
+                          bool final, double amin, double top_db, bool normalise, Tensor& loudness, Tensor& reference_power) {
+  loudness_stream_step_impl("loudness_stream_step", false, state, dft, n_fft, hop, lag, 1.0, true, chunk, n_seen, final, amin, top_db,
+                            normalise, loudness, reference_power);
+}
+
+void loudness_stream_step_release(Tensor& state, const Tensor& dft, int64_t n_fft, int64_t hop, int64_t lag, double release_factor,
+                                  bool track, const Tensor& chunk, int64_t n_seen, bool final, double amin, double top_db, bool normalise,
+                                  Tensor& loudness, Tensor& reference_power) {
+  loudness_stream_step_impl("loudness_stream_step_release", true, state, dft, n_fft, hop, lag, release_factor, track, chunk, n_seen,
+                            final, amin, top_db, normalise, loudness, reference_power);
+}
+
+// the loudness stream's feature of a whole clip (csrc/loudness_causal.hip): audio (B, N) -> loudness, reference_power,
+// frame_peak_power, (B, 1 + N / hop) each.  floor_power: (B) powers, the floors with track, the fixed references without
+std::tuple<Tensor, Tensor, Tensor> loudness_causal(const Tensor& audio, const Tensor& dft, int64_t n_fft, int64_t hop, int64_t lag,
+                                                   double release_factor, const Tensor& floor_power, bool track, double amin,
+                                                   double top_db, bool normalise) {
+  check_dev(audio, "audio");
+  check_dev(dft, "dft");
+  check_same_device(audio, "audio", dft, "dft");
+  check_dev(floor_power, "floor_power");
+  check_same_device(audio, "audio", floor_power, "floor_power");
+  TORCH_CHECK(audio.dim() == 2 && audio.size(0) >= 1, "loudness_causal: expected (B, N), got ", audio.sizes());
+  const int64_t B = audio.size(0), N = audio.size(1);
+  check_loudness_sizes("loudness_causal", dft, n_fft, hop);
+  TORCH_CHECK(N > n_fft / 2, "loudness_causal: N = ", N, ": the reflect padding needs more than n_fft / 2 = ", n_fft / 2, " samples");
+  TORCH_CHECK(lag >= 0 && lag <= 255, "loudness_causal: lag ", lag, " outside 0 .. 255");
+  TORCH_CHECK(amin > 0.0 && top_db >= 0.0, "loudness_causal: amin must be positive and top_db non-negative");
+  TORCH_CHECK(release_factor > 0.0 && release_factor <= 1.0, "loudness_causal: release_factor ", release_factor, " outside (0, 1]");
+  TORCH_CHECK(release_factor == 1.0 || track, "loudness_causal: a release needs a tracked reference");
+  TORCH_CHECK(floor_power.dim() == 1 && floor_power.size(0) == B, "loudness_causal: floor_power: expected (", B, "), got ",
+              floor_power.sizes());
+  const size_t nbytes = B <= 65535 && N <= INT32_MAX ? nws_loudness_causal_workspace_bytes((int)B, (int)N, (int)n_fft, (int)hop) : 0;
+  TORCH_CHECK(nbytes > 0, "loudness_causal: unsupported clip (B ", B, ", N ", N, ", n_fft ", n_fft, ", hop ", hop,
+              "): 1 <= B <= 65535, sizes the loudness stream serves (at most 256 hops in half a frame) and at most 2^21 hops");
+  Launch L(audio);
+  Tensor ws = at::empty({(int64_t)nbytes}, audio.options().dtype(at::kByte));
+  const int64_t T = nws_loudness_frames((int)N, (int)hop);
+  Tensor loud = at::empty({B, T}, audio.options()), ref = at::empty({B, T}, audio.options()), peak = at::empty({B, T}, audio.options());
+  nws_check(nws_loudness_causal(audio.data_ptr<float>(), (int)B, (int)N, (int)n_fft, (int)hop, dft.data_ptr<float>(), (int)lag,
+                                (float)release_factor, floor_power.data_ptr<float>(), track ? 1 : 0, (float)amin, (float)top_db,
+                                normalise ? 1 : 0, loud.data_ptr<float>(), ref.data_ptr<float>(), peak.data_ptr<float>(), ws.data_ptr(),
+                                nbytes, L.stream), "nws_loudness_causal");
+  return {loud, ref, peak};
 }
 
 // ---- pYIN F0 extractor (csrc/pyin.hip; data/utils/f0_extraction.py:61-92) ------------------------------------------------
@@ -1934,6 +2015,13 @@ TORCH_LIBRARY(newt_hip, m) {
         &loudness_stream_reset);
   m.def("loudness_stream_step(Tensor(a!) state, Tensor dft, int n_fft, int hop, int lag, Tensor chunk, int n_seen, bool final, "
         "float amin, float top_db, bool normalise, Tensor(b!) loudness, Tensor(c!) reference_power) -> ()", &loudness_stream_step);
+  m.def("loudness_stream_reset_release(Tensor(a!) state, int B, int n_fft, int hop, Tensor floor_power) -> ()",
+        &loudness_stream_reset_release);
+  m.def("loudness_stream_step_release(Tensor(a!) state, Tensor dft, int n_fft, int hop, int lag, float release_factor, bool track, "
+        "Tensor chunk, int n_seen, bool final, float amin, float top_db, bool normalise, Tensor(b!) loudness, "
+        "Tensor(c!) reference_power) -> ()", &loudness_stream_step_release);
+  m.def("loudness_causal(Tensor audio, Tensor dft, int n_fft, int hop, int lag, float release_factor, Tensor floor_power, bool track, "
+        "float amin, float top_db, bool normalise) -> (Tensor, Tensor, Tensor)", &loudness_causal);
   m.def("pyin_table(float sample_rate, float fmin, float fmax, int frame_length, int hop) -> Tensor", &pyin_table);
   m.def("pyin_cmnd(Tensor audio, float sample_rate, float fmin, float fmax, int frame_length, int hop) -> Tensor", &pyin_cmnd);
   m.def("pyin_observe(Tensor yin, Tensor table, float sample_rate, float fmin, float fmax, int frame_length, int hop) -> "

@@ -821,6 +821,10 @@ class _FrameStream:
     def frames_out(self) -> int:
         return self._emitted
 
+    def _rows_bytes(self) -> int:
+        """bytes of the B rows of the state blob (all of it, unless a subclass keeps more behind them)"""
+        return self._state.numel()
+
     def _restart(self):
         self._n_seen = 0
         self._emitted = 0
@@ -869,8 +873,8 @@ class _FrameStream:
 
     def check(self) -> None:
         """Read the device counters back once (synchronises) and compare them with the host's mirror; for tests and debugging."""
-        row = self._state.numel() // self.B
-        cnt = self._state.view(self.B, row)[:, :32].cpu().contiguous().view(torch.int64)
+        row = self._rows_bytes() // self.B
+        cnt = self._state[:self.B * row].view(self.B, row)[:, :32].cpu().contiguous().view(torch.int64)
         frames = -1 if self._n_seen <= self.frame_length // 2 and self.finished else self._frames_after(self._n_seen, self.finished)
         want = torch.tensor([self._n_seen, frames, self._emitted, int(self.finished)], dtype=torch.int64).expand(self.B, 4)
         if not torch.equal(cnt, want):
@@ -947,7 +951,10 @@ class StreamLoudness(_FrameStream):
     never on the chunking:
       * reference="running": the largest power heard up to frame e + lag (at the flush: up to the last frame).  Quiet starts
         are rendered too loud until the signal's peak has been heard; from then on the frames are the offline ones, bit for bit.
-        The maximum does not decay: one click pins the reference until `reset()`.
+        Without a release the maximum does not decay: one click pins the reference until `reset()`.
+      * release_db_per_s (with "running"): the tracked level falls by this many dB per second, never below
+        floor_power, so the reference recovers after a click; frame e is then measured against the largest level between
+        frames e and e + lag.  `sample_rate` turns the rate into the factor per hop.  0 (the default): no release, the stream above.
       * reference=a float or a (B,) tensor of powers: fixed, a calibration - `loudness_extraction.peak_power` of a sound check,
         for example.  With the clip's own peak power the stream is `loudness_frames` of the clip, bit for bit.  A signal louder
         than its reference gives values above 1 (above 0 dB without `normalise`); they are not clipped.
@@ -960,8 +967,9 @@ class StreamLoudness(_FrameStream):
     _half = "n_fft"
 
     def __init__(self, batch_size: int, n_fft: int = 1024, hop_length: int = 128, lag: int = 8, reference="running",
-                 floor_power=None, epsilon: float = 1e-5, normalise: bool = True, device=None):
-        from .data.utils.loudness_extraction import _dft_operand
+                 floor_power=None, epsilon: float = 1e-5, normalise: bool = True, device=None, release_db_per_s: float = 0.0,
+                 sample_rate: float = 16000):
+        from .data.utils.loudness_extraction import _dft_operand, release_factor
 
         self.B = int(batch_size)
         self.n_fft = self.frame_length = int(n_fft)
@@ -981,6 +989,12 @@ class StreamLoudness(_FrameStream):
                                "in half a frame")
         self.max_chunk = int(L.nws_loudness_stream_max_chunk(self.n_fft, self.hop_length))
         self.track = isinstance(reference, str)
+        self.release_db_per_s = float(release_db_per_s)
+        self.release_factor = release_factor(release_db_per_s, self.hop_length, sample_rate)
+        if self.release_factor < 1.0:
+            if not self.track:
+                raise RuntimeError("StreamLoudness: release_db_per_s belongs to reference='running'; a fixed reference does not move")
+            nbytes = L.nws_loudness_stream_release_state_bytes(self.B, self.n_fft, self.hop_length)      # the rows, then the floors
         if self.track:
             if reference != "running":
                 raise RuntimeError(f"StreamLoudness: reference {reference!r}: expected 'running', a power or a (B,) tensor of powers")
@@ -1006,6 +1020,9 @@ class StreamLoudness(_FrameStream):
             raise RuntimeError(f"StreamLoudness: {name}: powers must be finite and >= 0")
         return p
 
+    def _rows_bytes(self) -> int:
+        return int(_lib.lib().nws_loudness_stream_state_bytes(self.B, self.n_fft, self.hop_length))      # a release keeps floors behind
+
     def _emitted_after(self, n_seen: int, final: bool) -> int:
         return int(_lib.lib().nws_loudness_stream_emitted(n_seen, self.n_fft, self.hop_length, self.lag, int(final)))
 
@@ -1014,34 +1031,42 @@ class StreamLoudness(_FrameStream):
 
     def reset(self):
         """Back to the initial state: nothing consumed, nothing emitted, the reference level at its initial power."""
-        binding().loudness_stream_reset(self._state, self.B, self.n_fft, self.hop_length, self._initial, self.track)
+        if self.release_factor < 1.0:
+            binding().loudness_stream_reset_release(self._state, self.B, self.n_fft, self.hop_length, self._initial)
+        else:
+            binding().loudness_stream_reset(self._state, self.B, self.n_fft, self.hop_length, self._initial, self.track)
         self._restart()
 
     def _step(self, x, final, m):
         """-> (loudness fp32, reference_power fp32)"""
         loudness = torch.empty((self.B, max(m, 1)), dtype=torch.float32, device=self.dev)
         reference_power = torch.empty((self.B, max(m, 1)), dtype=torch.float32, device=self.dev)
-        binding().loudness_stream_step(self._state, self._dft, self.n_fft, self.hop_length, self.lag, x, self._n_seen, final,
-                                       self.epsilon, 80.0, self.normalise, loudness, reference_power)
+        if self.release_factor < 1.0:
+            binding().loudness_stream_step_release(self._state, self._dft, self.n_fft, self.hop_length, self.lag, self.release_factor,
+                                                   True, x, self._n_seen, final, self.epsilon, 80.0, self.normalise, loudness,
+                                                   reference_power)
+        else:
+            binding().loudness_stream_step(self._state, self._dft, self.n_fft, self.hop_length, self.lag, x, self._n_seen, final,
+                                           self.epsilon, 80.0, self.normalise, loudness, reference_power)
         return loudness, reference_power
 
 
 class StreamControl:
     """Chunked audio -> the model's two inputs: one `StreamF0` and one `StreamLoudness` on the model's sample rate and control
     hop (frames of 1024 samples, the same lag), and `checkpoint.make_control` on what they release - in float64 on the device,
-    cast to fp32 at the end, so the values are the bits of `make_control` on the two streams' frames.  `reference` and
-    `floor_power` are `StreamLoudness`'s, `fill_unvoiced` is `StreamF0`'s; `mean` / `std` are the dataset statistics of the
+    cast to fp32 at the end, so the values are the bits of `make_control` on the two streams' frames.  `reference`,
+    `floor_power` and `release_db_per_s` (at the model's sample rate) are `StreamLoudness`'s, `fill_unvoiced` is `StreamF0`'s; `mean` / `std` are the dataset statistics of the
     checkpoint ((f0, loudness) each; None: the features as they are); `octave_shift` transposes F0 by whole octaves.
     `push(x, final=False)` -> (f0 (B, 1, m) Hz, control (B, 2, m)), ready for `model.stream(B).push` whenever m > 0."""
 
     def __init__(self, model, batch_size: int, lag: int = 8, reference="running", floor_power=None, mean=None, std=None,
-                 octave_shift: int = 0, fill_unvoiced=None):
+                 octave_shift: int = 0, fill_unvoiced=None, release_db_per_s: float = 0.0):
         dev = next(model.parameters()).device
         sr, hop = float(model.sample_rate), int(model.control_hop)
         self.f0 = StreamF0(batch_size, sample_rate=sr, frame_length=1024, hop_length=hop, lag=lag, fill_unvoiced=fill_unvoiced,
                            device=dev)
         self.loudness = StreamLoudness(batch_size, n_fft=1024, hop_length=hop, lag=lag, reference=reference,
-                                       floor_power=floor_power, device=dev)
+                                       floor_power=floor_power, device=dev, release_db_per_s=release_db_per_s, sample_rate=sr)
         self.mean = (0.0, 0.0) if mean is None else (float(mean[0]), float(mean[1]))
         self.std = (1.0, 1.0) if std is None else (float(std[0]), float(std[1]))
         self.scale = 2.0 ** int(octave_shift)

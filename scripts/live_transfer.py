@@ -7,11 +7,13 @@ stream that keeps its state on the GPU.
     -> [StreamResampler to --output-rate] -> wav
 
     python scripts/live_transfer.py in.wav out.wav [--model-checkpoint ckpt] [--normalisation-dir dir] [--use-fastnewt]
-                                    [--chunk N] [--lag L] [--loudness-reference running|FLOAT_DBFS] [--output-rate R] [--seed S]
+                                    [--chunk N] [--lag L] [--loudness-reference running|FLOAT_DBFS] [--loudness-release DB_PER_S]
+                                    [--output-rate R] [--seed S]
 
 --loudness-reference running measures the loudness against the loudest power heard so far (a quiet start is
 rendered too loud until the peak has been heard); a number fixes the reference at the level of a sine of that many dBFS
-(0 = full scale), a calibration.  The script prints the chain's latency: the samples by which the output runs behind the input.
+(0 = full scale), a calibration.  --loudness-release DB_PER_S lets the running reference fall by that many dB per second
+(DESIGN.md 3.26), so that the level recovers after a click; 0, the default, keeps it where the loudest sound put it.  The script prints the chain's latency: the samples by which the output runs behind the input.
 The output has the input's length (at the model's rate, converted to --output-rate where given).  --seed fixes the model's two
 random draws, so that two runs write the same file.
 """
@@ -57,10 +59,12 @@ def sine_power(dbfs, n_fft=1024):
 @click.option("--chunk", default=256, type=click.IntRange(1), show_default=True, help="samples of the input file per push")
 @click.option("--lag", default=8, type=click.IntRange(0, 255), show_default=True, help="frames the analysis looks ahead")
 @click.option("--loudness-reference", default="running", show_default=True, help="running, or the reference level in dBFS of a sine")
+@click.option("--loudness-release", default=0.0, type=click.FloatRange(0.0), show_default=True,
+              help="dB per second by which the running reference falls (0: it never falls)")
 @click.option("--output-rate", default=None, type=int, help="convert the model's output to this sample rate")
 @click.option("--seed", default=None, type=int, help="seed torch's generators, so that two runs draw the same start phases and noise")
 def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, use_fastnewt, octave_shift, chunk, lag,
-         loudness_reference, output_rate, seed):
+         loudness_reference, loudness_release, output_rate, seed):
     nws = importlib.import_module("neural-waveshaping-synthesis_amd")
     ck = importlib.import_module("neural-waveshaping-synthesis_amd.checkpoint")
     pre = importlib.import_module("neural-waveshaping-synthesis_amd.data.utils.preprocess_audio")
@@ -70,6 +74,8 @@ def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, 
             loudness_reference = sine_power(float(loudness_reference))
         except ValueError:
             raise click.BadParameter(f"--loudness-reference {loudness_reference}: expected 'running' or a level in dBFS")
+        if loudness_release > 0.0:
+            raise click.BadParameter("--loudness-release belongs to --loudness-reference running: a fixed reference does not move")
     if model_gin:
         nws.gin.parse_config_file(model_gin)
     else:
@@ -85,7 +91,8 @@ def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, 
         torch.manual_seed(seed)
 
     to_model = streaming.StreamResampler(sr_in, sr, 1) if sr_in != sr else None
-    control = streaming.StreamControl(model, 1, lag=lag, reference=loudness_reference, mean=mean, std=std, octave_shift=octave_shift)
+    control = streaming.StreamControl(model, 1, lag=lag, reference=loudness_reference, mean=mean, std=std, octave_shift=octave_shift,
+                                      release_db_per_s=loudness_release)
     synth = model.stream(1)
     to_output = streaming.StreamResampler(sr, output_rate, 1) if output_rate is not None and output_rate != sr else None
     # the output runs behind the input by: the converter's look-ahead, half an analysis frame + the lag, the 64 samples the

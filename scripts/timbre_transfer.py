@@ -5,7 +5,7 @@ data/utils/preprocess_audio.py followed by its inference notebook, on the GPU en
 
     python scripts/timbre_transfer.py in.wav out.wav --model-checkpoint ckpt [--normalisation-dir dir] [--use-fastnewt]
                                       [--resample] [--output-rate R] [--stream-f0 LAG] [--stream-loudness LAG
-                                      [--loudness-reference running|clip]] [--chunk N] [--seed S]
+                                      [--loudness-reference running|clip] [--loudness-release DB_PER_S]] [--chunk N] [--seed S]
 
 Without --resample the wav must already be at the model's sample rate and mono.  With it the file may be at any rate and
 stereo: the left channel is kept and converted to the model's rate on the GPU (csrc/resample.hip), and the output has the
@@ -17,7 +17,8 @@ fix the model's two random draws - the oscillators' start phases and the noise -
 --stream-loudness LAG takes the loudness from the loudness stream (streaming.StreamLoudness) the same way.
 --loudness-reference running measures every frame against the loudest power heard up to LAG frames after it, as a live input
 must (a lag of the whole clip's frame count gives the plain run's file); clip fixes the reference at the clip's own peak power
-(loudness_extraction.peak_power), which gives the plain run's file at any lag.
+(loudness_extraction.peak_power), which gives the plain run's file at any lag.  --loudness-release DB_PER_S lets the running
+reference fall by that many dB per second; 0, the default, is the stream without a release.
 """
 import importlib
 import os
@@ -77,13 +78,14 @@ def stream_f0_frames(audio, sr, hop, lag, chunk):
     return f0, torch.cat([o[1] for o in outs], dim=1)[0].cpu().numpy()
 
 
-def stream_loudness_frames(audio, hop, lag, chunk, reference):
+def stream_loudness_frames(audio, hop, lag, chunk, reference, release_db_per_s=0.0, sample_rate=16000):
     """loudness of every frame through streaming.StreamLoudness, `chunk` samples a push; numpy like the offline call"""
     streaming = importlib.import_module("neural-waveshaping-synthesis_amd.streaming")
     ldx = importlib.import_module("neural-waveshaping-synthesis_amd.data.utils.loudness_extraction")
     x = torch.from_numpy(audio).cuda().unsqueeze(0)
     s = streaming.StreamLoudness(1, n_fft=1024, hop_length=hop, lag=lag,
-                                 reference="running" if reference == "running" else ldx.peak_power(x, 1024, hop))
+                                 reference="running" if reference == "running" else ldx.peak_power(x, 1024, hop),
+                                 release_db_per_s=release_db_per_s, sample_rate=sample_rate)
     outs = [s.push(x[:, at:at + chunk], final=at + chunk >= audio.size) for at in range(0, audio.size, chunk)]
     return torch.cat([o[0] for o in outs], dim=1)[0].cpu().numpy()
 
@@ -102,10 +104,14 @@ def stream_loudness_frames(audio, hop, lag, chunk, reference):
 @click.option("--stream-loudness", default=None, type=click.IntRange(0, 255), help="loudness from the loudness stream with this lag in frames")
 @click.option("--loudness-reference", default="running", type=click.Choice(["running", "clip"]), show_default=True,
               help="reference level of --stream-loudness: the running maximum, or fixed at the clip's peak power")
+@click.option("--loudness-release", default=0.0, type=click.FloatRange(0.0), show_default=True,
+              help="dB per second by which the running reference of --stream-loudness falls (0: it never falls)")
 @click.option("--chunk", default=128, type=click.IntRange(1), show_default=True, help="samples per push of the streams")
 @click.option("--seed", default=None, type=int, help="seed torch's generators, so that two runs draw the same start phases and noise")
 def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, use_fastnewt, octave_shift, resample, output_rate,
-         stream_f0, stream_loudness, loudness_reference, chunk, seed):
+         stream_f0, stream_loudness, loudness_reference, loudness_release, chunk, seed):
+    if loudness_release > 0.0 and (stream_loudness is None or loudness_reference != "running"):
+        raise click.BadParameter("--loudness-release belongs to --stream-loudness with --loudness-reference running")
     nws = importlib.import_module("neural-waveshaping-synthesis_amd")
     ck = importlib.import_module("neural-waveshaping-synthesis_amd.checkpoint")
     f0x = importlib.import_module("neural-waveshaping-synthesis_amd.data.utils.f0_extraction")
@@ -130,7 +136,7 @@ def main(input_wav, output_wav, model_gin, model_checkpoint, normalisation_dir, 
     if stream_loudness is None:
         loudness = ldx.extract_perceptual_loudness(audio, sr, n_fft=1024, hop_length=hop, interpolate_fn=None)
     else:
-        loudness = stream_loudness_frames(audio, hop, stream_loudness, chunk, loudness_reference)
+        loudness = stream_loudness_frames(audio, hop, stream_loudness, chunk, loudness_reference, loudness_release, sr)
     f0 = f0 * 2.0 ** octave_shift
     f0_t, control = ck.make_control(f0, loudness, mean, std)
     if seed is not None:
