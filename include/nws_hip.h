@@ -1053,6 +1053,58 @@ int nws_g_stream_reverb_tail(const NwsGenericModel* m, const NwsReverbPlan* plan
                              const void* reverb_spectrum, void* state, size_t state_bytes, int B, int max_frames,
                              float* tail_out /* (B, ir_len + 1) */, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * Note player (ABI v6; csrc/note_control.hip; no reference counterpart: the reference renders recordings only).
+ * The two launches around a hop of nws_stream_step_slots that turn notes into a signal.
+ *
+ * nws_note_control: ONE launch on `stream` in front of the hop.  Reads the hop's event words `events` (B) int32 with the NWS_SLOT_*
+ * bits - the tensor the slot stream itself reads -, the per-slot note table `notes` (B), which the host writes only when a note
+ * starts or ends, and the per-slot int32 frame counters in `state`; writes f0 (B, K) in Hz and control (B, 2, K), normalised with
+ * mean / std.  A slot with NWS_SLOT_ACTIVE gets frames j = j0 .. j0 + K - 1 of its voice, j0 = 0 with NWS_SLOT_START and the
+ * slot's counter otherwise, and leaves j0 + K in the counter (saturating at 2^30); every other slot gets f0 = 0, control = 0 and
+ * keeps its counter.  With p = peak_lo + velocity (peak_hi - peak_lo), q = silence, A / D / R = attack / decay / release:
+ *     h(j)  = p - (p - q) (A - 1 - j) / A  for j < A;   p - drop (j - A + 1) / D  for A <= j < A + D;   p - drop  beyond;  h(-1) = q
+ *     l(j)  = h(j)  for j < j_off;   q + (h(j_off - 1) - q) (R - min(j - j_off + 1, R)) / R  from j_off on
+ *     c(j)  = vib_depth clamp((j - vib_delay) / vib_ramp, 0, 1) sin(2 pi frac(vib_rate 128 j / sample_rate))      [cents]
+ *     f0(j) = 440 2^((pitch - 69) / 12 + c(j) / 1200),   control(j) = ((f0(j) - mean[0]) / std[0], (l(j) - mean[1]) / std[1])
+ * Closed forms in j: a voice's bits do not depend on how its frames are cut into hops.  The vibrato phase is formed and reduced in
+ * float64; the rest is fp32.  Nothing is read back, nothing is allocated, and no argument of a steady hop changes: the launch can
+ * be captured, or sit in front of a captured hop on that hop's own input buffers.
+ * nws_note_control_state_bytes: size of the counter blob (0 for B outside 1 .. 65 535); nws_note_control_reset zeroes it.
+ *
+ * nws_voice_mix: out[c, n] = sum_b gain[b, c] o[b, n] for o (B, N), gain (B, C), out (C, N), C = 1 or 2.  b ascending in one fp32
+ * chain of fused multiply-adds per output element, each element written by one thread, no atomics: two calls give equal bits.
+ * float4 loads and stores when N is a multiple of 4 and o and out are 16-byte aligned, a scalar kernel otherwise.
+ *
+ * Every refusal is decided before the first launch and leaves state and outputs untouched.  NWS_ERR_BAD_ARG: a NULL pointer,
+ * B / K / N < 1, K > 16, C outside {1, 2}, release < 1, vib_ramp < 1, a negative attack / decay / vib_delay / drop / vib_rate, a
+ * frame count above 2^24, sample_rate <= 0, std <= 0, a state blob below nws_note_control_state_bytes.  NWS_ERR_UNSUPPORTED:
+ * B > 65 535.
+ */
+typedef struct NwsNotePlayer {
+  double vib_rate;       /* Hz */
+  double sample_rate;    /* of the model: a frame is 128 samples */
+  int attack, decay, release;   /* A >= 0, D >= 0, R >= 1 frames */
+  int vib_delay, vib_ramp;      /* frames; ramp >= 1 */
+  float drop;            /* sustain level below the peak; loudness units: (dB + 80) / 80 */
+  float silence;         /* q */
+  float peak_lo, peak_hi; /* peak loudness at velocity -> 0 and at velocity 1 */
+  float vib_depth;       /* cents */
+  float mean[2], std[2]; /* the checkpoint's statistics of F0 and loudness */
+} NwsNotePlayer;
+typedef struct NwsNote {
+  float pitch;     /* MIDI note number */
+  float velocity;  /* (0, 1] */
+  int j_off;       /* first release frame; 2^31 - 1 while the note is held */
+  int reserved;
+} NwsNote;
+size_t nws_note_control_state_bytes(int B);
+int nws_note_control_reset(void* state, size_t state_bytes, int B, void* stream);
+int nws_note_control(const NwsNotePlayer* player, const int* events /* (B) */, const NwsNote* notes /* (B) */, void* state,
+                     size_t state_bytes, int B, int K, float* f0 /* (B, K) */, float* control /* (B, 2, K) */, void* stream);
+int nws_voice_mix(const float* o /* (B, N) */, const float* gain /* (B, C) */, int B, int N, int C, float* out /* (C, N) */,
+                  void* stream);
+
 /* Diagnostic entry points (kernel ablations for timing, the co-execution hazard probes) are declared in nws_hip_debug.h: they are
  * exported by the same library but are not part of the product ABI. */
 

@@ -927,6 +927,86 @@ class CtypesOps:
                                                ptr(bank), 1 if final else 0, ptr(out), out.shape[1], _stream(chunk.device)),
                   "nws_resample_stream_step")
 
+    # ---- note player (csrc/note_control.hip): the launches in front of and behind a slot stream's hop --------------------------
+    @staticmethod
+    def _note_player(params):
+        """the op's `params` tensor (16 float64 values on the CPU, _lib.NOTE_PARAMS) as the ctypes struct"""
+        if not (isinstance(params, torch.Tensor) and params.device.type == "cpu" and params.dtype == torch.float64
+                and params.is_contiguous() and params.numel() == 16):
+            raise RuntimeError("params: expected a CPU float64 tensor of 16 values [attack, decay, release, vib_delay, vib_ramp, drop, "
+                               "silence, peak_lo, peak_hi, vib_rate, vib_depth, sample_rate, mean0, std0, mean1, std1]")
+        p = params.tolist()
+        for v in p[:5]:
+            if not (-1e9 <= v <= 1e9 and v == int(v)):
+                raise RuntimeError(f"params: attack, decay, release, vib_delay and vib_ramp are whole frames, got {v}")
+        P = _lib.NwsNotePlayer()
+        P.attack, P.decay, P.release, P.vib_delay, P.vib_ramp = (int(v) for v in p[:5])
+        P.drop, P.silence, P.peak_lo, P.peak_hi = p[5:9]
+        P.vib_rate, P.vib_depth, P.sample_rate = p[9:12]
+        P.mean[0], P.std[0], P.mean[1], P.std[1] = p[12:16]
+        return P
+
+    @staticmethod
+    def _note_state_bytes(op, B):
+        nbytes = _lib.lib().nws_note_control_state_bytes(B) if 1 <= B <= 65535 else 0
+        if nbytes == 0:
+            raise RuntimeError(f"{op}: unsupported slot count {B}: 1 <= B <= 65535")
+        return nbytes
+
+    def note_control_reset(self, state, B):
+        _check_state(state)
+        nbytes = self._note_state_bytes("note_control_reset", B)
+        if state.numel() < nbytes:
+            raise RuntimeError(f"note_control_reset: state blob too small (expected {nbytes} bytes for B = {B}, got {state.numel()})")
+        with torch.cuda.device(state.device):
+            check(_lib.lib().nws_note_control_reset(ptr(state), state.numel(), B, _stream(state.device)), "nws_note_control_reset")
+
+    def note_control(self, params, events, notes, state, f0, control):
+        P = self._note_player(params)
+        _check_dev("f0", f0)
+        _check_dev("control", control, f0, "f0")
+        _check_state(state, f0)
+        for name, t in (("events", events), ("notes", notes)):
+            if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.device != f0.device:
+                raise RuntimeError(f"{name}: expected a contiguous Int tensor on {f0.device}, got {t.dtype} on {t.device}")
+        if f0.dim() != 2 or f0.shape[0] < 1:
+            raise RuntimeError(f"note_control: expected f0 (B, K), got {tuple(f0.shape)}")
+        B, K = f0.shape
+        if not 1 <= K <= 16:
+            raise RuntimeError(f"note_control: a hop has 1 .. 16 frames, got {K}")
+        if tuple(control.shape) != (B, 2, K):
+            raise RuntimeError(f"note_control: expected control ({B}, 2, {K}), got {tuple(control.shape)}")
+        if events.numel() != B:
+            raise RuntimeError(f"note_control: expected {B} event words, got {events.numel()}")
+        if tuple(notes.shape) != (B, 4):
+            raise RuntimeError(f"note_control: expected the note table as int32 ({B}, 4) [pitch bits, velocity bits, j_off, 0], got "
+                               f"{tuple(notes.shape)}")
+        if P.release < 1 or P.vib_ramp < 1:
+            raise RuntimeError("note_control: release and vib_ramp are at least one frame")
+        nbytes = self._note_state_bytes("note_control", B)
+        if state.numel() < nbytes:
+            raise RuntimeError(f"note_control: state blob too small (expected {nbytes} bytes for B = {B}, got {state.numel()})")
+        with torch.cuda.device(f0.device):
+            check(_lib.lib().nws_note_control(C.byref(P), ptr(events), ptr(notes), ptr(state), state.numel(), B, K, ptr(f0),
+                                              ptr(control), _stream(f0.device)), "nws_note_control")
+
+    def voice_mix(self, o, gain, out):
+        _check_dev("o", o)
+        _check_dev("gain", gain, o, "o")
+        _check_dev("out", out, o, "o")
+        if o.dim() != 2 or o.shape[0] < 1 or not 1 <= o.shape[1] < 2 ** 31:
+            raise RuntimeError(f"voice_mix: expected o (B, N), got {tuple(o.shape)}")
+        B, N = o.shape
+        if B > 65535:
+            raise RuntimeError(f"voice_mix: unsupported slot count {B}: 1 <= B <= 65535")
+        if gain.dim() != 2 or gain.shape[0] != B or gain.shape[1] not in (1, 2):
+            raise RuntimeError(f"voice_mix: expected gain ({B}, 1 or 2), got {tuple(gain.shape)}")
+        Cn = gain.shape[1]
+        if tuple(out.shape) != (Cn, N):
+            raise RuntimeError(f"voice_mix: expected out ({Cn}, {N}), got {tuple(out.shape)}")
+        with torch.cuda.device(o.device):
+            check(_lib.lib().nws_voice_mix(ptr(o), ptr(gain), B, N, Cn, ptr(out), _stream(o.device)), "nws_voice_mix")
+
     # ---- MFCC feature (csrc/mfcc.hip) --------------------------------------------------------------------------------------
     def mfcc_table(self, sample_rate, n_fft, n_mfcc, n_mels):
         words = _mfcc_dims(sample_rate, n_fft, n_mfcc, n_mels)[7]

@@ -116,6 +116,20 @@ class NwsGradTensor(C.Structure):
     _fields_ = [("src", _fp), ("n", C.c_size_t)]
 
 
+class NwsNotePlayer(C.Structure):
+    """the constants of a note player (nws_note_control): envelope, vibrato and the checkpoint's statistics"""
+    _fields_ = [("vib_rate", C.c_double), ("sample_rate", C.c_double),
+                ("attack", C.c_int32), ("decay", C.c_int32), ("release", C.c_int32), ("vib_delay", C.c_int32), ("vib_ramp", C.c_int32),
+                ("drop", C.c_float), ("silence", C.c_float), ("peak_lo", C.c_float), ("peak_hi", C.c_float), ("vib_depth", C.c_float),
+                ("mean", C.c_float * 2), ("std", C.c_float * 2)]
+
+
+# the `params` tensor of the note_control op: 16 float64 values on the CPU in this order
+NOTE_PARAMS = ("attack", "decay", "release", "vib_delay", "vib_ramp", "drop", "silence", "peak_lo", "peak_hi", "vib_rate", "vib_depth",
+               "sample_rate", "mean0", "std0", "mean1", "std1")
+NOTE_HELD = 2 ** 31 - 1   # NwsNote.j_off while the note is held
+
+
 _PYIN_CFG =(C.c_double, C.c_double, C.c_double, C.c_int, C.c_int)     # sample_rate, fmin, fmax, frame_length, hop
 
 _MFCC_CFG = (C.c_double, C.c_int, C.c_int, C.c_int)                       # sample_rate, n_fft, n_mfcc, n_mels
@@ -322,6 +336,10 @@ _PROTOTYPES = {
                                     _fp, _fp, C.c_int, _fp, _fp, _fp]),
     "nws_g_stream_reverb_tail": (C.c_int, [C.POINTER(NwsGenericModel), C.POINTER(NwsReverbPlan), _fp, _fp, _fp, C.c_size_t, C.c_int,
                                            C.c_int, _fp, _fp, C.c_size_t, _fp]),
+    "nws_note_control_state_bytes": (C.c_size_t, [C.c_int]),
+    "nws_note_control_reset": (C.c_int, [_fp, C.c_size_t, C.c_int, _fp]),
+    "nws_note_control": (C.c_int, [C.POINTER(NwsNotePlayer), _fp, _fp, _fp, C.c_size_t, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "nws_voice_mix": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "nws_profile_begin": (C.c_int, [C.c_int, C.c_uint]),
     "nws_profile_collect": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "nws_profile_end": (C.c_int, []),

@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libnws_hip.so")
 OPS_LIB = os.path.join(HERE, "libnws_torch_ops.so")     # torch.ops.newt_hip.* over the C-ABI (csrc/torch_ops.cpp)
 PROBE_LIB = os.path.join(HERE, "libnws_probe.so")       # include/nws_probe.h: hazard probe, tools / tests only
 SOURCES = ["exciter_newt.hip", "control_gru.hip", "control_gru_grad.hip", "frame_mlps.hip", "fir_noise.hip", "fir_noise_grad.hip", "reverb_fft.hip", "forward.hip",
-           "loudness.hip", "loudness_stream.hip", "loudness_causal.hip", "mfcc.hip", "stft_loss.hip", "stft_grad.hip", "pyin.hip", "pyin_stream.hip", "resample.hip", "resample_stream.hip", "stages.hip", "td_mlp_grad.hip", "newt_grad.hip", "g_newt_grad.hip", "adam_step.hip", "generic.hip", "stream.hip", "queue_probe.hip", "exchange.hip", "grad_reduce.hip"]
+           "loudness.hip", "loudness_stream.hip", "loudness_causal.hip", "mfcc.hip", "stft_loss.hip", "stft_grad.hip", "pyin.hip", "pyin_stream.hip", "resample.hip", "resample_stream.hip", "stages.hip", "td_mlp_grad.hip", "newt_grad.hip", "g_newt_grad.hip", "adam_step.hip", "generic.hip", "stream.hip", "queue_probe.hip", "exchange.hip", "grad_reduce.hip", "note_control.hip"]
 PROBE_SOURCES = ["coexec_probe.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=default",
          "-Wall", "-Wno-unused-function", "-Wno-pass-failed", "-Rpass-analysis=kernel-resource-usage"]

@@ -1928,6 +1928,85 @@ void g_stream_step(const Tensor& gdesc, const OptTensor& plan_t, const OptTensor
             "nws_g_stream_step");
 }
 
+// ---- note player (csrc/note_control.hip): the launches in front of and behind a slot stream's hop --------------
+// `params`: 16 float64 values on the CPU in the order of _lib.NOTE_PARAMS
+NwsNotePlayer note_player_of(const Tensor& params) {
+  TORCH_CHECK(params.device().is_cpu() && params.scalar_type() == at::kDouble && params.is_contiguous() && params.numel() == 16,
+              "params: expected a CPU float64 tensor of 16 values [attack, decay, release, vib_delay, vib_ramp, drop, silence, "
+              "peak_lo, peak_hi, vib_rate, vib_depth, sample_rate, mean0, std0, mean1, std1]");
+  const double* p = params.data_ptr<double>();
+  for (int i = 0; i < 5; ++i)
+    TORCH_CHECK(p[i] >= -1e9 && p[i] <= 1e9 && p[i] == (double)(int)p[i], "params: attack, decay, release, vib_delay and vib_ramp are whole frames, got ", p[i]);
+  NwsNotePlayer P{};
+  P.attack = (int)p[0], P.decay = (int)p[1], P.release = (int)p[2], P.vib_delay = (int)p[3], P.vib_ramp = (int)p[4];
+  P.drop = (float)p[5], P.silence = (float)p[6], P.peak_lo = (float)p[7], P.peak_hi = (float)p[8];
+  P.vib_rate = p[9], P.vib_depth = (float)p[10], P.sample_rate = p[11];
+  P.mean[0] = (float)p[12], P.std[0] = (float)p[13], P.mean[1] = (float)p[14], P.std[1] = (float)p[15];
+  return P;
+}
+
+size_t note_state_bytes(const char* op, int64_t B) {
+  const size_t nbytes = B >= 1 && B <= 65535 ? nws_note_control_state_bytes((int)B) : 0;
+  TORCH_CHECK(nbytes > 0, op, ": unsupported slot count ", B, ": 1 <= B <= 65535");
+  return nbytes;
+}
+
+void note_control_reset(Tensor& state, int64_t B) {
+  check_dev(state, "state", at::kByte);
+  const size_t nbytes = note_state_bytes("note_control_reset", B);
+  TORCH_CHECK((size_t)state.numel() >= nbytes, "note_control_reset: state blob too small (expected ", nbytes, " bytes for B = ", B,
+              ", got ", state.numel(), ")");
+  Launch L(state);
+  nws_check(nws_note_control_reset(state.data_ptr(), (size_t)state.numel(), (int)B, L.stream), "nws_note_control_reset");
+}
+
+void note_control(const Tensor& params, const Tensor& events, const Tensor& notes, Tensor& state, Tensor& f0, Tensor& control) {
+  const NwsNotePlayer P = note_player_of(params);
+  check_dev(events, "events", at::kInt);
+  check_dev(notes, "notes", at::kInt);
+  check_dev(state, "state", at::kByte);
+  check_dev(f0, "f0");
+  check_dev(control, "control");
+  check_same_device(f0, "f0", events, "events");
+  check_same_device(f0, "f0", notes, "notes");
+  check_same_device(f0, "f0", state, "state");
+  check_same_device(f0, "f0", control, "control");
+  TORCH_CHECK(f0.dim() == 2 && f0.size(0) >= 1, "note_control: expected f0 (B, K), got ", f0.sizes());
+  const int64_t B = f0.size(0), K = f0.size(1);
+  TORCH_CHECK(K >= 1 && K <= 16, "note_control: a hop has 1 .. 16 frames, got ", K);
+  TORCH_CHECK(control.dim() == 3 && control.size(0) == B && control.size(1) == 2 && control.size(2) == K,
+              "note_control: expected control (", B, ", 2, ", K, "), got ", control.sizes());
+  TORCH_CHECK(events.numel() == B, "note_control: expected ", B, " event words, got ", events.numel());
+  TORCH_CHECK(notes.dim() == 2 && notes.size(0) == B && notes.size(1) == 4,
+              "note_control: expected the note table as int32 (", B, ", 4) [pitch bits, velocity bits, j_off, 0], got ", notes.sizes());
+  TORCH_CHECK(P.release >= 1 && P.vib_ramp >= 1, "note_control: release and vib_ramp are at least one frame");
+  const size_t nbytes = note_state_bytes("note_control", B);
+  TORCH_CHECK((size_t)state.numel() >= nbytes, "note_control: state blob too small (expected ", nbytes, " bytes for B = ", B, ", got ",
+              state.numel(), ")");
+  Launch L(f0);
+  nws_check(nws_note_control(&P, events.data_ptr<int32_t>(), reinterpret_cast<const NwsNote*>(notes.data_ptr<int32_t>()),
+                             state.data_ptr(), (size_t)state.numel(), (int)B, (int)K, f0.data_ptr<float>(),
+                             control.data_ptr<float>(), L.stream), "nws_note_control");
+}
+
+void voice_mix(const Tensor& o, const Tensor& gain, Tensor& out) {
+  check_dev(o, "o");
+  check_dev(gain, "gain");
+  check_dev(out, "out");
+  check_same_device(o, "o", gain, "gain");
+  check_same_device(o, "o", out, "out");
+  TORCH_CHECK(o.dim() == 2 && o.size(0) >= 1 && o.size(1) >= 1 && o.size(1) <= INT32_MAX, "voice_mix: expected o (B, N), got ", o.sizes());
+  const int64_t B = o.size(0), N = o.size(1);
+  TORCH_CHECK(B <= 65535, "voice_mix: unsupported slot count ", B, ": 1 <= B <= 65535");
+  TORCH_CHECK(gain.dim() == 2 && gain.size(0) == B && (gain.size(1) == 1 || gain.size(1) == 2),
+              "voice_mix: expected gain (", B, ", 1 or 2), got ", gain.sizes());
+  const int64_t C = gain.size(1);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == C && out.size(1) == N, "voice_mix: expected out (", C, ", ", N, "), got ", out.sizes());
+  Launch L(o);
+  nws_check(nws_voice_mix(o.data_ptr<float>(), gain.data_ptr<float>(), (int)B, (int)N, (int)C, out.data_ptr<float>(), L.stream),
+            "nws_voice_mix");
+}
+
 int64_t abi_version() { return nws_abi_version(); }
 
 }  // namespace
@@ -2040,6 +2119,10 @@ TORCH_LIBRARY(newt_hip, m) {
   m.def("resample_stream_reset(Tensor(a!) state, int B, int sr_in, int sr_out) -> ()", &resample_stream_reset);
   m.def("resample_stream_step(Tensor(a!) state, Tensor bank, int sr_in, int sr_out, Tensor chunk, bool final, Tensor(b!) out) -> ()",
         &resample_stream_step);
+  m.def("note_control_reset(Tensor(a!) state, int B) -> ()", &note_control_reset);
+  m.def("note_control(Tensor params, Tensor events, Tensor notes, Tensor(a!) state, Tensor(b!) f0, Tensor(c!) control) -> ()",
+        &note_control);
+  m.def("voice_mix(Tensor o, Tensor gain, Tensor(a!) out) -> ()", &voice_mix);
   m.def("mfcc_table(float sample_rate, int n_fft, int n_mfcc, int n_mels) -> Tensor", &mfcc_table);
   m.def("stft_loss_dft(int n_fft, int win_length) -> Tensor", &stft_loss_dft);
   m.def("stft_loss(Tensor x, Tensor y, Tensor[] dfts, int[] n_ffts, int[] hops, int[] win_lengths, float w_sc, float w_log_mag, "

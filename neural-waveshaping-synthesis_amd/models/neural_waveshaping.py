@@ -495,4 +495,14 @@ def _stream(self, batch_size: int = 1, *, phase_u=None, noise=None, slots: bool 
     return cls(self, batch_size, phase_u=phase_u, noise=noise, **kw)
 
 
+def _player(self, voices: int, **kw):
+    """Polyphonic note player bound to this model (see streaming.NotePlayer; kw: hop_frames, channels, the envelope and vibrato
+    parameters, normalisation=(mean, std), phase_u, noise, graph): note_on / note_off in, one mixed signal out, hop by hop.  The
+    packaged architecture only."""
+    from ..streaming import NotePlayer
+
+    return NotePlayer(self, voices, **kw)
+
+
 NeuralWaveshaping.stream = _stream
+NeuralWaveshaping.player = _player

@@ -27,13 +27,18 @@ length): one push = one `g_stream_step` (`nws_g_stream_step`, the runtime-size k
 
 `VoiceStream` (`model.stream(B, slots=True)`, `nws_stream_step_slots`) is the slot mode: B voices that start and stop on their
 own in one batched stream, with per-slot events as device data; its docstring states the contract.
+
+`NotePlayer` (`model.player(voices)`) plays notes on a VoiceStream: `nws_note_control` writes every slot's controls
+of a hop from the notes, `nws_voice_mix` sums the slots into one signal; `NoteBook` is its host-side scheduling.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 import time
 import warnings
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -636,6 +641,266 @@ class VoiceStream(_StreamBase):
         """check(), then release the captured hops; push / hop / static_io raise afterwards."""
         self.check()
         self._graphs.clear()
+        self.finished = True
+
+
+# ---- note player: notes -> frame-rate controls -> slot stream -> one mixed signal (DESIGN.md 3.27) -----------------------
+NOTE_HELD = _lib.NOTE_HELD
+
+
+def pan_gains(pan: float, channels: int) -> tuple:
+    """Constant-power law: pan in [-1, 1] -> (left, right) = (cos, sin) of (pan + 1) pi / 4.  One channel: gain 1."""
+    if not -1.0 <= float(pan) <= 1.0:
+        raise RuntimeError(f"pan {pan} outside [-1, 1]")
+    if channels == 1:
+        return (1.0,)
+    a = (float(pan) + 1.0) * math.pi / 4.0
+    return (math.cos(a), math.sin(a))
+
+
+class NoteBook:
+    """Host-side scheduling of a NotePlayer (no GPU), beside SlotBook: notes to slots, events to hop boundaries, a voice's frame
+    count, and the hop that carries its slot `stop`.
+
+    `note_on` hands the idle slot of lowest index to the note at once (a slot that is `releasing`, or taken by an earlier note-on
+    of the same interval, is not idle) and queues the start; `note_off` queues the release.  `plan()` applies the queue at the hop
+    boundary - a note-off finds j_off = the frames its voice has had, 0 when the voice has not had a hop yet - and returns the
+    hop's (start, stop) slot lists; `commit()` books the hop.  A voice's slot `stop` goes on the hop that contains its frame
+    j_off + R - 1: voice hop (j_off + R - 1) // K.  `notes` (pitch, velocity, j_off) and `gains` per slot are what the device
+    tables must hold for the planned hop; `notes_dirty` / `gains_dirty` say that they changed since `clean()`."""
+
+    def __init__(self, voices: int, hop_frames: int, release_frames: int, channels: int = 1):
+        self.B, self.K, self.R, self.C = int(voices), int(hop_frames), int(release_frames), int(channels)
+        if self.B < 1 or not 1 <= self.K <= _SLOT_MAX_FRAMES or self.R < 1 or self.C not in (1, 2):
+            raise RuntimeError(f"NoteBook: voices >= 1, 1 <= hop_frames <= {_SLOT_MAX_FRAMES}, release_frames >= 1, channels 1 or 2")
+        self.slots = SlotBook(self.B)
+        self.frames = [0] * self.B                       # frames the slot's voice has had: the device counter's mirror
+        self.notes = [(0.0, 0.0, NOTE_HELD)] * self.B
+        self.gains = [(0.0,) * self.C] * self.B
+        self.notes_dirty = self.gains_dirty = True
+        self.hops = 0
+        self.dropped = 0
+        self._slot_of = {}                               # live handle -> slot, from note_on until the stop hop is booked
+        self._start_hop = [None] * self.B
+        self._on, self._off = [], []
+        self._next = 0
+        self._planned = None
+
+    # ---- between hops --------------------------------------------------------------------------------------------------
+    def note_on(self, pitch: float, velocity: float = 0.8, gains=None):
+        if not 0.0 < float(velocity) <= 1.0:
+            raise RuntimeError(f"velocity {velocity} outside (0, 1]")
+        gains = tuple(float(g) for g in (gains if gains is not None else (1.0,) * self.C))
+        if len(gains) != self.C:
+            raise RuntimeError(f"expected {self.C} gains, got {len(gains)}")
+        taken = set(self._slot_of.values())
+        for b in range(self.B):
+            if self.slots.states[b] == IDLE and b not in taken:
+                handle = self._next
+                self._next += 1
+                self._slot_of[handle] = b
+                self._on.append((b, float(pitch), float(velocity), gains))
+                return handle
+        self.dropped += 1
+        return None
+
+    def note_off(self, handle) -> None:
+        """Release the note; a handle whose voice has ended (or None) is ignored."""
+        if handle in self._slot_of:
+            self._off.append(handle)
+
+    def active(self) -> list:
+        """handles of the notes that sound or wait for their first hop, released ones included"""
+        return sorted(self._slot_of)
+
+    def stop_hop(self, handle):
+        """the hop (counted from the book's first) that carries the voice's slot `stop`; None while the note is held"""
+        b = self._slot_of.get(handle)
+        if b is None or self.notes[b][2] == NOTE_HELD or self._start_hop[b] is None:
+            return None
+        return self._start_hop[b] + (self.notes[b][2] + self.R - 1) // self.K
+
+    # ---- at the hop boundary -----------------------------------------------------------------------------------------------
+    def plan(self):
+        if self._planned is not None:
+            raise RuntimeError("NoteBook: plan() twice without commit()")
+        start = []
+        for b, pitch, velocity, gains in self._on:
+            self.notes = self.notes[:b] + [(pitch, velocity, NOTE_HELD)] + self.notes[b + 1:]
+            if self.gains[b] != gains:
+                self.gains = self.gains[:b] + [gains] + self.gains[b + 1:]
+                self.gains_dirty = True
+            self.notes_dirty = True
+            self.frames[b] = 0
+            self._start_hop[b] = self.hops
+            start.append(b)
+        for handle in self._off:
+            b = self._slot_of.get(handle)
+            if b is not None and self.notes[b][2] == NOTE_HELD:
+                self.notes = self.notes[:b] + [(self.notes[b][0], self.notes[b][1], self.frames[b])] + self.notes[b + 1:]
+                self.notes_dirty = True
+        self._on, self._off = [], []
+        stop = [b for b in sorted(self._slot_of.values())
+                if self.notes[b][2] != NOTE_HELD and self.frames[b] <= self.notes[b][2] + self.R - 1 < self.frames[b] + self.K]
+        words = self.slots.plan(start, stop)
+        self._planned = words
+        return start, stop
+
+    def commit(self) -> None:
+        words, self._planned = self._planned, None
+        self.slots.commit(words)
+        for b, w in enumerate(words):
+            if w & SLOT_ACTIVE:
+                self.frames[b] += self.K
+            if w & SLOT_STOP:
+                self._slot_of = {h: s for h, s in self._slot_of.items() if s != b}
+        self.hops += 1
+
+    def clean(self) -> None:
+        self.notes_dirty = self.gains_dirty = False
+
+
+class NotePlayer:
+    """A polyphonic instrument on a trained model (`model.player(voices, **kw)`): notes in, one mixed signal out.
+
+    One `hop()` = `hop_frames` control frames (128 samples each) = three pieces on torch's current stream:
+      * `note_control` (nws_note_control): every slot's F0 and normalised controls of this hop's frames, from the hop's event words,
+        the note table and the per-slot frame counters - closed forms in the voice's frame index, so a note's
+        controls do not depend on the hop size;
+      * the hop of the `VoiceStream` the player owns (used as it is: its captured hop once it exists, on that hop's own input
+        buffers, which the control launch fills in place);
+      * `voice_mix` (nws_voice_mix): out[c] = sum over the slots of gain[slot, c] * slot output.
+    The three are two launches around the stream's replayed graph, not one graph of their own.  Nothing is read back; the host
+    keeps a `NoteBook` and copies the event words, the note table or the gains to the device only when they change.
+
+    Envelope per note: a linear attack of `attack` frames from `silence` to the peak p = peak_lo + velocity (peak_hi - peak_lo), a
+    linear decay of `decay` frames by `drop`, the sustain at p - drop, and from `note_off` a linear release of `release` frames to
+    `silence`; loudness in the feature's units (dB + 80) / 80.  Vibrato: `vib_depth` cents at `vib_rate` Hz, faded in over
+    `vib_ramp` frames after `vib_delay`.  `peak_hi`, `peak_lo` and `silence` default to min(1, mean1 + 2 std1), mean1 - std1 and
+    max(0, mean1 - 4 std1) of the checkpoint's loudness statistics: these defaults, like those of the envelope times and the
+    vibrato, come from the statistics' meaning alone - nobody has listened to them.
+
+    `note_on` returns a handle, or None (and counts `dropped`) when no slot is idle: no voice is stolen.  A slot's gains are its
+    latest note's, so the reverb tail of an earlier voice of the slot follows a new note's pan.  Events take effect at the next
+    hop boundary.  `normalisation=(mean, std)` is the checkpoint's (checkpoint.load_normalisation); `phase_u`, `noise` and `graph`
+    go to the VoiceStream.  The packaged architecture only (VoiceStream's own refusal otherwise)."""
+
+    def __init__(self, model, voices: int, hop_frames: int = 1, channels: int = 1, *, attack: int = 3, decay: int = 12,
+                 release: int = 25, drop: float = 0.075, silence: float | None = None, peak_lo: float | None = None,
+                 peak_hi: float | None = None, vib_rate: float = 5.5, vib_depth: float = 15.0, vib_delay: int = 38,
+                 vib_ramp: int = 25, normalisation=None, phase_u: torch.Tensor | None = None, noise: torch.Tensor | None = None,
+                 graph: bool = True):
+        if normalisation is None:
+            raise RuntimeError("NotePlayer: pass normalisation=(mean, std), the checkpoint's data_mean / data_std "
+                               "(checkpoint.load_normalisation)")
+        mean, std = ([float(v) for v in list(x)[:2]] for x in normalisation)
+        self.book = NoteBook(voices, hop_frames, release, channels)          # validates voices, hop_frames, release, channels
+        self.B, self.K, self.C = self.book.B, self.book.K, self.book.C
+        hi = min(1.0, mean[1] + 2.0 * std[1]) if peak_hi is None else float(peak_hi)
+        lo = mean[1] - std[1] if peak_lo is None else float(peak_lo)
+        q = max(0.0, mean[1] - 4.0 * std[1]) if silence is None else float(silence)
+        self.params = dict(zip(_lib.NOTE_PARAMS, (int(attack), int(decay), int(release), int(vib_delay), int(vib_ramp), float(drop), q,
+                                                  lo, hi, float(vib_rate), float(vib_depth), float(model.sample_rate), mean[0], std[0],
+                                                  mean[1], std[1])))
+        p = self.params
+        if (p["attack"] < 0 or p["decay"] < 0 or p["vib_delay"] < 0 or p["vib_ramp"] < 1 or p["drop"] < 0 or p["vib_rate"] < 0
+                or not p["std0"] > 0 or not p["std1"] > 0 or max(p["attack"], p["decay"], p["release"], p["vib_delay"], p["vib_ramp"]) > 2 ** 24):
+            raise RuntimeError("NotePlayer: attack, decay, vib_delay >= 0, release, vib_ramp >= 1 (all at most 2^24 frames), drop >= 0, "
+                               "vib_rate >= 0 and positive standard deviations")
+        self.stream = VoiceStream(model, self.B, phase_u=phase_u, noise=noise, graph=graph)
+        self.dev = dev = self.stream.dev
+        self._params = torch.tensor([float(p[k]) for k in _lib.NOTE_PARAMS], dtype=torch.float64)
+        nbytes = _lib.lib().nws_note_control_state_bytes(self.B)
+        if nbytes == 0:
+            raise RuntimeError(f"NotePlayer: {self.B} voices: 1 <= voices <= 65535")
+        with torch.cuda.device(dev):
+            self._state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            binding().note_control_reset(self._state, self.B)
+            self._notes = torch.zeros((self.B, 4), dtype=torch.int32, device=dev)
+            self._gain = torch.zeros((self.B, self.C), dtype=torch.float32, device=dev)
+            self._f0 = torch.zeros((self.B, self.K), dtype=torch.float32, device=dev)         # a hop before the captured one exists
+            self._control = torch.zeros((self.B, 2, self.K), dtype=torch.float32, device=dev)
+            self._out = torch.zeros((self.C, HOP * self.K), dtype=torch.float32, device=dev)
+        self.finished = False
+        self.last_hop = None
+
+    # ---- notes --------------------------------------------------------------------------------------------------------------
+    @property
+    def dropped(self) -> int:
+        return self.book.dropped
+
+    def note_on(self, pitch: float, velocity: float = 0.8, pan: float = 0.0):
+        """Start a note at the next hop: MIDI note number, velocity in (0, 1], pan in [-1, 1] (left .. right; two channels only).
+        -> a handle for `note_off`, or None when every slot is taken (counted in `dropped`)."""
+        return self.book.note_on(pitch, velocity, pan_gains(pan, self.C))
+
+    def note_off(self, handle) -> None:
+        """Release the note from the next hop on; its slot is free again two hops after the release has ended."""
+        self.book.note_off(handle)
+
+    def active(self) -> list:
+        """handles of the notes that still sound (released ones until their release has ended)"""
+        return self.book.active()
+
+    # ---- one hop --------------------------------------------------------------------------------------------------------------
+    def _upload(self):
+        book = self.book
+        if book.notes_dirty:
+            table = np.zeros((self.B, 4), dtype=np.int32)
+            table[:, 0] = np.array([n[0] for n in book.notes], dtype=np.float32).view(np.int32)
+            table[:, 1] = np.array([n[1] for n in book.notes], dtype=np.float32).view(np.int32)
+            table[:, 2] = [n[2] for n in book.notes]
+            self._notes.copy_(torch.from_numpy(table).pin_memory(), non_blocking=True)
+        if book.gains_dirty:
+            self._gain.copy_(torch.tensor(book.gains, dtype=torch.float32).pin_memory(), non_blocking=True)
+        book.clean()
+
+    def hop(self) -> torch.Tensor:
+        """One hop -> (channels, 128 hop_frames): the player's own output buffer, overwritten by the next hop."""
+        if self.finished:
+            raise RuntimeError("NotePlayer: closed")
+        vs, K = self.stream, self.K
+        start, stop = self.book.plan()
+        vs._check_weights()
+        vs._set_events(vs.book.plan(start, stop))          # the control launch reads the words the stream's hop will read
+        self._upload()
+        ops = binding()
+        if vs._use_graph and vs._steady(K) and not torch.cuda.is_current_stream_capturing():
+            f0_in, control_in, ev, _ = vs.static_io(K)
+            ops.note_control(self._params, ev, self._notes, self._state, f0_in, control_in)
+            o = vs.hop(K, start=start, stop=stop)
+        else:
+            f0_in, control_in = self._f0, self._control
+            ops.note_control(self._params, vs._ev, self._notes, self._state, f0_in, control_in)
+            o = vs.push(f0_in.unsqueeze(1), control_in, start=start, stop=stop)
+        ops.voice_mix(o, self._gain, self._out)
+        self.book.commit()
+        self.last_hop = (f0_in, control_in, start, stop, o)    # what the hop fed the stream and got from it: for tests and debugging
+        return self._out
+
+    def render(self, n_hops: int) -> torch.Tensor:
+        """n_hops hops -> (channels, 128 hop_frames n_hops)"""
+        with torch.cuda.device(self.dev):
+            out = torch.empty((self.C, HOP * self.K * int(n_hops)), dtype=torch.float32, device=self.dev)
+        for h in range(int(n_hops)):
+            out[:, h * HOP * self.K:(h + 1) * HOP * self.K].copy_(self.hop())
+        return out
+
+    # ---- state ----------------------------------------------------------------------------------------------------------------
+    def check(self) -> None:
+        """VoiceStream.check(), and the device's frame counters against the host's mirror for every sounding slot (synchronises)."""
+        self.stream.check()
+        cnt = self._state[:4 * self.B].cpu().view(torch.int32).tolist()
+        for b, s in enumerate(self.book.slots.states):
+            if s == ACTIVE and cnt[b] != self.book.frames[b]:
+                raise RuntimeError(f"NotePlayer: slot {b}: device frame counter {cnt[b]}, host mirror {self.book.frames[b]}")
+        if self.book.slots.states != self.stream.book.states:
+            raise RuntimeError("NotePlayer: the note book and the stream's slot book disagree")
+
+    def close(self) -> None:
+        """check(), then close the stream; hop raises afterwards."""
+        self.check()
+        self.stream.close()
         self.finished = True
 
 
