@@ -1054,6 +1054,24 @@ int nws_g_stream_reverb_tail(const NwsGenericModel* m, const NwsReverbPlan* plan
                              float* tail_out /* (B, ir_len + 1) */, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Slot mode of the runtime-size stream (csrc/generic.hip): nws_stream_step_slots' contract - B voice slots, one hop
+ * of 1 <= K <= 16 frames per call, (B, 128 K) out, `events` a (B) int32 array of NWS_SLOT_* words in DEVICE memory read by the
+ * launches, the call with frames_seen == 0 the all-idle pre-roll - for every model nws_g_stream_step serves.  The argument list is
+ * nws_stream_step_slots' with the model descriptor in place of the weights, the design matrix and the impulse response.  A chain of
+ * launches: nothing waits inside a launch, so there is no give-up flag to read.  Refusals, all before the first launch with
+ * outputs and state untouched: those of nws_g_stream_step, NWS_ERR_BAD_ARG for events == NULL, NWS_ERR_UNSUPPORTED for K > 16 or
+ * max_frames > 16, NWS_ERR_WORKSPACE for a blob smaller than nws_g_stream_slot_state_bytes - which is 0 for every size
+ * nws_g_stream_state_bytes refuses and for max_frames > 16.  The blob is a plain stream's without a plan (every offset of it where it
+ * was) followed by two per-row arrays; nws_stream_reset and nws_g_stream_reverb_tail serve it.
+ */
+size_t nws_g_stream_slot_state_bytes(const NwsGenericModel* m, int B, int max_frames, int ir_len);
+int nws_g_stream_step_slots(const NwsGenericModel* m, void* state, size_t state_bytes, int B, int max_frames,
+                            const float* f0 /* (B,K) */, const float* control /* (B,C,K) */, int C, int K, long long frames_seen,
+                            long long nz_prev_start, float sample_rate, const float* phase_u, const float* rand_phase,
+                            const float* noise_new, const float* noise_all, int noise_all_len, const int* events /* (B) device */,
+                            float* out /* (B, 128 K) */, float* pre_out /* optional */, void* stream);
+
+/*
  * Note player (ABI v6; csrc/note_control.hip; no reference counterpart: the reference renders recordings only).
  * The two launches around a hop of nws_stream_step_slots that turn notes into a signal.
  *

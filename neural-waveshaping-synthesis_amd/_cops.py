@@ -1280,3 +1280,13 @@ class CtypesOps:
                 state.numel(), B, max_frames, ptr(f0), ptr(control), control.shape[1], K, int(first), int(final), frames_seen,
                 nz_prev_start, sample_rate, ptr(phase_u), ptr(rand_phase), ptr(noise_new), ptr(noise_all),
                 noise_all.numel() if noise_all is not None else 0, ptr(out), ptr(pre_out), _stream(f0.device)), "nws_g_stream_step")
+
+    def g_stream_step_slots(self, gdesc, state, max_frames, f0, control, frames_seen, nz_prev_start, sample_rate, phase_u, rand_phase,
+                            noise_new, noise_all, events, out, pre_out):
+        B, K = f0.shape
+        with torch.cuda.device(f0.device):
+            check(_lib.lib().nws_g_stream_step_slots(
+                C.byref(_struct(gdesc, NwsGenericModel)), ptr(state), state.numel(), B, max_frames, ptr(f0), ptr(control),
+                control.shape[1], K, frames_seen, nz_prev_start, sample_rate, ptr(phase_u), ptr(rand_phase), ptr(noise_new),
+                ptr(noise_all), noise_all.numel() if noise_all is not None else 0, ptr(events), ptr(out), ptr(pre_out),
+                _stream(f0.device)), "nws_g_stream_step_slots")

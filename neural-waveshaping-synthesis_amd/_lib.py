@@ -336,6 +336,9 @@ _PROTOTYPES = {
                                     _fp, _fp, C.c_int, _fp, _fp, _fp]),
     "nws_g_stream_reverb_tail": (C.c_int, [C.POINTER(NwsGenericModel), C.POINTER(NwsReverbPlan), _fp, _fp, _fp, C.c_size_t, C.c_int,
                                            C.c_int, _fp, _fp, C.c_size_t, _fp]),
+    "nws_g_stream_slot_state_bytes": (C.c_size_t, [C.POINTER(NwsGenericModel), C.c_int, C.c_int, C.c_int]),
+    "nws_g_stream_step_slots": (C.c_int, [C.POINTER(NwsGenericModel), _fp, C.c_size_t, C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int,
+                                          C.c_longlong, C.c_longlong, C.c_float, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp]),
     "nws_note_control_state_bytes": (C.c_size_t, [C.c_int]),
     "nws_note_control_reset": (C.c_int, [_fp, C.c_size_t, C.c_int, _fp]),
     "nws_note_control": (C.c_int, [C.POINTER(NwsNotePlayer), _fp, _fp, _fp, C.c_size_t, C.c_int, C.c_int, _fp, _fp, _fp]),

@@ -1820,6 +1820,7 @@ struct GsLayout {
   size_t h, h_next, prev_f0, prev_film, prev_fir, S, residue, ring, counters, nzwin;                         // state
   size_t gru_ws, gru_bth, gru_bht, emb, film_new, H, fir_new, dmat, f0_w, film_w, fir_w, f0_up, phase, tab;   // scratch
   size_t newt, newt_sum, exciter, shaped, osc, noise_w, pre, partial, x_lin, y_lin, rv_ws;
+  size_t vage, nzrows;   // slot mode: state, behind everything a plain stream lays out
   size_t gru_ws_bytes, rv_ws_bytes, total;
   int parts;
   bool stages;
@@ -1839,7 +1840,9 @@ bool gs_serves(const NwsGenericModel* m, int B) {
   return shaper_lds(&m->shaper) <= 160 * 1024;
 }
 
-GsLayout gs_layout(const NwsGenericModel* m, int B, int max_frames, int ir_len, size_t fft_ws_bytes) {
+// slots: the blob of nws_g_stream_step_slots - the two per-row arrays of slot mode follow everything a plain stream of the same
+// sizes lays out (without a plan: fft_ws_bytes = 0), so every offset stays where it is
+GsLayout gs_layout(const NwsGenericModel* m, int B, int max_frames, int ir_len, size_t fft_ws_bytes, bool slots = false) {
   GsLayout L{};
   size_t o = 0;
   auto take = [&](size_t bytes) {
@@ -1893,8 +1896,20 @@ GsLayout gs_layout(const NwsGenericModel* m, int B, int max_frames, int ir_len, 
     L.rv_ws_bytes = fft_ws_bytes;
     L.rv_ws = take(fft_ws_bytes);
   }
+  if (slots) {
+    L.vage = take((size_t)B * 4);       // frames of each row's voice before this hop
+    L.nzrows = take((size_t)B * 16);    // each row's noise bounds in this hop's window (int4)
+  }
   L.total = o;
   return L;
+}
+
+// slot mode: a row whose voice starts in this hop begins its recurrence from h = 0 (nws_g_gru takes one h0 for the whole batch, so
+// the zeros go into the carried state in front of its launch).  One workgroup per row.
+__global__ __launch_bounds__(256) void g_stream_slot_head_kernel(const int* __restrict__ ev, int Hh, float* __restrict__ h) {
+  const int b = blockIdx.x;
+  if (!(ev[b] & NWS_SLOT_START)) return;
+  for (int j = threadIdx.x; j < Hh; j += 256) h[(size_t)b * Hh + j] = 0.0f;
 }
 
 // The runtime-size counterpart of stream_prep_kernel.  blocks 0..B-1: one utterance each - the F0 window (B, Tw), the FiLM window
@@ -1906,7 +1921,9 @@ __global__ __launch_bounds__(256) void g_stream_windows_kernel(const float* __re
                                                                float* __restrict__ prev_f0, float* __restrict__ prev_film,
                                                                float* __restrict__ prev_fir, float* __restrict__ h,
                                                                const float* __restrict__ h_next, float* __restrict__ f0_w,
-                                                               float* __restrict__ film_w, float* __restrict__ fir_w, NwsStreamNoiseWin Z) {
+                                                               float* __restrict__ film_w, float* __restrict__ fir_w, NwsStreamNoiseWin Z,
+                                                               const int* __restrict__ ev, int* __restrict__ vage,
+                                                               int4* __restrict__ nzrows, int n_len) {
   const int tid = threadIdx.x;
   const int b = blockIdx.x;
   if (b == B) {
@@ -1914,6 +1931,44 @@ __global__ __launch_bounds__(256) void g_stream_windows_kernel(const float* __re
     return;
   }
   const int off = first ? 0 : 1, Tw = K + off;
+  if (ev != nullptr) {
+    // slot mode: the src(t) rule, the noise bounds and the voice's age of stream_prep_kernel (stream.hip) - window frame t of row b
+    // is the previous frame (-1), new frame s >= 0, or zeros (-2: an idle row's inputs are never read); all by selects
+    const int e = ev[b];
+    auto src = [&](int t) {
+      if (e & NWS_SLOT_RELEASE) return -1;
+      if (!(e & NWS_SLOT_ACTIVE)) return -2;
+      if (e & NWS_SLOT_START) return t < off ? 0 : t - off;
+      return t < off ? -1 : t - off;
+    };
+    for (int i = tid; i < Tw; i += 256) {
+      const int s = src(i);
+      f0_w[(size_t)b * Tw + i] = s >= 0 ? f0_new[(size_t)b * K + s] : (s == -1 ? prev_f0[b] : 0.0f);
+    }
+    for (int i = tid; i < FC * Tw; i += 256) {
+      const int c = i / Tw, t = i - c * Tw, s = src(t);
+      film_w[(size_t)b * FC * Tw + i] = s >= 0 ? film_new[((size_t)b * FC + c) * K + s] : (s == -1 ? prev_film[(size_t)b * FC + c] : 0.0f);
+    }
+    for (int i = tid; i < Tw * kGsHalf; i += 256) {
+      const int t = i / kGsHalf, c = i - t * kGsHalf, s = src(t);
+      fir_w[(size_t)b * Tw * kGsHalf + i] = s >= 0 ? fir_new[((size_t)b * K + s) * kGsHalf + c]
+                                                   : (s == -1 ? prev_fir[(size_t)b * kGsHalf + c] : 0.0f);
+    }
+    for (int j = tid; j < Hh; j += 256) h[(size_t)b * Hh + j] = h_next[(size_t)b * Hh + j];
+    if (tid == 0) {
+      const int age = (e & NWS_SLOT_START) ? 0 : vage[b];
+      const int lo = 256 - 128 * (age < 2 ? age : 2);
+      const int hi = (e & NWS_SLOT_STOP) ? 128 * (Tw + 1) - 2 : n_len - 1;
+      const bool live = !first && (e & NWS_SLOT_ACTIVE);
+      nzrows[b] = make_int4(live ? lo : 0, live ? hi : n_len - 1, (!first && (e & NWS_SLOT_START)) ? 1 : 0, 0);
+      vage[b] = (e & NWS_SLOT_ACTIVE) ? (age + K < (1 << 20) ? age + K : (1 << 20)) : 0;
+    }
+    __syncthreads();   // the windows are complete and prev_* has been consumed: the next hop's previous frame is the window's last
+    if (tid == 0) prev_f0[b] = f0_w[(size_t)b * Tw + Tw - 1];
+    for (int c = tid; c < FC; c += 256) prev_film[(size_t)b * FC + c] = film_w[((size_t)b * FC + c) * Tw + Tw - 1];
+    for (int c = tid; c < kGsHalf; c += 256) prev_fir[(size_t)b * kGsHalf + c] = fir_w[((size_t)b * Tw + Tw - 1) * kGsHalf + c];
+    return;
+  }
   for (int i = tid; i < Tw; i += 256) f0_w[(size_t)b * Tw + i] = (i < off) ? prev_f0[b] : f0_new[(size_t)b * K + i - off];
   for (int i = tid; i < FC * Tw; i += 256) {
     const int c = i / Tw, t = i - c * Tw;
@@ -1935,16 +1990,20 @@ __global__ __launch_bounds__(256) void g_stream_windows_kernel(const float* __re
 // a left clamp the one-shot never applied there and contribute nothing; their phase is a placeholder that is not emitted) and
 // S[b] becomes the sum through sample hi - 1, the last one this step emits.  Sums of fp32 values in float64 are exact, so the
 // sum at every emitted sample is the one-shot forward's whatever the chunking; the fp32 chain behind it is g_phase_kernel's.
-__global__ __launch_bounds__(1024) void g_stream_phase_kernel(const float* __restrict__ f0_w, int Tw, int N, float sample_rate, int lo,
+// Slot mode (ev != NULL): a row whose voice starts in this hop (never the stream's first) sums from 0.0 at window sample 128, its
+// voice's sample 0 - the one-shot's sum of that voice; every other row continues from S[b] at `lo`.
+__global__ __launch_bounds__(1024) void g_stream_phase_kernel(const float* __restrict__ f0_w, int Tw, int N, float sample_rate, int lo_in,
                                                               int hi, int keep, double* __restrict__ S, float* __restrict__ f0_up_out,
-                                                              float* __restrict__ phase_out) {
+                                                              float* __restrict__ phase_out, const int* __restrict__ ev, int first) {
   __shared__ double tot[1024];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int per = (N + 1023) / 1024;
   const int n0 = tid * per, n1 = n0 + per < N ? n0 + per : N;
   const float* x = f0_w + (size_t)b * Tw;
   const float scale = (float)Tw / (float)N;
-  const double s0 = S[b];
+  const bool fresh = ev != nullptr && !first && (ev[b] & NWS_SLOT_START) != 0;
+  const int lo = fresh ? 128 : lo_in;
+  const double s0 = fresh ? 0.0 : S[b];
   auto value = [&](int n) {
     const GLerp L = g_lerp_coeff(n, Tw, scale);
     return fmaf(L.w0, x[L.i0], L.w1 * x[L.i1]);
@@ -1990,18 +2049,24 @@ size_t nws_g_stream_state_bytes(const NwsGenericModel* m, int B, int max_frames,
   return gs_layout(m, B, max_frames, ir_len, plan ? nws_reverb_workspace_bytes(plan, B) : 0).total;
 }
 
-int nws_g_stream_step(const NwsGenericModel* m, const NwsReverbPlan* plan, const void* reverb_tables, const void* reverb_spectrum,
-                      void* state, size_t state_bytes, int B, int max_frames, const float* f0, const float* control, int C, int K,
-                      int first, int final, long long frames_seen, long long nz_prev_start, float sample_rate, const float* phase_u,
-                      const float* rand_phase, const float* noise_new, const float* noise_all, int noise_all_len, float* out,
-                      float* pre_out, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// ev == NULL: nws_g_stream_step.  ev != NULL: slot mode (nws_g_stream_step_slots) - the same chain of launches with
+// the per-row events in the recurrence's start state, the windows, the phase sum's start, the noise bounds and the emitted-sample gate
+int g_stream_step(const NwsGenericModel* m, const NwsReverbPlan* plan, const void* reverb_tables, const void* reverb_spectrum,
+                  void* state, size_t state_bytes, int B, int max_frames, const float* f0, const float* control, int C, int K,
+                  int first, int final, long long frames_seen, long long nz_prev_start, float sample_rate, const float* phase_u,
+                  const float* rand_phase, const float* noise_new, const float* noise_all, int noise_all_len, float* out,
+                  float* pre_out, const int* ev, void* stream) {
   if (!model_ok(m) || !state || !f0 || !control || !phase_u || !rand_phase || !out) return NWS_ERR_BAD_ARG;
   if (B <= 0 || K <= 0 || max_frames <= 0 || max_frames > (1 << 20) || K > max_frames || C < m->control_size || !(sample_rate > 0.0f))
     return NWS_ERR_BAD_ARG;
   if ((noise_new == nullptr) == (noise_all == nullptr)) return NWS_ERR_BAD_ARG;
   if ((first != 0) != (frames_seen == 0)) return NWS_ERR_BAD_ARG;
   if (!gs_serves(m, B)) return NWS_ERR_UNSUPPORTED;
-  const GsLayout L = gs_layout(m, B, max_frames, m->ir_len, plan ? nws_reverb_workspace_bytes(plan, B) : 0);
+  const GsLayout L = gs_layout(m, B, max_frames, m->ir_len, plan ? nws_reverb_workspace_bytes(plan, B) : 0, ev != nullptr);
   if (L.total > state_bytes) return NWS_ERR_WORKSPACE;
   const int Tw = first ? K : K + 1, Nw = 128 * Tw;
   const int lo = first ? 0 : 64, hi = final ? Nw : Nw - 64, M = hi - lo;
@@ -2035,6 +2100,10 @@ int nws_g_stream_step(const NwsGenericModel* m, const NwsReverbPlan* plan, const
     if (rc != NWS_OK) return rc; \
   } while (0)
   // 1. control encoder on the new frames, state carried; proj and both frame MLPs on the new frames only
+  if (ev != nullptr && !first) {
+    g_stream_slot_head_kernel<<<B, 256, 0, st>>>(ev, Hh, F(L.h));
+    NWS_CHECK_LAUNCH();
+  }
   G(nws_g_gru(m->gru_w_ih, m->gru_w_hh, m->gru_b_ih, m->gru_b_hh, control, B, C, m->control_size, Hh, K, first ? nullptr : F(L.h),
               F(L.gru_bth), F(L.h_next), base + L.gru_ws, L.gru_ws_bytes, stream));
   G(nws_g_bth_to_bht(F(L.gru_bth), B, K, Hh, F(L.gru_bht), stream));
@@ -2054,10 +2123,11 @@ int nws_g_stream_step(const NwsGenericModel* m, const NwsReverbPlan* plan, const
   // 2. windows, previous frame, GRU state hand-over, noise window, pending counters
   const NwsStreamNoiseWin Z{F(L.nzwin), noise_new, noise_all, counters, nz_shift, nz_keep, n_new, noise_all_len, first, K};
   g_stream_windows_kernel<<<B + 1, 256, 0, st>>>(f0, F(L.film_new), F(L.fir_new), K, first, B, FC, Hh, F(L.prev_f0), F(L.prev_film),
-                                                 F(L.prev_fir), F(L.h), F(L.h_next), F(L.f0_w), F(L.film_w), F(L.fir_w), Z);
+                                                 F(L.prev_fir), F(L.h), F(L.h_next), F(L.f0_w), F(L.film_w), F(L.fir_w), Z, ev,
+                                                 reinterpret_cast<int*>(base + L.vage), reinterpret_cast<int4*>(base + L.nzrows), n_len);
   NWS_CHECK_LAUNCH();
   // 3. phase with the carried float64 sum
-  g_stream_phase_kernel<<<B, 1024, 0, st>>>(F(L.f0_w), Tw, Nw, sample_rate, lo, hi, final ? 0 : 1, S, F(L.f0_up), F(L.phase));
+  g_stream_phase_kernel<<<B, 1024, 0, st>>>(F(L.f0_w), Tw, Nw, sample_rate, lo, hi, final ? 0 : 1, S, F(L.f0_up), F(L.phase), ev, first);
   NWS_CHECK_LAUNCH();
   // 4. oscillator bank -> NEWT output on the window (its FiLM upsample clamps at the window's edges: samples outside [lo, hi))
   float* exciter = L.exciter ? F(L.exciter) : nullptr;
@@ -2078,15 +2148,52 @@ int nws_g_stream_step(const NwsGenericModel* m, const NwsReverbPlan* plan, const
     NWS_CHECK_LAUNCH();
   }
   // 5. noise branch on the same window, then the emitted samples, the residue, the ring and the linear reverb (stream.hip)
-  G(nws_fir_noise_window(F(L.fir_w), F(L.nzwin), n_len, origin, nullptr, B, Tw, F(L.noise_w), stream));
+  if (ev != nullptr) {
+    G(nws_fir_noise_window_rows(F(L.fir_w), F(L.nzwin), origin, reinterpret_cast<const int4*>(base + L.nzrows), B, Tw, F(L.noise_w), stream));
+  } else {
+    G(nws_fir_noise_window(F(L.fir_w), F(L.nzwin), n_len, origin, nullptr, B, Tw, F(L.noise_w), stream));
+  }
 #undef G
   const int R0 = first ? 0 : 64, noise_off = first ? 0 : 128;
-  const NwsPreSrc P{F(L.newt_sum), F(L.noise_w), F(L.residue), Nw, lo, R0, noise_off, nullptr};
+  const NwsPreSrc P{F(L.newt_sum), F(L.noise_w), F(L.residue), Nw, lo, R0, noise_off, ev};
   const int tail_from = noise_off + M - R0;
   const NwsStreamEmit Em{F(L.ring), F(L.residue), counters, F(L.partial), L.parts, L.x_lin ? F(L.x_lin) : nullptr,
                          L.y_lin ? F(L.y_lin) : nullptr, base + L.rv_ws, L.rv_ws_bytes};
   return nws_stream_emit(&P, &Em, plan, reverb_tables, reverb_spectrum, m->ir, m->ir_len, B, K, M, final, tail_from, out,
                          pre_out ? pre_out : F(L.pre), stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int nws_g_stream_step(const NwsGenericModel* m, const NwsReverbPlan* plan, const void* reverb_tables, const void* reverb_spectrum,
+                      void* state, size_t state_bytes, int B, int max_frames, const float* f0, const float* control, int C, int K,
+                      int first, int final, long long frames_seen, long long nz_prev_start, float sample_rate, const float* phase_u,
+                      const float* rand_phase, const float* noise_new, const float* noise_all, int noise_all_len, float* out,
+                      float* pre_out, void* stream) {
+  return g_stream_step(m, plan, reverb_tables, reverb_spectrum, state, state_bytes, B, max_frames, f0, control, C, K, first, final,
+                       frames_seen, nz_prev_start, sample_rate, phase_u, rand_phase, noise_new, noise_all, noise_all_len, out, pre_out,
+                       nullptr, stream);
+}
+
+// Slot mode on the runtime-size path: nws_stream_step_slots' contract (stream.hip) with the model descriptor in place
+// of the weights.  B voice slots, one hop of K <= 16 frames, `events` (B) int32 in DEVICE memory read by the launches; the step with
+// frames_seen == 0 is the all-idle pre-roll.  A chain of launches like nws_g_stream_step - nothing waits inside a launch.
+size_t nws_g_stream_slot_state_bytes(const NwsGenericModel* m, int B, int max_frames, int ir_len) {
+  if (!model_ok(m) || B <= 0 || max_frames <= 0 || max_frames > kGsMaxDirect / 128 || ir_len != m->ir_len || !gs_serves(m, B)) return 0;
+  return gs_layout(m, B, max_frames, ir_len, 0, true).total;
+}
+
+int nws_g_stream_step_slots(const NwsGenericModel* m, void* state, size_t state_bytes, int B, int max_frames, const float* f0,
+                            const float* control, int C, int K, long long frames_seen, long long nz_prev_start, float sample_rate,
+                            const float* phase_u, const float* rand_phase, const float* noise_new, const float* noise_all,
+                            int noise_all_len, const int* events, float* out, float* pre_out, void* stream) {
+  if (!events) return NWS_ERR_BAD_ARG;
+  if (K > kGsMaxDirect / 128 || max_frames > kGsMaxDirect / 128) return NWS_ERR_UNSUPPORTED;     // the time-domain reverb's hops only
+  return g_stream_step(m, nullptr, nullptr, nullptr, state, state_bytes, B, max_frames, f0, control, C, K, frames_seen == 0 ? 1 : 0, 0,
+                       frames_seen, nz_prev_start, sample_rate, phase_u, rand_phase, noise_new, noise_all, noise_all_len, out, pre_out,
+                       events, stream);
 }
 
 int nws_g_stream_reverb_tail(const NwsGenericModel* m, const NwsReverbPlan* plan, const void* reverb_tables,

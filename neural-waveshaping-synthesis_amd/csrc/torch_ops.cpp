@@ -1928,6 +1928,34 @@ void g_stream_step(const Tensor& gdesc, const OptTensor& plan_t, const OptTensor
             "nws_g_stream_step");
 }
 
+// ---- slot mode on the runtime-size path (csrc/generic.hip nws_g_stream_step_slots) ---------------------------------
+void g_stream_step_slots(const Tensor& gdesc, Tensor& state, int64_t max_frames, const Tensor& f0, const Tensor& control,
+                         int64_t frames_seen, int64_t nz_prev_start, double sample_rate, const Tensor& phase_u, const Tensor& rand_phase,
+                         const OptTensor& noise_new, const OptTensor& noise_all, const Tensor& events, Tensor& out,
+                         const OptTensor& pre_out) {
+  const NwsGenericModel* m = struct_of<NwsGenericModel>(gdesc, "gdesc");
+  TORCH_CHECK(m->hop > 0 && m->n_harmonics > 0, "gdesc: not a NwsGenericModel");
+  const StepDims d = check_step_tensors("g_stream_step_slots", f0, control, nullptr, state, phase_u, rand_phase, nullptr, out);
+  const int64_t B = d.B, K = d.K, C = d.C;
+  check_dev(events, "events", at::kInt);
+  check_same_device(f0, "f0", events, "events");
+  TORCH_CHECK(K >= 1 && K <= 16 && K <= max_frames, "g_stream_step_slots: hops of 1 .. 16 frames (sized for ", max_frames, "), got ", K);
+  TORCH_CHECK(events.numel() == B, "g_stream_step_slots: events: one int32 word per slot, expected ", B, ", got ", events.numel());
+  check_step_io("g_stream_step_slots", d, frames_seen == 0, false, frames_seen, phase_u, rand_phase, noise_new, noise_all, out, pre_out,
+                m->n_harmonics);
+  const size_t need = nws_g_stream_slot_state_bytes(m, (int)B, (int)max_frames, m->ir_len);
+  TORCH_CHECK(need != 0, "g_stream_step_slots: the runtime-size slot stream does not serve this model or size (control hop 128, 256 "
+              "noise taps, an impulse response below 32768 taps, at most 16 frames per hop)");
+  TORCH_CHECK((size_t)state.numel() >= need, "g_stream_step_slots: state blob too small");
+  Launch L(f0);
+  nws_check(nws_g_stream_step_slots(m, state.data_ptr(), (size_t)state.numel(), (int)B, (int)max_frames, f0.data_ptr<float>(),
+                                    control.data_ptr<float>(), (int)C, (int)K, (long long)frames_seen, (long long)nz_prev_start,
+                                    (float)sample_rate, phase_u.data_ptr<float>(), rand_phase.data_ptr<float>(), fptr(noise_new),
+                                    fptr(noise_all), noise_all.has_value() ? (int)noise_all->numel() : 0, events.data_ptr<int>(),
+                                    out.data_ptr<float>(), pre_out.has_value() ? pre_out->data_ptr<float>() : nullptr, L.stream),
+            "nws_g_stream_step_slots");
+}
+
 // ---- note player (csrc/note_control.hip): the launches in front of and behind a slot stream's hop --------------
 // `params`: 16 float64 values on the CPU in the order of _lib.NOTE_PARAMS
 NwsNotePlayer note_player_of(const Tensor& params) {
@@ -2088,6 +2116,10 @@ TORCH_LIBRARY(newt_hip, m) {
         "Tensor f0, Tensor control, bool first, bool final, int frames_seen, int nz_prev_start, float sample_rate, Tensor phase_u, "
         "Tensor rand_phase, Tensor? noise_new, Tensor? noise_all, Tensor(b!) out, Tensor(c!)? pre_out) -> ()",
         &g_stream_step);
+  m.def("g_stream_step_slots(Tensor gdesc, Tensor(a!) state, int max_frames, Tensor f0, Tensor control, int frames_seen, "
+        "int nz_prev_start, float sample_rate, Tensor phase_u, Tensor rand_phase, Tensor? noise_new, Tensor? noise_all, "
+        "Tensor events, Tensor(b!) out, Tensor(c!)? pre_out) -> ()",
+        &g_stream_step_slots);
   m.def("loudness(Tensor audio, Tensor dft, int n_fft, int hop, float amin, float top_db, bool normalise) -> Tensor", &loudness);
   m.def("loudness_peak_power(Tensor audio, Tensor dft, int n_fft, int hop) -> Tensor", &loudness_peak_power);
   m.def("loudness_stream_reset(Tensor(a!) state, int B, int n_fft, int hop, Tensor initial_power, bool track) -> ()",

@@ -486,7 +486,8 @@ def ensure_default_config():
 def _stream(self, batch_size: int = 1, *, phase_u=None, noise=None, slots: bool = False, **kw):
     """Stateful streaming synthesiser bound to this model (see streaming.NewtStream; kw: max_chunk_frames, graph).  A model of
     another architecture than gin/models/newt.gin gets the same stream on the runtime-size kernels (streaming.GenericNewtStream).
-    slots=True: B voice slots that start and stop on their own (streaming.VoiceStream; kw: graph; the packaged architecture only)."""
+    slots=True: B voice slots that start and stop on their own (streaming.VoiceStream; kw: graph; the packaged architecture only -
+    `model.voices(B)` gives the slot stream of any architecture)."""
     from ..streaming import GenericNewtStream, NewtStream, VoiceStream
 
     if slots:
@@ -495,14 +496,24 @@ def _stream(self, batch_size: int = 1, *, phase_u=None, noise=None, slots: bool 
     return cls(self, batch_size, phase_u=phase_u, noise=noise, **kw)
 
 
+def _voices(self, batch_size: int = 1, **kw):
+    """B voice slots that start and stop on their own, for this model whatever its architecture (kw: phase_u, noise, graph):
+    streaming.VoiceStream on the fused kernels for gin/models/newt.gin, streaming.GenericVoiceStream on the runtime-size kernels
+     for every other configuration."""
+    from ..streaming import voice_stream
+
+    return voice_stream(self, batch_size, **kw)
+
+
 def _player(self, voices: int, **kw):
     """Polyphonic note player bound to this model (see streaming.NotePlayer; kw: hop_frames, channels, the envelope and vibrato
-    parameters, normalisation=(mean, std), phase_u, noise, graph): note_on / note_off in, one mixed signal out, hop by hop.  The
-    packaged architecture only."""
+    parameters, normalisation=(mean, std), phase_u, noise, graph): note_on / note_off in, one mixed signal out, hop by hop.  Any
+    architecture with a two-channel control input: the player's stream is `model.voices(voices)`."""
     from ..streaming import NotePlayer
 
     return NotePlayer(self, voices, **kw)
 
 
 NeuralWaveshaping.stream = _stream
+NeuralWaveshaping.voices = _voices
 NeuralWaveshaping.player = _player

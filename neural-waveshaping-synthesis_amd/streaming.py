@@ -26,9 +26,10 @@ hipGraph and replayed (`graph=True`, the default): a 256-sample hop is then one 
 length): one push = one `g_stream_step` (`nws_g_stream_step`, the runtime-size kernels); `model.stream` picks the class.
 
 `VoiceStream` (`model.stream(B, slots=True)`, `nws_stream_step_slots`) is the slot mode: B voices that start and stop on their
-own in one batched stream, with per-slot events as device data; its docstring states the contract.
+own in one batched stream, with per-slot events as device data; its docstring states the contract.  `GenericVoiceStream` is the
+same for a model of another architecture (`nws_g_stream_step_slots`); `model.voices(B)` picks the class.
 
-`NotePlayer` (`model.player(voices)`) plays notes on a VoiceStream: `nws_note_control` writes every slot's controls
+`NotePlayer` (`model.player(voices)`) plays notes on that slot stream: `nws_note_control` writes every slot's controls
 of a hop from the notes, `nws_voice_mix` sums the slots into one signal; `NoteBook` is its host-side scheduling.
 """
 from __future__ import annotations
@@ -464,17 +465,13 @@ class VoiceStream(_StreamBase):
 
     def __init__(self, model, batch_size: int, phase_u: torch.Tensor | None = None, noise: torch.Tensor | None = None,
                  graph: bool = True):
-        if not model._engine.specialised():
-            raise RuntimeError("stateful streaming runs on the fused kernels: the model must have the architecture of "
-                               "gin/models/newt.gin")
         self.model = model
         self.eng = model._engine
-        _, _, dev = self.eng.weights()
-        self.dev = dev
+        self._bind()               # self.dev, self._ir_len, self._n_harmonics, self._control_size: from the path's own record
+        dev = self.dev
         self.B = int(batch_size)
         if self.B < 1:
             raise RuntimeError("VoiceStream: at least one slot")
-        self._ir_len = int(self.eng.ir().numel())
         self.tail_len = self._ir_len + 1
         if self._ir_len >= _RING // 2:
             raise RuntimeError(f"stateful streaming keeps {_RING // 2 - 1} samples of reverb history per slot; this model's impulse "
@@ -482,15 +479,14 @@ class VoiceStream(_StreamBase):
         self._plan_n = next(n for n in (32000, 64000, 128000, 256000) if n >= 2 * self.tail_len)
         self.max_frames = _SLOT_MAX_FRAMES
         self.phase_u = _req((phase_u if phase_u is not None else torch.rand_like(model.osc.rand_phase)).reshape(-1),
-                            "phase_u", _lib.N_HARMONICS)
+                            "phase_u", self._n_harmonics)
         self._noise_all = None
         if noise is not None:
             nz = _req(noise, "noise").reshape(-1)
             # the pre-roll's frames come first in the device's noise positions: its samples are never read into an output
             self._noise_all = torch.cat([torch.zeros(HOP * _PREROLL, dtype=nz.dtype, device=nz.device), nz])
         L = _lib.lib()
-        nbytes = L.nws_stream_slot_state_bytes(self.B, self.max_frames, self._ir_len)
-        self._counters_at = int(L.nws_stream_counters_offset(self.B, self.max_frames, self._ir_len))
+        nbytes = self._state_bytes(L)
         with torch.cuda.device(dev):
             self._state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             _lib.check(L.nws_stream_reset(self._state.data_ptr(), nbytes, stream_ptr(dev)), "nws_stream_reset")
@@ -509,13 +505,28 @@ class VoiceStream(_StreamBase):
         # pre-roll: every slot idle, output dropped; afterwards each hop is an ordinary (not first) one of the same shape
         with torch.cuda.device(dev):
             f0 = torch.zeros((self.B, _PREROLL), dtype=torch.float32, device=dev)
-            c = torch.zeros((self.B, 2, _PREROLL), dtype=torch.float32, device=dev)
+            c = torch.zeros((self.B, self._control_size, _PREROLL), dtype=torch.float32, device=dev)
             M = L.nws_stream_out_samples(_PREROLL, 1, 0)
             out = torch.empty((self.B, M), dtype=torch.float32, device=dev)
             nz = torch.rand(L.nws_stream_noise_draws(_PREROLL, 1, 0), device=dev) if self._noise_all is None else None
             self._step(f0, c, nz, out, None)
         self._advance(_PREROLL)
         self._last_K = None
+
+    # ---- what depends on the path (GenericVoiceStream overrides these) -------------------------------------------------------
+    def _bind(self):
+        if not self.eng.specialised():
+            raise RuntimeError("stateful streaming runs on the fused kernels: the model must have the architecture of "
+                               "gin/models/newt.gin - model.voices(B) gives the slot stream of any architecture")
+        _, _, self.dev = self.eng.weights()
+        self._ir_len = int(self.eng.ir().numel())
+        self._n_harmonics = _lib.N_HARMONICS
+        self._control_size = 2
+
+    def _state_bytes(self, L):
+        nbytes = L.nws_stream_slot_state_bytes(self.B, self.max_frames, self._ir_len)
+        self._counters_at = int(L.nws_stream_counters_offset(self.B, self.max_frames, self._ir_len))
+        return nbytes
 
     # ---- one call of the binding ------------------------------------------------------------------------------------
     def _step(self, f0_2d, control, noise_new, out, pre):
@@ -644,6 +655,54 @@ class VoiceStream(_StreamBase):
         self.finished = True
 
 
+class GenericVoiceStream(VoiceStream):
+    """VoiceStream for a model that `Engine.specialised()` turns down (what GenericNewtStream is to NewtStream): the same contract
+    and methods, one hop = one `g_stream_step_slots` of the binding (`nws_g_stream_step_slots`, csrc/generic.hip).
+    The construction-time refusals are GenericNewtStream's (control hop 128, 256 noise taps, a symmetric window) and VoiceStream's
+    (reverb history); what it watches for weight updates is the GenericEngine's descriptor record.  The hop is a chain of launches
+    in which nothing waits, so `check()` has no give-up flag to read."""
+
+    def _bind(self):
+        GenericNewtStream._bind(self)
+        self._control_size = int(self.eng.generic.model_desc().struct.control_size)
+
+    def _state_bytes(self, L):
+        r = self.eng.generic.model_desc()
+        nbytes = L.nws_g_stream_slot_state_bytes(C.byref(r.struct), self.B, self.max_frames, self._ir_len)
+        if nbytes == 0:
+            raise RuntimeError("stateful streaming: the runtime-size kernels do not serve this model's layer sizes - render it "
+                               "with the one-shot forward")
+        return nbytes
+
+    _record = GenericNewtStream._record
+    _rewalk = GenericNewtStream._rewalk
+    _reverb_plan = GenericNewtStream._reverb_plan
+    _tail_call = GenericNewtStream._tail_call
+
+    def _capture(self, K, C_in):
+        self.eng.generic.model_desc()     # a rebuild synchronises: in front of the capture, never inside it
+        return super()._capture(K, C_in)
+
+    def _step(self, f0_2d, control, noise_new, out, pre):
+        r = self.eng.generic.model_desc()
+        binding().g_stream_step_slots(r.gdesc, self._state, self.max_frames, f0_2d, control, int(self.frames_seen),
+                                      int(self._nz_prev_start), self.eng.osc_sample_rate(), self.phase_u, r.rand_phase, noise_new,
+                                      self._noise_all, self._ev, out, pre)
+
+    _steady_step = _step
+
+    def check(self) -> None:
+        """Synchronises; the runtime-size hop has no wait inside a launch and so nothing it could have given up on."""
+        torch.cuda.synchronize(self.dev)
+
+
+def voice_stream(model, batch_size: int, **kw):
+    """The slot stream of `model` whatever its architecture (`model.voices`): VoiceStream on the fused kernels when
+    `Engine.specialised()`, GenericVoiceStream on the runtime-size kernels otherwise."""
+    cls = VoiceStream if model._engine.specialised() else GenericVoiceStream
+    return cls(model, batch_size, **kw)
+
+
 # ---- note player: notes -> frame-rate controls -> slot stream -> one mixed signal (DESIGN.md 3.27) -----------------------
 NOTE_HELD = _lib.NOTE_HELD
 
@@ -767,7 +826,7 @@ class NotePlayer:
       * `note_control` (nws_note_control): every slot's F0 and normalised controls of this hop's frames, from the hop's event words,
         the note table and the per-slot frame counters - closed forms in the voice's frame index, so a note's
         controls do not depend on the hop size;
-      * the hop of the `VoiceStream` the player owns (used as it is: its captured hop once it exists, on that hop's own input
+      * the hop of the `VoiceStream` / `GenericVoiceStream` the player owns (used as it is: its captured hop once it exists, on that hop's own input
         buffers, which the control launch fills in place);
       * `voice_mix` (nws_voice_mix): out[c] = sum over the slots of gain[slot, c] * slot output.
     The three are two launches around the stream's replayed graph, not one graph of their own.  Nothing is read back; the host
@@ -783,7 +842,8 @@ class NotePlayer:
     `note_on` returns a handle, or None (and counts `dropped`) when no slot is idle: no voice is stolen.  A slot's gains are its
     latest note's, so the reverb tail of an earlier voice of the slot follows a new note's pan.  Events take effect at the next
     hop boundary.  `normalisation=(mean, std)` is the checkpoint's (checkpoint.load_normalisation); `phase_u`, `noise` and `graph`
-    go to the VoiceStream.  The packaged architecture only (VoiceStream's own refusal otherwise)."""
+    go to the stream.  Any architecture: the stream is `voice_stream(model, voices)` - VoiceStream on the packaged one,
+    GenericVoiceStream otherwise; the model's control input must have 2 channels (F0 and loudness)."""
 
     def __init__(self, model, voices: int, hop_frames: int = 1, channels: int = 1, *, attack: int = 3, decay: int = 12,
                  release: int = 25, drop: float = 0.075, silence: float | None = None, peak_lo: float | None = None,
@@ -794,6 +854,10 @@ class NotePlayer:
             raise RuntimeError("NotePlayer: pass normalisation=(mean, std), the checkpoint's data_mean / data_std "
                                "(checkpoint.load_normalisation)")
         mean, std = ([float(v) for v in list(x)[:2]] for x in normalisation)
+        n_control = int(model.embedding.gru.input_size)
+        if n_control != 2:
+            raise RuntimeError(f"NotePlayer: ControlModule.control_size = {n_control}: note_control writes two control channels, F0 and "
+                               f"loudness, so the model's control input must have 2")
         self.book = NoteBook(voices, hop_frames, release, channels)          # validates voices, hop_frames, release, channels
         self.B, self.K, self.C = self.book.B, self.book.K, self.book.C
         hi = min(1.0, mean[1] + 2.0 * std[1]) if peak_hi is None else float(peak_hi)
@@ -807,7 +871,7 @@ class NotePlayer:
                 or not p["std0"] > 0 or not p["std1"] > 0 or max(p["attack"], p["decay"], p["release"], p["vib_delay"], p["vib_ramp"]) > 2 ** 24):
             raise RuntimeError("NotePlayer: attack, decay, vib_delay >= 0, release, vib_ramp >= 1 (all at most 2^24 frames), drop >= 0, "
                                "vib_rate >= 0 and positive standard deviations")
-        self.stream = VoiceStream(model, self.B, phase_u=phase_u, noise=noise, graph=graph)
+        self.stream = voice_stream(model, self.B, phase_u=phase_u, noise=noise, graph=graph)
         self.dev = dev = self.stream.dev
         self._params = torch.tensor([float(p[k]) for k in _lib.NOTE_PARAMS], dtype=torch.float64)
         nbytes = _lib.lib().nws_note_control_state_bytes(self.B)

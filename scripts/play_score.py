@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Play a score on a trained model on MI355X: notes -> the note player (streaming.NotePlayer) -> wav.
 
-    python scripts/play_score.py score.csv out.wav --model-checkpoint ckpt [--normalisation-dir dir] [--use-fastnewt]
+    python scripts/play_score.py score.csv out.wav --model-checkpoint ckpt [--model-gin FILE] [--normalisation-dir dir] [--use-fastnewt]
                                  [--voices 16] [--hop-frames 1] [--stereo] [--tail-seconds S] [--seed N]
                                  [--attack F] [--decay F] [--release F] [--drop-db DB] [--silence X] [--peak-lo X] [--peak-hi X]
                                  [--vibrato-rate HZ] [--vibrato-depth CENTS] [--vibrato-delay F] [--vibrato-ramp F]
@@ -12,7 +12,9 @@ Onsets and ends are rounded to hop boundaries (128 --hop-frames samples; a note 
 voice taken is dropped and counted.  After the last voice has stopped the reverb rings for --tail-seconds (default: the length of
 the model's impulse response).  Times F are control frames of 128 samples; loudness values X are in the feature's units,
 (dB + 80) / 80; the defaults are NotePlayer's.  Normalisation statistics are found as scripts/timbre_transfer.py finds them; the
-wav is written as it writes its own (float32 at the model's rate).  Standard MIDI files are not read."""
+wav is written as it writes its own (float32 at the model's rate).  Standard MIDI files are not read.  --model-gin FILE: a model of
+another architecture (parsed on top of the packaged gin; the player then runs on the runtime-size slot stream), with
+the weights of --model-checkpoint, or seeded random ones when none is named."""
 import importlib
 import math
 import os
@@ -84,8 +86,8 @@ def play(player, notes, sample_rate, tail_seconds):
 @click.command()
 @click.argument("score_csv", type=click.Path(exists=True))
 @click.argument("output_wav", type=click.Path())
-@click.option("--model-gin", default=None)
-@click.option("--model-checkpoint", default=os.path.join(ROOT, "tests", "golden", "weights_vn.npz"), show_default=True)
+@click.option("--model-gin", default=None, help="the model's gin file when it is not the packaged one (parsed on top of it)")
+@click.option("--model-checkpoint", default=None, help="default: the packaged weights, or seeded random ones with --model-gin")
 @click.option("--normalisation-dir", default=None, help="directory of data_mean.npy / data_std.npy (default: the checkpoint's)")
 @click.option("--use-fastnewt", is_flag=True)
 @click.option("--voices", default=16, type=click.IntRange(1, 65535), show_default=True, help="notes that can sound at once")
@@ -108,11 +110,17 @@ def main(score_csv, output_wav, model_gin, model_checkpoint, normalisation_dir, 
          seed, attack, decay, release, drop_db, silence, peak_lo, peak_hi, vibrato_rate, vibrato_depth, vibrato_delay, vibrato_ramp):
     nws = importlib.import_module("neural-waveshaping-synthesis_amd")
     ck = importlib.import_module("neural-waveshaping-synthesis_amd.checkpoint")
+    packaged = os.path.join(ROOT, "tests", "golden", "weights_vn.npz")
+    nws.ensure_default_config()
     if model_gin:
         nws.gin.parse_config_file(model_gin)
+    if model_checkpoint is None and model_gin:
+        # another architecture without trained weights: what the player does and costs depends on the sizes, not on the values
+        torch.manual_seed(0 if seed is None else seed)
+        model = nws.NeuralWaveshaping().eval()
     else:
-        nws.ensure_default_config()
-    model = nws.NeuralWaveshaping.load_from_checkpoint(model_checkpoint).eval()
+        model = nws.NeuralWaveshaping.load_from_checkpoint(model_checkpoint or packaged).eval()
+    model_checkpoint = model_checkpoint or packaged             # where the normalisation statistics are looked for
     if use_fastnewt:
         model.newt = nws.FastNEWT(model.newt)
     model = model.cuda()

@@ -4,7 +4,10 @@ DESIGN.md 3.27) under a random note-on / note-off schedule, HIP-event timed per 
 --slots --static-io.  The bare VoiceStream.hop of the same size is timed in the same call, alternated with the player hop by hop
 under a schedule of the same statistics, so that both see the same machine.  Every hop each idle slot gets a note with
 probability --note-on and each held note is released with probability --note-off.  Host wall-clock is reported beside the
-HIP-event latency."""
+HIP-event latency.
+--model-gin FILE: a model of another architecture (parsed on top of the packaged gin; player and bare stream then run on the
+runtime-size slot stream), with the weights of --checkpoint, or seeded random ones when none is named.
+--runtime-size: the packaged model on the runtime-size slot stream, to compare the two paths on one set of sizes."""
 import gc
 import importlib
 import json
@@ -31,7 +34,9 @@ def timed(fn):
 
 
 @click.command()
-@click.option("--checkpoint", default=os.path.join(ROOT, "tests", "golden", "weights_vn.npz"), show_default=True)
+@click.option("--checkpoint", default=None, help="default: the packaged weights, or seeded random ones with --model-gin")
+@click.option("--model-gin", default=None, help="the model's gin file when it is not the packaged one")
+@click.option("--runtime-size", is_flag=True, default=False, help="force the runtime-size slot stream (GenericVoiceStream)")
 @click.option("--voices", default="4,16", show_default=True, help="comma-separated voice counts")
 @click.option("--hop-frames", default=2, show_default=True)
 @click.option("--channels", default=1, type=click.IntRange(1, 2), show_default=True)
@@ -43,10 +48,19 @@ def timed(fn):
 @click.option("--seed", default=0)
 @click.option("--gc/--no-gc", "keep_gc", default=True, help="--no-gc: Python's cyclic garbage collector off during the timed hops")
 @click.option("--json-out", default=None)
-def main(checkpoint, voices, hop_frames, channels, num_hops, use_fast_newt, note_on, note_off, release, seed, keep_gc, json_out):
+def main(checkpoint, model_gin, runtime_size, voices, hop_frames, channels, num_hops, use_fast_newt, note_on, note_off, release, seed,
+         keep_gc, json_out):
     nws = importlib.import_module("neural-waveshaping-synthesis_amd")
+    streaming = importlib.import_module("neural-waveshaping-synthesis_amd.streaming")
     nws.ensure_default_config()
-    model = nws.NeuralWaveshaping.load_from_checkpoint(checkpoint).cuda().eval()
+    if model_gin:
+        nws.gin.parse_config_file(model_gin)
+    if checkpoint is None and model_gin:
+        torch.manual_seed(seed)
+        model = nws.NeuralWaveshaping().cuda().eval()
+    else:
+        model = nws.NeuralWaveshaping.load_from_checkpoint(checkpoint or os.path.join(ROOT, "tests", "golden", "weights_vn.npz")).cuda().eval()
+    checkpoint = checkpoint or os.path.join(ROOT, "tests", "golden", "weights_vn.npz")      # the normalisation statistics
     if use_fast_newt:
         model.newt = nws.FastNEWT(model.newt)
     K = hop_frames
@@ -57,7 +71,12 @@ def main(checkpoint, voices, hop_frames, channels, num_hops, use_fast_newt, note
         rng = np.random.default_rng(seed)
         with torch.no_grad():
             player = model.player(B, hop_frames=K, channels=channels, normalisation=norm, release=release)
-            bare = model.stream(B, slots=True)
+            if runtime_size:
+                # the player's stream is what model.voices picks: swap in the runtime-size class before the first hop
+                player.stream = streaming.GenericVoiceStream(model, B)
+                bare = streaming.GenericVoiceStream(model, B)
+            else:
+                bare = model.voices(B)
             held = {}
 
             def player_events():
@@ -103,7 +122,7 @@ def main(checkpoint, voices, hop_frames, channels, num_hops, use_fast_newt, note
             dropped = player.dropped
             player.close()
             bare.close()
-        res = {"voices": B, "hop_samples": K * 128, "channels": channels, "hops": num_hops, "python_gc": bool(keep_gc), "dropped": dropped}
+        res = {"stream": type(bare).__name__, "voices": B, "hop_samples": K * 128, "channels": channels, "hops": num_hops, "python_gc": bool(keep_gc), "dropped": dropped}
         for name in ("player", "bare"):
             res.update({f"{name}_p50_us": float(np.percentile(lat[name], 50)), f"{name}_p99_us": float(np.percentile(lat[name], 99)),
                         f"{name}_max_us": float(np.max(lat[name])), f"{name}_wall_p50_us": float(np.percentile(wall[name], 50)),
@@ -111,7 +130,7 @@ def main(checkpoint, voices, hop_frames, channels, num_hops, use_fast_newt, note
         res["player_p99_over_period"] = res["player_p99_us"] / period
         print(f"NotePlayer.hop, {B} voices, hop {K * 128} samples ({period / 1e3:.1f} ms): p50 {res['player_p50_us']:.1f} us  p99 "
               f"{res['player_p99_us']:.1f} us  (host wall p50 {res['player_wall_p50_us']:.1f} / p99 {res['player_wall_p99_us']:.1f} us) = "
-              f"{100 * res['player_p99_over_period']:.1f} % of the hop at p99;  bare VoiceStream.hop: p50 {res['bare_p50_us']:.1f} us  p99 "
+              f"{100 * res['player_p99_over_period']:.1f} % of the hop at p99;  bare {type(bare).__name__}.hop: p50 {res['bare_p50_us']:.1f} us  p99 "
               f"{res['bare_p99_us']:.1f} us  (host wall p50 {res['bare_wall_p50_us']:.1f} / p99 {res['bare_wall_p99_us']:.1f} us)")
         if json_out:
             with open(json_out, "a") as f:

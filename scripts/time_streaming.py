@@ -4,11 +4,13 @@
 every push carries GRU / phase / noise / reverb state and applies the 2 s reverb as a linear convolution of the stream
 (csrc/stream.hip); steady-state hops replay a hipGraph unless --no-graph.  Host wall-clock per push is reported beside the
 HIP-event latency (a push returns a fresh tensor: input copy + graph launch + output copy).
---slots: the slot mode (model.stream(B, slots=True)) under a random note-on / note-off schedule (every hop each idle slot starts
+--slots: the slot mode (model.voices(B)) under a random note-on / note-off schedule (every hop each idle slot starts
 with probability --note-on, each active one stops with probability --note-off); same timing, events written every hop.
---model-gin FILE: a model of another architecture (its stream runs on the runtime-size kernels), with the weights
-of --checkpoint, or seeded random ones when none is named: the hop's latency depends on the sizes, not on the values.
---runtime-size: the packaged model on the runtime-size stream, to compare the two paths on one set of sizes.
+--model-gin FILE: a model of another architecture (its stream runs on the runtime-size kernels, DESIGN.md 3.21, its slot stream
+too, 3.28), with the weights of --checkpoint, or seeded random ones when none is named: the hop's latency depends on the sizes,
+not on the values.
+--runtime-size: the packaged model on the runtime-size stream (with --slots: on the runtime-size slot stream), to compare the two
+paths on one set of sizes.
 --output-rate R: after every hop its samples go through a StreamResampler(model rate -> R) (csrc/resample_stream.hip, DESIGN.md
 3.23), with --static-io through its captured hop: the hop's latency with and without the converter, the converter's own time
 and the output sample count are reported beside the figures above.  Not with --slots."""
@@ -73,10 +75,11 @@ def main(checkpoint, model_gin, runtime_size, batch_size, hop_frames, num_hops, 
         return {"start": start, "stop": stop}
 
     with torch.no_grad():
-        if runtime_size and not slots:
-            s = importlib.import_module("neural-waveshaping-synthesis_amd.streaming").GenericNewtStream(model, batch_size, graph=graph)
+        st_mod = importlib.import_module("neural-waveshaping-synthesis_amd.streaming")
+        if runtime_size:
+            s = (st_mod.GenericVoiceStream if slots else st_mod.GenericNewtStream)(model, batch_size, graph=graph)
         else:
-            s = model.stream(batch_size, graph=graph, slots=True) if slots else model.stream(batch_size, graph=graph)
+            s = model.voices(batch_size, graph=graph) if slots else model.stream(batch_size, graph=graph)
         conv = None
         if output_rate is not None:
             conv = importlib.import_module("neural-waveshaping-synthesis_amd.streaming").StreamResampler(

@@ -1,0 +1,118 @@
+"""No GPU: the host side of slot mode on the runtime-size stream - the sizing and every refusal of
+nws_g_stream_step_slots (decided on the host before the first launch: dummy pointers are never followed, a host buffer handed in
+as state keeps its pattern), the error a CPU-resident model gets from `model.voices`, the stream class's public surface and the
+player's refusal of a control input that is not F0 and loudness."""
+import ctypes as C
+import importlib
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+from g_stream_models import BANK_GIN, build, build_from_gin
+from test_cpu_g_streaming import BAD_ARG, UNSUPPORTED, WORKSPACE, descriptor
+
+PKG = "neural-waveshaping-synthesis_amd"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _lib():
+    return importlib.import_module(PKG + "._lib")
+
+
+def test_entry_points_declared_and_bound():
+    lib = _lib()
+    hdr = open(os.path.join(ROOT, "include", "nws_hip.h")).read()
+    for name in ("nws_g_stream_slot_state_bytes", "nws_g_stream_step_slots"):
+        assert re.search(rf"\b{name}\(", hdr) and name in lib.EXPORTED_SYMBOLS
+        assert getattr(lib.lib(), name) is not None
+    assert lib.ABI_VERSION == 6 and re.search(r"#define NWS_ABI_VERSION 6\b", hdr)
+    cops = importlib.import_module(PKG + "._cops")
+    assert "events" in inspect.signature(cops.CtypesOps.g_stream_step_slots).parameters
+
+
+def test_slot_state_bytes_hold_a_plain_stream_and_are_zero_when_refused():
+    L = _lib().lib()
+    g = descriptor()
+    slot = lambda m, B, K, ir=None: L.nws_g_stream_slot_state_bytes(C.byref(m), B, K, m.ir_len if ir is None else ir)
+    plain = lambda m, B, K: L.nws_g_stream_state_bytes(C.byref(m), B, K, m.ir_len, None)
+    for m in (g, descriptor(out_channels=2), descriptor(gru_hidden=33, embedding=17, hgen_hidden=20, n_harmonics=7, ir_len=999)):
+        for B, K in ((1, 1), (1, 2), (3, 2), (17, 8), (16, 15), (3, 16)):
+            assert slot(m, B, K) >= plain(m, B, K) > 0, (B, K)
+            assert slot(m, B, K) <= plain(m, B, K) + 2 * 256 * ((16 * B + 255) // 256 + 1)        # two per-row arrays, nothing else
+        assert slot(m, 2, 16) > slot(m, 2, 8) > slot(m, 1, 8) > 4 * 65536
+    for bad in (dict(hop=64), dict(fir_len=128), dict(ir_len=32768), dict(ir_len=44099), dict(gru_hidden=0), dict(n_shapers=0),
+                dict(embedding=700)):
+        assert slot(descriptor(**bad), 1, 2) == 0, bad
+    assert slot(g, 0, 2) == 0 and slot(g, 1, 0) == 0 and slot(g, 70000, 2) == 0 and slot(g, 1, 2, ir=1000) == 0
+    assert slot(g, 1, 17) == 0 and slot(g, 1, 249) == 0                                          # max_frames > 16
+    assert L.nws_g_stream_slot_state_bytes(None, 1, 2, 31999) == 0
+    broken = descriptor()
+    broken.mixer_w = None
+    assert slot(broken, 1, 2) == 0
+
+
+def test_every_refusal_returns_its_code_and_leaves_the_buffers_alone():
+    """raw ctypes; state, out and events are host buffers filled with a pattern - a refused call may not follow a pointer"""
+    L = _lib().lib()
+    g = descriptor()
+    B, maxf, K = 2, 4, 2
+    nbytes = L.nws_g_stream_slot_state_bytes(C.byref(g), B, maxf, g.ir_len)
+    assert nbytes > 0
+    state = np.full(nbytes, 0x5A, dtype=np.uint8)
+    out = np.full((B, 128 * K), 7.0, dtype=np.float32)
+    ev = np.full(B, 8, dtype=np.int32)
+    p = 0x1000
+    sp, op, ep = state.ctypes.data, out.ctypes.data, ev.ctypes.data
+
+    def call(m=g, st=sp, nb=nbytes, f0=p, control=p, Cn=2, k=K, seen=2, sr=16000.0, pu=p, rp=p, nz_new=None, nz_all=p, events=ep, o=op,
+             b=B, mf=maxf):
+        return L.nws_g_stream_step_slots(C.byref(m) if m is not None else None, st, nb, b, mf, f0, control, Cn, k, seen, 0, sr, pu, rp,
+                                         nz_new, nz_all, 1024, events, o, None, None)
+
+    assert call(events=None) == BAD_ARG
+    assert call(m=None) == BAD_ARG
+    for kw in (dict(st=None), dict(f0=None), dict(control=None), dict(pu=None), dict(rp=None), dict(o=None), dict(k=0), dict(k=maxf + 1),
+               dict(b=0), dict(Cn=1), dict(nz_new=p), dict(nz_all=None), dict(sr=0.0), dict(mf=0)):
+        assert call(**kw) == BAD_ARG, kw
+    assert call(k=17, mf=32) == UNSUPPORTED and call(k=17) == UNSUPPORTED               # K > 16
+    assert call(mf=17) == UNSUPPORTED                                                    # max_frames > 16
+    for bad in (dict(hop=64), dict(fir_len=128), dict(ir_len=40000)):
+        assert call(m=descriptor(**bad)) == UNSUPPORTED, bad
+    assert call(b=70000) == UNSUPPORTED
+    assert call(nb=nbytes - 4) == WORKSPACE
+    # a blob sized for the plain stream is shorter than the slot stream's
+    assert call(nb=L.nws_g_stream_state_bytes(C.byref(g), B, maxf, g.ir_len, None)) == WORKSPACE
+    # (the pre-roll is the call with frames_seen == 0: `first` is derived, so the two cannot disagree)
+    assert bool((state == 0x5A).all()) and bool((out == 7.0).all()) and bool((ev == 8).all())
+
+
+def test_cpu_resident_model_gets_the_no_cpu_fallback_error():
+    model, _ = build("bank", False, device="cpu")
+    assert not model._engine.specialised()
+    with pytest.raises(RuntimeError, match="no CPU fallback") as e:
+        model.voices(2)
+    assert "fused kernels" not in str(e.value)
+    with pytest.raises(RuntimeError, match=r"fused kernels.*model\.voices\(B\)"):
+        model.stream(2, slots=True)                            # the packaged class keeps its refusal and points at the new entry
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        model.player(2, normalisation=([0.0, 0.5], [1.0, 0.2]))
+
+
+def test_public_surface_equals_the_packaged_slot_stream():
+    st = importlib.import_module(PKG + ".streaming")
+    assert issubclass(st.GenericVoiceStream, st.VoiceStream)
+    for name in ("__init__", "push", "static_io", "hop", "refresh", "reverb_tail", "slot_states", "idle_slots", "check", "close"):
+        assert inspect.signature(getattr(st.GenericVoiceStream, name)) == inspect.signature(getattr(st.VoiceStream, name)), name
+    # only what depends on the path is overridden
+    own = {k for k in vars(st.GenericVoiceStream) if not k.startswith("__")}
+    assert own == {"_bind", "_state_bytes", "_record", "_rewalk", "_reverb_plan", "_tail_call", "_capture", "_step", "_steady_step", "check"}
+
+
+def test_note_player_refuses_a_control_input_that_is_not_two_channels():
+    model, _ = build_from_gin(BANK_GIN + "ControlModule.control_size = 3\n", device="cpu")
+    assert int(model.embedding.gru.input_size) == 3
+    with pytest.raises(RuntimeError, match=r"control_size = 3"):
+        model.player(2, normalisation=([0.0, 0.5], [1.0, 0.2]))
