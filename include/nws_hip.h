@@ -262,6 +262,14 @@ int nws_frame_mlps_spec_serves(const NwsWeights* w, int B, int T);
 /* nws_frame_mlps with the folded weights: film_out (B,T,256) as before, spec_out (B,T,NWS_SPEC_ROW) rows G[0 .. 128] (the three
  * floats behind them are not written).  NWS_ERR_UNSUPPORTED where nws_frame_mlps_spec_serves is 0. */
 int nws_frame_mlps_spec(const NwsWeights* w, const float* gru_out, int B, int T, float* film_out, float* spec_out, void* stream);
+/* The same launch for a caller that runs it apart from the recurrence that produced gru_out (the audio half of a pipeline), so
+ * that the per-utterance recurrence of a neighbouring batch of B utterances is expected to hold B compute units meanwhile
+ * (beside_recurrence != 0).  Where the 2 ceil(B T / 256) workgroups of the 8-wave kernel no longer fit the remaining compute
+ * units in one round and the 2 ceil(B T / 384) workgroups of its 12-wave form do, that form runs: the same bits.
+ * nws_frame_mlps_spec_waves answers which form it would be (8 or 12; 0 where nws_frame_mlps_spec_serves is 0) and launches nothing. */
+int nws_frame_mlps_spec_beside(const NwsWeights* w, const float* gru_out, int B, int T, float* film_out, float* spec_out,
+                               int beside_recurrence, void* stream);
+int nws_frame_mlps_spec_waves(const NwsWeights* w, int B, int T, int beside_recurrence);
 
 /*
  * Time-varying FIR noise (models/modules/generators.py:30-35): rectangular-window STFT of the

@@ -18,6 +18,18 @@ int nws_debug_frame_mlps_kernel(int mode);
  * filter spectra over (nws_frame_mlps_spec_serves then answers 0); any other value restores the default. */
 int nws_debug_forward_spec(int on);
 
+/* Tests / A-B measurements: the form of the folded frame-MLP launch (nws_frame_mlps_spec, nws_frame_mlps_spec_beside and the
+ * forwards) - 0 by the rule of nws_frame_mlps_spec_beside, 8 or 12 that many waves per workgroup wherever it runs.  Any other
+ * value: NWS_ERR_BAD_ARG.  nws_debug_frame_mlps_last_waves: the form of the most recent folded launch of this process (0: none yet). */
+int nws_debug_frame_mlps_waves(int waves);
+int nws_debug_frame_mlps_last_waves(void);
+
+/* Tests: the folded wave-resident kernel in the form of `waves` (8 or 12) waves per workgroup on F flattened frames of any
+ * count (gru_out (F,128) -> film_out (F,256), spec_out (F,NWS_SPEC_ROW)), whatever the size rules of nws_frame_mlps_spec say.
+ * NWS_ERR_UNSUPPORTED without the folded tables (w->mlp_spec) or beyond the kernel's 32-bit byte offsets. */
+int nws_debug_frame_mlps_spec_waves(const NwsWeights* w, const float* gru_out, int F, float* film_out, float* spec_out, int waves,
+                                    void* stream);
+
 /* Diagnostics only (tools/cu_pressure.py): a resident load of `groups` 256-thread workgroups that keep their CUs' vector pipes
  * busy for `spin_us` microseconds of the wall clock - what a collective's ring kernels take from the oscillator kernel. */
 int nws_debug_queue_busy(int groups, int spin_us, float* sink /* device float[256] */, void* stream);

@@ -166,6 +166,11 @@ _PROTOTYPES = {
     "nws_mlp_spec_frags": (C.c_int, [_fp, _fp, _fp]),
     "nws_frame_mlps_spec_serves": (C.c_int, [C.POINTER(NwsWeights), C.c_int, C.c_int]),
     "nws_frame_mlps_spec": (C.c_int, [C.POINTER(NwsWeights), _fp, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "nws_frame_mlps_spec_beside": (C.c_int, [C.POINTER(NwsWeights), _fp, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp]),
+    "nws_frame_mlps_spec_waves": (C.c_int, [C.POINTER(NwsWeights), C.c_int, C.c_int, C.c_int]),
+    "nws_debug_frame_mlps_waves": (C.c_int, [C.c_int]),
+    "nws_debug_frame_mlps_last_waves": (C.c_int, []),
+    "nws_debug_frame_mlps_spec_waves": (C.c_int, [C.POINTER(NwsWeights), _fp, C.c_int, _fp, _fp, C.c_int, _fp]),
     "nws_fir_noise_spec": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp]),
     "nws_fir_design_matrix": (C.c_int, [_fp, _fp, _fp]),
     "nws_fir_noise": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp]),

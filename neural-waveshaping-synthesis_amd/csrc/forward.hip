@@ -121,7 +121,11 @@ int control_half(const NwsWeights* w, const float* f0, const float* control, int
 
 int audio_half(const NwsWeights* w, const NwsForwardAux* aux, const float* f0, int B, int T, float sample_rate,
                const float* phase_u, const float* rand_phase, const float* noise, float* out, const Arena& a, void* stream,
-               void* wait_before_exciter = nullptr, void* record_after_exciter = nullptr, bool with_reverb = true) {
+               void* wait_before_exciter = nullptr, void* record_after_exciter = nullptr, bool with_reverb = true,
+               bool apart_from_control = true) {
+  // apart_from_control: the caller launches this half on its own (nws_forward_audio*), i.e. it pipelines batches and the
+  // recurrence of a neighbouring batch is expected to be resident beside the frame MLPs, which then take the form that fits the
+  // compute units it leaves (nws_frame_mlps_spec_beside); nws_forward has just run its recurrence in front on the same stream
   hipStream_t st = (hipStream_t)stream;
   int rc = NWS_OK;
   const size_t N = (size_t)T * NWS_HOP;
@@ -129,7 +133,7 @@ int audio_half(const NwsWeights* w, const NwsForwardAux* aux, const float* f0, i
   // two hand over filter spectra instead of taps: the same two stages, one decision for every caller
   const bool spec = nws_frame_mlps_spec_serves(w, B, T) != 0;
   if (spec)
-    NWS_STAGE(2, nws_frame_mlps_spec(w, a.gru_out, B, T, a.film, a.fir, stream));
+    NWS_STAGE(2, nws_frame_mlps_spec_beside(w, a.gru_out, B, T, a.film, a.fir, apart_from_control ? 1 : 0, stream));
   else
     NWS_STAGE(2, nws_frame_mlps(w, a.gru_out, aux->fir_design, B, T, nullptr, a.film, nullptr, a.fir, stream));
   // the noise branch first (its output starts the NEWT sum), then the oscillator kernel adds its own sum on top and leaves
@@ -192,7 +196,7 @@ int nws_forward(const NwsWeights* w, const NwsForwardAux* aux, const float* f0, 
   // one stream, one call: the per-utterance recurrence (64 CUs for 64 utterances) has the shorter latency
   const int rc = control_half(w, f0, control, B, C, T, 0, a, stream);
   if (rc != NWS_OK) return rc;
-  return audio_half(w, aux, f0, B, T, sample_rate, phase_u, rand_phase, noise, out, a, stream);
+  return audio_half(w, aux, f0, B, T, sample_rate, phase_u, rand_phase, noise, out, a, stream, nullptr, nullptr, true, false);
 }
 
 int nws_forward_control(const NwsWeights* w, const float* f0, const float* control, int B, int C, int T, int batched_gru,

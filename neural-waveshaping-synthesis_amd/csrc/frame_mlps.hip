@@ -869,10 +869,24 @@ __device__ __forceinline__ const char* wr_spec_chunk(const char* frags, int path
   return frags + kT2Base + (size_t)kT2Kb[0][5] * 1024;
 }
 
-// this wave's share (1/8) of a chunk: global -> LDS by the DMA path, 1 KB per instruction
+// this wave's share (1/NW) of a chunk: global -> LDS by the DMA path, 1 KB per instruction
+// 12 waves: piece 12 j + wave for j = 0 .. 5, i.e. 64 pieces as 6 per wave for waves 0..3 and 5 for the others, 72 as 6 each;
+// kWrDmaMin12 requests per wave are unconditional (what the first barrier may leave in flight)
+constexpr int kWrDmaMin12 = 5;
+template <int NW>
 __device__ __forceinline__ void wr_dma(const char* __restrict__ src, char* dst, int kb, int wave, int lane) {
   typedef __attribute__((address_space(1))) const void* gptr_t;
   typedef __attribute__((address_space(3))) void* lptr_t;
+  static_assert(NW == 8 || NW == 12, "waves per workgroup");
+  if constexpr (NW == 12) {
+    const char* s = src + wave * 1024 + lane * 16;
+    char* d = dst + wave * 1024;
+#pragma unroll
+    for (int j = 0; j < kWrDmaMin12; ++j) __builtin_amdgcn_global_load_lds((gptr_t)(s + j * 12288), (lptr_t)(d + j * 12288), 16, 0, 0);
+    if (kWrDmaMin12 * 12 + wave < kb)
+      __builtin_amdgcn_global_load_lds((gptr_t)(s + kWrDmaMin12 * 12288), (lptr_t)(d + kWrDmaMin12 * 12288), 16, 0, 0);
+    return;
+  }
   const int per = kb * 128;   // bytes per wave: 8192 or 9216
   const char* s = src + wave * per + lane * 16;
   char* d = dst + wave * per;
@@ -887,24 +901,26 @@ __device__ __forceinline__ void wr_dma(const char* __restrict__ src, char* dst, 
 // independent accumulator chains) and the fragments of step s + 2 are requested before the three MFMAs of step s are issued:
 // left to itself hipcc requests each pair right in front of its first use and the matrix pipe idles for an LDS latency per
 // three MFMAs (measured: 34 us of a 49 us kernel in the MFMA phases against 16 us of MFMA time).
-template <int KS, int NMT, bool TRANSPOSED, bool ZERO = false>
+// PF: the prefetch distance in steps (PF + 1 fragment buffers).  Two with two waves per SIMD; the 12-wave form runs one - a
+// third wave on the SIMD hides what the third buffer hid, and the eight registers are what lets it live in 168.
+template <int KS, int NMT, bool TRANSPOSED, bool ZERO = false, int PF = 2>
 __device__ __forceinline__ void wr_layer_mma(const char* slot, int mt0, const WrAct& x, f32x16* acc, int lane) {
   const char* a = slot + (size_t)mt0 * KS * 2048 + lane * 16;
   constexpr int S = KS * NMT;
-  f16x8 wh[3], wl[3];
+  f16x8 wh[PF + 1], wl[PF + 1];
   auto ld = [&](int s2, int b) {
     const int mt = s2 % NMT, ks = s2 / NMT;
     wh[b] = *reinterpret_cast<const f16x8*>(a + (mt * KS + ks) * 2048);
     wl[b] = *reinterpret_cast<const f16x8*>(a + (mt * KS + ks) * 2048 + 1024);
   };
   ld(0, 0);
-  if (S > 1) ld(1, 1);
+  if (S > 1 && PF > 1) ld(1, 1);
   __builtin_amdgcn_sched_barrier(0x6);
   __builtin_amdgcn_s_setprio(2);
 #pragma unroll
   for (int s2 = 0; s2 < S; ++s2) {
-    const int mt = s2 % NMT, ks = s2 / NMT, b = s2 % 3;
-    if (s2 + 2 < S) ld(s2 + 2, (s2 + 2) % 3);
+    const int mt = s2 % NMT, ks = s2 / NMT, b = s2 % (PF + 1);
+    if (s2 + PF < S) ld(s2 + PF, (s2 + PF) % (PF + 1));
     __builtin_amdgcn_sched_barrier(0x6);
     if (!TRANSPOSED) {
       acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[b], x.lo[ks], (ZERO && ks == 0) ? f32x16{} : acc[mt], 0, 0, 0);
@@ -949,6 +965,7 @@ __device__ __forceinline__ void wr_pack(const f32x16 (&v)[4], WrAct& out) {
 }
 
 // LeakyReLU(LayerNorm(v)) over the 128 channels of the lane's frame (v includes the bias), in place
+template <bool SEQ = false>
 __device__ __forceinline__ void wr_layer_norm(f32x16 (&v)[4], const float* g, const float* bt, int half) {
   float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
 #pragma unroll
@@ -976,8 +993,19 @@ __device__ __forceinline__ void wr_layer_norm(f32x16 (&v)[4], const float* g, co
   float q = (q0 + q1) + (q2 + q3);
   q += nws_swap_halves(q);
   const float rstd = 1.0f / sqrtf(q * (1.0f / NWS_HIDDEN) + kLnEps);
+  if (SEQ) {
+    // (the lane's offset made opaque: one address register and sixteen immediates - hipcc otherwise forms the sixteen addresses
+    // with v_or and keeps them in registers from layer to layer)
+    int ho = 4 * half;
+    asm volatile("" : "+v"(ho));
+    g += ho;
+    bt += ho;
+    half = 0;
+  }
 #pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
+  for (int mt = 0; mt < 4; ++mt) {
+    // (SEQ: the gains and offsets of one M-tile at a time - left alone hipcc requests all 128 values ahead of the statistics)
+    if (SEQ) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int qd = 0; qd < 4; ++qd) {
       const int c = 32 * mt + 8 * qd + 4 * half;
@@ -989,6 +1017,11 @@ __device__ __forceinline__ void wr_layer_norm(f32x16 (&v)[4], const float* g, co
         v[mt][4 * qd + i] = fmaxf(y, 0.01f * y);
       }
     }
+    // (an empty statement that "writes" the tile: without it the arithmetic above, which no barrier orders, is placed behind
+    // all four groups of requests when the block is first linearised)
+    if (SEQ) asm volatile("" : "+v"(v[mt]));
+  }
+  if (SEQ) __builtin_amdgcn_sched_barrier(0);
 }
 
 // a transposed accumulator tile (lane = channel, register r = frame f0 + nws_frag_row(r, half)) -> frame-major rows of LD floats: two
@@ -1007,12 +1040,19 @@ __device__ __forceinline__ void wr_store_rows(__amdgpu_buffer_rsrc_t out, const 
 // path (layer 0, its weight chunk and its barrier are gone: newt.mlp runs five chunks and barriers, h_generator four)
 // and h_generator's output layer is W_G = S W_out, so `fir_out` receives rows of NWS_SPEC_ROW floats, the real filter spectrum
 // G[0 .. 128] of the frame as the noise kernel multiplies it, instead of half-taps: the FIR-design contraction is gone as well.
-template <bool TAPS, bool SPEC = false>
-__global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, const float* __restrict__ gru_out, int F, int T,
-                                                                 float* __restrict__ emb_out, float* __restrict__ film_out,
-                                                                 float* __restrict__ H_out, float* __restrict__ fir_out,
-                                                                 const int xcd_blocks = 0) {
+// NW waves per workgroup, 32 NW frames per block.  8: two waves per SIMD, one round of 2 x 125 workgroups on 256 free CUs at
+// B x T = 32000.  12 (folded form only): three waves per SIMD in <= 168 registers, 2 x 84 workgroups - one round on the 192 CUs a
+// neighbouring batch's resident recurrence (64 workgroups of 256 registers per wave, which shut a CU to this kernel) leaves
+// free.  The same slots, chunk order and barriers; a wave's chain over its 32 frames is the same instructions on the same
+// values, so both forms write the same bits.
+template <bool TAPS, bool SPEC = false, int NW = 8>
+__global__ __launch_bounds__(64 * NW, NW / 4) void frame_mlps_wr_kernel(NwsWeights w, const float* __restrict__ gru_out, int F, int T,
+                                                                          float* __restrict__ emb_out, float* __restrict__ film_out,
+                                                                          float* __restrict__ H_out, float* __restrict__ fir_out,
+                                                                          const int xcd_blocks = 0) {
   static_assert(!(TAPS && SPEC), "the folded form has neither an embedding nor H to store");
+  static_assert(NW == 8 || (NW == 12 && SPEC), "12 waves: the folded form only");
+  constexpr int PF = NW == 8 ? 2 : 1;   // weight prefetch distance (wr_layer_mma)
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   WrLds& L = *reinterpret_cast<WrLds*>(smem_raw);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1025,7 +1065,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
   const int path = xcd_blocks > 0 ? (int)((blockIdx.x >> 3) & 1) : (int)blockIdx.y;   // 0: proj + newt.mlp -> film; 1: proj + h_generator -> H -> fir
   if (xcd_blocks > 0 && fb >= xcd_blocks) return;
   const int half = lane >> 5, col = lane & 31;
-  const int f0 = fb * kWrFrames + 32 * wave;         // first frame of this wave
+  const int f0 = fb * (32 * NW) + 32 * wave;         // first frame of this wave
   const int frame = f0 + col;                        // this lane's frame (standard orientation)
   const char* const frags = static_cast<const char*>(w.mlp_frags);
   const char* T2 = frags + kT2Base;
@@ -1038,10 +1078,11 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
   // request in front of the first use of a loaded register while an LDS-bound load is in flight, so chunk 1 is requested only
   // after that point, LAST: the first barrier waits for everything but the eight most recent requests (memory reads return in
   // order) and the first layer runs while chunk 1 is still arriving ----
-  wr_dma(SPEC ? wr_spec_chunk(frags, path, 0) : T2 + (size_t)kT2Kb[0][0] * 1024, S0, 64, wave, lane);
+  wr_dma<NW>(SPEC ? wr_spec_chunk(frags, path, 0) : T2 + (size_t)kT2Kb[0][0] * 1024, S0, 64, wave, lane);
   const int grp = wave >> 1, pc = tid & 127;
-  float pv[4];
-  {
+  const bool fetches = NW == 8 || grp < 4;   // 12 waves: the twelve vectors are fetched by waves 0..7 as in the 8-wave form
+  float pv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (fetches) {
     // vector n of the parameter block goes to par[128 n ..]; quarter `grp` of the workgroup fetches vectors grp, grp + 4, ...
     // (compile-time struct indices selected by scalar compares: a run-time index into the by-value struct would be a private copy)
     auto sel4 = [&](const float* a, const float* b, const float* c, const float* d) { return grp == 0 ? a : grp == 1 ? b : grp == 2 ? c : d; };
@@ -1069,9 +1110,11 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
 #pragma unroll
     for (int k = 0; k < 16; ++k) in[k] = src[k];
   }
-  L.par[128 * grp + pc] = pv[0];
-  L.par[128 * (4 + grp) + pc] = pv[1];
-  L.par[128 * (8 + grp) + pc] = pv[2];
+  if (fetches) {
+    L.par[128 * grp + pc] = pv[0];
+    L.par[128 * (4 + grp) + pc] = pv[1];
+    L.par[128 * (8 + grp) + pc] = pv[2];
+  }
   if (grp == 0) L.par[pc] = pv[3];
   if (tid == 0) L.par[1536] = b128;
   // (the conversion of the GRU row stays in front of the request for chunk 1: a first use of a loaded register behind it
@@ -1083,20 +1126,22 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
     wr_pack8(y, X.hi[ks], X.lo[ks]);
   }
   __builtin_amdgcn_sched_barrier(0);
-  wr_dma(SPEC ? wr_spec_chunk(frags, path, 1) : T2 + (size_t)(path ? kT2Kb[1][1] : kT2Kb[0][1]) * 1024, S1, 64, wave, lane);   // the wave's 8 most recent requests
+  wr_dma<NW>(SPEC ? wr_spec_chunk(frags, path, 1) : T2 + (size_t)(path ? kT2Kb[1][1] : kT2Kb[0][1]) * 1024, S1, 64, wave, lane);   // the wave's 8 most recent requests
   __builtin_amdgcn_sched_barrier(0);
   // barrier k closes interval k: every wave has finished reading slot (k - 1) & 1, and its share of chunk k (requested one
   // interval earlier) has landed; then chunk k + 1 goes into the slot just released
   auto sync = [&](int k) {
-    if (k == 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // everything but chunk 1
+    if (k == 0 && NW == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // everything but chunk 1
+    else if (k == 0 && wave < 64 - 12 * kWrDmaMin12) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // 12 waves: six pieces of it here,
+    else if (k == 0) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");                                    // five there (wr_dma)
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // (not __syncthreads(): hipcc puts a vmcnt(0) in front of it while LDS-bound loads are in flight, which would wait for
     // chunk 1 as well; the LDS writes of the parameters are drained by the lgkmcnt(0))
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     if (SPEC) {
-      if (k >= 1 && k + 1 <= (path ? 3 : 4)) wr_dma(wr_spec_chunk(frags, path, k + 1), ((k + 1) & 1) ? S1 : S0, 64, wave, lane);
+      if (k >= 1 && k + 1 <= (path ? 3 : 4)) wr_dma<NW>(wr_spec_chunk(frags, path, k + 1), ((k + 1) & 1) ? S1 : S0, 64, wave, lane);
     } else if (k >= 1 && k <= 4) {
-      wr_dma(T2 + (size_t)(path ? kT2Kb[1][k + 1] : kT2Kb[0][k + 1]) * 1024, ((k + 1) & 1) ? S1 : S0, (path == 1 && k == 4) ? 72 : 64, wave, lane);
+      wr_dma<NW>(T2 + (size_t)(path ? kT2Kb[1][k + 1] : kT2Kb[0][k + 1]) * 1024, ((k + 1) & 1) ? S1 : S0, (path == 1 && k == 4) ? 72 : 64, wave, lane);
     }
   };
   sync(0);
@@ -1105,7 +1150,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
   if constexpr (!SPEC) {
     // ---- layer 0: emb = proj(gru_out) ----
     wr_lane_vec(L.par, half, v);
-    wr_layer_mma<8, 4, false, false>(S0, 0, X, v, lane);
+    wr_layer_mma<8, 4, false, false, PF>(S0, 0, X, v, lane);
     if (TAPS && path == 0 && emb_out != nullptr && frame < F) {
       const int b = frame / T, t = frame - b * T;
 #pragma unroll
@@ -1124,8 +1169,8 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
     const float* par = L.par + 128 + 384 * l;
     const char* slot = ((l & 1) != 0) != SPEC ? S0 : S1;   // chunks 1, 2, 3 -> slots 1, 0, 1; SPEC: chunks 0, 1, 2 -> slots 0, 1, 0
     wr_lane_vec(par, half, v);
-    wr_layer_mma<8, 4, false, false>(slot, 0, X, v, lane);
-    wr_layer_norm(v, par + 128, par + 256, half);
+    wr_layer_mma<8, 4, false, false, PF>(slot, 0, X, v, lane);
+    wr_layer_norm<NW == 12>(v, par + 128, par + 256, half);
     if (l == 2 && path == 1) {
       // band 128 of H: fp32 dot product of the frame's 128 activations with row 128 of the last layer
       f32x16 w128[4];
@@ -1143,6 +1188,13 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
       h128 = d + L.par[1536];
     }
     wr_pack(v, X);
+    // (12 waves: the split is finished before the next layer's accumulators exist - interleaved with that layer's MFMAs, as
+    // the 8-wave form has it, both sets of 64 registers are live at once)
+    if constexpr (NW == 12) {
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) asm volatile("" : "+v"(X.hi[ks]), "+v"(X.lo[ks]));
+      __builtin_amdgcn_sched_barrier(0);
+    }
     sync(SPEC ? l + 1 : l + 2);
   }
 
@@ -1157,7 +1209,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
 #pragma unroll
       for (int pr = 0; pr < 2; ++pr) {           // two tiles at a time: two accumulator chains
         f32x16 acc[2];
-        wr_layer_mma<8, 2, true, true>(slot, 2 * pr, X, acc, lane);
+        wr_layer_mma<8, 2, true, true, PF>(slot, 2 * pr, X, acc, lane);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           wr_store_rows<NWS_FILM_CH, true>(film_rs, acc[j], lane_off, 4 * c + 2 * pr + j, L.par[1280 + 32 * (4 * c + 2 * pr + j) + col]);
@@ -1172,7 +1224,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
       f32x16 acc[2];
-      wr_layer_mma<8, 2, true, true>(S1, 2 * pr, X, acc, lane);
+      wr_layer_mma<8, 2, true, true, PF>(S1, 2 * pr, X, acc, lane);
 #pragma unroll
       for (int j = 0; j < 2; ++j) wr_store_rows<NWS_SPEC_ROW, true>(g_rs, acc[j], lane_off, 2 * pr + j, L.par[1280 + 32 * (2 * pr + j) + col]);
     }
@@ -1180,7 +1232,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
   } else {
     // ---- H = last layer of h_generator (bands 0..127 on the matrix pipe, band 128 from above) -> operand of the FIR design ----
     wr_lane_vec(L.par + 1280, half, v);
-    wr_layer_mma<8, 4, false, false>(S0, 0, X, v, lane);
+    wr_layer_mma<8, 4, false, false, PF>(S0, 0, X, v, lane);
     if (TAPS && H_out != nullptr && frame < F) {
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
@@ -1200,7 +1252,7 @@ __global__ __launch_bounds__(512, 2) void frame_mlps_wr_kernel(NwsWeights w, con
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
       f32x16 acc[2];
-      wr_layer_mma<9, 2, true, true>(S1, 2 * pr, X, acc, lane);
+      wr_layer_mma<9, 2, true, true, PF>(S1, 2 * pr, X, acc, lane);
 #pragma unroll
       for (int j = 0; j < 2; ++j) wr_store_rows<NWS_FIR_HALF, false>(fir_rs, acc[j], lane_off, 2 * pr + j, 0.0f);
     }
@@ -1450,27 +1502,101 @@ static bool spec_serves(const NwsWeights* w, int B, int T) {
 
 int nws_frame_mlps_spec_serves(const NwsWeights* w, int B, int T) { return g_forward_spec && spec_serves(w, B, T) ? 1 : 0; }
 
-int nws_frame_mlps_spec(const NwsWeights* w, const float* gru_out, int B, int T, float* film_out, float* spec_out, void* stream) {
-  if (!w || !gru_out || !film_out || !spec_out || B <= 0 || T <= 0) return NWS_ERR_BAD_ARG;
-  for (int i = 0; i < 4; ++i)
-    if (!w->newt_mlp_w[i] || !w->newt_mlp_b[i] || !w->hgen_w[i] || !w->hgen_b[i]) return NWS_ERR_BAD_ARG;
-  for (int i = 0; i < 3; ++i)
-    if (!w->newt_ln_g[i] || !w->newt_ln_b[i] || !w->hgen_ln_g[i] || !w->hgen_ln_b[i]) return NWS_ERR_BAD_ARG;
-  if (!w->proj_b) return NWS_ERR_BAD_ARG;
-  if (!spec_serves(w, B, T)) return NWS_ERR_UNSUPPORTED;
+// compute units of the calling thread's current device (0: unknown), asked once per device
+static int device_cus() {
+  static int cus[64] = {};
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d > 63) return 0;
+  if (cus[d] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0) return 0;
+    cus[d] = n;
+  }
+  return cus[d];
+}
+
+// Waves per workgroup of the folded launch.  A per-utterance recurrence (control_gru.hip) holds one CU per utterance with 256
+// registers per wave, and the 8-wave form's two waves per SIMD (184 registers each) do not fit beside it: such a CU is shut to
+// it.  The 12-wave form runs where all of this holds: the caller expects the recurrence of a neighbouring batch of the same B to
+// be resident (the audio half launched apart from its control half: a pipeline); the 2 ceil(F / 256) workgroups of the 8-wave
+// form do not fit the CUs - B that are left in one round; the 2 ceil(F / 384) workgroups of the 12-wave form do.
+static int g_spec_waves = 0;   // tests, measurements: 8 or 12 whatever the rule says (nws_debug_frame_mlps_waves)
+static int g_spec_last_waves = 0;
+static int spec_waves(int B, int T, bool beside_recurrence) {
+  if (g_spec_waves != 0) return g_spec_waves;
+  if (!beside_recurrence) return 8;
+  const long long F = (long long)B * T;
+  const long long left = (long long)device_cus() - B;
+  return (2 * ((F + 255) / 256) > left && left >= 2 * ((F + 383) / 384)) ? 12 : 8;
+}
+
+int nws_debug_frame_mlps_waves(int waves) {
+  if (waves != 0 && waves != 8 && waves != 12) return NWS_ERR_BAD_ARG;
+  g_spec_waves = waves;
+  return NWS_OK;
+}
+
+int nws_debug_frame_mlps_last_waves(void) { return g_spec_last_waves; }
+
+int nws_frame_mlps_spec_waves(const NwsWeights* w, int B, int T, int beside_recurrence) {
+  return nws_frame_mlps_spec_serves(w, B, T) ? spec_waves(B, T, beside_recurrence != 0) : 0;
+}
+
+// the folded wave-resident kernel on F flattened frames in either form (the 12-wave form's 32-bit byte offsets: F <= 2^20)
+static int launch_wr_spec(const NwsWeights* w, const float* gru_out, long long F, int T, float* film_out, float* spec_out, int waves,
+                          void* stream) {
+  if (waves == 12 && F > (1ll << 20)) return NWS_ERR_UNSUPPORTED;
   static unsigned long long attr_devices = 0;
   if (nws_first_use_on_device(attr_devices)) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(frame_mlps_wr_kernel<false, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WrLds));
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(frame_mlps_wr_kernel<false, true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WrLds));
+    if (e != hipSuccess) return (int)e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(frame_mlps_wr_kernel<false, true, 12>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(WrLds));
     if (e != hipSuccess) return (int)e;
   }
-  const long long F = (long long)B * T;
-  const unsigned nblk = (unsigned)((F + kWrFrames - 1) / kWrFrames);
+  const int per = 32 * waves;
+  const unsigned nblk = (unsigned)((F + per - 1) / per);
   const dim3 gridw(16 * ((nblk + 7) / 8), 1);      // both paths of a frame block on one XCD (see the kernel)
-  frame_mlps_wr_kernel<false, true><<<gridw, 512, sizeof(WrLds), (hipStream_t)stream>>>(*w, gru_out, (int)F, T, nullptr, film_out, nullptr,
-                                                                                         spec_out, (int)nblk);
+  if (waves == 12)
+    frame_mlps_wr_kernel<false, true, 12><<<gridw, 768, sizeof(WrLds), (hipStream_t)stream>>>(*w, gru_out, (int)F, T, nullptr, film_out,
+                                                                                               nullptr, spec_out, (int)nblk);
+  else
+    frame_mlps_wr_kernel<false, true><<<gridw, 512, sizeof(WrLds), (hipStream_t)stream>>>(*w, gru_out, (int)F, T, nullptr, film_out, nullptr,
+                                                                                           spec_out, (int)nblk);
   NWS_CHECK_LAUNCH();
+  g_spec_last_waves = waves;
   return NWS_OK;
+}
+
+static bool spec_weights_ok(const NwsWeights* w) {
+  if (!w || !w->proj_b) return false;
+  for (int i = 0; i < 4; ++i)
+    if (!w->newt_mlp_w[i] || !w->newt_mlp_b[i] || !w->hgen_w[i] || !w->hgen_b[i]) return false;
+  for (int i = 0; i < 3; ++i)
+    if (!w->newt_ln_g[i] || !w->newt_ln_b[i] || !w->hgen_ln_g[i] || !w->hgen_ln_b[i]) return false;
+  return true;
+}
+
+int nws_frame_mlps_spec_beside(const NwsWeights* w, const float* gru_out, int B, int T, float* film_out, float* spec_out,
+                               int beside_recurrence, void* stream) {
+  if (!w || !gru_out || !film_out || !spec_out || B <= 0 || T <= 0) return NWS_ERR_BAD_ARG;
+  if (!spec_weights_ok(w)) return NWS_ERR_BAD_ARG;
+  if (!spec_serves(w, B, T)) return NWS_ERR_UNSUPPORTED;
+  return launch_wr_spec(w, gru_out, (long long)B * T, T, film_out, spec_out, spec_waves(B, T, beside_recurrence != 0), stream);
+}
+
+int nws_frame_mlps_spec(const NwsWeights* w, const float* gru_out, int B, int T, float* film_out, float* spec_out, void* stream) {
+  return nws_frame_mlps_spec_beside(w, gru_out, B, T, film_out, spec_out, 0, stream);
+}
+
+int nws_debug_frame_mlps_spec_waves(const NwsWeights* w, const float* gru_out, int F, float* film_out, float* spec_out, int waves,
+                                    void* stream) {
+  if (!w || !gru_out || !film_out || !spec_out || F <= 0 || (waves != 8 && waves != 12)) return NWS_ERR_BAD_ARG;
+  if (!spec_weights_ok(w)) return NWS_ERR_BAD_ARG;
+  if (w->mlp_frags == nullptr || w->mlp_spec == 0 || (long long)F * NWS_FILM_CH * (long long)sizeof(float) >= (1ll << 31))
+    return NWS_ERR_UNSUPPORTED;
+  return launch_wr_spec(w, gru_out, F, F, film_out, spec_out, waves, stream);
 }
 
 // NWS_MLP_FEW=0: utterances of one or two frames take the 32-frame tile kernel like longer ones (measurements, bit-identity tests)
