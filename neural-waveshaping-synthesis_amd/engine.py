@@ -149,6 +149,19 @@ def reverb_plan_and_tables(device: torch.device, n_samples: int, ir_len_plus1: i
     return hit
 
 
+def reverb_ir_spectrum(device: torch.device, plan, tables, ir):
+    """The spectrum of the impulse response `ir` in the plan's own (k1, k2) order, complete when this returns."""
+    L = _lib.lib()
+    with torch.cuda.device(device):
+        spec = torch.empty(L.nws_reverb_spectrum_bytes(C.byref(plan)) // 4, dtype=torch.float32, device=device)
+        nbytes = L.nws_reverb_workspace_bytes(C.byref(plan), 1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        check(L.nws_reverb_ir_spectrum(C.byref(plan), ptr(tables), ptr(ir), ir.numel(), ptr(spec), ptr(ws), nbytes, stream_ptr(device)),
+              "nws_reverb_ir_spectrum")
+        torch.cuda.current_stream(device).synchronize()
+    return spec
+
+
 class Weights(NamedTuple):
     """What Engine caches per weights version: the pointer struct, the same struct as the bytes tensor the binding takes, and
     the tensors the launchers pass beside it.  `keep` holds every tensor the struct points into."""
@@ -397,6 +410,11 @@ class Engine:
         self._fp = fp
         return self._w
 
+    def record(self):
+        """The current Weights record as it stands, without a fingerprint walk (None before the first build).  A rebuild replaces
+        it and never edits it, so `is` tells a stream whether its captured hops still point into live tables."""
+        return self._w
+
     HYBRID_W_BOUND = 1e-5     # worst-case output error (a tenth of the 1e-4 parity bar) under which "auto" may drop mixer terms
 
     def exciter_opts(self) -> int:
@@ -529,14 +547,7 @@ class Engine:
         skey = (plan.L, plan.N1, plan.N2)      # stored in the transform's own (k1, k2) order: one spectrum per factorisation
         spec = self._spectra.get(skey)
         if spec is None:
-            with torch.cuda.device(dev):
-                spec = torch.empty(_lib.lib().nws_reverb_spectrum_bytes(C.byref(plan)) // 4, dtype=torch.float32, device=dev)
-                nbytes = _lib.lib().nws_reverb_workspace_bytes(C.byref(plan), 1)
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                check(_lib.lib().nws_reverb_ir_spectrum(C.byref(plan), ptr(tables), ptr(ir), ir.numel(), ptr(spec), ptr(ws),
-                                                        nbytes, stream_ptr(dev)), "nws_reverb_ir_spectrum")
-                torch.cuda.current_stream(dev).synchronize()
-            self._spectra[skey] = spec
+            spec = self._spectra[skey] = reverb_ir_spectrum(dev, plan, tables, ir)
         return plan, tables, spec, plan_t
 
     # ---- stage launchers (public for the parity tests; each is one call of the binding) ------------------------------------

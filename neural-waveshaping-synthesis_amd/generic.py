@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import NwsGenericModel, NwsReverbPlan, NwsShaperDesc, check, ptr
+from ._lib import NwsGenericModel, NwsReverbPlan, NwsShaperDesc
 
 
 def _p(t: torch.Tensor, name: str, numel: int | None = None) -> torch.Tensor:
@@ -84,6 +84,10 @@ class GenericEngine:
         self._cache = None      # the current GenericModel record, replaced on rebuild
         self._reverb = {}       # N -> (plan | None, tables, spectrum, plan tensor)
         self._workspaces = {}
+
+    def record(self):
+        """The current GenericModel record as it stands, without a fingerprint walk (Engine.record's counterpart)."""
+        return self._cache
 
     def invalidate(self):
         self._cache = None
@@ -191,23 +195,13 @@ class GenericEngine:
     def _reverb_aux(self, N, dev, ir):
         hit = self._reverb.get(N)
         if hit is None:
-            from .engine import reverb_plan_and_tables
+            from .engine import reverb_ir_spectrum, reverb_plan_and_tables
 
-            plan = NwsReverbPlan()
-            rc = _lib.lib().nws_reverb_plan(int(N), int(ir.numel()) + 1, C.byref(plan))
-            if rc != 0:
+            if _lib.lib().nws_reverb_plan(int(N), int(ir.numel()) + 1, C.byref(NwsReverbPlan())) != 0:
                 hit = (None, None, None, None)      # no factorisation: nws_g_reverb_direct
             else:
                 plan, tables, plan_t = reverb_plan_and_tables(dev, N, ir.numel() + 1)
-                L = _lib.lib()
-                with torch.cuda.device(dev):
-                    spec = torch.empty(L.nws_reverb_spectrum_bytes(C.byref(plan)) // 4, dtype=torch.float32, device=dev)
-                    nb = L.nws_reverb_workspace_bytes(C.byref(plan), 1)
-                    ws1 = torch.empty(nb, dtype=torch.uint8, device=dev)
-                    check(L.nws_reverb_ir_spectrum(C.byref(plan), ptr(tables), ptr(ir), ir.numel(), ptr(spec), ptr(ws1), nb,
-                                                   torch.cuda.current_stream(dev).cuda_stream), "nws_reverb_ir_spectrum")
-                    torch.cuda.current_stream(dev).synchronize()
-                hit = (plan, tables, spec, plan_t)
+                hit = (plan, tables, reverb_ir_spectrum(dev, plan, tables, ir), plan_t)
             self._reverb[N] = hit
         return hit
 
@@ -229,5 +223,5 @@ class GenericEngine:
             if len(self._workspaces) >= 8:
                 self._workspaces.pop(next(iter(self._workspaces)))
             self._workspaces[key] = ws
-        sr = float(getattr(getattr(self._model_ref, 'osc', None), 'sample_rate', self._model_ref.sample_rate))   # the oscillator's own binding (generators.py:41)
-        return binding().forward_generic(r.gdesc, f0, control, phase_u, r.rand_phase, noise, plan_t, tables, spec, ws[1], ws[0], sr)
+        return binding().forward_generic(r.gdesc, f0, control, phase_u, r.rand_phase, noise, plan_t, tables, spec, ws[1], ws[0],
+                                         self._model_ref._engine.osc_sample_rate())

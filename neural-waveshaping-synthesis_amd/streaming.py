@@ -22,12 +22,13 @@ hipGraph and replayed (`graph=True`, the default): a 256-sample hop is then one 
     RMS, not bit for bit (hops of one or two frames take another frame-MLP kernel than longer chunks, chunks beyond 2048
     samples sum the reverb in another order).
 
-`GenericNewtStream` is the same stream for a model of another architecture (bank, harmonics, layer sizes, sample rate, reverb
-length): one push = one `g_stream_step` (`nws_g_stream_step`, the runtime-size kernels); `model.stream` picks the class.
-
 `VoiceStream` (`model.stream(B, slots=True)`, `nws_stream_step_slots`) is the slot mode: B voices that start and stop on their
-own in one batched stream, with per-slot events as device data; its docstring states the contract.  `GenericVoiceStream` is the
-same for a model of another architecture (`nws_g_stream_step_slots`); `model.voices(B)` picks the class.
+own in one batched stream, with per-slot events as device data; its docstring states the contract.
+
+Which kernel family serves a stream is one object, its path: `_FusedPath` (the packaged architecture) or `_GenericPath` (any other
+bank, harmonic count, layer sizes, sample rate, reverb length: `nws_g_stream_step` / `nws_g_stream_step_slots`, the runtime-size
+kernels).  `GenericNewtStream` and `GenericVoiceStream` are the two streams with the second path and nothing
+else of their own; `model.stream` and `model.voices(B)` pick the class.
 
 `NotePlayer` (`model.player(voices)`) plays notes on that slot stream: `nws_note_control` writes every slot's controls
 of a hop from the notes, `nws_voice_mix` sums the slots into one signal; `NoteBook` is its host-side scheduling.
@@ -51,14 +52,201 @@ _RING = 65536             # kRing of csrc/stream.hip: reverb-input ring per utte
 _GRAPH_AFTER = 2          # consecutive steady-state pushes of one (K, channels) before that hop is captured
 
 
+class _FusedPath:
+    """What a stream asks of the kernel family that serves its model; here the fused kernels (the architecture of
+    gin/models/newt.gin), in _GenericPath the same calls for the runtime-size kernels.  Construction refuses a model the family does
+    not serve and reads `dev`, `ir_len`, `n_harmonics` and `control_size` from the family's own record of the model; a call that
+    needs the stream's state takes the stream `s`.  The two path classes are this module's only code that touches engine privates."""
+
+    def __init__(self, model, slots: bool):
+        self.eng = eng = model._engine
+        if not eng.specialised():
+            raise RuntimeError("stateful streaming runs on the fused kernels: the model must have the architecture of "
+                               "gin/models/newt.gin" + (" - model.voices(B) gives the slot stream of any architecture" if slots else ""))
+        _, _, self.dev = eng.weights()
+        self.ir_len = int(eng.ir().numel())
+        self.n_harmonics, self.control_size = _lib.N_HARMONICS, 2
+
+    # ---- the watch on the weights -------------------------------------------------------------------------------------
+    def record(self):
+        """The engine's current record of pointers and derived tables (replaced, never edited, on a rebuild)."""
+        return self.eng.record()
+
+    def rewalk(self):
+        """One fingerprint walk over an existing record; rebuilds it if a parameter changed (drains the device first)."""
+        if self.eng.record() is not None:
+            self.eng._wd()
+
+    def settle(self):
+        """In front of a capture.  Nothing to do here: a step that finds the record stale inside a capture raises (Engine._wd), the
+        capture fails and the stream goes on with eager pushes."""
+
+    def reverb_aux(self, plan_n):
+        """(plan, tables, IR spectrum, plan tensor) of the FFT reverb length `plan_n`, for the current weights."""
+        return self.eng.reverb_aux(plan_n)
+
+    # ---- sizing ---------------------------------------------------------------------------------------------------------
+    def state_bytes(self, B, max_frames, plan):
+        return _lib.lib().nws_stream_state_bytes(B, max_frames, self.ir_len, C.byref(plan) if plan is not None else None)
+
+    def slot_state_bytes(self, B, max_frames):
+        """(bytes of a slot stream's state, offset of its counters: where `gave_up` reads the flag)"""
+        L = _lib.lib()
+        return L.nws_stream_slot_state_bytes(B, max_frames, self.ir_len), int(L.nws_stream_counters_offset(B, max_frames, self.ir_len))
+
+    # ---- one call of the binding ------------------------------------------------------------------------------------
+    def step(self, s, f0_2d, control, first, final, noise_new, out, pre):
+        eng = self.eng
+        r = eng._wd()
+        _, tables, spec, plan_t = eng._reverb_aux(s._plan_n) if s._need_fft else (None, None, None, None)
+        binding().stream_step(r.wdesc, r.fir_design, plan_t, tables, spec, s._state, s.max_frames, f0_2d, control, bool(first),
+                              bool(final), int(s.frames_seen), int(s._nz_prev_start), eng.osc_sample_rate(), s.phase_u,
+                              r.rand_phase, noise_new, s._noise_all, r.ir.reshape(-1), out, pre)
+
+    def step_slots(self, s, f0_2d, control, noise_new, out, pre):
+        eng = self.eng
+        r = eng._wd()
+        binding().stream_step_slots(r.wdesc, r.fir_design, s._state, s.max_frames, f0_2d, control, int(s.frames_seen),
+                                    int(s._nz_prev_start), eng.osc_sample_rate(), s.phase_u, r.rand_phase, noise_new,
+                                    s._noise_all, r.ir.reshape(-1), s._ev, out, pre)
+
+    def reverb_tail(self, s, plan, tables, spec, tail, ws, nb):
+        _lib.check(_lib.lib().nws_stream_reverb_tail(C.byref(plan), tables.data_ptr(), spec.data_ptr(), s._state.data_ptr(),
+                                                     s._state.numel(), s.B, s.max_frames, self.ir_len, tail.data_ptr(),
+                                                     ws.data_ptr(), nb, stream_ptr(self.dev)), "nws_stream_reverb_tail")
+
+    def gave_up(self, s) -> bool:
+        """Did a slot hop's device work report that it gave up waiting (counters[5])?  Synchronises."""
+        return int(s._state[s._counters_at + 40: s._counters_at + 48].cpu().view(torch.int64)[0]) != 0
+
+
+class _GenericPath:
+    """_FusedPath for a model that `Engine.specialised()` turns down (another bank, harmonic count, GRU / MLP size, sample rate,
+    reverb length, several NEWT output channels): the runtime-size stage kernels of csrc/generic.hip on the window, the noise
+    branch, ring and reverb of csrc/stream.hip.  The noise branch, the ring and the 64-sample emission delay
+    are the packaged stream's, so three sizes are fixed: control hop 128, 256 noise taps, a window symmetric about tap 128.  What it
+    watches for weight updates is the GenericEngine's descriptor record."""
+
+    def __init__(self, model, slots: bool):
+        self.eng = eng = model._engine
+        m, ns = model, model.noise_synth
+        if int(m.control_hop) != HOP or int(ns.hop_length) != HOP:
+            raise RuntimeError(f"stateful streaming runs at a control hop of {HOP} samples: this model has control_hop = "
+                               f"{int(m.control_hop)}, FIRNoiseSynth.hop_length = {int(ns.hop_length)} - render it with the one-shot "
+                               f"forward, which serves every hop")
+        if int(ns.ir_length) != _lib.FIR_LEN:
+            raise RuntimeError(f"stateful streaming filters the noise with {_lib.FIR_LEN} taps per frame: this model has "
+                               f"FIRNoiseSynth.ir_length = {int(ns.ir_length)} - render it with the one-shot forward, which serves "
+                               f"every even length")
+        if not eng._window_symmetric():
+            w = ns.window.detach().float().cpu()
+            asym = float((w[1:HOP] - w[HOP + 1:].flip(0)).abs().max())
+            raise RuntimeError(f"stateful streaming hands half of every frame's noise taps on: the window must be symmetric about tap "
+                               f"{HOP} with window[0] = 0, this model's has window[0] = {float(w[0]):.6g} and differs by up to "
+                               f"{asym:.3g} between mirrored taps - render it with the one-shot forward, which serves every window")
+        r = eng.generic.model_desc()
+        self.dev, self.ir_len = r.device, int(r.ir.numel())
+        self.n_harmonics, self.control_size = int(r.struct.n_harmonics), int(r.struct.control_size)
+
+    def record(self):
+        return self.eng.generic.record()
+
+    def rewalk(self):
+        self.eng.generic.model_desc()
+
+    settle = rewalk     # a rebuild synchronises: in front of the capture, never inside it
+
+    def reverb_aux(self, plan_n):
+        g = self.eng.generic
+        r = g.model_desc()
+        return g._reverb_aux(plan_n, r.device, r.ir)
+
+    def _served(self, nbytes):
+        if nbytes == 0:
+            raise RuntimeError("stateful streaming: the runtime-size kernels do not serve this model's layer sizes - render it "
+                               "with the one-shot forward")
+        return nbytes
+
+    def state_bytes(self, B, max_frames, plan):
+        r = self.eng.generic.model_desc()
+        return self._served(_lib.lib().nws_g_stream_state_bytes(C.byref(r.struct), B, max_frames, self.ir_len,
+                                                                C.byref(plan) if plan is not None else None))
+
+    def slot_state_bytes(self, B, max_frames):
+        r = self.eng.generic.model_desc()
+        return self._served(_lib.lib().nws_g_stream_slot_state_bytes(C.byref(r.struct), B, max_frames, self.ir_len)), None
+
+    def step(self, s, f0_2d, control, first, final, noise_new, out, pre):
+        g = self.eng.generic
+        r = g.model_desc()
+        _, tables, spec, plan_t = g._reverb_aux(s._plan_n, r.device, r.ir) if s._need_fft else (None, None, None, None)
+        binding().g_stream_step(r.gdesc, plan_t, tables, spec, s._state, s.max_frames, f0_2d, control, bool(first), bool(final),
+                                int(s.frames_seen), int(s._nz_prev_start), self.eng.osc_sample_rate(), s.phase_u,
+                                r.rand_phase, noise_new, s._noise_all, out, pre)
+
+    def step_slots(self, s, f0_2d, control, noise_new, out, pre):
+        r = self.eng.generic.model_desc()
+        binding().g_stream_step_slots(r.gdesc, s._state, s.max_frames, f0_2d, control, int(s.frames_seen),
+                                      int(s._nz_prev_start), self.eng.osc_sample_rate(), s.phase_u, r.rand_phase, noise_new,
+                                      s._noise_all, s._ev, out, pre)
+
+    def reverb_tail(self, s, plan, tables, spec, tail, ws, nb):
+        r = self.eng.generic.model_desc()
+        _lib.check(_lib.lib().nws_g_stream_reverb_tail(C.byref(r.struct), C.byref(plan), tables.data_ptr(), spec.data_ptr(),
+                                                       s._state.data_ptr(), s._state.numel(), s.B, s.max_frames, tail.data_ptr(),
+                                                       ws.data_ptr(), nb, stream_ptr(self.dev)), "nws_g_stream_reverb_tail")
+
+    def gave_up(self, s) -> bool:
+        """Synchronises; the runtime-size hop has no wait inside a launch and so nothing it could have given up on."""
+        torch.cuda.synchronize(self.dev)
+        return False
+
+
 class _StreamBase:
-    """What NewtStream and VoiceStream share: the captured steady-state hop and its fall-back to eager pushes, the watch on the
-    engine's weights record, and the reverb tail.  A subclass provides `_steady_step(f0_2d, control, noise_new, out, pre)`: one
-    steady-state hop through the binding."""
+    """What NewtStream and VoiceStream share: the opening of a stream, the captured steady-state hop and its fall-back to eager
+    pushes, the watch on the engine's weights record, and the reverb tail.  Whatever depends on the kernel family goes through
+    `self._path`, an object of the class `_PATH` names (the one thing the Generic* subclasses change).  A subclass provides
+    `_steady_step(f0_2d, control, noise_new, out, pre)`: one steady-state hop through the binding."""
+
+    _PATH = _FusedPath
+
+    def _open(self, model, batch_size, phase_u, slots):
+        """The opening, before the subclass sizes its state: the path with its refusals, the ring refusal, the FFT reverb length
+        and the stream's one phase draw."""
+        self.model, self.eng = model, model._engine
+        self._path = p = self._PATH(model, slots)
+        self.dev, self._ir_len, self.B = p.dev, p.ir_len, int(batch_size)
+        if slots and self.B < 1:
+            raise RuntimeError("VoiceStream: at least one slot")
+        self.tail_len = self._ir_len + 1
+        if self._ir_len >= _RING // 2:
+            span = "" if slots else f" ({self._ir_len / float(model.sample_rate):.2f} s at {model.sample_rate} Hz)"
+            raise RuntimeError(f"stateful streaming keeps {_RING // 2 - 1} samples of reverb history per {'slot' if slots else 'utterance'}; "
+                               f"this model's impulse response has {self._ir_len} taps{span} - render it with the one-shot forward")
+        # the FFT reverb of a long chunk is one direct transform of [ir_len samples of history | chunk]: the smallest standard
+        # length that holds twice the tail (64000 at 16 kHz, 32000 at 8 kHz) bounds the chunk
+        self._plan_n = next(n for n in (32000, 64000, 128000, 256000) if n >= 2 * self.tail_len)
+        self.phase_u = _req((phase_u if phase_u is not None else torch.rand_like(model.osc.rand_phase)).reshape(-1),
+                            "phase_u", p.n_harmonics)
+
+    def _alloc(self, nbytes, graph):
+        """The rest of the opening: the state blob, reset, and the bookkeeping of positions and captured hops."""
+        with torch.cuda.device(self.dev):
+            self._state = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+            _lib.check(_lib.lib().nws_stream_reset(self._state.data_ptr(), nbytes, stream_ptr(self.dev)), "nws_stream_reset")
+        self._use_graph = bool(graph)
+        self._graphs = {}          # (K, channels) -> (graph, f0_in, control_in, noise_new, out, pre)
+        self._steady_runs = {}     # (K, channels) -> CONSECUTIVE steady-state pushes seen
+        self.frames_seen = 0       # (the slot stream counts its pre-roll in)
+        self._nz_prev_start = 0
+        self._last_K = None
+        self._last_pre = None
+        self.finished = False
 
     def _capture(self, K, C_in):
         """hipGraph of one steady-state hop of K frames: static input / output buffers, the fresh noise draws inside."""
         dev = self.dev
+        self._path.settle()
         with torch.cuda.device(dev):
             f0_in = torch.zeros((self.B, K), dtype=torch.float32, device=dev)
             c_in = torch.zeros((self.B, C_in, K), dtype=torch.float32, device=dev)
@@ -105,8 +293,8 @@ class _StreamBase:
         now = time.monotonic()
         if now - self.__dict__.get("_last_walk", 0.0) >= 0.25:
             self._last_walk = now
-            self._rewalk()
-        rec = self._record()
+            self._path.rewalk()
+        rec = self._path.record()
         if rec is not self.__dict__.get("_w_seen"):
             if self._graphs:
                 torch.cuda.synchronize(self.dev)
@@ -114,98 +302,35 @@ class _StreamBase:
                 self._steady_runs.clear()
             self._w_seen = rec
 
-    def _record(self):
-        """The engine's current record of pointers and derived tables (replaced, never edited, on a rebuild)."""
-        return self.eng._w
-
-    def _rewalk(self):
-        """One fingerprint walk; rebuilds the record if a parameter changed (drains the device first)."""
-        eng = self.eng
-        if eng._w is not None and eng._fingerprint() != eng._fp:
-            eng._wd()
-
-    def _tail_call(self, L, plan, tables, spec, tail, ws, nb):
-        return L.nws_stream_reverb_tail(C.byref(plan), tables.data_ptr(), spec.data_ptr(), self._state.data_ptr(),
-                                        self._state.numel(), self.B, self.max_frames, self._ir_len, tail.data_ptr(),
-                                        ws.data_ptr(), nb, stream_ptr(self.dev)), "nws_stream_reverb_tail"
-
     def reverb_tail(self) -> torch.Tensor:
         """The remaining (B, ir_len + 1) reverb tail of every row after the last chunk (what a linear reverb still rings out)."""
-        plan, tables, spec, _ = self._reverb_plan()
-        L = _lib.lib()
+        plan, tables, spec, _ = self._path.reverb_aux(self._plan_n)
         with torch.cuda.device(self.dev):
             tail = torch.empty((self.B, self.tail_len), dtype=torch.float32, device=self.dev)
-            nb = 2 * ((self.B * (2 * self._ir_len + 1) * 4 + 255) // 256 * 256) + L.nws_reverb_workspace_bytes(C.byref(plan), self.B)
+            nb = 2 * ((self.B * (2 * self._ir_len + 1) * 4 + 255) // 256 * 256) + _lib.lib().nws_reverb_workspace_bytes(C.byref(plan), self.B)
             ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
-            _lib.check(*self._tail_call(L, plan, tables, spec, tail, ws, nb))
+            self._path.reverb_tail(self, plan, tables, spec, tail, ws, nb)
         return tail
-
-    def _reverb_plan(self):
-        """(plan, tables, IR spectrum, plan tensor) of the stream's FFT reverb length, for the current weights."""
-        self.eng._wd()
-        return self.eng._reverb_aux(self._plan_n)
 
 
 class NewtStream(_StreamBase):
     def __init__(self, model, batch_size: int, phase_u: torch.Tensor | None = None, noise: torch.Tensor | None = None,
                  max_chunk_frames: int = _MAX_CHUNK_FRAMES, graph: bool = True):
-        self.model = model
-        self.eng = model._engine
-        self.B = int(batch_size)
-        self._bind()               # self.dev, self._ir_len, self._n_harmonics: from the path's own record of the model
-        self.tail_len = self._ir_len + 1
-        if self._ir_len >= _RING // 2:
-            raise RuntimeError(f"stateful streaming keeps {_RING // 2 - 1} samples of reverb history per utterance; this model's impulse "
-                               f"response has {self._ir_len} taps ({self._ir_len / float(model.sample_rate):.2f} s at "
-                               f"{model.sample_rate} Hz) - render it with the one-shot forward")
-        # the FFT reverb of a long chunk is one direct transform of [ir_len samples of history | chunk]: the smallest standard
-        # length that holds twice the tail (64000 at 16 kHz, 32000 at 8 kHz) bounds the chunk
-        self._plan_n = next(n for n in (32000, 64000, 128000, 256000) if n >= 2 * self.tail_len)
+        self._open(model, batch_size, phase_u, slots=False)
         fit = (self._plan_n - self._ir_len) // HOP - 1
         self.max_frames = int(min(max(1, max_chunk_frames), fit))
-        self.phase_u = _req((phase_u if phase_u is not None else torch.rand_like(model.osc.rand_phase)).reshape(-1),
-                            "phase_u", self._n_harmonics)
         self._noise_all = _req(noise, "noise") if noise is not None else None    # parity mode: the reference's whole draw
-        self.frames_seen = 0
         self.samples_emitted = 0
-        self.finished = False
-        self._nz_prev_start = 0
         self._need_fft = HOP * (self.max_frames + 1) > 2048
-        L = _lib.lib()
-        plan = self._reverb_plan()[0] if self._need_fft else None
-        nbytes = self._state_bytes(L, C.byref(plan) if plan is not None else None)
-        dev = self.dev
-        with torch.cuda.device(dev):
-            self._state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(L.nws_stream_reset(self._state.data_ptr(), nbytes, stream_ptr(dev)), "nws_stream_reset")
-        self._use_graph = bool(graph)
-        self._graphs = {}          # (K, channels) -> (graph, f0_in, control_in, noise_new, out, pre)
-        self._steady_runs = {}     # (K, channels) -> CONSECUTIVE steady-state pushes seen
-        self._last_K = None
-        self._last_pre = None
-
-    def _bind(self):
-        if not self.eng.specialised():
-            raise RuntimeError("stateful streaming runs on the fused kernels: the model must have the architecture of "
-                               "gin/models/newt.gin")
-        _, _, self.dev = self.eng.weights()
-        self._ir_len = int(self.eng.ir().numel())
-        self._n_harmonics = _lib.N_HARMONICS
-
-    def _state_bytes(self, L, plan_ref):
-        return L.nws_stream_state_bytes(self.B, self.max_frames, self._ir_len, plan_ref)
+        plan = self._path.reverb_aux(self._plan_n)[0] if self._need_fft else None
+        self._alloc(self._path.state_bytes(self.B, self.max_frames, plan), graph)
 
     # ---- one call of the binding ------------------------------------------------------------------------------------
     def _step(self, f0_2d, control, first, final, noise_new, out, pre):
-        eng = self.eng
-        r = eng._wd()
-        _, tables, spec, plan_t = eng._reverb_aux(self._plan_n) if self._need_fft else (None, None, None, None)
-        binding().stream_step(r.wdesc, r.fir_design, plan_t, tables, spec, self._state, self.max_frames, f0_2d, control, bool(first),
-                              bool(final), int(self.frames_seen), int(self._nz_prev_start), eng.osc_sample_rate(), self.phase_u,
-                              r.rand_phase, noise_new, self._noise_all, r.ir.reshape(-1), out, pre)
+        self._path.step(self, f0_2d, control, first, final, noise_new, out, pre)
 
     def _steady_step(self, f0_2d, control, noise_new, out, pre):
-        self._step(f0_2d, control, False, False, noise_new, out, pre)
+        self._path.step(self, f0_2d, control, False, False, noise_new, out, pre)
 
     # ---- one chunk ----------------------------------------------------------------------------------------------------
     def push(self, f0: torch.Tensor, control: torch.Tensor, final: bool = False) -> torch.Tensor:
@@ -292,71 +417,10 @@ class NewtStream(_StreamBase):
 
 
 class GenericNewtStream(NewtStream):
-    """NewtStream for a model that `Engine.specialised()` turns down (another bank, harmonic count, GRU / MLP size, sample rate,
-    reverb length, several NEWT output channels): the same contract and methods, one push = one `g_stream_step` of the binding
-    (`nws_g_stream_step`, csrc/generic.hip) - the runtime-size stage kernels on the window, the noise branch,
-    ring and reverb of csrc/stream.hip.  The noise branch, the ring and the 64-sample emission delay are the packaged stream's,
-    so three sizes are fixed: control hop 128, 256 noise taps, a window symmetric about tap 128.  What it watches for weight
-    updates is the GenericEngine's descriptor record."""
+    """NewtStream for a model that `Engine.specialised()` turns down: the same contract and methods on the runtime-size kernels,
+    one push = one `g_stream_step` of the binding (`nws_g_stream_step`).  _GenericPath states what it needs."""
 
-    def _bind(self):
-        m, eng = self.model, self.eng
-        ns = m.noise_synth
-        if int(m.control_hop) != HOP or int(ns.hop_length) != HOP:
-            raise RuntimeError(f"stateful streaming runs at a control hop of {HOP} samples: this model has control_hop = "
-                               f"{int(m.control_hop)}, FIRNoiseSynth.hop_length = {int(ns.hop_length)} - render it with the one-shot "
-                               f"forward, which serves every hop")
-        if int(ns.ir_length) != _lib.FIR_LEN:
-            raise RuntimeError(f"stateful streaming filters the noise with {_lib.FIR_LEN} taps per frame: this model has "
-                               f"FIRNoiseSynth.ir_length = {int(ns.ir_length)} - render it with the one-shot forward, which serves "
-                               f"every even length")
-        if not eng._window_symmetric():
-            w = ns.window.detach().float().cpu()
-            asym = float((w[1:HOP] - w[HOP + 1:].flip(0)).abs().max())
-            raise RuntimeError(f"stateful streaming hands half of every frame's noise taps on: the window must be symmetric about tap "
-                               f"{HOP} with window[0] = 0, this model's has window[0] = {float(w[0]):.6g} and differs by up to "
-                               f"{asym:.3g} between mirrored taps - render it with the one-shot forward, which serves every window")
-        r = eng.generic.model_desc()
-        self.dev = r.device
-        self._ir_len = int(r.ir.numel())
-        self._n_harmonics = int(r.struct.n_harmonics)
-
-    def _state_bytes(self, L, plan_ref):
-        r = self.eng.generic.model_desc()
-        nbytes = L.nws_g_stream_state_bytes(C.byref(r.struct), self.B, self.max_frames, self._ir_len, plan_ref)
-        if nbytes == 0:
-            raise RuntimeError("stateful streaming: the runtime-size kernels do not serve this model's layer sizes - render it "
-                               "with the one-shot forward")
-        return nbytes
-
-    def _record(self):
-        return self.eng.generic._cache
-
-    def _rewalk(self):
-        self.eng.generic.model_desc()
-
-    def _reverb_plan(self):
-        g = self.eng.generic
-        r = g.model_desc()
-        return g._reverb_aux(self._plan_n, r.device, r.ir)
-
-    def _capture(self, K, C_in):
-        self.eng.generic.model_desc()     # a rebuild synchronises: in front of the capture, never inside it
-        return super()._capture(K, C_in)
-
-    def _tail_call(self, L, plan, tables, spec, tail, ws, nb):
-        r = self.eng.generic.model_desc()
-        return L.nws_g_stream_reverb_tail(C.byref(r.struct), C.byref(plan), tables.data_ptr(), spec.data_ptr(), self._state.data_ptr(),
-                                          self._state.numel(), self.B, self.max_frames, tail.data_ptr(), ws.data_ptr(), nb,
-                                          stream_ptr(self.dev)), "nws_g_stream_reverb_tail"
-
-    def _step(self, f0_2d, control, first, final, noise_new, out, pre):
-        g = self.eng.generic
-        r = g.model_desc()
-        _, tables, spec, plan_t = g._reverb_aux(self._plan_n, r.device, r.ir) if self._need_fft else (None, None, None, None)
-        binding().g_stream_step(r.gdesc, plan_t, tables, spec, self._state, self.max_frames, f0_2d, control, bool(first), bool(final),
-                                int(self.frames_seen), int(self._nz_prev_start), self.eng.osc_sample_rate(), self.phase_u,
-                                r.rand_phase, noise_new, self._noise_all, out, pre)
+    _PATH = _GenericPath
 
 
 # ---- slot mode: B voices with their own lifetimes in one batched stream ------------------------------------------------
@@ -465,47 +529,25 @@ class VoiceStream(_StreamBase):
 
     def __init__(self, model, batch_size: int, phase_u: torch.Tensor | None = None, noise: torch.Tensor | None = None,
                  graph: bool = True):
-        self.model = model
-        self.eng = model._engine
-        self._bind()               # self.dev, self._ir_len, self._n_harmonics, self._control_size: from the path's own record
+        self._open(model, batch_size, phase_u, slots=True)
         dev = self.dev
-        self.B = int(batch_size)
-        if self.B < 1:
-            raise RuntimeError("VoiceStream: at least one slot")
-        self.tail_len = self._ir_len + 1
-        if self._ir_len >= _RING // 2:
-            raise RuntimeError(f"stateful streaming keeps {_RING // 2 - 1} samples of reverb history per slot; this model's impulse "
-                               f"response has {self._ir_len} taps - render it with the one-shot forward")
-        self._plan_n = next(n for n in (32000, 64000, 128000, 256000) if n >= 2 * self.tail_len)
         self.max_frames = _SLOT_MAX_FRAMES
-        self.phase_u = _req((phase_u if phase_u is not None else torch.rand_like(model.osc.rand_phase)).reshape(-1),
-                            "phase_u", self._n_harmonics)
         self._noise_all = None
         if noise is not None:
             nz = _req(noise, "noise").reshape(-1)
             # the pre-roll's frames come first in the device's noise positions: its samples are never read into an output
             self._noise_all = torch.cat([torch.zeros(HOP * _PREROLL, dtype=nz.dtype, device=nz.device), nz])
-        L = _lib.lib()
-        nbytes = self._state_bytes(L)
-        with torch.cuda.device(dev):
-            self._state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(L.nws_stream_reset(self._state.data_ptr(), nbytes, stream_ptr(dev)), "nws_stream_reset")
-            self._ev = torch.zeros(self.B, dtype=torch.int32, device=dev)     # the hop's event words, read by its launches
-        self._ev_words = [0] * self.B
+        nbytes, self._counters_at = self._path.slot_state_bytes(self.B, self.max_frames)   # (no counters offset: no give-up flag)
+        self._alloc(nbytes, graph)
         self.book = SlotBook(self.B)
-        self._use_graph = bool(graph)
-        self._graphs = {}          # (K, channels) -> (graph, f0_in, control_in, noise_new, out, pre)
-        self._steady_runs = {}
-        self.frames_seen = 0       # device frames, pre-roll included
+        self._ev_words = [0] * self.B
         self.hops = 0
-        self._nz_prev_start = 0
-        self._last_K = None
-        self._last_pre = None
-        self.finished = False
+        L = _lib.lib()
         # pre-roll: every slot idle, output dropped; afterwards each hop is an ordinary (not first) one of the same shape
         with torch.cuda.device(dev):
+            self._ev = torch.zeros(self.B, dtype=torch.int32, device=dev)     # the hop's event words, read by its launches
             f0 = torch.zeros((self.B, _PREROLL), dtype=torch.float32, device=dev)
-            c = torch.zeros((self.B, self._control_size, _PREROLL), dtype=torch.float32, device=dev)
+            c = torch.zeros((self.B, self._path.control_size, _PREROLL), dtype=torch.float32, device=dev)
             M = L.nws_stream_out_samples(_PREROLL, 1, 0)
             out = torch.empty((self.B, M), dtype=torch.float32, device=dev)
             nz = torch.rand(L.nws_stream_noise_draws(_PREROLL, 1, 0), device=dev) if self._noise_all is None else None
@@ -513,28 +555,9 @@ class VoiceStream(_StreamBase):
         self._advance(_PREROLL)
         self._last_K = None
 
-    # ---- what depends on the path (GenericVoiceStream overrides these) -------------------------------------------------------
-    def _bind(self):
-        if not self.eng.specialised():
-            raise RuntimeError("stateful streaming runs on the fused kernels: the model must have the architecture of "
-                               "gin/models/newt.gin - model.voices(B) gives the slot stream of any architecture")
-        _, _, self.dev = self.eng.weights()
-        self._ir_len = int(self.eng.ir().numel())
-        self._n_harmonics = _lib.N_HARMONICS
-        self._control_size = 2
-
-    def _state_bytes(self, L):
-        nbytes = L.nws_stream_slot_state_bytes(self.B, self.max_frames, self._ir_len)
-        self._counters_at = int(L.nws_stream_counters_offset(self.B, self.max_frames, self._ir_len))
-        return nbytes
-
     # ---- one call of the binding ------------------------------------------------------------------------------------
     def _step(self, f0_2d, control, noise_new, out, pre):
-        eng = self.eng
-        r = eng._wd()
-        binding().stream_step_slots(r.wdesc, r.fir_design, self._state, self.max_frames, f0_2d, control, int(self.frames_seen),
-                                    int(self._nz_prev_start), eng.osc_sample_rate(), self.phase_u, r.rand_phase, noise_new,
-                                    self._noise_all, r.ir.reshape(-1), self._ev, out, pre)
+        self._path.step_slots(self, f0_2d, control, noise_new, out, pre)
 
     _steady_step = _step
 
@@ -643,9 +666,9 @@ class VoiceStream(_StreamBase):
     def check(self) -> None:
         """Raise if a hop's device work reported that it gave up waiting (counters[5]; synchronises).  The flag belongs to the
         four-launch hop (K <= 2 frames, at most 512 slots), whose frame-MLP workgroups wait inside the launch for their slot's
-        recurrence with a bounded wait; the seven-launch form of every other hop has no such wait and never sets it."""
-        flag = int(self._state[self._counters_at + 40: self._counters_at + 48].cpu().view(torch.int64)[0])
-        if flag != 0:
+        recurrence with a bounded wait; the seven-launch form of every other hop has no such wait and never sets it, and on the
+        runtime-size kernels no hop has one: there the call only synchronises."""
+        if self._path.gave_up(self):
             raise RuntimeError("VoiceStream: a hop's frame-MLP work gave up waiting for its recurrence rows (its output is NaN)")
 
     def close(self) -> None:
@@ -658,42 +681,10 @@ class VoiceStream(_StreamBase):
 class GenericVoiceStream(VoiceStream):
     """VoiceStream for a model that `Engine.specialised()` turns down (what GenericNewtStream is to NewtStream): the same contract
     and methods, one hop = one `g_stream_step_slots` of the binding (`nws_g_stream_step_slots`, csrc/generic.hip).
-    The construction-time refusals are GenericNewtStream's (control hop 128, 256 noise taps, a symmetric window) and VoiceStream's
-    (reverb history); what it watches for weight updates is the GenericEngine's descriptor record.  The hop is a chain of launches
-    in which nothing waits, so `check()` has no give-up flag to read."""
+    The hop is a chain of launches in which nothing waits, so `check()` has no give-up flag to read.  _GenericPath states what it
+    needs."""
 
-    def _bind(self):
-        GenericNewtStream._bind(self)
-        self._control_size = int(self.eng.generic.model_desc().struct.control_size)
-
-    def _state_bytes(self, L):
-        r = self.eng.generic.model_desc()
-        nbytes = L.nws_g_stream_slot_state_bytes(C.byref(r.struct), self.B, self.max_frames, self._ir_len)
-        if nbytes == 0:
-            raise RuntimeError("stateful streaming: the runtime-size kernels do not serve this model's layer sizes - render it "
-                               "with the one-shot forward")
-        return nbytes
-
-    _record = GenericNewtStream._record
-    _rewalk = GenericNewtStream._rewalk
-    _reverb_plan = GenericNewtStream._reverb_plan
-    _tail_call = GenericNewtStream._tail_call
-
-    def _capture(self, K, C_in):
-        self.eng.generic.model_desc()     # a rebuild synchronises: in front of the capture, never inside it
-        return super()._capture(K, C_in)
-
-    def _step(self, f0_2d, control, noise_new, out, pre):
-        r = self.eng.generic.model_desc()
-        binding().g_stream_step_slots(r.gdesc, self._state, self.max_frames, f0_2d, control, int(self.frames_seen),
-                                      int(self._nz_prev_start), self.eng.osc_sample_rate(), self.phase_u, r.rand_phase, noise_new,
-                                      self._noise_all, self._ev, out, pre)
-
-    _steady_step = _step
-
-    def check(self) -> None:
-        """Synchronises; the runtime-size hop has no wait inside a launch and so nothing it could have given up on."""
-        torch.cuda.synchronize(self.dev)
+    _PATH = _GenericPath
 
 
 def voice_stream(model, batch_size: int, **kw):

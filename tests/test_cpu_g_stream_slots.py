@@ -106,9 +106,9 @@ def test_public_surface_equals_the_packaged_slot_stream():
     assert issubclass(st.GenericVoiceStream, st.VoiceStream)
     for name in ("__init__", "push", "static_io", "hop", "refresh", "reverb_tail", "slot_states", "idle_slots", "check", "close"):
         assert inspect.signature(getattr(st.GenericVoiceStream, name)) == inspect.signature(getattr(st.VoiceStream, name)), name
-    # only what depends on the path is overridden
+    # only what depends on the path is overridden: the path itself
     own = {k for k in vars(st.GenericVoiceStream) if not k.startswith("__")}
-    assert own == {"_bind", "_state_bytes", "_record", "_rewalk", "_reverb_plan", "_tail_call", "_capture", "_step", "_steady_step", "check"}
+    assert own == {"_PATH"} and st.GenericVoiceStream._PATH is st._GenericPath and st.VoiceStream._PATH is st._FusedPath
 
 
 def test_note_player_refuses_a_control_input_that_is_not_two_channels():

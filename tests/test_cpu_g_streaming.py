@@ -110,3 +110,41 @@ def test_public_surface_equals_the_packaged_stream():
     assert issubclass(st.GenericNewtStream, st._StreamBase)
     for name in ("__init__", "push", "static_io", "hop", "refresh", "reverb_tail"):
         assert inspect.signature(getattr(st.GenericNewtStream, name)) == inspect.signature(getattr(st.NewtStream, name)), name
+    # only what depends on the path is overridden: the path itself
+    own = {k for k in vars(st.GenericNewtStream) if not k.startswith("__")}
+    assert own == {"_PATH"} and st.GenericNewtStream._PATH is st._GenericPath and st.NewtStream._PATH is st._FusedPath
+
+
+def test_the_two_paths_have_one_surface():
+    st = importlib.import_module(PKG + ".streaming")
+    public = lambda cls: {k: inspect.signature(v) for k, v in vars(cls).items() if not k.startswith("_") and callable(v)}
+    fused, generic = public(st._FusedPath), public(st._GenericPath)
+    assert fused == generic
+    assert set(fused) == {"record", "rewalk", "settle", "reverb_aux", "state_bytes", "slot_state_bytes", "step", "step_slots",
+                          "reverb_tail", "gave_up"}
+    assert inspect.signature(st._FusedPath.__init__) == inspect.signature(st._GenericPath.__init__)
+
+
+NO_CPU = ("{}gru.weight_ih_l0 lives on cpu: the NEWT forward path only runs as HIP kernels on an AMD GPU (move the model and inputs "
+          "with .to('cuda')); there is no CPU fallback.")
+FUSED_ONLY = "stateful streaming runs on the fused kernels: the model must have the architecture of gin/models/newt.gin"
+SLOTS_HINT = " - model.voices(B) gives the slot stream of any architecture"
+
+
+def test_each_stream_class_keeps_its_refusal_of_a_cpu_model():
+    """The four constructors called directly on CPU-resident models: the path's construction-time refusal comes first, word for
+    word (the fused path names the parameter as the packaged engine does, the runtime-size path as the descriptor does)."""
+    nws = importlib.import_module(PKG)
+    st = importlib.import_module(PKG + ".streaming")
+    bank, _ = build("bank", False, device="cpu")
+    nws.ensure_default_config()
+    packaged = nws.NeuralWaveshaping().eval()
+    assert packaged._engine.specialised() and not bank._engine.specialised()
+    expected = {(st.NewtStream, packaged): NO_CPU.format("embedding."), (st.VoiceStream, packaged): NO_CPU.format("embedding."),
+                (st.GenericNewtStream, packaged): NO_CPU.format(""), (st.GenericVoiceStream, packaged): NO_CPU.format(""),
+                (st.NewtStream, bank): FUSED_ONLY, (st.VoiceStream, bank): FUSED_ONLY + SLOTS_HINT,
+                (st.GenericNewtStream, bank): NO_CPU.format(""), (st.GenericVoiceStream, bank): NO_CPU.format("")}
+    for (cls, model), text in expected.items():
+        with pytest.raises(RuntimeError) as e:
+            cls(model, 2)
+        assert str(e.value) == text, cls.__name__
